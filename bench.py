@@ -9,19 +9,24 @@ One "step" = one pass of the full per-frame chain (FramePipeline.run: class map 
 + isotope sums -> classification -> proximity merge -> particle fill -> refine (EDT, maxima, watershed) -> ROI sums)
 over one batch of 64 frames of 1024x1024x5 float32 that is already resident in HBM (BASELINE config 2).  Frames are
 independent, so N ranks each process their own batch (weak scaling, no data-path collective); the only exchange is
-the RCCL all-gather of the ROI table, done once after the timed region.
+the RCCL all-gather of the ROI table, done once after the timed region of a `--full` run.
 
 The timed region carries no instrumentation (no event records, no counter reads).  How its steps are LAUNCHED is settled in the
 setup phase (`--launch auto`, the default): eight untimed steps, twice, as eager launches from 8 host threads with five streams
 each and as hipGraph replays with four in flight from one host thread; the timed region runs the faster (`config.launch`,
 `config.launch_probe_ms_per_step`).  On a quiet host the two are within 3 %; on a busy one the eight launch threads fall behind
-and replays win by 15 %.  `--launch eager|graph` fixes the mode.  The JSON line carries `roofline` (dominant kernel by
-serial time; HIP events on the launch stream in two extra single-stream steps right after the timed region -- the
-reproducible figure -- with the same kernel's duration while 8 batches share the chip as `in_flight`, and `stage_frac` =
-the watershed stage's compulsory 13 B/px over the serial time of all its kernels) and `cpu_baseline` (the CPU oracle timed
-on this box's host cores on a bounded sample; reported, not the target).  `end_to_end` (dataset run incl. table assembly,
-download and gather), `mosaic4096` / `frames2048` (BASELINE configs 4 / 5 shapes), `batch64` / `secondary` (quantised
-input) are further legs of the same run, never `value`.
+and replays win by 15 %.  `--launch eager|graph` fixes the mode.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, and the JSON line (`metric`, `value`,
+`unit`, `ms_per_step`, `config`, ...).  `--dump-outputs DIR` also writes what the last timed step computed (see
+`dump_outputs`).  Everything else runs with `--full` only.  With `--full` the JSON line also carries `roofline`
+(dominant kernel by serial time; HIP events on the launch stream in two extra single-stream steps right after the timed
+region -- the reproducible figure -- with the same kernel's duration while 8 batches share the chip as `in_flight`, and
+`stage_frac` = the watershed stage's compulsory 13 B/px over the serial time of all its kernels), the device table assembly
+and all-gather of the ROI table, and `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample, whose
+frames double as the parity check of the run; reported, not the target).  `end_to_end` (dataset run incl. table assembly,
+download and gather), `graph_replay`, `mosaic4096` / `frames2048` (BASELINE configs 4 / 5 shapes), `batch64` / `secondary`
+(quantised input) are further `--full` legs of the same run, never `value`.
 """
 import argparse
 import ctypes
@@ -58,7 +63,7 @@ def parse_args():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames of the CPU-baseline sample (0 = 2 per core)")
-    ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel event table to stderr")
+    ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel event table to stderr (with --full)")
     ap.add_argument("--lanes", type=int, default=0,
                     help="batches in flight (0 = the pipeline's default: 8 host threads, or 2 graph replays with --graph)")
     ap.add_argument("--graph", action="store_true",
@@ -94,7 +99,18 @@ def parse_args():
     ap.add_argument("--watershed-mode", type=int, default=0,
                     help="profiling aid for ABLATION builds (libraries that skip a phase: wrong labels, right timing): 2 = frames "
                          "the proof fails on are reported, not recomputed by the exact flood.  The headline runs mode 0")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: per-kernel roofline, table assembly and "
+                         "all-gather, CPU baseline with its parity check, and the end-to-end, graph, batch64, shape and "
+                         "secondary legs (the options above that name them act on --full runs only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.kernel_table and not args.full:
+        ap.error("--kernel-table needs --full (the per-kernel table comes from the --full measurements)")
+    return args
 
 
 def cpu_baseline(res, stack, cell_types, n_frames, tables=None):
@@ -251,6 +267,68 @@ def secondary_leg(args, stack, cell_types, pipe):
             "peak_device_memory_GB": round(torch.cuda.max_memory_allocated() / 1e9, 1)}
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: .npy payload of one run (under 64 MB with the headers)
+DUMP_PIXELS = 1 << 19    # pixels sampled from every per-pixel image
+DUMP_SEED = 12345
+PIXEL_KEYS = ("denoised", "labels", "recreated", "mask", "markers", "ws_labels")
+FRAME_KEYS = ("counts", "n_markers", "n_list", "type_stats", "particle_area", "overlap_area", "tie_flags", "nan_flag",
+              "overflow", "ws_overflow")
+
+
+def _host_exact(t):
+    """device tensor -> numpy, float32 for 8/16-bit and float32 data, float64 for the rest: exact either way"""
+    import torch
+    small = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.float16, torch.bfloat16, torch.float32)
+    return t.to(torch.float32 if t.dtype in small else torch.float64).cpu().numpy()
+
+
+def dump_outputs(out_dir, res, pipe, check):
+    """What the timed path computed in its last step (rank 0's batch), as ``out_dir/<name>.npy``, float32 or float64, at
+    most DUMP_BYTES in all; the same arguments give the same files:
+
+    * the per-pixel images of the result (PIXEL_KEYS), each at the same DUMP_PIXELS pixels, a fixed seeded sample whose
+      flat (frame, row, col) indices are ``pixel_index``;
+    * the per-frame vectors (FRAME_KEYS), whole;
+    * the region tables as a caller reads them (``FramePipeline.tables_device``: ``table_rois``, ``table_cells``,
+      ``table_groups``, ``table_frames_rec``), whole, or at fixed seeded rows where a table exceeds its share of what the
+      budget has left.  (The raw (B, cap, ...) region arrays of the result hold undefined rows past each frame's count;
+      the tables are their defined content.)"""
+    import numpy as np
+    import torch
+    res.synchronize()
+    arrays = {}
+    shape = res["labels"].shape
+    n_px = int(res["labels"].numel())
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, min(DUMP_PIXELS, n_px), replace=False))
+    arrays["pixel_index"] = pick.astype(np.float64)
+    idx = None
+    for k in PIXEL_KEYS:
+        if k in res:
+            t = res[k]
+            assert t.shape == shape, (k, tuple(t.shape))
+            if idx is None:
+                idx = torch.from_numpy(pick).to(t.device)
+            arrays[k] = _host_exact(t.reshape(-1)[idx])
+    for k in FRAME_KEYS:
+        if k in res:
+            arrays[k] = _host_exact(res[k])
+    tables = pipe.tables_device(res, check=check)
+    left = DUMP_BYTES - sum(a.nbytes for a in arrays.values())
+    names = sorted((k for k in ("rois", "cells", "groups", "frames_rec") if k in tables), key=lambda k: tables[k].numel())
+    for i, k in enumerate(names):
+        t = tables[k]
+        share = left // (len(names) - i)  # smallest first: what a small table leaves goes to the larger ones
+        row_bytes = 8 * max(1, int(t.numel() // max(1, t.shape[0])))
+        if t.shape[0] * row_bytes > share:
+            rows = np.sort(np.random.default_rng(DUMP_SEED + i).choice(t.shape[0], share // row_bytes, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        arrays["table_" + k] = _host_exact(t)
+        left -= arrays["table_" + k].nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 class _StdoutToStderr:
     """Library banners (RCCL prints its host / library path on stdout at init) must not pollute the one JSON line:
     route file descriptor 1 to stderr while the benchmark runs, restore it for the final print."""
@@ -397,6 +475,88 @@ def shape_leg(name, B, H, W, cell_types, lib, dev, steps, seed):
     return out
 
 
+def roofline_block(args, insitu, alone, B, H, W, value, world, lanes):
+    """`roofline` of a --full run, from the per-kernel passes of `_run`: `insitu` = the chain as the timed region runs it,
+    `alone` = the same kernels on one stream (None with --serial)."""
+    kernels, tiles_i, launches_i, steps_i = insitu
+    if args.kernel_table:
+        for name, (calls, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1]):
+            print("%10.3f ms %7d launches %9.2f us/launch  %s" % (ms, calls, 1e3 * ms / calls, name), file=sys.stderr)
+    # the dominant kernel: by its time with nothing beside it (the serial table) when that table exists
+    rank_table = alone[0] if alone is not None else kernels
+    dom_name = max(rank_table.items(), key=lambda kv: kv[1][1])[0]
+    if dom_name not in kernels:
+        dom_name = max(kernels.items(), key=lambda kv: kv[1][1])[0]
+    dom_calls, dom_ms = kernels[dom_name]
+    short = dom_name.split("<")[0].split(" ")[0].strip("()")
+    bpp = KERNEL_BYTES_PER_PIXEL.get(short, 0.0)
+
+    # the relaxation is TWO kernels since round 4 (full grids for the first rounds, list walks for the late ones): its tile
+    # counter and its launch counter cover both, so the roofline block prices them together
+    def joint(kern):
+        if short != "ws_relax_kernel":
+            return kern[dom_name]
+        parts = [v for k, v in kern.items() if k.lstrip("(").startswith(("ws_relax_kernel", "ws_relax_list_kernel"))]
+        return sum(c for c, _ in parts), sum(m for _, m in parts)
+
+    def launch_block(kern, tiles, launches, steps):
+        calls, ms = joint(kern)
+        avg_s = ms / calls / 1e3
+        units = float(B * H * W)  # pixels one launch processes
+        nbytes = bpp * units
+        if short == "ws_relax_kernel" and launches:
+            # the relaxation only touches marked tiles: count the 64x64 tiles it really processed; one launch per step
+            # is the set-up round, which reads the three inputs (9 B/px) and writes value keys, seed labels and levels
+            # (12 B/px) for every pixel instead of the 12 B/px of a plain round
+            units = 4096.0 * tiles / launches
+            nbytes = 12.0 * 4096.0 * tiles / launches + 9.0 * B * H * W * steps / launches
+        return {"launches_per_step": calls / steps, "avg_launch_us": round(1e6 * avg_s, 2),
+                "algorithmic_bytes_per_launch": round(nbytes), "pixels_per_launch": round(units),
+                "achieved": round(nbytes / avg_s / 1e9, 2), "frac": round(nbytes / avg_s / 1e9 / HBM_PEAK_GBS, 5)}
+
+    insitu_block = launch_block(kernels, tiles_i, launches_i, steps_i)
+    insitu_block["how"] = ("%d steps of the same chain with %d batches in flight (the launches of a step then share the CUs "
+                           "with seven other batches: a launch's duration here is a concurrency figure, not a kernel time -- "
+                           "launches_per_step x avg_launch_us may exceed ms_per_step)" % (steps_i, lanes))
+    main_block, stage_frac, ws_serial_ms = insitu_block, None, None
+    if alone is not None and dom_name in alone[0]:
+        # THE roofline figure: the kernel with nothing beside it (one stream), reproducible from profiles/
+        main_block = launch_block(alone[0], alone[1], alone[2], alone[3])
+        main_block["serial_kernel_ms_per_step"] = round(sum(ms for _, ms in alone[0].values()) / alone[3], 3)
+        # the watershed stage as a whole: its compulsory bytes (13 B/px, once) over the serial time of all its kernels
+        ws_serial_ms = sum(ms for name, (_, ms) in alone[0].items() if name.lstrip("(").startswith("ws_")) / alone[3]
+        if ws_serial_ms > 0:
+            stage_frac = WS_STAGE_BYTES_PER_PIXEL * B * H * W / (ws_serial_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+    total_kernel_ms = sum(ms for _, ms in kernels.values())
+    traffic = None
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tpath):
+        tj = json.load(open(tpath))
+        traffic = tj.get(short)
+        if short == "ws_relax_kernel" and tj.get("ws_relax_list_kernel") is not None and traffic is not None:
+            # per launch of the pair, weighted by their launch counts in this run
+            src_table = alone[0] if alone is not None else kernels
+            n_full = sum(c for k, (c, _) in src_table.items() if k.lstrip("(").startswith("ws_relax_kernel"))
+            n_list = sum(c for k, (c, _) in src_table.items() if k.lstrip("(").startswith("ws_relax_list_kernel"))
+            if n_full + n_list:
+                traffic = round((traffic * n_full + tj["ws_relax_list_kernel"] * n_list) / (n_full + n_list))
+    return dict({"bound": "hbm", "kernel": short if short != "ws_relax_kernel" else "ws_relax_kernel + ws_relax_list_kernel",
+                 "algorithmic_bytes_per_pixel": bpp},
+                **{k: v for k, v in main_block.items() if k != "how"},
+                **{"peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": traffic,
+                   "how": ("HIP events on the launch stream, 2 extra steps of the same chain on ONE stream right after "
+                           "the timed region (nothing beside the kernel); `in_flight` = the same kernel while 8 batches "
+                           "share the chip") if main_block is not insitu_block else insitu_block["how"],
+                   "in_flight": insitu_block if main_block is not insitu_block else None,
+                   "stage": "watershed (ws_* kernels): %.1f B/px compulsory, once" % WS_STAGE_BYTES_PER_PIXEL,
+                   "stage_serial_ms_per_step": None if ws_serial_ms is None else round(ws_serial_ms, 3),
+                   "stage_frac": None if stage_frac is None else round(stage_frac, 5),
+                   "share_of_kernel_time": round(joint(kernels)[1] / total_kernel_ms, 4),
+                   "chain_bytes_per_pixel": CHAIN_BYTES_PER_PIXEL,
+                   "chain_achieved_GBps": round(CHAIN_BYTES_PER_PIXEL * value / world / 1e3, 3),
+                   "chain_frac": round(CHAIN_BYTES_PER_PIXEL * value / world / 1e3 / HBM_PEAK_GBS, 6)})
+
+
 def _run(args):
     import torch
     import torch.distributed as dist
@@ -486,26 +646,6 @@ def _run(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- per-kernel durations (rank 0): HIP events on the launch streams.  (a) the chain as the timed region runs it --
-    # same streams, same number of batches in flight -- launched eagerly, because the kernels of a graph replay cannot be
-    # bracketed one by one; (b) the same kernels with nothing beside them (one stream): a launch's duration under (a) says
-    # how the CUs were shared, under (b) how good the kernel is.
-    insitu = alone = None
-    if rank == 0:
-        steps_i = max(2, min(args.steps, 8))
-        probe = FramePipeline(ct, overlap=not args.serial, lanes=pipe.lanes, multi_stream=not args.single_class_stream)
-        for _ in range(pipe.lanes + 1):
-            probe.run(stack)
-        probe.synchronize()
-        insitu = _timing_pass(lib, lambda: [probe.run(stack) for _ in range(steps_i)], probe.synchronize) + (steps_i,)
-        if not args.serial:
-            solo = FramePipeline(ct, overlap=False)
-            solo.run(stack)
-            torch.cuda.synchronize()
-            alone = _timing_pass(lib, lambda: [solo.run(stack) for _ in range(2)], torch.cuda.synchronize) + (2,)
-            del solo
-        del probe
-
     # a table overflow would invalidate the measurement; frames on which the reference itself raises (clusters of a type
     # without a single cell -> int(NaN), tiff_analysis.py:776-781) are only counted: they cost the same work
     if int(res["overflow"].sum().item()) or int(res["ws_overflow"].sum().item()):
@@ -513,101 +653,12 @@ def _run(args):
     nan_frames = int(res["nan_flag"].sum().item())
     tie_frames = int(res["tie_flags"].sum().item())
 
-    # the one exchange step of the path: all-gather of the per-ROI table (outside the timed region)
-    t_tab = time.perf_counter()
-    tables = pipe.tables_device(res, frame_ids=[rank * B + i for i in range(B)], check=nan_frames == 0)
-    torch.cuda.synchronize()
-    table_ms = 1e3 * (time.perf_counter() - t_tab)
-    all_gather_table(tables["rois"])  # first call: communicator set-up / torch's sort kernels are loaded
-    torch.cuda.synchronize()
-    t_gat = time.perf_counter()
-    gathered = all_gather_table(tables["rois"])  # device tensor straight into the collective (RCCL when world > 1)
-    torch.cuda.synchronize()
-    gather_ms = 1e3 * (time.perf_counter() - t_gat)
-    n_rois = int(gathered.shape[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, pipe, check=nan_frames == 0)
 
-    # parity evidence of THIS run, before anything replays the pipeline's graphs again (a replay overwrites `res`):
-    # world == 1: the CPU baseline's frames double as the check (32 by default); world > 1: no CPU baseline (rank 0 at
-    # N = 1 only, by contract), but rank 0 still checks two frames of its timed batch against the oracle
-    cpu_block, checked, cpu_refs = None, None, None
-    if rank == 0 and not args.no_cpu_baseline:
-        if world == 1:
-            cpu_block, checked, cpu_refs = cpu_baseline(res, stack, ct, args.cpu_frames, tables)
-        else:
-            from oracle import parity
-            refs, _, _ = parity.run_oracle(stack[[0, B - 1]].cpu().numpy(), ct, merged=True, processes=2)
-            checked = parity.compare(res, [0, B - 1], refs, sums_rtol=1e-6)
-    e2e_block = None
-    legs_pipe = None
-    if not args.serial and not args.no_end_to_end:
-        # (the dataset legs refill rotating input buffers: they run the eager pipeline whichever way the timed region was launched)
-        legs_pipe = pipe if not graph else FramePipeline(ct, merged=not args.no_merge, watershed_mode=args.watershed_mode)
-        e2e_block = end_to_end_leg(args, stack, ct, legs_pipe, dev, world, world * B * H * W * args.steps / elapsed / 1e6,
-                                   refs=cpu_refs if world == 1 else None)
+    value = world * B * H * W * args.steps / elapsed / 1e6
+    out = None
     if rank == 0:
-        kernels, tiles_i, launches_i, steps_i = insitu
-        if args.kernel_table:
-            for name, (calls, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1]):
-                print("%10.3f ms %7d launches %9.2f us/launch  %s" % (ms, calls, 1e3 * ms / calls, name), file=sys.stderr)
-        # the dominant kernel: by its time with nothing beside it (the serial table) when that table exists
-        rank_table = alone[0] if alone is not None else kernels
-        dom_name = max(rank_table.items(), key=lambda kv: kv[1][1])[0]
-        if dom_name not in kernels:
-            dom_name = max(kernels.items(), key=lambda kv: kv[1][1])[0]
-        dom_calls, dom_ms = kernels[dom_name]
-        short = dom_name.split("<")[0].split(" ")[0].strip("()")
-        bpp = KERNEL_BYTES_PER_PIXEL.get(short, 0.0)
-
-        # the relaxation is TWO kernels since round 4 (full grids for the first rounds, list walks for the late ones): its tile
-        # counter and its launch counter cover both, so the roofline block prices them together
-        def joint(kern):
-            if short != "ws_relax_kernel":
-                return kern[dom_name]
-            parts = [v for k, v in kern.items() if k.lstrip("(").startswith(("ws_relax_kernel", "ws_relax_list_kernel"))]
-            return sum(c for c, _ in parts), sum(m for _, m in parts)
-
-        def launch_block(kern, tiles, launches, steps):
-            calls, ms = joint(kern)
-            avg_s = ms / calls / 1e3
-            units = float(B * H * W)  # pixels one launch processes
-            nbytes = bpp * units
-            if short == "ws_relax_kernel" and launches:
-                # the relaxation only touches marked tiles: count the 64x64 tiles it really processed; one launch per step
-                # is the set-up round, which reads the three inputs (9 B/px) and writes value keys, seed labels and levels
-                # (12 B/px) for every pixel instead of the 12 B/px of a plain round
-                units = 4096.0 * tiles / launches
-                nbytes = 12.0 * 4096.0 * tiles / launches + 9.0 * B * H * W * steps / launches
-            return {"launches_per_step": calls / steps, "avg_launch_us": round(1e6 * avg_s, 2),
-                    "algorithmic_bytes_per_launch": round(nbytes), "pixels_per_launch": round(units),
-                    "achieved": round(nbytes / avg_s / 1e9, 2), "frac": round(nbytes / avg_s / 1e9 / HBM_PEAK_GBS, 5)}
-
-        insitu_block = launch_block(kernels, tiles_i, launches_i, steps_i)
-        insitu_block["how"] = ("%d steps of the same chain with %d batches in flight (the launches of a step then share the CUs "
-                               "with seven other batches: a launch's duration here is a concurrency figure, not a kernel time -- "
-                               "launches_per_step x avg_launch_us may exceed ms_per_step)" % (steps_i, pipe.lanes))
-        main_block, stage_frac, ws_serial_ms = insitu_block, None, None
-        if alone is not None and dom_name in alone[0]:
-            # THE roofline figure: the kernel with nothing beside it (one stream), reproducible from profiles/
-            main_block = launch_block(alone[0], alone[1], alone[2], alone[3])
-            main_block["serial_kernel_ms_per_step"] = round(sum(ms for _, ms in alone[0].values()) / alone[3], 3)
-            # the watershed stage as a whole: its compulsory bytes (13 B/px, once) over the serial time of all its kernels
-            ws_serial_ms = sum(ms for name, (_, ms) in alone[0].items() if name.lstrip("(").startswith("ws_")) / alone[3]
-            if ws_serial_ms > 0:
-                stage_frac = WS_STAGE_BYTES_PER_PIXEL * B * H * W / (ws_serial_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-        total_kernel_ms = sum(ms for _, ms in kernels.values())
-        value = world * B * H * W * args.steps / elapsed / 1e6
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            tj = json.load(open(tpath))
-            traffic = tj.get(short)
-            if short == "ws_relax_kernel" and tj.get("ws_relax_list_kernel") is not None and traffic is not None:
-                # per launch of the pair, weighted by their launch counts in this run
-                src_table = alone[0] if alone is not None else kernels
-                n_full = sum(c for k, (c, _) in src_table.items() if k.lstrip("(").startswith("ws_relax_kernel"))
-                n_list = sum(c for k, (c, _) in src_table.items() if k.lstrip("(").startswith("ws_relax_list_kernel"))
-                if n_full + n_list:
-                    traffic = round((traffic * n_full + tj["ws_relax_list_kernel"] * n_list) / (n_full + n_list))
         out = {
             "metric": "Mpixels/sec segmented (5-ch 1024x1024 TIFF), ROI mask IoU=1.0",
             "value": round(value, 3), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -620,51 +671,88 @@ def _run(args):
                        "frames_per_gpu": B, "height": H, "width": W, "planes": 5, "parallelism": "frames x%d" % world,
                        "launch": ("one hipGraph replay per step, %d in flight" if graph else "eager launches from %d host threads") % pipe.lanes,
                        "tie_fallback_frames_last_step": tie_frames, "reference_nan_frames_rank0": nan_frames,
-                       "gathered_roi_rows": n_rois, "table_assembly_ms_last_batch": round(table_ms, 3),
-                       "roi_table_all_gather_ms": round(gather_ms, 3),
                        "launch_probe_ms_per_step": launch_probe},
-            "roofline": dict({"bound": "hbm", "kernel": short if short != "ws_relax_kernel" else "ws_relax_kernel + ws_relax_list_kernel",
-                              "algorithmic_bytes_per_pixel": bpp},
-                             **{k: v for k, v in main_block.items() if k != "how"},
-                             **{"peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": traffic,
-                                "how": ("HIP events on the launch stream, 2 extra steps of the same chain on ONE stream right after "
-                                        "the timed region (nothing beside the kernel); `in_flight` = the same kernel while 8 batches "
-                                        "share the chip") if main_block is not insitu_block else insitu_block["how"],
-                                "in_flight": insitu_block if main_block is not insitu_block else None,
-                                "stage": "watershed (ws_* kernels): %.1f B/px compulsory, once" % WS_STAGE_BYTES_PER_PIXEL,
-                                "stage_serial_ms_per_step": None if ws_serial_ms is None else round(ws_serial_ms, 3),
-                                "stage_frac": None if stage_frac is None else round(stage_frac, 5),
-                                "share_of_kernel_time": round(joint(kernels)[1] / total_kernel_ms, 4),
-                                "chain_bytes_per_pixel": CHAIN_BYTES_PER_PIXEL,
-                                "chain_achieved_GBps": round(CHAIN_BYTES_PER_PIXEL * value / world / 1e3, 3),
-                                "chain_frac": round(CHAIN_BYTES_PER_PIXEL * value / world / 1e3 / HBM_PEAK_GBS, 6)}),
         }
-        if cpu_block is not None:
-            out["cpu_baseline"] = cpu_block
-        if checked is not None:
-            out["config"]["parity_checked_frames"] = checked
-        out["end_to_end"] = e2e_block
-        if graph and launch_probe is not None:
-            # the timed region ran as graph replays: their private pools go back before the other legs allocate (see
-            # secondary_leg), and those legs take the eager pipeline
-            import gc
-            res = None
-            pipe = legs_pipe if legs_pipe is not None else FramePipeline(ct, merged=not args.no_merge, watershed_mode=args.watershed_mode)
-            gc.collect()
-            torch.cuda.empty_cache()
-        if world == 1 and not args.levels and not args.serial:
-            if args.graph_leg_steps > 0 and not (graph and launch_probe is None):
-                out["graph_replay"] = graph_leg(args, stack, ct, 1e3 * elapsed / args.steps)
-            if args.batch64_frames > 0:
-                out["batch64"] = batch64_leg(args, stack, ct)
-            if not args.no_shape_legs:
-                out["mosaic4096"] = shape_leg("mosaic4096", 1, 4096, 4096, ct, lib, dev, 16, 40_000)
-                out["frames2048"] = shape_leg("frames2048", 16, 2048, 2048, ct, lib, dev, 8, 50_000)
-            if args.secondary_batch > 0:
-                out["secondary"] = secondary_leg(args, stack, ct, pipe)
-        line = json.dumps(out)
-    else:
-        line = None
+    if args.full:
+        # ---- per-kernel durations (rank 0): HIP events on the launch streams.  (a) the chain as the timed region runs it --
+        # same streams, same number of batches in flight -- launched eagerly, because the kernels of a graph replay cannot be
+        # bracketed one by one; (b) the same kernels with nothing beside them (one stream): a launch's duration under (a) says
+        # how the CUs were shared, under (b) how good the kernel is.
+        insitu = alone = None
+        if rank == 0:
+            steps_i = max(2, min(args.steps, 8))
+            probe = FramePipeline(ct, overlap=not args.serial, lanes=pipe.lanes, multi_stream=not args.single_class_stream)
+            for _ in range(pipe.lanes + 1):
+                probe.run(stack)
+            probe.synchronize()
+            insitu = _timing_pass(lib, lambda: [probe.run(stack) for _ in range(steps_i)], probe.synchronize) + (steps_i,)
+            if not args.serial:
+                solo = FramePipeline(ct, overlap=False)
+                solo.run(stack)
+                torch.cuda.synchronize()
+                alone = _timing_pass(lib, lambda: [solo.run(stack) for _ in range(2)], torch.cuda.synchronize) + (2,)
+                del solo
+            del probe
+
+        # the one exchange step of the path: all-gather of the per-ROI table (outside the timed region)
+        t_tab = time.perf_counter()
+        tables = pipe.tables_device(res, frame_ids=[rank * B + i for i in range(B)], check=nan_frames == 0)
+        torch.cuda.synchronize()
+        table_ms = 1e3 * (time.perf_counter() - t_tab)
+        all_gather_table(tables["rois"])  # first call: communicator set-up / torch's sort kernels are loaded
+        torch.cuda.synchronize()
+        t_gat = time.perf_counter()
+        gathered = all_gather_table(tables["rois"])  # device tensor straight into the collective (RCCL when world > 1)
+        torch.cuda.synchronize()
+        gather_ms = 1e3 * (time.perf_counter() - t_gat)
+        n_rois = int(gathered.shape[0])
+
+        # parity evidence of THIS run, before anything replays the pipeline's graphs again (a replay overwrites `res`):
+        # world == 1: the CPU baseline's frames double as the check (32 by default); world > 1: no CPU baseline (rank 0 at
+        # N = 1 only, by contract), but rank 0 still checks two frames of its timed batch against the oracle
+        cpu_block, checked, cpu_refs = None, None, None
+        if rank == 0 and not args.no_cpu_baseline:
+            if world == 1:
+                cpu_block, checked, cpu_refs = cpu_baseline(res, stack, ct, args.cpu_frames, tables)
+            else:
+                from oracle import parity
+                refs, _, _ = parity.run_oracle(stack[[0, B - 1]].cpu().numpy(), ct, merged=True, processes=2)
+                checked = parity.compare(res, [0, B - 1], refs, sums_rtol=1e-6)
+        e2e_block = None
+        legs_pipe = None
+        if not args.serial and not args.no_end_to_end:
+            # (the dataset legs refill rotating input buffers: they run the eager pipeline whichever way the timed region was launched)
+            legs_pipe = pipe if not graph else FramePipeline(ct, merged=not args.no_merge, watershed_mode=args.watershed_mode)
+            e2e_block = end_to_end_leg(args, stack, ct, legs_pipe, dev, world, world * B * H * W * args.steps / elapsed / 1e6,
+                                       refs=cpu_refs if world == 1 else None)
+        if rank == 0:
+            out["config"].update({"gathered_roi_rows": n_rois, "table_assembly_ms_last_batch": round(table_ms, 3),
+                                  "roi_table_all_gather_ms": round(gather_ms, 3)})
+            out["roofline"] = roofline_block(args, insitu, alone, B, H, W, value, world, pipe.lanes)
+            if cpu_block is not None:
+                out["cpu_baseline"] = cpu_block
+            if checked is not None:
+                out["config"]["parity_checked_frames"] = checked
+            out["end_to_end"] = e2e_block
+            if graph and launch_probe is not None:
+                # the timed region ran as graph replays: their private pools go back before the other legs allocate (see
+                # secondary_leg), and those legs take the eager pipeline
+                import gc
+                res = None
+                pipe = legs_pipe if legs_pipe is not None else FramePipeline(ct, merged=not args.no_merge, watershed_mode=args.watershed_mode)
+                gc.collect()
+                torch.cuda.empty_cache()
+            if world == 1 and not args.levels and not args.serial:
+                if args.graph_leg_steps > 0 and not (graph and launch_probe is None):
+                    out["graph_replay"] = graph_leg(args, stack, ct, 1e3 * elapsed / args.steps)
+                if args.batch64_frames > 0:
+                    out["batch64"] = batch64_leg(args, stack, ct)
+                if not args.no_shape_legs:
+                    out["mosaic4096"] = shape_leg("mosaic4096", 1, 4096, 4096, ct, lib, dev, 16, 40_000)
+                    out["frames2048"] = shape_leg("frames2048", 16, 2048, 2048, ct, lib, dev, 8, 50_000)
+                if args.secondary_batch > 0:
+                    out["secondary"] = secondary_leg(args, stack, ct, pipe)
+    line = json.dumps(out) if rank == 0 else None
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -5,7 +5,7 @@
 P=particle_col_image_segmentation_amd
 PAT=$1; shift
 cp $P/libpcseg.so /tmp/libpcseg_keep.so
-Q="--no-cpu-baseline --secondary-batch 0 --no-end-to-end"
+Q="--full --no-cpu-baseline --secondary-batch 0 --no-end-to-end"
 for v in "$@"; do
   cp "$v" $P/libpcseg.so
   python bench.py $Q --serial --kernel-table --steps 4 2> /tmp/ab_err.txt | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v serial', d['ms_per_step'])"

@@ -9,7 +9,7 @@ set -x
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_r02
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --secondary-batch 0 --no-end-to-end"
+Q="--full --no-cpu-baseline --secondary-batch 0 --no-end-to-end"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/default -o t -- python3 $GRAFT_REPO_ROOT/bench.py $Q > $OUT/bench_default_under_rocprof.json 2> $OUT/default.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python3 $GRAFT_REPO_ROOT/bench.py --serial --steps 6 $Q > $OUT/bench_serial_under_rocprof.json 2> $OUT/trace.log
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o t -- python3 $GRAFT_REPO_ROOT/bench.py --serial --steps 3 --warmup 0 $Q > /dev/null 2> $OUT/fetch.log

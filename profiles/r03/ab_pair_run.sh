@@ -4,7 +4,7 @@
 V=$1
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${2:-abpair}
 mkdir -p $OUT
-Q="--no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0 --no-end-to-end"
+Q="--full --no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0 --no-end-to-end"
 (cd $GRAFT_REPO_ROOT/ab/$V && timeout -k 10 200 python bench.py $Q --serial --steps 6 --kernel-table > $OUT/${V}_serial.json 2> $OUT/${V}_serial.err)
 (cd $GRAFT_REPO_ROOT && timeout -k 10 200 python bench.py $Q --serial --steps 6 --kernel-table > $OUT/main_serial.json 2> $OUT/main_serial.err)
 for rep in 1 2 3; do

@@ -3,7 +3,7 @@
 # relaxation us per launch and overlapped ms per step, twice
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${1:-abrelax}
 mkdir -p $OUT
-Q="--no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0 --no-end-to-end"
+Q="--full --no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0 --no-end-to-end"
 for v in s0 s1o2 s1o3 s1o4; do
   (cd $GRAFT_REPO_ROOT/ab/$v && timeout -k 10 200 python bench.py $Q --serial --steps 6 --kernel-table > $OUT/${v}_serial.json 2> $OUT/${v}_serial.err)
 done

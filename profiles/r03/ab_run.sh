@@ -3,8 +3,8 @@
 # overlapped ms per step and the serial per-kernel table (relaxation us per launch)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${1:-ab}
 mkdir -p $OUT
-Q2="--no-cpu-baseline --secondary-batch 0 --no-end-to-end"
-Q3="--eager --no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --no-end-to-end"
+Q2="--full --no-cpu-baseline --secondary-batch 0 --no-end-to-end"
+Q3="--full --eager --no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --no-end-to-end"
 for rep in 1 2; do
   (cd $GRAFT_REPO_ROOT/ab/r2 && timeout -k 10 200 python bench.py $Q2 > $OUT/r2_$rep.json 2> $OUT/r2_$rep.err)
   for v in v0 v1; do

@@ -13,7 +13,7 @@ for V in "$@"; do
   PCSEG_LIB=$(lib $V) timeout -k 10 600 python -m pytest tests/test_gpu_primitives.py tests/test_gpu_edge_cases.py -q -x -m gpu -k "$KEXPR" 2>&1 | tail -2 || exit 1
 done
 for V in main "$@" main; do
-  PCSEG_LIB=$(lib $V) timeout -k 10 200 python bench.py $Q --serial --steps 6 --kernel-table > $OUT/${V}_serial.json 2> $OUT/${V}_serial.err || exit 1
+  PCSEG_LIB=$(lib $V) timeout -k 10 200 python bench.py $Q --full --serial --steps 6 --kernel-table > $OUT/${V}_serial.json 2> $OUT/${V}_serial.err || exit 1
   echo "== serial $V: $(python3 -c "import json;d=json.load(open('$OUT/${V}_serial.json'));print(d['ms_per_step'])") ms/step"; grep -E "$PAT" $OUT/${V}_serial.err
 done
 for rep in $(seq 1 ${REPS:-2}); do

@@ -10,9 +10,9 @@ step() {
 }
 if [ "$1" = a ]; then
 step pytest 500 python -m pytest tests -m gpu -x -q
-step bench 600 python bench.py --kernel-table
+step bench 600 python bench.py --full --kernel-table
 exit 0
 fi
 step collect 600 bash profiles/collect_r04.sh
 step pmc_sq 300 bash profiles/pmc_sq.sh "ws_relax_kernel"
-step torchrun 250 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline --no-shape-legs --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0
+step torchrun 250 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline --no-shape-legs --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0

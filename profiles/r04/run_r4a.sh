@@ -10,4 +10,4 @@ step() { # name, timeout, command...: stops the whole script when a step was KIL
 step pytest 500 python -m pytest tests -m gpu -x -q
 step diag 300 python profiles/r04/diag_quantised_components.py
 step ab 600 bash profiles/r04/ab_run.sh r4a/ab "watershed" "ws_relax|ws_uf_tile" pipe min64 pipe64
-step bench 400 python bench.py --kernel-table
+step bench 400 python bench.py --full --kernel-table

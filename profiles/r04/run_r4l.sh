@@ -21,7 +21,7 @@ for V in main fe1 fe2 fe3 main; do
   echo "== classmap $V"; grep -E "classmap_median|ccl_border|relabel" $O/classmap_$V.log
 done
 Q="--no-shape-legs --no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0 --no-end-to-end"
-step serial 200 python bench.py $Q --serial --steps 6 --kernel-table
+step serial 200 python bench.py $Q --full --serial --steps 6 --kernel-table
 head -45 $O/serial.err
 for rep in 1 2 3; do
   step bench_$rep 200 python bench.py $Q

@@ -8,7 +8,7 @@ step() {
   echo "=== $name rc=$rc"; tail -1 $O/$name.log | cut -c1-300
   if [ $rc -ge 124 ]; then echo "killed: stopping"; exit $rc; fi
 }
-step bench 600 python bench.py --kernel-table
+step bench 600 python bench.py --full --kernel-table
 Q="--no-shape-legs --no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0 --no-end-to-end"
 for rep in 1 2; do
   for L in 8 6 10 12; do

@@ -9,7 +9,7 @@ step() {
   if [ $rc -ne 0 ]; then tail -5 $O/$name.err; fi
   if [ $rc -ge 124 ]; then echo "killed: stopping"; exit $rc; fi
 }
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 python3 -c "import json;d=json.load(open('$O/bench.log'));print('== default', d['ms_per_step'], d['value'], d['config']['launch'], d['config']['launch_probe_ms_per_step'], d.get('graph_replay',{}).get('ms_per_step'))"
 Q="--no-shape-legs --no-cpu-baseline --secondary-batch 0 --batch64-frames 0 --graph-leg-steps 0 --no-end-to-end"
 for rep in 1 2 3; do

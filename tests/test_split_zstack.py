@@ -41,15 +41,18 @@ def test_writer_round_trip(tmp_path):
             assert b.dtype == a.dtype
 
 
-def test_process_folder_matches_reference(tmp_path):
+def test_process_folder_matches_reference(tmp_path, monkeypatch):
     g = load_golden("split_zstack")
+    # paths relative to the working directory, as the reference is called (its main: "3D05_6B07"): it cuts names at the
+    # FIRST '.' of the whole path (split_zstack.py:20), so a dot in an absolute temp path would move files out of it
+    monkeypatch.chdir(tmp_path)
     for ci in range(3):
         root = tmp_path / ("case%d" % ci)
         sub = root / "top" / "day1"
         sub.mkdir(parents=True)
         name = str(g["sp_%d_name" % ci])
         (sub / name).write_bytes(g["sp_%d_tif" % ci].tobytes())
-        sz.process_folder(str(root / "top"), [1, 2])
+        sz.process_folder(os.path.join("case%d" % ci, "top"), [1, 2])
         assert _listing(str(root)) == [str(s) for s in g["sp_%d_listing" % ci]]
         for k in g.files:
             pre = "sp_%d_px:" % ci
@@ -58,15 +61,17 @@ def test_process_folder_matches_reference(tmp_path):
                 np.testing.assert_array_equal(got, g[k])
 
 
-def test_five_channel_option(tmp_path):
+def test_five_channel_option(tmp_path, monkeypatch):
     """additive: a (Z,5,H,W) isotope stack split with an explicit 5-entry channel map (the reference would treat it
     as 2-channel, split_zstack.py:53-55)."""
+    monkeypatch.chdir(tmp_path)  # relative paths (see test_process_folder_matches_reference)
     sub = tmp_path / "top" / "d"
     sub.mkdir(parents=True)
     a = np.arange(2 * 5 * 4 * 6, dtype=np.uint16).reshape(2, 5, 4, 6)
     tiffio.imwrite(str(sub / "S_1_zstack.tif"), a)
     cmap = {0: "12C", 1: "13C", 2: "14N12C", 3: "15N12C", 4: "32S"}
-    files = sz.process_tif(str(sub / "S_1_zstack.tif"), [0, 1, 2, 3, 4], channel_map=cmap)
+    files = sz.process_tif(os.path.join("top", "d", "S_1_zstack.tif"), [0, 1, 2, 3, 4], channel_map=cmap)
     assert len(files) == 10
+    assert all(os.path.isfile(tmp_path / f) for f in files)
     frames = sz.load_frames(files).reshape(2, 5, 4, 6)
     np.testing.assert_array_equal(frames, a)
