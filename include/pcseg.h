@@ -218,7 +218,16 @@ int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers
  * frames are NOT proven exact); add 4 to also run the explicit per-pixel proof
  * check (implied by the component test, kept for verification).  tie_flags:
  * device int32[B] (may be NULL).
+ * Test-only bits (at most one of them, never with mode 1; the pipeline never sets them): between two passes of the
+ * union-find label assignment, overwrite up to four root entries of its internal parent image per frame, chosen by
+ * the frame index b (b % 6: 0 none, 1 2000000000, 2 -1, 3 INT_MIN, 4 a two-cycle of two roots, 5 H*W + 5), to show
+ * that every walk over that image is fenced -- a poisoned frame comes back flagged (mode 2) or recomputed by the
+ * exact flood (mode 0), never with wrong labels or an access outside its frame:
+ *   PCSEG_WS_POISON_BORDER  first level, before the cross-tile border pass (roots named from a union-find tile seam)
+ *   PCSEG_WS_POISON_LABEL   first level, before the label pass
+ *   PCSEG_WS_POISON_LEVEL2  second level (listed frames, active tiles), before its label passes
  * frame_stride: as for pcseg_edt_sq_lt_f32 (0 = H*W). */
+enum pcseg_ws_poison { PCSEG_WS_POISON_BORDER = 8, PCSEG_WS_POISON_LABEL = 16, PCSEG_WS_POISON_LEVEL2 = 32 };
 size_t pcseg_watershed_workspace_bytes(int B, int H, int W);
 /* measurement aid: out[0] = 64x64 tiles the minimax relaxation actually processed (marked tiles over all rounds;
  * kept in a counter on the current device and read with a blocking copy, i.e. after everything queued so far),

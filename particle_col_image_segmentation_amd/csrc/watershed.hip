@@ -23,6 +23,7 @@
 //     exact emulation of the reference's binary heap, one wave per frame.
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <mutex>
 #include <type_traits>
 
@@ -1196,15 +1197,18 @@ __global__ void __launch_bounds__(256) ws_uf_label_tiles_kernel(WsTileList tiles
 // chain waits a memory latency per step (89 % of this kernel's wave cycles were waits).  A quad's chain belongs to its
 // first reachable pixel; a pixel with another parent entry walks on its own afterwards.
 #ifndef PCSEG_LABEL4_Q
-#define PCSEG_LABEL4_Q 3  // quads a lane carries (3 x 2 lockstep chains): 78 scalar / 53 vector registers, 194 us; 4: 94 / 69, 216 us
+#define PCSEG_LABEL4_Q 3  // quads a lane carries (3 x 2 lockstep chains): 78 scalar / 55 vector registers, 194 us; 4: 94 / 69, 216 us
 #endif
 constexpr int LABEL4_Q = PCSEG_LABEL4_Q;
 
 // NCH chains in lockstep: root[q] (-1 = none) walks to its root, lab[q] becomes the root's label (0: no seed)
-// The fence of these chains costs TWO vector instructions a step and no compare: every load goes to a CLAMPED index (never
-// outside the frame, whatever the entry says) and an entry above its node's virtual index is cut down to the node itself by an
-// unsigned min -- the chain then simply ends there (strictly decreasing: never a cycle); `root - next < 0` accumulates as a
-// sign bit and one compare at the end raises the frame's flag.  (vwalk_ok written out per chain -- as `if`s or as selects fed
+// The fence of these chains costs two vector instructions a step and no compare of its own: every load goes to a CLAMPED index
+// (never outside the frame, whatever the entry says), a node whose pixel lies outside the frame reads as -1 (the compare that
+// tells a live chain from none does it), and an entry above its node's virtual index -- or a negative one -- is cut down to
+// the node itself by an unsigned min: the chain then simply ends there (strictly decreasing: never a cycle).  `cut` (entry ^
+// its cut value, nonzero once an entry was cut) holds everything vwalk_ok tests, one compare at the end raises the frame's
+// flag -- a chain that ENDS outside the frame, e.g. on a seed index in [n, UF_NS), included: its last node is loaded too.
+// (vwalk_ok written out per chain -- as `if`s or as selects fed
 // by compares -- parks sixteen lane masks in scalar register pairs: the kernel went from 96 to 106 scalar registers, i.e.
 // from seven to six workgroups per CU, and this pass is nothing but memory latency: 204 -> 265 us.  What the compiler's
 // occupancy figure does not show: residency of 256-thread workgroups is min(8, 800 / (ceil(sgpr / 16) * 16 + 16)) --
@@ -1214,23 +1218,26 @@ template <int NCH>
 __device__ __forceinline__ void label4_chains(const int *par, const int *F, int64_t fbase, int n, int (&root)[NCH], int (&lab)[NCH], bool &bad)
 {
     const int n1 = n - 1;
-    int viol = 0;
+    int cut = 0;
     bool more = true;
     while (more) {
         int nx[NCH];
 #pragma unroll
-        for (int q = 0; q < NCH; ++q) nx[q] = root[q] >= 0 ? par[min(root[q] & (UF_NS - 1), n1)] : -1;
+        for (int q = 0; q < NCH; ++q) {
+            const unsigned px = (unsigned)(root[q] & (INT_MIN | (UF_NS - 1)));  // the node's pixel (no chain: above every pixel)
+            nx[q] = px <= (unsigned)n1 ? par[min(px, (unsigned)n1)] : -1;      // a node outside the frame -- or no chain -- reads -1
+        }
         int differ = 0;
 #pragma unroll
         for (int q = 0; q < NCH; ++q) {
-            viol |= root[q] - nx[q];                               // sign bit: an entry above its node (both < 2^31; no chain: 0)
-            nx[q] = (int)min((unsigned)nx[q], (unsigned)root[q]);  // ... which ends the chain where it stands
-            differ |= nx[q] ^ root[q];
-            root[q] = nx[q];
+            const int t = (int)min((unsigned)nx[q], (unsigned)root[q]);  // an entry above its node, or negative, ends the chain
+            cut |= nx[q] ^ t;                                             // ... and is remembered (no chain: -1 ^ -1 = 0)
+            differ |= t ^ root[q];
+            root[q] = t;
         }
         more = differ != 0;
     }
-    bad = bad || viol < 0;
+    bad = bad || cut != 0;
     const int seeds_end = min(UF_NS, n);  // (a root is a seed pixel of the frame -- anything else is not to be trusted)
 #pragma unroll
     for (int q = 0; q < NCH; ++q)
@@ -1322,13 +1329,22 @@ __global__ void __launch_bounds__(256, PCSEG_LABEL4_OCC) ws_uf_label4_kernel(con
             if (x == lead[q]) { x_root = root[q]; x_lab = lab[q]; }
             else if (x == lead2[q]) { x_root = root2[q]; x_lab = lab2[q]; }
             else {  // (third: a quad with three different entries)
-                // fenced like the chains: clamped index, an entry above its node ends the walk
-                int t;
-                while ((t = (int)min((unsigned)par[min(x & (UF_NS - 1), (int)n - 1)], (unsigned)x)) != x) x = t;
+                // fenced like the chains: clamped index, a node outside the frame reads as -1, an entry above its node or a
+                // negative one ends the walk and breaks the frame (x >= 0 throughout: the min keeps it there)
+                int t, cut = 0;
+                for (;;) {
+                    const int px = x & (UF_NS - 1), e = par[min(px, (int)n - 1)] | (((int)n - 1 - px) >> 31);
+                    t = (int)min((unsigned)e, (unsigned)x);
+                    cut |= e ^ t;
+                    if (t == x) break;
+                    x = t;
+                }
+                broken = broken || cut != 0;
                 x_root = x;
-                x_lab = (x >= 0 && x < min(UF_NS, (int)n)) ? F[fbase + x] : 0;
+                x_lab = x < (int)n ? F[fbase + x] : 0;
             }
-            if (x_root < 0 || x_root >= UF_NS) continue;  // no labelled pixel in the component (or a chain that broke its fence)
+            // no labelled pixel in the component (x_root >= UF_NS), or a chain that broke its fence: never an index into bad / F
+            if ((unsigned)x_root >= (unsigned)n) continue;
             if (!seed) {
                 fv[j] = x_lab;
                 wrote = true;
@@ -1340,6 +1356,58 @@ __global__ void __launch_bounds__(256, PCSEG_LABEL4_OCC) ws_uf_label4_kernel(con
         if (wrote) *reinterpret_cast<int4 *>(F + fbase + i) = make_int4(fv[0], fv[1], fv[2], fv[3]);
     }
     if (broken) exact_flags[b] = 1;  // a walk left its fence (vwalk_ok): recomputed by the exact flood / reported
+}
+
+// ---- test-only hook (PCSEG_WS_POISON_*, pcseg.h): overwrite root entries of the parent image between two passes of the label
+// assignment, to show that every walk over it is fenced.  Never launched unless the caller sets one of those mode bits.
+// One lane per frame scans the frame serially in raster order (the test frames are small).  A target is a ROOT (its entry is
+// its own virtual index) that some OTHER reachable pixel names directly, so that the next pass has to walk through it; the
+// first four distinct ones in raster order of the naming pixel are taken.  seam: only naming pixels next to a union-find tile
+// seam (UF_TH rows / UF_TW columns) with a minimum-neighbour link across it count -- the border pass walks from exactly
+// those.  active (may be null): the naming pixel and the root both lie in active 64 x 64 tiles.  What is written depends on
+// the frame index (b % 6): 0 nothing (control frame), 1 2000000000 (past the frame and above UF_NS), 2 -1, 3 INT_MIN, 4 the
+// targets in pairs point at each other's virtual index (a two-cycle, one of the two entries a forward pointer), 5 H * W + 5
+// (past the frame, below UF_NS).
+__global__ void __launch_bounds__(64) ws_poison_kernel(const int *__restrict__ frame_list, const uint8_t *__restrict__ minmask,
+                                                       const uint8_t *__restrict__ active, int *__restrict__ parent, int B, int H,
+                                                       int W, int tilesX, int tilesY, bool seam)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (frame_list ? frame_list[-1] : B)) return;
+    const int b = frame_list ? frame_list[i] : i, kind = b % 6;
+    if (kind == 0) return;
+    const int n = H * W;
+    int *par = parent + (int64_t)b * n;
+    const uint8_t *mm = minmask + (int64_t)b * n;
+    int tgt[4], nt = 0;
+    for (int p = 0; p < n && nt < 4; ++p) {
+        const int r = p / W, c = p % W;
+        const int v = par[p];
+        if (v < 0 || !ws_active(active, b, r, c, tilesX, tilesY)) continue;
+        const int m = v & (UF_NS - 1);
+        if (m >= n || m == p || par[m] != v || !ws_active(active, b, m / W, m % W, tilesX, tilesY)) continue;
+        if (seam) {
+            const bool up = r % UF_TH == 0 && r > 0 && ((mm[p] & 1) || (mm[p - W] & 8));
+            const bool down = r % UF_TH == UF_TH - 1 && r + 1 < H && ((mm[p] & 8) || (mm[p + W] & 1));
+            const bool left = c % UF_TW == 0 && c > 0 && ((mm[p] & 2) || (mm[p - 1] & 4));
+            const bool right = c % UF_TW == UF_TW - 1 && c + 1 < W && ((mm[p] & 4) || (mm[p + 1] & 2));
+            if (!(up || down || left || right)) continue;
+        }
+        bool seen = false;
+        for (int k = 0; k < nt; ++k) seen = seen || tgt[k] == v;
+        if (!seen) tgt[nt++] = v;
+    }
+    for (int k = 0; k < nt; ++k) {
+        int v = n + 5;
+        if (kind == 1) v = 2000000000;
+        else if (kind == 2) v = -1;
+        else if (kind == 3) v = INT_MIN;
+        else if (kind == 4) {
+            if ((k ^ 1) >= nt) break;  // (an odd target out stays a root)
+            v = tgt[k ^ 1];
+        }
+        par[tgt[k] & (UF_NS - 1)] = v;
+    }
 }
 
 // (3) proof check: every neighbour whose key equals the minimum neighbour key carries the pixel's label
@@ -2034,7 +2102,10 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
                          int32_t *tie_flags, int B, int H, int W, int mode, void *workspace, size_t workspace_bytes,
                          pcseg_stream_t stream)
 {
-    PCSEG_REQUIRE(img && markers && mask && out && workspace && check_shape(B, H, W) && mode >= 0 && (mode & 3) <= 2 && mode < 8, "bad arguments");
+    const int poison = mode & (PCSEG_WS_POISON_BORDER | PCSEG_WS_POISON_LABEL | PCSEG_WS_POISON_LEVEL2);  // test-only (ws_poison_kernel)
+    PCSEG_REQUIRE(img && markers && mask && out && workspace && check_shape(B, H, W) && mode >= 0 && (mode & 3) <= 2 && mode < 64 &&
+                      (poison & (poison - 1)) == 0 && !(poison && (mode & 3) == 1),
+                  "bad arguments");
     const bool verify = (mode & 4) != 0;  // also run the explicit per-pixel proof check (implied by the component test)
     mode &= 3;
     PCSEG_REQUIRE(frame_stride == 0 || frame_stride >= (int64_t)H * W, "frame_stride smaller than a frame");
@@ -2139,6 +2210,13 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
         // label assignment = union-find over "minimum-key neighbour" links.  A component holding two marker ids flags
         // its frame, stays unlabelled and (first level) marks its tiles active for the next level.
         const WsTileList tiles{tile_list, tilesX * tilesY, tilesX};
+        auto poison_at = [&](int stage, const int *flist, const uint8_t *act) -> int {
+            if (poison != stage) return PCSEG_OK;
+            PCSEG_LAUNCH(ws_poison_kernel, dim3((B + 63) / 64), dim3(64), 0, s, flist, (const uint8_t *)uf_mask, act, uf_parent, B, H, W,
+                         tilesX, tilesY, stage == PCSEG_WS_POISON_BORDER);
+            PCSEG_CHECK_LAUNCH();
+            return PCSEG_OK;
+        };
         auto assign_labels = [&](auto *keys, const int *flist, const uint8_t *act, int *out_flags, bool first_level) -> int {
             using KeyT = std::remove_const_t<std::remove_pointer_t<decltype(keys)>>;
             const int span = ws_frame_span(flist, B);  // frame dimension of the grids (see ws_for_frames)
@@ -2151,11 +2229,13 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
                 PCSEG_LAUNCH((ws_uf_tile_kernel<KeyT, false>), ugrid, dim3(256), 0, s, tiles, (const KeyT *)keys, (const int *)out, act,
                              uf_parent, uf_mask, level_bad, H, W, tilesX, tilesY);
             PCSEG_CHECK_LAUNCH();
+            if (const int e = first_level ? poison_at(PCSEG_WS_POISON_BORDER, flist, act) : PCSEG_OK) return e;
             if (border_px > 0) {
                 PCSEG_LAUNCH(ws_uf_border_kernel, bgrid, dim3(256), 0, s, flist, (const uint8_t *)uf_mask, act, uf_parent, H, W,
                              tilesX, tilesY, flags2);
                 PCSEG_CHECK_LAUNCH();
             }
+            if (const int e = poison_at(first_level ? PCSEG_WS_POISON_LABEL : PCSEG_WS_POISON_LEVEL2, flist, act)) return e;
             if (first_level && act == nullptr && flist == nullptr && (W & 3) == 0 && (((uintptr_t)out | (uintptr_t)uf_parent) & 15) == 0 &&
                 ((uintptr_t)uf_mask & 3) == 0) {
                 PCSEG_LAUNCH(ws_uf_label4_kernel, dim3((unsigned)((npx + 1024 * LABEL4_Q - 1) / (1024 * LABEL4_Q)), B), dim3(256), 0, s,

@@ -295,6 +295,10 @@ def local_maxima(img, want_mask=True, want_markers=True):
     return is_max, markers, counts
 
 
+# test-only mode bits of pcseg_watershed4_f32 (include/pcseg.h): poison the union-find parent image before one pass
+WS_POISON_BORDER, WS_POISON_LABEL, WS_POISON_LEVEL2 = 8, 16, 32
+
+
 def watershed(img, markers, mask, mode=0):
     """skimage.segmentation.watershed(img, markers, mask=mask) (refine_boundaries.py:73).
 
