@@ -356,6 +356,28 @@ int pcseg_table_write(const pcseg_table_inputs *in, double *rois, double *cells,
 int pcseg_cell_distances(const double *cells, int64_t n_rows, int ncol, const uint8_t *class_slot, double raster, double size,
                          double *dist, int B, const void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
 
+/* ---- goal 3 of refine_boundaries.py:8-12 (per-strain nearest neighbours and pair distances), batched: points in
+ * frame-contiguous order -- xy device float64 (n, 2), slot device int32 (n) in 0..K-1 (any other value: the point takes
+ * part in nothing and gets NaN / -1), id device int32 (n), frame_offsets device int64 (B + 1), K <= 4, n < 2^24.
+ *   dist  device float64 (n, K): for point i and slot t, sqrt(min d2) / scale over the OTHER points j of slot t in i's
+ *         frame (excluded by index: a duplicate position gives 0); d2 = dx*dx + dy*dy, each product and the sum rounded
+ *         on their own (no FMA; pcseg_cell_distances is compiled to fma(dx, dx, dy*dy), up to 1 ulp apart); NaN when there is no candidate
+ *   nn_id device int32 (n, K): id of that neighbour, the smallest id among equal minimal d2; -1 when there is none
+ *   pair_hist device int64 (B, K (K + 1) / 2, m + 2), rows in (slot_a <= slot_b) order: [n_pairs, bin_0 .. bin_m-1, over]
+ *         over the unordered pairs of the frame, bin k = edges[k] <= d < edges[k + 1], over = d >= edges[m], so that
+ *         bins + over = n_pairs = n_a (n_a - 1) / 2 or n_a n_b.  edges: HOST float64 (n_edges = m + 1, 2..1025),
+ *         edges[0] == 0, strictly increasing; edges == NULL, n_edges == 0, pair_hist == NULL: no histogram.
+ * pcseg_neighbours_pack_cells: the points of the dense `cells` table pcseg_table_write has just filled -- xy =
+ * (centroid_col + 1, centroid_row + 1), slot = class_slot[class] (a HOST array, 255 -> -1), id = label -- and the
+ * frames' offsets (B + 1); `table_workspace` is the one pcseg_table_layout / pcseg_table_write used. */
+size_t pcseg_neighbours_workspace_bytes(int64_t n_points, int B, int K, int n_edges);
+int pcseg_point_neighbours(const double *xy, const int32_t *slot, const int32_t *id, const int64_t *frame_offsets, int64_t n_points,
+                           int B, int K, double scale, const double *edges, int n_edges, double *dist, int32_t *nn_id,
+                           int64_t *pair_hist, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_neighbours_pack_cells(const double *cells, int ncol, const uint8_t *class_slot, int B, const void *table_workspace,
+                                size_t table_workspace_bytes, double *xy, int32_t *slot, int32_t *id, int64_t *frame_offsets,
+                                pcseg_stream_t stream);
+
 /* ---- X1 (north_star extension; refine_boundaries.py:22 imports skimage.filters and never calls it): the library
  * SURVEY.md 8a names is the oracle -- skimage.filters.threshold_otsu(float32 image, nbins=256), pinned by
  * tests/golden/extensions.npz.  pcseg_otsu_f32: threshold[b] (device float64 (B,), the value is the float32 bin

@@ -71,6 +71,9 @@ SIGNATURES = {
     "pcseg_table_layout": (c_int, [_P, _P, _P, c_size_t, _P]),
     "pcseg_table_write": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "pcseg_cell_distances": (c_int, [_P, c_int64, _I, _P, c_double, c_double, _P, _I, _P, c_size_t, _P]),
+    "pcseg_neighbours_workspace_bytes": (c_size_t, [c_int64, _I, _I, _I]),
+    "pcseg_point_neighbours": (c_int, [_P, _P, _P, _P, c_int64, _I, _I, c_double, _P, _I, _P, _P, _P, _P, c_size_t, _P]),
+    "pcseg_neighbours_pack_cells": (c_int, [_P, _I, _P, _I, _P, c_size_t, _P, _P, _P, _P, _P]),
     "pcseg_otsu_hist_f32": (c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "pcseg_otsu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "pcseg_morph3x3": (c_int, [_P, _P, _I, _I, _I, _I, _P]),

@@ -537,10 +537,14 @@ def classify_regions(stats, cls_out, counts, tables):
     return out
 
 
-def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0):
+def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
+                 n_types=0, pair_edges=None):
     """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device).  ``distance_slots``: the
     class value -> type slot table (uint8[256] numpy); with it the result carries ``cell_dist`` (one value per row of
-    ``cells``, NaN = no entry) of pcseg_cell_distances."""
+    ``cells``, NaN = no entry) of pcseg_cell_distances.  ``neighbour_slots`` (the same kind of table) with ``n_types``
+    slots: the result also carries ``cell_nn`` = (dist, nn_id, pair_hist) of :func:`point_neighbours` over the rows of
+    ``cells`` (packed on the device by pcseg_neighbours_pack_cells), at the scale of ``cell_dist``; ``pair_hist`` is
+    None unless ``pair_edges`` is given."""
     lib = _lib.load()
     B, cap = res["stats"].shape[0], res["stats"].shape[1]
     dev = res["stats"].device
@@ -609,7 +613,53 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
         _lib.check(lib.pcseg_cell_distances(_ptr(cells), n_cell, cells.shape[1], ctypes.c_void_p(distance_slots.ctypes.data),
                                             float(raster), 512.0, _ptr(dist), B, _ptr(ws), nbytes, _stream()), "cell_distances")
         out["cell_dist"] = dist[:n_cell]
+    if neighbour_slots is not None:
+        xy = torch.empty((n_cell + 1, 2), dtype=torch.float64, device=dev)
+        slot = torch.empty((n_cell + 1,), dtype=torch.int32, device=dev)
+        ids = torch.empty((n_cell + 1,), dtype=torch.int32, device=dev)
+        foff = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+        _lib.check(lib.pcseg_neighbours_pack_cells(_ptr(cells), cells.shape[1], ctypes.c_void_p(neighbour_slots.ctypes.data), B,
+                                                   _ptr(ws), nbytes, _ptr(xy), _ptr(slot), _ptr(ids), _ptr(foff), _stream()),
+                   "neighbours_pack_cells")
+        out["cell_nn"] = point_neighbours(xy[:n_cell], slot[:n_cell], ids[:n_cell], foff, n_types, 512.0 / float(raster),
+                                          pair_edges)
     return out
+
+
+def point_neighbours(xy, slot, ids, frame_offsets, K, scale, edges=None):
+    """Per-type nearest neighbours and pair-distance histograms, frame by frame (refine_boundaries.py:8-12, goal 3;
+    csrc/neighbours.hip).  ``xy`` (n, 2) float64, ``slot`` (n,) int32 in 0..K-1, ``ids`` (n,) int32 and
+    ``frame_offsets`` (B + 1,) int64 CUDA tensors, points of a frame contiguous.  Returns ``(dist, nn_id, pair_hist)``:
+    (n, K) float64 distances ``sqrt(d2) / scale`` to the nearest OTHER point of each slot in the same frame (NaN: none),
+    (n, K) int32 ids of those points (smallest id on ties, -1: none), and with ``edges`` (m + 1 increasing values from
+    0) the (B, K (K + 1) / 2, m + 2) int64 histogram ``[n_pairs, bin_0 .. bin_m-1, over]`` of the unordered pairs of
+    every slot pair ``a <= b`` (bin k: ``edges[k] <= d < edges[k + 1]``), else None."""
+    xy = _req(xy, torch.float64, 2)
+    slot = _req(slot, torch.int32, 1)
+    ids = _req(ids, torch.int32, 1)
+    frame_offsets = _req(frame_offsets, torch.int64, 1)
+    n, B, K = xy.shape[0], frame_offsets.shape[0] - 1, int(K)
+    if xy.shape[1] != 2 or slot.shape[0] != n or ids.shape[0] != n:
+        raise ValueError("xy must be (n, 2) with n slots and ids")
+    import numpy as np
+    e = None if edges is None else np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))  # checked by the library
+    dev = xy.device
+    dist = torch.empty((n + 1, K), dtype=torch.float64, device=dev)  # (a spare row: never a null pointer)
+    nn_id = torch.empty((n + 1, K), dtype=torch.int32, device=dev)
+    P = K * (K + 1) // 2
+    hist = None
+    if e is not None:
+        hist = torch.empty((max(B, 1), P, max(e.shape[0] + 1, 1)), dtype=torch.int64, device=dev)
+    if B < 1:
+        return dist[:n], nn_id[:n], (hist[:0] if hist is not None else None)
+    lib = _lib.load()
+    n_edges = 0 if e is None else int(e.shape[0])
+    nbytes = lib.pcseg_neighbours_workspace_bytes(n, B, K, n_edges)
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.pcseg_point_neighbours(_ptr(xy), _ptr(slot), _ptr(ids), _ptr(frame_offsets), n, B, K, float(scale),
+                                          ctypes.c_void_p(e.ctypes.data) if e is not None else ctypes.c_void_p(0), n_edges,
+                                          _ptr(dist), _ptr(nn_id), _ptr(hist), _ptr(ws), nbytes, _stream()), "point_neighbours")
+    return dist[:n], nn_id[:n], hist
 
 
 def remove_overlapping(dapi, other, threshold):

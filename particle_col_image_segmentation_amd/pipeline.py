@@ -498,12 +498,13 @@ class FramePipeline:
         _, _, res["ws_sums"], _ = ops.region_reduce(res["ws_labels"], res["n_markers"], planes=stack, cap=cap)
 
     # ------------------------------------------------------------------ table output
-    def table_columns(self, C, ratios=RATIOS_5):
+    def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None):
         """Column names of every table of :meth:`tables` (known without any data: ranks that own no frame of a
-        dataset still agree on the schema, see ``distributed.run_sharded``)."""
+        dataset still agree on the schema, see ``distributed.run_sharded``).  ``neighbours`` / ``pair_edges`` add the
+        ``neighbours`` / ``pair_hist`` tables of :meth:`tables_device`."""
         tb = self.tables_
         rn = [r[0] for r in ratios]
-        return {
+        cols = {
             "cells": ["frame", "label", "class", "kind", "area", "centroid_row", "centroid_col", "min_row", "min_col",
                       "max_row1", "max_col1", "cells", "group", "group_combined"] + ["S%d" % k for k in range(C)] + rn,
             "rois": ["frame", "label", "area", "centroid_row", "centroid_col"] + ["S%d" % k for k in range(C)] + rn,
@@ -513,15 +514,30 @@ class FramePipeline:
             "groups": ["frame", "slot", "group", "area", "centroid_row", "centroid_col", "min_row", "min_col",
                        "max_row1", "max_col1", "members"],
         }
+        if neighbours:
+            cols["neighbours"] = (["frame", "label", "slot"] + ["nn_um_%s" % n for n in tb.slot_names]
+                                  + ["nn_label_%s" % n for n in tb.slot_names])
+        if pair_edges is not None:
+            cols["pair_hist"] = (["frame", "slot_a", "slot_b", "n_pairs"] + ["bin_%d" % k for k in range(len(pair_edges) - 1)]
+                                 + ["over"])
+        return cols
 
-    def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0):
+    def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0, neighbours=False,
+                      pair_edges=None):
         """The batch as dense row tables, assembled ON THE DEVICE (``csrc/tables.hip``): float64 CUDA tensors ``rois``,
         ``cells``, ``groups`` and ``frames_rec`` (one row per frame: frame id + the int64 record of
         ``pcseg_table_write``, see include/pcseg.h).  One small device-to-host copy (three row totals) sizes the
         outputs; nothing else leaves the GPU, so the tables can go straight into the all-gather.  ``distances``: also the
         nearest-other-type table of BASELINE config 5 (.m:260-268) as ``distances`` = ``[frame, label, distance]`` -- one
         batched launch over the cell rows of every frame (rows of type slot 0, then of slot 1, inside each frame); always
-        present (empty unless requested) so that every rank gathers the same set of tables."""
+        present (empty unless requested) so that every rank gathers the same set of tables.
+
+        ``neighbours``: also ``neighbours`` = ``[frame, label, slot, nn_um_<type>.., nn_label_<type>..]``, one row per row
+        of ``cells`` in its order: the distance (same scale as ``distances``) to the nearest OTHER row of every cell type
+        of the frame, NaN / -1 when there is none, and its label (refine_boundaries.py:8-12, goal 3).  ``pair_edges``
+        (m + 1 increasing values from 0, in um): also ``pair_hist`` = ``[frame, slot_a, slot_b, n_pairs, bin_0..
+        bin_m-1, over]``, K (K + 1) / 2 rows per frame (slot_a <= slot_b, all-zero rows included): the pairs of rows of
+        the two types whose distance d lies in ``[edges[k], edges[k + 1])``, and those at ``d >= edges[m]``."""
         res.synchronize()
         B, C, H, W = res["shape"]
         dev = res["stats"].device
@@ -540,10 +556,17 @@ class FramePipeline:
                 fid = torch.tensor(ids, dtype=torch.int64).to(dev)
             groups = (res.get("groups") or {}) if self.merged else {}
             dt = ops.build_tables(res, groups, fid, C, ratios, check=check,  # raises what BatchResult.check() raises
-                                  distance_slots=self.tables_.slot if distances else None, raster=raster)
+                                  distance_slots=self.tables_.slot if distances else None, raster=raster,
+                                  neighbour_slots=self.tables_.slot if neighbours or pair_edges is not None else None,
+                                  n_types=len(self.tables_.slot_names), pair_edges=pair_edges)
             dt["frames_rec"] = torch.cat([fid[:, None].to(torch.float64), dt.pop("frames").to(torch.float64)], dim=1)
             del dt["frame_ids"]
             dt["distances"] = self._distance_rows(dt["cells"], dt.pop("cell_dist", None))
+            nn = dt.pop("cell_nn", None)
+            if neighbours:
+                dt["neighbours"] = self._neighbour_rows(dt["cells"], nn[0], nn[1])
+            if pair_edges is not None:
+                dt["pair_hist"] = self._pair_rows(fid, nn[2])
             if res._slot is not None:  # graph mode: the lane may overwrite this result once the tables are out
                 res._check_alive()
                 res._slot.release = torch.cuda.Event()
@@ -569,20 +592,38 @@ class FramePipeline:
         order = torch.sort(pos * 2 + slot, stable=True)[1]
         return torch.stack([rows[order, 0], rows[order, 1], cell_dist[keep][order]], dim=1)
 
-    def empty_device_tables(self, C, ratios=RATIOS_5, device=None):
-        """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset)."""
-        cols = self.table_columns(C, ratios)
-        mk = lambda n: torch.zeros((0, n), dtype=torch.float64, device=device)
-        return {"rois": mk(len(cols["rois"])), "cells": mk(len(cols["cells"])), "groups": mk(len(cols["groups"])),
-                "frames_rec": mk(18), "distances": mk(3)}
+    def _neighbour_rows(self, cells, dist, nn_id):
+        """``[frame, label, slot, nn_um_<type>.., nn_label_<type>..]`` for every row of ``cells``."""
+        lut = torch.from_numpy(self.tables_.slot.astype("int64")).to(cells.device)
+        slot = lut[cells[:, 2].to(torch.int64)].to(torch.float64)
+        return torch.cat([cells[:, :2], slot[:, None], dist, nn_id.to(torch.float64)], dim=1)
 
-    def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0):
+    def _pair_rows(self, fid, hist):
+        """``[frame, slot_a, slot_b, n_pairs, bins.., over]``: K (K + 1) / 2 rows per frame, slot pairs in (a <= b) order."""
+        B, P = hist.shape[0], hist.shape[1]
+        K = len(self.tables_.slot_names)
+        ab = torch.tensor([(a, b) for a in range(K) for b in range(a, K)], dtype=torch.float64, device=hist.device)
+        return torch.cat([fid.to(torch.float64)[:, None, None].expand(B, P, 1), ab[None].expand(B, P, 2),
+                          hist.to(torch.float64)], dim=2).reshape(B * P, -1)
+
+    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None):
+        """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset)."""
+        cols = self.table_columns(C, ratios, neighbours, pair_edges)
+        mk = lambda n: torch.zeros((0, n), dtype=torch.float64, device=device)
+        out = {"rois": mk(len(cols["rois"])), "cells": mk(len(cols["cells"])), "groups": mk(len(cols["groups"])),
+               "frames_rec": mk(18), "distances": mk(3)}
+        for k in ("neighbours", "pair_hist"):
+            if k in cols:
+                out[k] = mk(len(cols[k]))
+        return out
+
+    def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0, neighbours=False, pair_edges=None):
         """numpy tables from (downloaded or gathered) :meth:`tables_device` output: ``cells`` / ``rois`` / ``groups`` /
         ``distances`` as they are, ``frames`` after the two ``round(x, 5)`` of get_cell_counts_and_densities
         (tiff_analysis.py:1018-1038; Python's decimal rounding, a handful of numbers per frame).  Every table's width
         must be the one :meth:`table_columns` names for ``C`` planes and these ``ratios``."""
         host = _download(dt)
-        cols = self.table_columns(C, ratios)
+        cols = self.table_columns(C, ratios, neighbours, pair_edges)
         tb = self.tables_
         out = {k: host[k] for k in ("cells", "rois", "groups")}
         for k in out:
@@ -607,15 +648,23 @@ class FramePipeline:
         if distances and "distances" not in host:
             raise ValueError("host_tables(distances=True) needs tables made by tables_device(..., distances=True)")
         out["distances"] = host["distances"].reshape(-1, 3) if distances and "distances" in host else np.zeros((0, 3), np.float64)
+        for k in ("neighbours", "pair_hist"):
+            if k in cols:
+                if k not in host:
+                    raise ValueError("host_tables(%s) needs tables made by tables_device with it" % k)
+                out[k] = host[k].reshape(-1, len(cols[k]))
         for k, v in cols.items():
             out[k + "_columns"] = v
         return out
 
-    def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True):
+    def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, neighbours=False,
+               pair_edges=None):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per
         refined ROI), ``frames`` (one row per frame) and ``groups`` (one row per merged group): :meth:`tables_device`
         followed by :meth:`host_tables`.  ``check=False`` skips ``BatchResult.check`` (a caller that has looked at the
         flags itself, e.g. to keep the ROI rows of a batch in which the reference would have raised on one frame's
-        cluster statistics)."""
+        cluster statistics).  ``neighbours`` / ``pair_edges``: the ``neighbours`` / ``pair_hist`` tables of
+        :meth:`tables_device`."""
         C = res["shape"][1]
-        return self.host_tables(self.tables_device(res, frame_ids, ratios, check, distances, raster), C, ratios, distances, raster)
+        dt = self.tables_device(res, frame_ids, ratios, check, distances, raster, neighbours, pair_edges)
+        return self.host_tables(dt, C, ratios, distances, raster, neighbours, pair_edges)

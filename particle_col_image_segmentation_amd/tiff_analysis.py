@@ -195,6 +195,42 @@ def get_cell_positions_and_areas(z_slice, cell_types, merged=False):
     return cell_pos, cell_clusters, particle_area, merged_clusters
 
 
+def get_cell_neighbour_distances(cell_pos, px_to_um=PX_TO_UM_CONV, edges=None):
+    """Goal 3 of refine_boundaries.py:8-12 for one frame, on the regions of ``cell_pos`` (strain -> regions, as
+    get_cell_positions_and_areas returns it): per strain a dict with ``labels`` (the regions' labels in list order),
+    ``same_um`` / ``same_label`` (distance in um to the nearest OTHER region of the same strain and its label) and
+    ``other_um`` / ``other_label`` (other strain -> the same for that strain); NaN / -1 where there is no such region.
+    Distances are between raw centroids, ``sqrt(drow^2 + dcol^2) / px_to_um``.  With ``edges`` (increasing, from 0, in
+    um) the pair histogram comes back as well: ``(per_strain, pair_hist)``, ``pair_hist[(a, b)]`` (strain names in
+    ``cell_pos`` order, ``a`` before or equal to ``b``) = ``{"n_pairs", "bins", "over"}``."""
+    names = list(cell_pos)
+    if len(names) > 4:
+        raise ValueError("at most 4 strains")
+    regs = [(t, r) for t, name in enumerate(names) for r in cell_pos[name]]
+    dev = _device()
+    xy = torch.tensor([[float(r.centroid[1]), float(r.centroid[0])] for _, r in regs], dtype=torch.float64).reshape(-1, 2).to(dev)
+    slot = torch.tensor([t for t, _ in regs], dtype=torch.int32).to(dev)
+    ids = torch.tensor([int(r.label) for _, r in regs], dtype=torch.int32).to(dev)
+    foff = torch.tensor([0, len(regs)], dtype=torch.int64).to(dev)
+    K = max(len(names), 1)
+    dist, nn_id, hist = ops.point_neighbours(xy, slot, ids, foff, K, px_to_um, edges)
+    dist, nn_id = dist.cpu().numpy(), nn_id.cpu().numpy()
+    out, row = {}, 0
+    for t, name in enumerate(names):
+        n = len(cell_pos[name])
+        d, i = dist[row:row + n], nn_id[row:row + n]
+        out[name] = {"labels": ids[row:row + n].cpu().numpy(), "same_um": d[:, t], "same_label": i[:, t],
+                     "other_um": {o: d[:, u] for u, o in enumerate(names) if u != t},
+                     "other_label": {o: i[:, u] for u, o in enumerate(names) if u != t}}
+        row += n
+    if edges is None:
+        return out
+    h = hist[0].cpu().numpy()
+    pairs = [(a, b) for a in range(K) for b in range(a, K)]
+    return out, {(names[a], names[b]): {"n_pairs": int(h[p, 0]), "bins": h[p, 1:-1], "over": int(h[p, -1])}
+                 for p, (a, b) in enumerate(pairs) if b < len(names)}
+
+
 def _group_regions(dl_dev, stats_dev, og_cell_regions):
     """device grouping (pcseg_merge_groups) + host assembly of the reference's merged-region dicts (:850-872)."""
     n = len(og_cell_regions)
