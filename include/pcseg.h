@@ -378,6 +378,56 @@ int pcseg_neighbours_pack_cells(const double *cells, int ncol, const uint8_t *cl
                                 size_t table_workspace_bytes, double *xy, int32_t *slot, int32_t *id, int64_t *frame_offsets,
                                 pcseg_stream_t stream);
 
+/* ---- goal 2 of refine_boundaries.py:1-12 (refined ROIs related to the class-map components they split), batched.
+ * pcseg_label_parent: labels_a (class-map components) and labels_r (refined ROIs), device int32 (B, H, W), any width
+ * and alignment; counts_r device int32 (B).  ov(r, a) = #pixels with labels_r = r and labels_a = a, a >= 1 (pixels on
+ * a = 0 or r = 0 count for nothing); rows r = 1 .. min(counts_r[b], cap) (row r - 1 of the (B, cap) outputs; other rows
+ * 0), labels_r above that are skipped.
+ *   parent    device int32 (B, cap): the a maximising ov(r, a), the smallest on ties; 0 when there is none
+ *   parent_px device int32 (B, cap): ov(r, parent);  n_overlap device int32 (B, cap): #distinct a with ov(r, a) > 0
+ *   cls_r     device uint8 (B, cap), may be NULL: cls_a[b, parent - 1] (cls_a device uint8 (B, cap), may be NULL: 0)
+ *   overflow  device int32 (B): 1 when a parent label exceeds cap (its class is unknown; parent itself stays exact)
+ *   n_spilled device int32 (1), may be NULL: the rows with more than 16 distinct a (resolved by the exact bounding-box pass)
+ * stats_r (device int64 (B, cap, 8), may be NULL: the whole frame) gives the refined ROIs' bounding boxes in columns 3..6
+ * as pcseg_region_reduce writes them.  Exact and deterministic; nothing goes back to the host.
+ *
+ * pcseg_refined_layout / pcseg_refined_table_write: the refined tables from the struct below (device pointers, the
+ * pcseg_classify_regions outputs of the class-map components and of the refined ROIs, the latter run on (ws_stats, cls_r,
+ * n_markers)), asynchronous on `stream`:
+ *   refined    (n_rois, 11)  frame, label, parent, parent_px, n_overlap, class, kind, cells, area, centroid_row,
+ *                            centroid_col; one row per row of `rois`, in its order
+ *   resolution (n_cells, 5)  frame, label, children, resolved, cells_integrated; one row per row of `cells`, in its order.
+ *                            children = #refined ROIs of kind >= 1 whose parent is the row; resolved = cluster with >= 2
+ *                            children; cells_integrated = 1 (cell), sum of the children's cells (resolved), the row's
+ *                            own cells (residual cluster), -1 when a term it uses is -1
+ *   frames     (B, 2 + 5 n_slots)  frame, refined nan flag, then per slot: refined cells, refined clusters, resolved,
+ *                            residual, count_integrated (sum of cells_integrated over the slot's rows, -1 if one is -1)
+ *   xy / slot / id / frame_offsets (all or none): the refined rows of kind >= 1 as pcseg_point_neighbours points --
+ *                            (centroid_col + 1, centroid_row + 1), slot_r, label -- and their frames' offsets (B + 1).
+ * pcseg_refined_layout's totals (device int64[2]) = {points, frames with parent_overflow set}; `table_workspace` is the
+ * one pcseg_table_layout / pcseg_table_write used (the row offsets of `rois` and `cells`). */
+typedef struct pcseg_refined_inputs {
+    int32_t B, cap, n_slots;
+    const int64_t *frame_ids;                                                                    /* (B) */
+    const int32_t *counts; const uint8_t *kind; const uint8_t *slot_of; const int32_t *cells;   /* class-map components */
+    const int32_t *n_markers; const int64_t *ws_stats;                                           /* refined ROIs */
+    const int32_t *parent; const int32_t *parent_px; const int32_t *n_overlap; const uint8_t *cls_r;  /* pcseg_label_parent */
+    const uint8_t *kind_r; const uint8_t *slot_r; const int32_t *cells_r; const int64_t *type_stats_r;
+    const int32_t *nan_flag_r;                                                 /* pcseg_classify_regions on the refined ROIs */
+    const int32_t *parent_overflow;                                            /* (B) overflow of pcseg_label_parent, may be NULL */
+} pcseg_refined_inputs;
+size_t pcseg_label_parent_workspace_bytes(int B, int H, int W, int cap);
+int pcseg_label_parent(const int32_t *labels_a, const int32_t *labels_r, const int32_t *counts_r, const int64_t *stats_r,
+                       const uint8_t *cls_a, int32_t *parent, int32_t *parent_px, int32_t *n_overlap, uint8_t *cls_r,
+                       int32_t *overflow, int32_t *n_spilled, int B, int H, int W, int cap, void *workspace,
+                       size_t workspace_bytes, pcseg_stream_t stream);
+size_t pcseg_refined_workspace_bytes(int B, int cap);
+int pcseg_refined_layout(const pcseg_refined_inputs *in, int64_t *totals, void *workspace, size_t workspace_bytes,
+                         pcseg_stream_t stream);
+int pcseg_refined_table_write(const pcseg_refined_inputs *in, const void *table_workspace, size_t table_workspace_bytes,
+                              double *refined, double *resolution, double *frames, double *xy, int32_t *slot, int32_t *id,
+                              int64_t *frame_offsets, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+
 /* ---- X1 (north_star extension; refine_boundaries.py:22 imports skimage.filters and never calls it): the library
  * SURVEY.md 8a names is the oracle -- skimage.filters.threshold_otsu(float32 image, nbins=256), pinned by
  * tests/golden/extensions.npz.  pcseg_otsu_f32: threshold[b] (device float64 (B,), the value is the float32 bin

@@ -74,6 +74,11 @@ SIGNATURES = {
     "pcseg_neighbours_workspace_bytes": (c_size_t, [c_int64, _I, _I, _I]),
     "pcseg_point_neighbours": (c_int, [_P, _P, _P, _P, c_int64, _I, _I, c_double, _P, _I, _P, _P, _P, _P, c_size_t, _P]),
     "pcseg_neighbours_pack_cells": (c_int, [_P, _I, _P, _I, _P, c_size_t, _P, _P, _P, _P, _P]),
+    "pcseg_label_parent_workspace_bytes": (c_size_t, [_I, _I, _I, _I]),
+    "pcseg_label_parent": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, c_size_t, _P]),
+    "pcseg_refined_workspace_bytes": (c_size_t, [_I, _I]),
+    "pcseg_refined_layout": (c_int, [_P, _P, _P, c_size_t, _P]),
+    "pcseg_refined_table_write": (c_int, [_P, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "pcseg_otsu_hist_f32": (c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "pcseg_otsu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "pcseg_morph3x3": (c_int, [_P, _P, _I, _I, _I, _I, _P]),
@@ -92,6 +97,18 @@ class TableInputs(ctypes.Structure):
                 ("n_markers", _P), ("ws_stats", _P), ("ws_sums", _P),
                 ("ratio_num", ctypes.c_int32 * 8), ("ratio_den", (ctypes.c_int32 * 4) * 8),
                 ("overflow", _P), ("ws_overflow", _P), ("nan_flag", _P)]
+
+
+class RefinedInputs(ctypes.Structure):
+    """struct pcseg_refined_inputs of include/pcseg.h, field for field."""
+    _fields_ = [("B", ctypes.c_int32), ("cap", ctypes.c_int32), ("n_slots", ctypes.c_int32),
+                ("frame_ids", _P),
+                ("counts", _P), ("kind", _P), ("slot_of", _P), ("cells", _P),
+                ("n_markers", _P), ("ws_stats", _P),
+                ("parent", _P), ("parent_px", _P), ("n_overlap", _P), ("cls_r", _P),
+                ("kind_r", _P), ("slot_r", _P), ("cells_r", _P), ("type_stats_r", _P),
+                ("nan_flag_r", _P),
+                ("parent_overflow", _P)]
 
 
 def load():

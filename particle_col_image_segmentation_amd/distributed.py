@@ -86,7 +86,8 @@ def all_gather_table(table, group=None, sort_cols=(0, 1), presorted=False, chunk
 TABLE_KEYS = ("cells", "rois", "frames", "groups", "distances")
 # key columns per table.  `distances`: frame only -- a frame lives on one rank and the sort is stable, so the rows of a
 # frame keep the order their rank made them in (type slot 0 first, then slot 1), with any number of ranks
-_SORT_COLS = {"frames": (0,), "frames_rec": (0,), "groups": (0, 1, 2), "distances": (0,), "pair_hist": (0, 1, 2)}
+_SORT_COLS = {"frames": (0,), "frames_rec": (0,), "groups": (0, 1, 2), "distances": (0,), "pair_hist": (0, 1, 2),
+              "refined_pair_hist": (0, 1, 2)}
 
 
 def gather_tables(tables, device=None, group=None, presorted=False, chunk_bytes=None):
@@ -183,8 +184,8 @@ def run_sharded(n_frames, make_batch, pipe, batch=64, group=None, device=None, p
     the host epilogue (``pipe.host_tables``) then runs on the gathered rows.  A rank that owns no frame
     (``n_frames < world``) contributes ``pipe.empty_device_tables``, so that every rank enters the same collectives with
     the same column counts.  The plane count comes from the data (the first batch a rank makes; ranks agree on it with one
-    all-reduce), ``planes`` only overrides it.  ``table_kwargs`` (ratios, distances, raster, neighbours, pair_edges) go to
-    ``tables_device`` and ``host_tables``, each only when the caller gives it.
+    all-reduce), ``planes`` only overrides it.  ``table_kwargs`` (ratios, distances, raster, neighbours, pair_edges,
+    refined) go to ``tables_device`` and ``host_tables``, each only when the caller gives it.
 
     ``force_gather``: one rank normally streams its rows to pinned host memory batch by batch (``_HostRows``: there is
     nothing to gather); with this switch it takes the route every rank of a larger world takes -- device tables
@@ -198,7 +199,8 @@ def run_sharded(n_frames, make_batch, pipe, batch=64, group=None, device=None, p
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     mine = shard_frames(n_frames, rank, world)
-    ratio_kw = {k: table_kwargs[k] for k in ("ratios", "distances", "raster", "neighbours", "pair_edges") if k in table_kwargs}
+    ratio_kw = {k: table_kwargs[k] for k in ("ratios", "distances", "raster", "neighbours", "pair_edges", "refined")
+                if k in table_kwargs}
     parts = []
     n_batches = (len(mine) + batch - 1) // batch
     host_rows = None  # one rank: the rows go to the host as the batches finish (see _HostRows)
@@ -243,8 +245,8 @@ def run_sharded(n_frames, make_batch, pipe, batch=64, group=None, device=None, p
     if parts:
         merged = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
     else:
-        merged = pipe.empty_device_tables(planes, device=device, **{k: ratio_kw[k] for k in ("ratios", "neighbours", "pair_edges")
-                                                                    if k in ratio_kw})
+        merged = pipe.empty_device_tables(planes, device=device, **{k: ratio_kw[k] for k in ("ratios", "neighbours", "pair_edges",
+                                                                                        "refined") if k in ratio_kw})
     # (a rank's own rows come out of the batches in frame order, labels ascending: with one rank that IS the gathered
     # order and the sort is skipped)
     gathered = gather_tables(merged, device=device, group=group, presorted=world == 1 and mine == sorted(mine),

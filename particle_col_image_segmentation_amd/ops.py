@@ -538,13 +538,15 @@ def classify_regions(stats, cls_out, counts, tables):
 
 
 def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
-                 n_types=0, pair_edges=None):
+                 n_types=0, pair_edges=None, refined=None, refined_points=False):
     """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device).  ``distance_slots``: the
     class value -> type slot table (uint8[256] numpy); with it the result carries ``cell_dist`` (one value per row of
     ``cells``, NaN = no entry) of pcseg_cell_distances.  ``neighbour_slots`` (the same kind of table) with ``n_types``
     slots: the result also carries ``cell_nn`` = (dist, nn_id, pair_hist) of :func:`point_neighbours` over the rows of
     ``cells`` (packed on the device by pcseg_neighbours_pack_cells), at the scale of ``cell_dist``; ``pair_hist`` is
-    None unless ``pair_edges`` is given."""
+    None unless ``pair_edges`` is given.  ``refined`` (a :class:`ClassTables`): also the outputs of
+    :func:`refined_tables`, and with ``refined_points`` ``refined_nn`` = :func:`point_neighbours` over the refined
+    rows of kind >= 1 (same scale and edges as ``cell_nn``) followed by the points (xy, slot, ids, frame_offsets)."""
     lib = _lib.load()
     B, cap = res["stats"].shape[0], res["stats"].shape[1]
     dev = res["stats"].device
@@ -623,6 +625,132 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
                    "neighbours_pack_cells")
         out["cell_nn"] = point_neighbours(xy[:n_cell], slot[:n_cell], ids[:n_cell], foff, n_types, 512.0 / float(raster),
                                           pair_edges)
+    if refined is not None:
+        out.update(refined_tables(res, frame_ids, refined, ws, (n_roi, n_cell), check=check, points=refined_points))
+        if refined_points:
+            pts = out.pop("points")
+            out["refined_nn"] = point_neighbours(*pts, n_types, 512.0 / float(raster), pair_edges) + pts
+    return out
+
+
+def label_parent(labels_a, labels_r, counts_r, cls_a=None, cap=None, stats_r=None, return_spilled=False):
+    """The class-map component every refined ROI lies in (refine_boundaries.py:1-12, goal 2; csrc/refined.hip).
+    ``labels_a`` / ``labels_r`` (B, H, W) int32 CUDA tensors (A: class-map components, R: refined ROIs), ``counts_r``
+    (B,) int32: rows r = 1 .. min(counts_r[b], cap).  With ov(r, a) = #pixels where R = r and A = a >= 1, returns
+    ``(parent, parent_px, n_overlap, cls_r, overflow)``: (B, cap) int32 argmax_a ov(r, a) (the smallest a on ties, 0:
+    none), (B, cap) int32 ov(r, parent), (B, cap) int32 #distinct a with ov > 0, (B, cap) uint8 ``cls_a[b, parent - 1]``
+    (0 without ``cls_a`` or parent) and (B,) int32 set where a parent label exceeds ``cap`` (default: ``cls_a``'s
+    second dimension, else max(counts_r)).  ``stats_r`` ((B, cap, 8) int64 of :func:`region_reduce` over ``labels_r``)
+    bounds the exact pass that ROIs over more than sixteen components take; without it that pass scans the frame.
+    ``return_spilled``: also the number of such ROIs, a (1,) int32 tensor."""
+    la = _req(labels_a, torch.int32, 3)
+    lr = _req(labels_r, torch.int32, 3)
+    counts_r = _req(counts_r, torch.int32, 1)
+    B, H, W = lr.shape
+    if tuple(la.shape) != (B, H, W) or counts_r.shape[0] != B:
+        raise ValueError("labels_a, labels_r and counts_r must agree on (B, H, W)")
+    if cls_a is not None:
+        cls_a = _req(cls_a, torch.uint8, 2)
+        if cap is None:
+            cap = cls_a.shape[1]
+        if tuple(cls_a.shape) != (B, cap):
+            raise ValueError("cls_a must be (B, cap)")
+    if cap is None:
+        cap = max(int(counts_r.max().item()) if B else 1, 1)
+    cap = int(cap)
+    if stats_r is not None:
+        stats_r = _req(stats_r, torch.int64, 3)
+        if tuple(stats_r.shape) != (B, cap, 8):
+            raise ValueError("stats_r must be (B, cap, 8)")
+    dev = lr.device
+    parent = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    parent_px = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    n_overlap = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    cls_r = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    overflow = torch.empty((B,), dtype=torch.int32, device=dev)
+    n_spilled = torch.empty((1,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.pcseg_label_parent_workspace_bytes(B, H, W, cap)
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.pcseg_label_parent(_ptr(la), _ptr(lr), _ptr(counts_r), _ptr(stats_r), _ptr(cls_a), _ptr(parent),
+                                      _ptr(parent_px), _ptr(n_overlap), _ptr(cls_r), _ptr(overflow), _ptr(n_spilled), B, H, W,
+                                      cap, _ptr(ws), nbytes, _stream()), "label_parent")
+    out = (parent, parent_px, n_overlap, cls_r, overflow)
+    return out + (n_spilled,) if return_spilled else out
+
+
+def refined_inputs(res, lp, rc, frame_ids, n_slots):
+    """struct pcseg_refined_inputs of one batch: ``res`` (the pipeline's result), ``lp`` (:func:`label_parent` on it),
+    ``rc`` (:func:`classify_regions` on the refined ROIs).  Returns (struct, tensors the pointers refer to)."""
+    B, cap = res["stats"].shape[0], res["stats"].shape[1]
+    ri = _lib.RefinedInputs()
+    ri.B, ri.cap, ri.n_slots = B, cap, int(n_slots)
+    keep = []
+
+    def ptr(t, dtype, shape):
+        t = _req(t, dtype, len(shape))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("refined input of shape %s, expected %s" % (tuple(t.shape), tuple(shape)))
+        keep.append(t)
+        return t.data_ptr()
+
+    parent, parent_px, n_overlap, cls_r, overflow = lp[:5]
+    ri.frame_ids = ptr(frame_ids, torch.int64, (B,))
+    ri.counts = ptr(res["counts"], torch.int32, (B,))
+    ri.kind = ptr(res["kind"], torch.uint8, (B, cap))
+    ri.slot_of = ptr(res["slot_of"], torch.uint8, (B, cap))
+    ri.cells = ptr(res["cells"], torch.int32, (B, cap))
+    ri.n_markers = ptr(res["n_markers"], torch.int32, (B,))
+    ri.ws_stats = ptr(res["ws_stats"], torch.int64, (B, cap, 8))
+    ri.parent = ptr(parent, torch.int32, (B, cap))
+    ri.parent_px = ptr(parent_px, torch.int32, (B, cap))
+    ri.n_overlap = ptr(n_overlap, torch.int32, (B, cap))
+    ri.cls_r = ptr(cls_r, torch.uint8, (B, cap))
+    ri.kind_r = ptr(rc["kind"], torch.uint8, (B, cap))
+    ri.slot_r = ptr(rc["slot_of"], torch.uint8, (B, cap))
+    ri.cells_r = ptr(rc["cells"], torch.int32, (B, cap))
+    ri.type_stats_r = ptr(rc["type_stats"], torch.int64, (B, 4, 4))
+    ri.nan_flag_r = ptr(rc["nan_flag"], torch.int32, (B,))
+    ri.parent_overflow = ptr(overflow, torch.int32, (B,))
+    return ri, keep
+
+
+def refined_tables(res, frame_ids, tables, table_ws, table_rows, check=False, points=False):
+    """Goal 2 of refine_boundaries.py:1-12 for one batch whose dense tables :func:`build_tables` has just written
+    (``table_ws``: its workspace, ``table_rows``: its (rois, cells) row counts): :func:`label_parent` of the refined
+    ROIs, :func:`classify_regions` on them with their parent's class, then ``refined`` / ``cell_resolution`` /
+    ``frames_refined`` (float64, see include/pcseg.h).  ``points``: also ``points`` = (xy, slot, ids, frame_offsets) of
+    the refined rows of kind >= 1 for :func:`point_neighbours`.  ``check``: raise where a parent label exceeds cap."""
+    B, cap = res["stats"].shape[0], res["stats"].shape[1]
+    dev = res["stats"].device
+    lp = label_parent(res["labels"], res["ws_labels"], res["n_markers"], cls_a=res["cls_out"], cap=cap, stats_r=res["ws_stats"])
+    rc = classify_regions(res["ws_stats"], lp[3], res["n_markers"], tables)
+    ri, keep = refined_inputs(res, lp, rc, frame_ids, len(tables.slot_names))
+    lib = _lib.load()
+    nbytes = lib.pcseg_refined_workspace_bytes(B, cap)
+    ws = _ws(nbytes, dev)
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.pcseg_refined_layout(ctypes.byref(ri), _ptr(totals), _ptr(ws), nbytes, _stream()), "refined_layout")
+    n_pts, n_over = (int(v) for v in totals.cpu())
+    if check and n_over:
+        raise RuntimeError("refined ROI parent label above the region table capacity: raise FramePipeline(cap=...)")
+    n_roi, n_cell = table_rows
+    K = len(tables.slot_names)
+    refined = torch.empty((n_roi + 1, 11), dtype=torch.float64, device=dev)
+    resolution = torch.empty((n_cell + 1, 5), dtype=torch.float64, device=dev)
+    frames = torch.empty((B, 2 + 5 * K), dtype=torch.float64, device=dev)
+    pts = [None] * 4
+    if points:
+        pts = [torch.empty((n_pts + 1, 2), dtype=torch.float64, device=dev), torch.empty((n_pts + 1,), dtype=torch.int32, device=dev),
+               torch.empty((n_pts + 1,), dtype=torch.int32, device=dev), torch.empty((B + 1,), dtype=torch.int64, device=dev)]
+    _lib.check(lib.pcseg_refined_table_write(ctypes.byref(ri), _ptr(table_ws), table_ws.numel(), _ptr(refined), _ptr(resolution),
+                                             _ptr(frames), *[_ptr(t) for t in pts], _ptr(ws), nbytes, _stream()),
+               "refined_table_write")
+    out = {"refined": refined[:n_roi], "cell_resolution": resolution[:n_cell], "frames_refined": frames,
+           "parent_overflow": lp[4], "refined_nan_flag": rc["nan_flag"]}
+    if points:
+        out["points"] = (pts[0][:n_pts], pts[1][:n_pts], pts[2][:n_pts], pts[3])
+    del keep
     return out
 
 

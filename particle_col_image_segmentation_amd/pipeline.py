@@ -164,6 +164,11 @@ def _lanes_for(device, lanes):
     return _LANES[key]
 
 
+# optional tables of tables_device, in schema order (table_columns names each only when its keyword asks for it)
+_EXTRA_TABLES = ("neighbours", "pair_hist", "refined", "cell_resolution", "frames_refined", "refined_neighbours",
+                 "refined_pair_hist")
+
+
 def _download(tables):
     """device tensors -> numpy through PINNED staging buffers (torch caches them): all copies are enqueued, then one
     wait.  A pageable ``.cpu()`` of the ~100 MB ROI table of a dataset costs more than the kernels of a batch."""
@@ -498,10 +503,12 @@ class FramePipeline:
         _, _, res["ws_sums"], _ = ops.region_reduce(res["ws_labels"], res["n_markers"], planes=stack, cap=cap)
 
     # ------------------------------------------------------------------ table output
-    def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None):
+    def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None, refined=False):
         """Column names of every table of :meth:`tables` (known without any data: ranks that own no frame of a
         dataset still agree on the schema, see ``distributed.run_sharded``).  ``neighbours`` / ``pair_edges`` add the
-        ``neighbours`` / ``pair_hist`` tables of :meth:`tables_device`."""
+        ``neighbours`` / ``pair_hist`` tables of :meth:`tables_device`, ``refined`` its ``refined`` /
+        ``cell_resolution`` / ``frames_refined`` tables (and with the other two ``refined_neighbours`` /
+        ``refined_pair_hist``)."""
         tb = self.tables_
         rn = [r[0] for r in ratios]
         cols = {
@@ -520,10 +527,21 @@ class FramePipeline:
         if pair_edges is not None:
             cols["pair_hist"] = (["frame", "slot_a", "slot_b", "n_pairs"] + ["bin_%d" % k for k in range(len(pair_edges) - 1)]
                                  + ["over"])
+        if refined:
+            cols["refined"] = ["frame", "label", "parent", "parent_px", "n_overlap", "class", "kind", "cells", "area",
+                               "centroid_row", "centroid_col"]
+            cols["cell_resolution"] = ["frame", "label", "children", "resolved", "cells_integrated"]
+            cols["frames_refined"] = (["frame", "refined_nan_flag"]
+                                      + [c % n for n in tb.slot_names for c in ("%s_refined_cells", "%s_refined_clusters",
+                                                                                "%s_resolved", "%s_residual",
+                                                                                "%s_count_integrated")])
+            for k in ("neighbours", "pair_hist"):
+                if k in cols:
+                    cols["refined_" + k] = list(cols[k])
         return cols
 
     def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0, neighbours=False,
-                      pair_edges=None):
+                      pair_edges=None, refined=False):
         """The batch as dense row tables, assembled ON THE DEVICE (``csrc/tables.hip``): float64 CUDA tensors ``rois``,
         ``cells``, ``groups`` and ``frames_rec`` (one row per frame: frame id + the int64 record of
         ``pcseg_table_write``, see include/pcseg.h).  One small device-to-host copy (three row totals) sizes the
@@ -537,7 +555,14 @@ class FramePipeline:
         of the frame, NaN / -1 when there is none, and its label (refine_boundaries.py:8-12, goal 3).  ``pair_edges``
         (m + 1 increasing values from 0, in um): also ``pair_hist`` = ``[frame, slot_a, slot_b, n_pairs, bin_0..
         bin_m-1, over]``, K (K + 1) / 2 rows per frame (slot_a <= slot_b, all-zero rows included): the pairs of rows of
-        the two types whose distance d lies in ``[edges[k], edges[k + 1])``, and those at ``d >= edges[m]``."""
+        the two types whose distance d lies in ``[edges[k], edges[k + 1])``, and those at ``d >= edges[m]``.
+
+        ``refined`` (refine_boundaries.py:1-12, goal 2): the refined ROIs classified by their parent class-map
+        component (``ops.refined_tables``).  ``refined`` = one row per row of ``rois`` (its parent, overlap, class, kind
+        and cells), ``cell_resolution`` = one row per row of ``cells`` (children, resolved, cells_integrated) and
+        ``frames_refined`` = one row per frame (per-type refined counts, resolved / residual clusters,
+        count_integrated); with ``neighbours`` / ``pair_edges`` also ``refined_neighbours`` / ``refined_pair_hist``,
+        the same tables over the refined rows of kind >= 1.  ``check`` also raises where a parent label exceeds cap."""
         res.synchronize()
         B, C, H, W = res["shape"]
         dev = res["stats"].device
@@ -558,7 +583,9 @@ class FramePipeline:
             dt = ops.build_tables(res, groups, fid, C, ratios, check=check,  # raises what BatchResult.check() raises
                                   distance_slots=self.tables_.slot if distances else None, raster=raster,
                                   neighbour_slots=self.tables_.slot if neighbours or pair_edges is not None else None,
-                                  n_types=len(self.tables_.slot_names), pair_edges=pair_edges)
+                                  n_types=len(self.tables_.slot_names), pair_edges=pair_edges,
+                                  refined=self.tables_ if refined else None,
+                                  refined_points=refined and (neighbours or pair_edges is not None))
             dt["frames_rec"] = torch.cat([fid[:, None].to(torch.float64), dt.pop("frames").to(torch.float64)], dim=1)
             del dt["frame_ids"]
             dt["distances"] = self._distance_rows(dt["cells"], dt.pop("cell_dist", None))
@@ -567,6 +594,17 @@ class FramePipeline:
                 dt["neighbours"] = self._neighbour_rows(dt["cells"], nn[0], nn[1])
             if pair_edges is not None:
                 dt["pair_hist"] = self._pair_rows(fid, nn[2])
+            for k in ("parent_overflow", "refined_nan_flag"):
+                dt.pop(k, None)
+            rn = dt.pop("refined_nn", None)
+            if rn is not None:
+                dist, nn_id, hist, _, slot, ids, foff = rn
+                if neighbours:
+                    frame = torch.repeat_interleave(fid.to(torch.float64), foff[1:] - foff[:-1], output_size=ids.shape[0])
+                    dt["refined_neighbours"] = torch.cat([frame[:, None], ids.to(torch.float64)[:, None],
+                                                          slot.to(torch.float64)[:, None], dist, nn_id.to(torch.float64)], dim=1)
+                if pair_edges is not None:
+                    dt["refined_pair_hist"] = self._pair_rows(fid, hist)
             if res._slot is not None:  # graph mode: the lane may overwrite this result once the tables are out
                 res._check_alive()
                 res._slot.release = torch.cuda.Event()
@@ -606,24 +644,25 @@ class FramePipeline:
         return torch.cat([fid.to(torch.float64)[:, None, None].expand(B, P, 1), ab[None].expand(B, P, 2),
                           hist.to(torch.float64)], dim=2).reshape(B * P, -1)
 
-    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None):
+    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None, refined=False):
         """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset)."""
-        cols = self.table_columns(C, ratios, neighbours, pair_edges)
+        cols = self.table_columns(C, ratios, neighbours, pair_edges, refined)
         mk = lambda n: torch.zeros((0, n), dtype=torch.float64, device=device)
         out = {"rois": mk(len(cols["rois"])), "cells": mk(len(cols["cells"])), "groups": mk(len(cols["groups"])),
                "frames_rec": mk(18), "distances": mk(3)}
-        for k in ("neighbours", "pair_hist"):
+        for k in _EXTRA_TABLES:
             if k in cols:
                 out[k] = mk(len(cols[k]))
         return out
 
-    def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0, neighbours=False, pair_edges=None):
+    def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0, neighbours=False, pair_edges=None,
+                    refined=False):
         """numpy tables from (downloaded or gathered) :meth:`tables_device` output: ``cells`` / ``rois`` / ``groups`` /
         ``distances`` as they are, ``frames`` after the two ``round(x, 5)`` of get_cell_counts_and_densities
         (tiff_analysis.py:1018-1038; Python's decimal rounding, a handful of numbers per frame).  Every table's width
         must be the one :meth:`table_columns` names for ``C`` planes and these ``ratios``."""
         host = _download(dt)
-        cols = self.table_columns(C, ratios, neighbours, pair_edges)
+        cols = self.table_columns(C, ratios, neighbours, pair_edges, refined)
         tb = self.tables_
         out = {k: host[k] for k in ("cells", "rois", "groups")}
         for k in out:
@@ -648,7 +687,7 @@ class FramePipeline:
         if distances and "distances" not in host:
             raise ValueError("host_tables(distances=True) needs tables made by tables_device(..., distances=True)")
         out["distances"] = host["distances"].reshape(-1, 3) if distances and "distances" in host else np.zeros((0, 3), np.float64)
-        for k in ("neighbours", "pair_hist"):
+        for k in _EXTRA_TABLES:
             if k in cols:
                 if k not in host:
                     raise ValueError("host_tables(%s) needs tables made by tables_device with it" % k)
@@ -658,13 +697,13 @@ class FramePipeline:
         return out
 
     def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, neighbours=False,
-               pair_edges=None):
+               pair_edges=None, refined=False):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per
         refined ROI), ``frames`` (one row per frame) and ``groups`` (one row per merged group): :meth:`tables_device`
         followed by :meth:`host_tables`.  ``check=False`` skips ``BatchResult.check`` (a caller that has looked at the
         flags itself, e.g. to keep the ROI rows of a batch in which the reference would have raised on one frame's
-        cluster statistics).  ``neighbours`` / ``pair_edges``: the ``neighbours`` / ``pair_hist`` tables of
-        :meth:`tables_device`."""
+        cluster statistics).  ``neighbours`` / ``pair_edges`` / ``refined``: the ``neighbours`` / ``pair_hist`` and
+        refined tables of :meth:`tables_device`."""
         C = res["shape"][1]
-        dt = self.tables_device(res, frame_ids, ratios, check, distances, raster, neighbours, pair_edges)
-        return self.host_tables(dt, C, ratios, distances, raster, neighbours, pair_edges)
+        dt = self.tables_device(res, frame_ids, ratios, check, distances, raster, neighbours, pair_edges, refined)
+        return self.host_tables(dt, C, ratios, distances, raster, neighbours, pair_edges, refined)

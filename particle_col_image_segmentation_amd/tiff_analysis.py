@@ -79,9 +79,10 @@ class _LabelImage:
 class Region:
     """Duck type of skimage RegionProperties restricted to what the reference touches:
     .label (:270), .area (:275, 769-781, 855, 1031, 1055), ["area"] (:1033), .centroid (:406, 844, 1054),
-    .bbox (:860-863, 912), .coords[0] (:1042), dynamically added .cells (:781, 1029, 1063)."""
+    .bbox (:860-863, 912), .coords[0] (:1042), dynamically added .cells (:781, 1029, 1063); refined regions
+    (get_refined_cell_positions_and_areas) also carry .parent, the class-map label they lie in."""
 
-    __slots__ = ("label", "area", "centroid", "bbox", "first", "sum_row", "sum_col", "cells", "_im")
+    __slots__ = ("label", "area", "centroid", "bbox", "first", "sum_row", "sum_col", "cells", "parent", "_im")
 
     def __init__(self, label_id, row, width, label_image=None):
         self.label = int(label_id)
@@ -193,6 +194,88 @@ def get_cell_positions_and_areas(z_slice, cell_types, merged=False):
     if merged:
         merged_clusters, _ = _clusters_from_distances(z_dev, stats, cell_pos, cell_clusters, cell_types, False)
     return cell_pos, cell_clusters, particle_area, merged_clusters
+
+
+def get_refined_cell_positions_and_areas(z_slice, boundary_map, cell_types, threshold=0.5):
+    """Goal 2 of refine_boundaries.py:1-12 for one frame: the watershed-refined ROIs of ``boundary_map`` (the chain of
+    refine_boundaries.refine_boundaries) classified by the class-map component of ``z_slice`` they share the most
+    pixels with (``ops.label_parent``), with the reference's own per-region loop (tiff_analysis.py:754-781) run on
+    them.  Returns ``(cell_pos, cell_clusters, particle_area, resolution)``: refined ``Region``s per strain (keyed in
+    first-appearance order, with ``.parent`` and, for clusters, ``.cells``), the class map's particle area, and per
+    strain ``{"resolved": [class-map labels of clusters split into >= 2 refined cells / clusters], "residual":
+    [(label, cells) of the other clusters], "count_integrated": cells + sum of the integrated cluster counts}``
+    (-1 where a term is -1).  Raises ValueError as the reference loop does where a strain has refined clusters but no
+    refined cell."""
+    from .refine_boundaries import refine_boundaries_batch
+    z_dev, _ = _to_dev_u8(z_slice)
+    bm = boundary_map if isinstance(boundary_map, torch.Tensor) else torch.from_numpy(
+        np.ascontiguousarray(np.asarray(boundary_map, dtype=np.float32)))
+    if bm.dim() != 2 or tuple(bm.shape) != tuple(z_dev.shape[1:]):
+        raise ValueError("boundary_map must be a 2-D map of the class map's shape %s, got %s"
+                         % (tuple(z_dev.shape[1:]), tuple(bm.shape)))
+    bm = bm.to(device=z_dev.device, dtype=torch.float32).contiguous()[None]
+    regions, classes, holder, (stats, cls_out, counts) = _regions_of(z_dev)
+    for value in np.unique(classes):
+        cell_types[int(value)]  # KeyError for an unmapped class value, as at :756
+    tables = ops.ClassTables(cell_types, CELL_TYPES, MIN_CELL_AREA, MIN_CLUSTER_AREA)
+    verdict = ops.classify_regions(stats, cls_out, counts, tables)
+    st = refine_boundaries_batch(bm, threshold)
+    ws_labels, n_markers = st["labels"], st["n_markers"]
+    n, m = len(regions), int(n_markers[0].item())
+    cap = max(n, m, 1)
+    cls_a = torch.zeros((1, cap), dtype=torch.uint8, device=z_dev.device)
+    cls_a[:, :n] = cls_out[:, :n]
+    ws_stats, _, _, _ = ops.region_reduce(ws_labels, n_markers, cap=cap)
+    parent, _, _, cls_r, _ = ops.label_parent(holder.dev[None], ws_labels, n_markers, cls_a=cls_a, cap=cap, stats_r=ws_stats)
+    rv = ops.classify_regions(ws_stats, cls_r, n_markers, tables)
+    if int(rv["nan_flag"][0].item()):
+        raise ValueError("cannot convert float NaN to integer")  # :776-781 on the refined regions
+    wst = ws_stats[0, :m].cpu().numpy()
+    r_kind = rv["kind"][0, :m].cpu().numpy()
+    r_slot = rv["slot_of"][0, :m].cpu().numpy()
+    r_cells = rv["cells"][0, :m].cpu().numpy()
+    r_parent = parent[0, :m].cpu().numpy()
+    first_region = rv["type_stats"][0, :, 3].cpu().numpy()
+    order = sorted((int(first_region[t]), t) for t in range(len(tables.slot_names)) if first_region[t] != 0x7FFFFFFF)
+    cell_pos = {tables.slot_names[t]: [] for _, t in order}
+    cell_clusters = {tables.slot_names[t]: [] for _, t in order}
+    r_holder = _LabelImage(ws_labels[0])
+    for i in np.nonzero(r_kind)[0]:
+        reg = Region(i + 1, wst[i], z_dev.shape[2], r_holder)
+        reg.parent = int(r_parent[i])
+        if r_kind[i] == 1:
+            cell_pos[tables.slot_names[r_slot[i]]].append(reg)
+        else:
+            reg.cells = int(r_cells[i])
+            cell_clusters[tables.slot_names[r_slot[i]]].append(reg)
+    # cluster resolution: a class-map cluster with >= 2 refined children is counted by its children
+    kind = verdict["kind"][0, :n].cpu().numpy()
+    slot = verdict["slot_of"][0, :n].cpu().numpy()
+    cells = verdict["cells"][0, :n].cpu().numpy()
+    live = (r_kind >= 1) & (r_parent >= 1) & (r_parent <= n)
+    children = np.bincount(r_parent[live] - 1, minlength=n)[:n]
+    child_sum = np.bincount(r_parent[live] - 1, weights=np.maximum(r_cells[live], 0), minlength=n)[:n].astype(np.int64)
+    child_neg = np.bincount(r_parent[live] - 1, weights=(r_cells[live] < 0), minlength=n)[:n] > 0
+    resolution = {}
+    for t, name in enumerate(tables.slot_names):
+        res = {"resolved": [], "residual": [], "count_integrated": 0}
+        neg = False
+        for a in np.nonzero((kind >= 1) & (slot == t))[0]:
+            if kind[a] == 1:
+                res["count_integrated"] += 1
+            elif children[a] >= 2:
+                res["resolved"].append(int(a + 1))
+                neg = neg or bool(child_neg[a])
+                res["count_integrated"] += int(child_sum[a])
+            else:
+                res["residual"].append((int(a + 1), int(cells[a])))
+                neg = neg or cells[a] < 0
+                res["count_integrated"] += int(cells[a])
+        if neg:
+            res["count_integrated"] = -1
+        if res["resolved"] or res["residual"] or res["count_integrated"]:
+            resolution[name] = res
+    return cell_pos, cell_clusters, int(verdict["particle_area"][0].item()), resolution
 
 
 def get_cell_neighbour_distances(cell_pos, px_to_um=PX_TO_UM_CONV, edges=None):
