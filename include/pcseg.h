@@ -304,7 +304,8 @@ int pcseg_classify_regions(const int64_t *stats, const uint8_t *cls_out, const i
                            int B, int cap, pcseg_stream_t stream);
 
 /* ---- C14: nearest distance from every point of a (na, 2) float64 set to a (nb, 2) set = min(pdist2(a, b), [], 2)
- * (.m:260-263 between the two ROI classes, .m:301-305 to the aggregate boundary); out_a: float64[na]. */
+ * (.m:260-263 between the two ROI classes, .m:301-305 to the aggregate boundary, one frame and one brute-force block at a
+ * time; the batched, pruned route to a mask's surface is pcseg_surface_points + pcseg_surface_distances); out_a: float64[na]. */
 int pcseg_nearest_dist_f64(const double *a, int na, const double *b, int nb, double *out_a, pcseg_stream_t stream);
 
 /* ---- C6: combine_cell_positions_and_clusters (tiff_analysis.py:252-287):
@@ -427,6 +428,62 @@ int pcseg_refined_layout(const pcseg_refined_inputs *in, int64_t *totals, void *
 int pcseg_refined_table_write(const pcseg_refined_inputs *in, const void *table_workspace, size_t table_workspace_bytes,
                               double *refined, double *resolution, double *frames, double *xy, int32_t *slot, int32_t *id,
                               int64_t *frame_offsets, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+
+/* ---- distance of every cell to the particle surface and colonisation profiles, batched
+ * (HCN_nanosims_rois_activity_distance_5iso_YG.m:271-309, data_dist_nearest_bound.csv).
+ * Surface S of the mask M = ((value_bits >> in) & 1): the pixels of M with a 4-neighbour outside M, pixels outside the
+ * image counting as outside M (the point set of bwboundaries).  Any width and alignment.
+ * pcseg_surface_points (no host read-back):
+ *   bits    device uint32 (B, H, ceil(W / 32)): S as bit words, bit j of word w of a row = column 32 w + j, 0 beyond W
+ *   counts  device int64 (B): #S per frame;  offsets device int64 (B + 1): their exclusive prefix, offsets[B] = total
+ *   area    device int64 (B), may be NULL: #M per frame
+ *   points  device int32 (points_cap, 2), may be NULL with points_cap = 0: (row, col) of S in raster order, frame by frame
+ *           (count -> scan -> write: the order never depends on scheduling); points beyond points_cap are not written
+ * pcseg_surface_distances: queries in frame-contiguous order -- rc device float64 (n, 2) = (row, col), 0-based,
+ * frame_offsets device int64 (B + 1), n < 2^31 -- against the bits.  d2(q, s) = fl(fl(dr*dr) + fl(dc*dc)) (no FMA),
+ *   dist    device float64 (n): sqrt(min d2) / scale;  nearest device int32 (n, 2): the surface point of minimal d2, the
+ *           smallest raster index row * W + col among equal d2;  NaN, -1, -1 for a frame without surface, and for a query
+ *           with a NaN coordinate or one beyond +-2^24
+ *   inside  device uint8 (n), may be NULL: mask != 0 at pixel (floor(row + 0.5), floor(col + 0.5)) (mask: device uint8
+ *           (B, H, W), may be NULL: 0), 0 outside the image and for a query without distance
+ *   counts  as pcseg_surface_points wrote them, may be NULL (a frame without surface is then searched in full)
+ *   hist    device int64 (B, 2, K, m + 2), with edges (HOST float64, n_edges = m + 1 in 2..1025, edges[0] == 0, strictly
+ *           increasing; needs slot device int32 (n), mask and K <= 4): per frame, side (0 outside, 1 inside) and slot
+ *           [n, bin_0 .. bin_m-1, over] over the queries that have a distance and a slot in 0..K-1, bin k = edges[k] <= d <
+ *           edges[k + 1], over = d >= edges[m], n = bins + over.  edges == NULL, n_edges == 0, hist == NULL: none
+ *   rows_visited device int32 (n), may be NULL: image rows whose words the search read (a measurement aid)
+ * The search is exact and pruned: one wave per query, rows outward from the query's row, a row skipped once
+ * fl(dr*dr) > best d2 (strictly), words walked left / right of the query column until a bit or the bound.
+ * Workspace of both: pcseg_surface_workspace_bytes(B, H, W).
+ * pcseg_surface_thresholds (HOST only, touches no device): out[k] = the smallest integer n >= 0 with
+ * sqrt((double)n) / scale >= edges[k] (INT64_MAX if none up to 2^53), so that for an integer squared distance D2
+ * edges[k] <= sqrt(D2) / scale  <=>  D2 >= out[k].
+ * pcseg_surface_shells: D2(p) = exact squared distance of every pixel to S (pcseg_edt_sq_u8 on the image that is 0 on S),
+ * shells device int64 (B, 2, m + 2) = per frame and side (mask at the pixel) [n_px, bin_0 .. bin_m-1, over] with the bins
+ * of pcseg_surface_thresholds; every pixel of a frame without surface is `over`.  B <= 65535.
+ * Workspace: pcseg_surface_shells_workspace_bytes(B, H, W).
+ * pcseg_surface_pack_cells: the queries of the dense `cells` table pcseg_table_write has just filled -- rc =
+ * (centroid_row, centroid_col) as the table prints them, slot = class_slot[class] (a HOST array, 255 -> -1), id = label --
+ * and the frames' offsets; `table_workspace` as for pcseg_neighbours_pack_cells.  pcseg_surface_pack_refined: rc of the
+ * refined points pcseg_refined_table_write packed (id = refined label, frame_offsets) = their centroids as the `refined`
+ * table prints them, from ws_stats device int64 (B, cap, 8). */
+size_t pcseg_surface_workspace_bytes(int B, int H, int W);
+int pcseg_surface_points(const uint8_t *in, uint64_t value_bits, uint32_t *bits, int64_t *counts, int64_t *offsets, int64_t *area,
+                         int32_t *points, int64_t points_cap, int B, int H, int W, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_surface_distances(const double *rc, const int32_t *slot, const int64_t *frame_offsets, int64_t n_points,
+                            const uint32_t *bits, const int64_t *counts, const uint8_t *mask, int B, int H, int W, double scale,
+                            const double *edges, int n_edges, int K, double *dist, int32_t *nearest, uint8_t *inside, int64_t *hist,
+                            int32_t *rows_visited, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_surface_thresholds(const double *edges, int n_edges, double scale, int64_t *out);
+size_t pcseg_surface_shells_workspace_bytes(int B, int H, int W);
+int pcseg_surface_shells(const uint32_t *bits, const int64_t *counts, const uint8_t *mask, int B, int H, int W, double scale,
+                         const double *edges, int n_edges, int64_t *shells, void *workspace, size_t workspace_bytes,
+                         pcseg_stream_t stream);
+int pcseg_surface_pack_cells(const double *cells, int ncol, const uint8_t *class_slot, int B, const void *table_workspace,
+                             size_t table_workspace_bytes, double *rc, int32_t *slot, int32_t *id, int64_t *frame_offsets,
+                             pcseg_stream_t stream);
+int pcseg_surface_pack_refined(const int64_t *ws_stats, int cap, const int32_t *id, const int64_t *frame_offsets, int64_t n_points,
+                               int B, double *rc, pcseg_stream_t stream);
 
 /* ---- X1 (north_star extension; refine_boundaries.py:22 imports skimage.filters and never calls it): the library
  * SURVEY.md 8a names is the oracle -- skimage.filters.threshold_otsu(float32 image, nbins=256), pinned by

@@ -354,7 +354,8 @@ __global__ void __launch_bounds__(256) nb_pack_cells_kernel(const double *__rest
 static double nb_dist_host(double d2, double scale) { return std::sqrt(d2) / scale; }
 
 // smallest non-negative double t with d(t) >= e (d is non-decreasing in d2): a bisection over the ordered bit patterns
-static double nb_threshold(double e, double scale)
+// (declared in common.h: surface.hip bins its query rows with the same thresholds)
+double nb_threshold(double e, double scale)
 {
     uint64_t lo = 0, hi = 0x7FF0000000000000ULL;  // d(+inf) = inf >= e
     auto val = [](uint64_t u) { double d; memcpy(&d, &u, 8); return d; };

@@ -538,7 +538,7 @@ def classify_regions(stats, cls_out, counts, tables):
 
 
 def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
-                 n_types=0, pair_edges=None, refined=None, refined_points=False):
+                 n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None):
     """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device).  ``distance_slots``: the
     class value -> type slot table (uint8[256] numpy); with it the result carries ``cell_dist`` (one value per row of
     ``cells``, NaN = no entry) of pcseg_cell_distances.  ``neighbour_slots`` (the same kind of table) with ``n_types``
@@ -546,7 +546,11 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
     ``cells`` (packed on the device by pcseg_neighbours_pack_cells), at the scale of ``cell_dist``; ``pair_hist`` is
     None unless ``pair_edges`` is given.  ``refined`` (a :class:`ClassTables`): also the outputs of
     :func:`refined_tables`, and with ``refined_points`` ``refined_nn`` = :func:`point_neighbours` over the refined
-    rows of kind >= 1 (same scale and edges as ``cell_nn``) followed by the points (xy, slot, ids, frame_offsets)."""
+    rows of kind >= 1 (same scale and edges as ``cell_nn``) followed by the points (xy, slot, ids, frame_offsets).
+    ``surface`` (a :class:`ClassTables`; .m:271-309): ``cell_sf`` = the dict of :func:`_surface_rows` over the rows of
+    ``cells`` against the surface of ``binary_fill_holes(res["recreated"] == Particle)``, at the scale of ``cell_dist``,
+    plus ``surface_px`` / ``filled_area`` (B,) and with ``surface_edges`` ``hist`` and ``shells``
+    (:func:`surface_shells`); with ``refined`` also ``refined_sf``, the same over the refined rows of kind >= 1."""
     lib = _lib.load()
     B, cap = res["stats"].shape[0], res["stats"].shape[1]
     dev = res["stats"].device
@@ -625,12 +629,42 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
                    "neighbours_pack_cells")
         out["cell_nn"] = point_neighbours(xy[:n_cell], slot[:n_cell], ids[:n_cell], foff, n_types, 512.0 / float(raster),
                                           pair_edges)
+    sf = None
+    if surface is not None:
+        K, scale = max(len(surface.slot_names), 1), 512.0 / float(raster)
+        mask, sf = particle_surface(res["recreated"], surface.particle_value)
+        rc = torch.empty((n_cell + 1, 2), dtype=torch.float64, device=dev)
+        slot = torch.empty((n_cell + 1,), dtype=torch.int32, device=dev)
+        ids = torch.empty((n_cell + 1,), dtype=torch.int32, device=dev)
+        foff = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+        _lib.check(lib.pcseg_surface_pack_cells(_ptr(cells), cells.shape[1], ctypes.c_void_p(surface.slot.ctypes.data), B, _ptr(ws),
+                                                nbytes, _ptr(rc), _ptr(slot), _ptr(ids), _ptr(foff), _stream()), "surface_pack_cells")
+        out["cell_sf"] = _surface_rows(rc[:n_cell], slot[:n_cell], ids[:n_cell], foff, sf, mask, scale, K, surface_edges)
+        out["cell_sf"].update(surface_px=sf["counts"], filled_area=sf["area"])
+        if surface_edges is not None:
+            out["cell_sf"]["shells"] = surface_shells(sf, mask, surface_edges, scale)
     if refined is not None:
-        out.update(refined_tables(res, frame_ids, refined, ws, (n_roi, n_cell), check=check, points=refined_points))
-        if refined_points:
+        want_points = refined_points or sf is not None
+        out.update(refined_tables(res, frame_ids, refined, ws, (n_roi, n_cell), check=check, points=want_points))
+        if want_points:
             pts = out.pop("points")
+        if refined_points:
             out["refined_nn"] = point_neighbours(*pts, n_types, 512.0 / float(raster), pair_edges) + pts
+        if sf is not None:
+            _, pslot, pids, pfoff = pts
+            n_pts = pids.shape[0]
+            rc = torch.empty((n_pts + 1, 2), dtype=torch.float64, device=dev)
+            _lib.check(lib.pcseg_surface_pack_refined(_ptr(_req(res["ws_stats"], torch.int64, 3)), cap, _ptr(pids), _ptr(pfoff), n_pts,
+                                                      B, _ptr(rc), _stream()), "surface_pack_refined")
+            out["refined_sf"] = _surface_rows(rc[:n_pts], pslot, pids, pfoff, sf, mask, scale, K, surface_edges)
     return out
+
+
+def _surface_rows(rc, slot, ids, foff, surface, mask, scale, K, edges):
+    """:func:`surface_distances` of packed query rows, with what a table of them needs: dict of ``dist``, ``nearest``,
+    ``inside``, ``hist`` (None without ``edges``), ``slot``, ``ids`` and ``frame_offsets``."""
+    dist, nearest, inside, hist = surface_distances(rc, foff, surface, scale, mask=mask, slot=slot, n_types=K, edges=edges)
+    return {"dist": dist, "nearest": nearest, "inside": inside, "hist": hist, "slot": slot, "ids": ids, "frame_offsets": foff}
 
 
 def label_parent(labels_a, labels_r, counts_r, cls_a=None, cap=None, stats_r=None, return_spilled=False):
@@ -788,6 +822,127 @@ def point_neighbours(xy, slot, ids, frame_offsets, K, scale, edges=None):
                                           ctypes.c_void_p(e.ctypes.data) if e is not None else ctypes.c_void_p(0), n_edges,
                                           _ptr(dist), _ptr(nn_id), _ptr(hist), _ptr(ws), nbytes, _stream()), "point_neighbours")
     return dist[:n], nn_id[:n], hist
+
+
+def _edges_arg(edges):
+    import numpy as np
+    e = None if edges is None else np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))  # checked by the library
+    return e, (ctypes.c_void_p(e.ctypes.data) if e is not None else ctypes.c_void_p(0)), (0 if e is None else int(e.shape[0]))
+
+
+def surface_points(x, value_bits, want_points=True):
+    """Surface of the mask ``(value_bits >> x) & 1`` of a (B, H, W) uint8 batch: its pixels with a 4-neighbour outside the
+    mask, outside the image counting as outside (the point set of bwboundaries, .m:271-292; csrc/surface.hip).  Returns a
+    dict: ``bits`` int32 (B, H, ceil(W / 32)) bit words (bit j of word w = column 32 w + j), ``counts`` int64 (B,),
+    ``offsets`` int64 (B + 1,), ``area`` int64 (B,) = mask pixels per frame, ``shape`` and, with ``want_points`` (one
+    host read of the total to size it), ``points`` int32 (n, 2) = (row, col) in raster order, frame by frame."""
+    x = _req(x, torch.uint8, 3)
+    B, H, W = x.shape
+    dev = x.device
+    lib = _lib.load()
+    out = {"bits": torch.empty((B, H, (W + 31) // 32), dtype=torch.int32, device=dev),
+           "counts": torch.empty((B,), dtype=torch.int64, device=dev),
+           "offsets": torch.empty((B + 1,), dtype=torch.int64, device=dev),
+           "area": torch.empty((B,), dtype=torch.int64, device=dev), "shape": (B, H, W)}
+    nbytes = lib.pcseg_surface_workspace_bytes(B, H, W)
+    ws = _ws(nbytes, dev)
+
+    def call(points, cap):
+        _lib.check(lib.pcseg_surface_points(_ptr(x), ctypes.c_uint64(int(value_bits)), _ptr(out["bits"]), _ptr(out["counts"]),
+                                            _ptr(out["offsets"]), _ptr(out["area"]), _ptr(points), cap, B, H, W, _ptr(ws), nbytes,
+                                            _stream()), "surface_points")
+
+    call(None, 0)
+    if want_points:
+        n = int(out["offsets"][B].item())
+        pts = torch.empty((n + 1, 2), dtype=torch.int32, device=dev)
+        call(pts, n)
+        out["points"] = pts[:n]
+    return out
+
+
+def surface_distances(points_rc, frame_offsets, surface, scale, mask=None, slot=None, n_types=0, edges=None, rows_visited=False):
+    """Distance of every query point to the surface of its frame (.m:271-309, without the script's (x, y) / (row, col)
+    mix; csrc/surface.hip, an exact pruned search, one wave per query).  ``points_rc`` (n, 2) float64 (row, col),
+    0-based, frame-contiguous, ``frame_offsets`` (B + 1,) int64, ``surface`` from :func:`surface_points`.  Returns
+    ``(dist, nearest, inside, hist)``: (n,) float64 ``sqrt(min d2) / scale`` with d2 = drow*drow + dcol*dcol (each
+    product and the sum rounded on their own), (n, 2) int32 surface pixel of minimal d2 (the smallest raster index on
+    ties), (n,) uint8 ``mask`` at pixel (floor(row + 0.5), floor(col + 0.5)) (0 without ``mask``); NaN, -1, -1, 0 in a
+    frame without surface.  With ``edges`` (m + 1 increasing values from 0; needs ``slot`` (n,) int32, ``n_types`` and
+    ``mask``): ``hist`` int64 (B, 2, n_types, m + 2) = per frame, side (0 outside, 1 inside) and slot ``[n, bin_0 ..
+    bin_m-1, over]``, else None.  ``rows_visited``: a fifth result, (n,) int32 image rows each search read."""
+    rc = _req(points_rc, torch.float64, 2)
+    foff = _req(frame_offsets, torch.int64, 1)
+    B, H, W = surface["shape"]
+    n = rc.shape[0]
+    if rc.shape[1] != 2 or foff.shape[0] != B + 1:
+        raise ValueError("points_rc must be (n, 2) and frame_offsets (B + 1,) for the surface's B frames")
+    dev = rc.device
+    if mask is not None:
+        mask = _req(mask, torch.uint8, 3)
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError("mask must have the surface's shape")
+    if slot is not None:
+        slot = _req(slot, torch.int32, 1)
+        if slot.shape[0] != n:
+            raise ValueError("slot must be (n,)")
+    e, e_ptr, n_edges = _edges_arg(edges)
+    K = int(n_types)
+    dist = torch.empty((n + 1,), dtype=torch.float64, device=dev)  # (a spare row: never a null pointer)
+    nearest = torch.empty((n + 1, 2), dtype=torch.int32, device=dev)
+    inside = torch.empty((n + 1,), dtype=torch.uint8, device=dev)
+    hist = torch.empty((B, 2, max(K, 1), n_edges + 1), dtype=torch.int64, device=dev) if e is not None else None
+    visited = torch.empty((n + 1,), dtype=torch.int32, device=dev) if rows_visited else None
+    lib = _lib.load()
+    nbytes = lib.pcseg_surface_workspace_bytes(B, H, W)
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.pcseg_surface_distances(_ptr(rc), _ptr(slot), _ptr(foff), n, _ptr(surface["bits"]), _ptr(surface["counts"]),
+                                           _ptr(mask), B, H, W, float(scale), e_ptr, n_edges, K, _ptr(dist), _ptr(nearest),
+                                           _ptr(inside), _ptr(hist), _ptr(visited), _ptr(ws), nbytes, _stream()), "surface_distances")
+    out = (dist[:n], nearest[:n], inside[:n], hist)
+    return out + (visited[:n],) if rows_visited else out
+
+
+def surface_thresholds(edges, scale):
+    """Host only: for every edge the smallest integer squared distance n with ``sqrt(n) / scale >= edge`` (numpy int64),
+    so that ``searchsorted(edges, sqrt(D2) / scale, side="right") - 1 == searchsorted(thresholds, D2, side="right") - 1``."""
+    import numpy as np
+    e, e_ptr, n_edges = _edges_arg(edges)
+    out = np.zeros(max(n_edges, 1), np.int64)
+    lib = _lib.load()
+    _lib.check(lib.pcseg_surface_thresholds(e_ptr, n_edges, float(scale), ctypes.c_void_p(out.ctypes.data)), "surface_thresholds")
+    return out[:n_edges]
+
+
+def surface_shells(surface, mask, edges, scale):
+    """Pixels of every frame by their distance to the surface (the denominators of a colonisation profile, .m:271-309):
+    int64 (B, 2, m + 2) = per frame and side (0 outside ``mask``, 1 inside) ``[n_px, bin_0 .. bin_m-1, over]``, bin k =
+    ``edges[k] <= sqrt(D2) / scale < edges[k + 1]`` with D2 the exact squared distance to the nearest surface pixel;
+    every pixel of a frame without surface is ``over``."""
+    B, H, W = surface["shape"]
+    mask = _req(mask, torch.uint8, 3)
+    if tuple(mask.shape) != (B, H, W):
+        raise ValueError("mask must have the surface's shape")
+    e, e_ptr, n_edges = _edges_arg(edges)
+    dev = mask.device
+    shells = torch.empty((B, 2, n_edges + 1), dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    nbytes = lib.pcseg_surface_shells_workspace_bytes(B, H, W)
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.pcseg_surface_shells(_ptr(surface["bits"]), _ptr(surface["counts"]), _ptr(mask), B, H, W, float(scale), e_ptr,
+                                        n_edges, _ptr(shells), _ptr(ws), nbytes, _stream()), "surface_shells")
+    return shells
+
+
+def particle_surface(recreated, particle_value):
+    """The surface mask of the tables: ``binary_fill_holes(recreated == particle_value)`` (an empty mask without a
+    particle class) and :func:`surface_points` of it (bit words only).  Returns (mask uint8 (B, H, W), surface)."""
+    recreated = _req(recreated, torch.uint8, 3)
+    if particle_value is None:
+        mask = torch.zeros_like(recreated)
+    else:
+        mask = fill_holes((recreated == int(particle_value)).view(torch.uint8))
+    return mask, surface_points(mask, 2, want_points=False)
 
 
 def remove_overlapping(dapi, other, threshold):

@@ -166,7 +166,8 @@ def _lanes_for(device, lanes):
 
 # optional tables of tables_device, in schema order (table_columns names each only when its keyword asks for it)
 _EXTRA_TABLES = ("neighbours", "pair_hist", "refined", "cell_resolution", "frames_refined", "refined_neighbours",
-                 "refined_pair_hist")
+                 "refined_pair_hist", "surface", "frames_surface", "surface_hist", "surface_shells", "refined_surface",
+                 "refined_surface_hist")
 
 
 def _download(tables):
@@ -503,12 +504,15 @@ class FramePipeline:
         _, _, res["ws_sums"], _ = ops.region_reduce(res["ws_labels"], res["n_markers"], planes=stack, cap=cap)
 
     # ------------------------------------------------------------------ table output
-    def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None, refined=False):
+    def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None, refined=False, surface=False,
+                      surface_edges=None):
         """Column names of every table of :meth:`tables` (known without any data: ranks that own no frame of a
         dataset still agree on the schema, see ``distributed.run_sharded``).  ``neighbours`` / ``pair_edges`` add the
         ``neighbours`` / ``pair_hist`` tables of :meth:`tables_device`, ``refined`` its ``refined`` /
         ``cell_resolution`` / ``frames_refined`` tables (and with the other two ``refined_neighbours`` /
-        ``refined_pair_hist``)."""
+        ``refined_pair_hist``), ``surface`` its ``surface`` / ``frames_surface`` tables, ``surface_edges`` its
+        ``surface_hist`` / ``surface_shells`` tables (and with ``refined`` ``refined_surface`` /
+        ``refined_surface_hist``)."""
         tb = self.tables_
         rn = [r[0] for r in ratios]
         cols = {
@@ -538,10 +542,21 @@ class FramePipeline:
             for k in ("neighbours", "pair_hist"):
                 if k in cols:
                     cols["refined_" + k] = list(cols[k])
+        if surface:
+            cols["surface"] = ["frame", "label", "slot", "inside", "surface_um", "nearest_row", "nearest_col"]
+            cols["frames_surface"] = ["frame", "surface_px", "filled_area"]
+        if surface_edges is not None:
+            bins = ["bin_%d" % k for k in range(len(surface_edges) - 1)] + ["over"]
+            cols["surface_hist"] = ["frame", "side", "slot", "n"] + bins
+            cols["surface_shells"] = ["frame", "side", "n_px"] + bins
+        if refined:
+            for k in ("surface", "surface_hist"):
+                if k in cols:
+                    cols["refined_" + k] = list(cols[k])
         return cols
 
     def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0, neighbours=False,
-                      pair_edges=None, refined=False):
+                      pair_edges=None, refined=False, surface=False, surface_edges=None):
         """The batch as dense row tables, assembled ON THE DEVICE (``csrc/tables.hip``): float64 CUDA tensors ``rois``,
         ``cells``, ``groups`` and ``frames_rec`` (one row per frame: frame id + the int64 record of
         ``pcseg_table_write``, see include/pcseg.h).  One small device-to-host copy (three row totals) sizes the
@@ -562,7 +577,21 @@ class FramePipeline:
         and cells), ``cell_resolution`` = one row per row of ``cells`` (children, resolved, cells_integrated) and
         ``frames_refined`` = one row per frame (per-type refined counts, resolved / residual clusters,
         count_integrated); with ``neighbours`` / ``pair_edges`` also ``refined_neighbours`` / ``refined_pair_hist``,
-        the same tables over the refined rows of kind >= 1.  ``check`` also raises where a parent label exceeds cap."""
+        the same tables over the refined rows of kind >= 1.  ``check`` also raises where a parent label exceeds cap.
+
+        ``surface`` (HCN_nanosims_rois_activity_distance_5iso_YG.m:271-309, the distance of every ROI to the aggregate
+        boundary): where the cells sit relative to the particle.  The surface mask is ``binary_fill_holes(recreated ==
+        Particle)``, its surface the mask pixels with a 4-neighbour outside it (or outside the image).  ``surface`` =
+        ``[frame, label, slot, inside, surface_um, nearest_row, nearest_col]``, one row per row of ``cells`` in its
+        order: whether the centroid's pixel lies in the mask, the distance (scale of ``distances``) from the centroid to
+        the nearest surface pixel and that pixel (the smallest raster index among equally near ones); NaN, -1, -1 and
+        inside 0 in a frame without particle.  ``frames_surface`` = ``[frame, surface_px, filled_area]``.
+        ``surface_edges`` (m + 1 increasing values from 0, in um): ``surface_hist`` = ``[frame, side, slot, n, bin_0..
+        bin_m-1, over]``, 2 K rows per frame in (side, slot) order (side 0 outside, 1 inside): the rows of ``surface`` by
+        distance, and ``surface_shells`` = ``[frame, side, n_px, bin_0.., over]``, 2 rows per frame: the frame's pixels
+        by their distance to the surface in the same bins -- ``surface_hist`` over ``surface_shells`` is the
+        colonisation profile.  With ``refined`` also ``refined_surface`` / ``refined_surface_hist``: the same over the
+        refined rows of kind >= 1, in the order of ``refined_neighbours``."""
         res.synchronize()
         B, C, H, W = res["shape"]
         dev = res["stats"].device
@@ -585,7 +614,9 @@ class FramePipeline:
                                   neighbour_slots=self.tables_.slot if neighbours or pair_edges is not None else None,
                                   n_types=len(self.tables_.slot_names), pair_edges=pair_edges,
                                   refined=self.tables_ if refined else None,
-                                  refined_points=refined and (neighbours or pair_edges is not None))
+                                  refined_points=refined and (neighbours or pair_edges is not None),
+                                  surface=self.tables_ if surface or surface_edges is not None else None,
+                                  surface_edges=surface_edges)
             dt["frames_rec"] = torch.cat([fid[:, None].to(torch.float64), dt.pop("frames").to(torch.float64)], dim=1)
             del dt["frame_ids"]
             dt["distances"] = self._distance_rows(dt["cells"], dt.pop("cell_dist", None))
@@ -605,6 +636,18 @@ class FramePipeline:
                                                           slot.to(torch.float64)[:, None], dist, nn_id.to(torch.float64)], dim=1)
                 if pair_edges is not None:
                     dt["refined_pair_hist"] = self._pair_rows(fid, hist)
+            csf, rsf = dt.pop("cell_sf", None), dt.pop("refined_sf", None)
+            for name, sf in (("surface", csf), ("refined_surface", rsf)):
+                if sf is None:
+                    continue
+                if surface:
+                    dt[name] = self._surface_rows(fid, sf)
+                if surface_edges is not None:
+                    dt[name + "_hist"] = self._side_rows(fid, sf["hist"])
+            if surface:
+                dt["frames_surface"] = torch.stack([fid, csf["surface_px"], csf["filled_area"]], dim=1).to(torch.float64)
+            if surface_edges is not None:
+                dt["surface_shells"] = self._side_rows(fid, csf["shells"])
             if res._slot is not None:  # graph mode: the lane may overwrite this result once the tables are out
                 res._check_alive()
                 res._slot.release = torch.cuda.Event()
@@ -644,9 +687,27 @@ class FramePipeline:
         return torch.cat([fid.to(torch.float64)[:, None, None].expand(B, P, 1), ab[None].expand(B, P, 2),
                           hist.to(torch.float64)], dim=2).reshape(B * P, -1)
 
-    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None, refined=False):
+    def _surface_rows(self, fid, sf):
+        """``[frame, label, slot, inside, surface_um, nearest_row, nearest_col]`` for every packed query row."""
+        foff, ids = sf["frame_offsets"], sf["ids"]
+        frame = torch.repeat_interleave(fid.to(torch.float64), foff[1:] - foff[:-1], output_size=ids.shape[0])
+        f64 = lambda t: t.to(torch.float64)
+        return torch.cat([frame[:, None], f64(ids)[:, None], f64(sf["slot"])[:, None], f64(sf["inside"])[:, None],
+                          sf["dist"][:, None], f64(sf["nearest"])], dim=1)
+
+    def _side_rows(self, fid, hist):
+        """(B, 2, m + 2) or (B, 2, K, m + 2) counts -> ``[frame, side, (slot,) n, bins.., over]`` rows, (side, slot) order."""
+        B = hist.shape[0]
+        keys = [(s,) for s in range(2)] if hist.dim() == 3 else [(s, t) for s in range(2) for t in range(hist.shape[2])]
+        key = torch.tensor(keys, dtype=torch.float64, device=hist.device)
+        R = len(keys)
+        return torch.cat([fid.to(torch.float64)[:, None, None].expand(B, R, 1), key[None].expand(B, R, key.shape[1]),
+                          hist.reshape(B, R, -1).to(torch.float64)], dim=2).reshape(B * R, -1)
+
+    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None, refined=False,
+                            surface=False, surface_edges=None):
         """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset)."""
-        cols = self.table_columns(C, ratios, neighbours, pair_edges, refined)
+        cols = self.table_columns(C, ratios, neighbours, pair_edges, refined, surface, surface_edges)
         mk = lambda n: torch.zeros((0, n), dtype=torch.float64, device=device)
         out = {"rois": mk(len(cols["rois"])), "cells": mk(len(cols["cells"])), "groups": mk(len(cols["groups"])),
                "frames_rec": mk(18), "distances": mk(3)}
@@ -656,13 +717,13 @@ class FramePipeline:
         return out
 
     def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0, neighbours=False, pair_edges=None,
-                    refined=False):
+                    refined=False, surface=False, surface_edges=None):
         """numpy tables from (downloaded or gathered) :meth:`tables_device` output: ``cells`` / ``rois`` / ``groups`` /
         ``distances`` as they are, ``frames`` after the two ``round(x, 5)`` of get_cell_counts_and_densities
         (tiff_analysis.py:1018-1038; Python's decimal rounding, a handful of numbers per frame).  Every table's width
         must be the one :meth:`table_columns` names for ``C`` planes and these ``ratios``."""
         host = _download(dt)
-        cols = self.table_columns(C, ratios, neighbours, pair_edges, refined)
+        cols = self.table_columns(C, ratios, neighbours, pair_edges, refined, surface, surface_edges)
         tb = self.tables_
         out = {k: host[k] for k in ("cells", "rois", "groups")}
         for k in out:
@@ -697,13 +758,14 @@ class FramePipeline:
         return out
 
     def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, neighbours=False,
-               pair_edges=None, refined=False):
+               pair_edges=None, refined=False, surface=False, surface_edges=None):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per
         refined ROI), ``frames`` (one row per frame) and ``groups`` (one row per merged group): :meth:`tables_device`
         followed by :meth:`host_tables`.  ``check=False`` skips ``BatchResult.check`` (a caller that has looked at the
         flags itself, e.g. to keep the ROI rows of a batch in which the reference would have raised on one frame's
         cluster statistics).  ``neighbours`` / ``pair_edges`` / ``refined``: the ``neighbours`` / ``pair_hist`` and
-        refined tables of :meth:`tables_device`."""
+        refined tables of :meth:`tables_device`; ``surface`` / ``surface_edges``: its surface-distance tables."""
         C = res["shape"][1]
-        dt = self.tables_device(res, frame_ids, ratios, check, distances, raster, neighbours, pair_edges, refined)
-        return self.host_tables(dt, C, ratios, distances, raster, neighbours, pair_edges, refined)
+        dt = self.tables_device(res, frame_ids, ratios, check, distances, raster, neighbours, pair_edges, refined, surface,
+                                surface_edges)
+        return self.host_tables(dt, C, ratios, distances, raster, neighbours, pair_edges, refined, surface, surface_edges)

@@ -314,6 +314,53 @@ def get_cell_neighbour_distances(cell_pos, px_to_um=PX_TO_UM_CONV, edges=None):
                  for p, (a, b) in enumerate(pairs) if b < len(names)}
 
 
+def get_cell_surface_distances(z_slice, cell_types, cell_pos=None, cell_clusters=None, px_to_um=PX_TO_UM_CONV, edges=None):
+    """Where the cells of one denoised class map sit relative to the particle
+    (HCN_nanosims_rois_activity_distance_5iso_YG.m:271-309, the distance of every ROI to the aggregate boundary): the
+    particle is reconstructed as ``recreate_particle_area`` does, its holes are filled, and every region of ``cell_pos``
+    and ``cell_clusters`` (strain -> regions; those of ``get_cell_positions_and_areas`` when none are passed) is measured
+    from its centroid to the nearest pixel of that mask's surface.  Returns per strain a list of ``(region, inside,
+    distance_um, (nearest_row, nearest_col))`` (cells first, then clusters): ``inside`` = the centroid's pixel lies in
+    the filled particle, ``distance_um = sqrt(drow^2 + dcol^2) / px_to_um``; ``(False, nan, (-1, -1))`` without a
+    particle.  With ``edges`` (increasing, from 0, in um) also the two histograms of a colonisation profile:
+    ``(per_strain, {"hist": {(side, strain): {"n", "bins", "over"}}, "shells": {side: {"n_px", "bins", "over"}}})``,
+    side 0 = outside the particle, 1 = inside; regions per um2 of a shell = hist bins / (shell bins / px_to_um^2)."""
+    if cell_pos is None:
+        cell_pos, found_clusters, _, _ = get_cell_positions_and_areas(z_slice, cell_types)
+        cell_clusters = found_clusters if cell_clusters is None else cell_clusters
+    cell_clusters = cell_clusters or {}
+    names = list(cell_pos) + [n for n in cell_clusters if n not in cell_pos]
+    if len(names) > 4:
+        raise ValueError("at most 4 strains")
+    regs = [(t, r) for t, name in enumerate(names) for r in list(cell_pos.get(name, [])) + list(cell_clusters.get(name, []))]
+    z_dev, _ = _to_dev_u8(z_slice)
+    dev = z_dev.device
+    cell_labels = [label for label, name in cell_types.items() if name in CELL_TYPES]
+    particle_labels = [label for label, name in cell_types.items() if name == "Particle"]
+    particle_label = particle_labels[-1] if particle_labels else None
+    gained = None
+    for cell_label in (cell_labels if particle_label is not None else []):
+        z_dev, gained = ops.fill_particle(z_dev, particle_label, cell_label, particle_label, DILATION_RADIUS, DISTANCE_THRESHOLD,
+                                          gained)
+    mask, surface = ops.particle_surface(z_dev, particle_label)
+    rc = torch.tensor([[float(r.centroid[0]), float(r.centroid[1])] for _, r in regs], dtype=torch.float64).reshape(-1, 2).to(dev)
+    slot = torch.tensor([t for t, _ in regs], dtype=torch.int32).to(dev)
+    foff = torch.tensor([0, len(regs)], dtype=torch.int64).to(dev)
+    K = max(len(names), 1)
+    dist, nearest, inside, hist = ops.surface_distances(rc, foff, surface, px_to_um, mask=mask, slot=slot, n_types=K, edges=edges)
+    dist, nearest, inside = dist.cpu().numpy(), nearest.cpu().numpy(), inside.cpu().numpy()
+    out = {name: [] for name in names}
+    for i, (t, r) in enumerate(regs):
+        out[names[t]].append((r, bool(inside[i]), float(dist[i]), (int(nearest[i, 0]), int(nearest[i, 1]))))
+    if edges is None:
+        return out
+    h = hist[0].cpu().numpy()
+    sh = ops.surface_shells(surface, mask, edges, px_to_um)[0].cpu().numpy()
+    return out, {"hist": {(side, name): {"n": int(h[side, t, 0]), "bins": h[side, t, 1:-1], "over": int(h[side, t, -1])}
+                          for side in (0, 1) for t, name in enumerate(names)},
+                 "shells": {side: {"n_px": int(sh[side, 0]), "bins": sh[side, 1:-1], "over": int(sh[side, -1])} for side in (0, 1)}}
+
+
 def _group_regions(dl_dev, stats_dev, og_cell_regions):
     """device grouping (pcseg_merge_groups) + host assembly of the reference's merged-region dicts (:850-872)."""
     n = len(og_cell_regions)
