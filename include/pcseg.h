@@ -328,7 +328,10 @@ int pcseg_remove_overlapping(const uint8_t *dapi, const uint8_t *other, double t
  *                                  before its two round(x, 5), which the host applies)
  * pcseg_table_layout counts and scans (totals: device int64[6] = rows of rois, cells, groups, then the number of frames
  * with overflow / ws_overflow / nan_flag set, so that one read-back serves the caller's checks too); the caller reads the
- * totals, allocates, and pcseg_table_write fills the tables.  Both asynchronous on `stream`; every pointer of the
+ * totals, allocates, and pcseg_table_write fills the tables.  The workspace then holds the frames' row counts and row
+ * offsets (layout: table_offsets() in csrc/table_common.h, the only definition); it is the `table_workspace` that
+ * pcseg_cell_distances, pcseg_neighbours_pack_cells, pcseg_surface_pack_cells and pcseg_refined_table_write read, opaque
+ * to callers.  Both asynchronous on `stream`; every pointer of the
  * struct is a device pointer, group_of / n_groups / group_stats entries may be NULL (slot absent / merged = False). */
 typedef struct pcseg_table_inputs {
     int32_t B, cap, C, n_ratios;
@@ -370,7 +373,7 @@ int pcseg_cell_distances(const double *cells, int64_t n_rows, int ncol, const ui
  *         edges[0] == 0, strictly increasing; edges == NULL, n_edges == 0, pair_hist == NULL: no histogram.
  * pcseg_neighbours_pack_cells: the points of the dense `cells` table pcseg_table_write has just filled -- xy =
  * (centroid_col + 1, centroid_row + 1), slot = class_slot[class] (a HOST array, 255 -> -1), id = label -- and the
- * frames' offsets (B + 1); `table_workspace` is the one pcseg_table_layout / pcseg_table_write used. */
+ * frames' offsets (B + 1); `table_workspace`: see pcseg_table_layout. */
 size_t pcseg_neighbours_workspace_bytes(int64_t n_points, int B, int K, int n_edges);
 int pcseg_point_neighbours(const double *xy, const int32_t *slot, const int32_t *id, const int64_t *frame_offsets, int64_t n_points,
                            int B, int K, double scale, const double *edges, int n_edges, double *dist, int32_t *nn_id,
@@ -464,7 +467,7 @@ int pcseg_refined_table_write(const pcseg_refined_inputs *in, const void *table_
  * Workspace: pcseg_surface_shells_workspace_bytes(B, H, W).
  * pcseg_surface_pack_cells: the queries of the dense `cells` table pcseg_table_write has just filled -- rc =
  * (centroid_row, centroid_col) as the table prints them, slot = class_slot[class] (a HOST array, 255 -> -1), id = label --
- * and the frames' offsets; `table_workspace` as for pcseg_neighbours_pack_cells.  pcseg_surface_pack_refined: rc of the
+ * and the frames' offsets; `table_workspace`: see pcseg_table_layout.  pcseg_surface_pack_refined: rc of the
  * refined points pcseg_refined_table_write packed (id = refined label, frame_offsets) = their centroids as the `refined`
  * table prints them, from ws_stats device int64 (B, cap, 8). */
 size_t pcseg_surface_workspace_bytes(int B, int H, int W);

@@ -308,7 +308,4 @@ int ccl_plan(void *workspace, size_t workspace_bytes, int B, int H, int W, CclPl
 int ccl_equal_u8_finish(const uint8_t *in, const CclPlan &plan, bool tile_pass_done, int *labels, int *counts, int B, int H, int W,
                         hipStream_t s);
 
-// neighbours.hip: the smallest non-negative double t with sqrt(t) / scale >= e -- the d2 threshold of a histogram edge
-double nb_threshold(double e, double scale);
-
 }  // namespace pcseg

@@ -15,26 +15,14 @@
 //                        an LDS histogram, flushed with one global atomic per non-zero bin
 //   nb_merge_kernel      one thread per point: minimum over the splits, -> distance, in the caller's point order
 //   nb_hist_finish_kernel one thread per (frame, slot pair): n_pairs and the overflow count = n_pairs - sum of bins
-#include <cmath>
-
-#include "common.h"
+#include "table_common.h"
 
 namespace pcseg {
 
 constexpr int NB_TILE = 256;
-constexpr int NB_MAX_K = 4;
-constexpr int NB_MAX_BINS = 1024;
+constexpr int NB_MAX_K = MAX_TYPE_SLOTS;
 constexpr int NB_GRID = 1024;      // persistent blocks: 4 per CU
 constexpr int NB_MAX_SPLITS = 8;
-constexpr int NB_THR_CHUNK = 256;  // thresholds handed to the device per launch, as a kernel argument
-
-struct ClassSlotsNb {
-    uint8_t slot[256];  // class value -> cell-type slot, 255 = not a cell type
-};
-
-struct NbThrChunk {
-    double v[NB_THR_CHUNK];
-};
 
 // candidate splits per query tile: enough work items to cover the persistent grid twice when the batch has few tiles
 static int nb_splits(int64_t n, int B)
@@ -175,14 +163,8 @@ __device__ __forceinline__ void nb_scan_tile(const double2 *__restrict__ cxy, co
         if (CHECK) better = better && j0 + k != i;
         bd = better ? d2 : bd;
         bid = better ? cand : bid;
-        if (HIST && (!CHECK || j0 + k > i) && d2 < tlast) {
-            int lo = 0, hi = m;  // thr[lo] <= d2 < thr[hi]
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (thr[mid] <= d2) lo = mid; else hi = mid;
-            }
-            atomicAdd(&hrow[lo], 1u);
-        }
+        // thr[bin] <= d2 < thr[bin + 1]
+        if (HIST && (!CHECK || j0 + k > i) && d2 < tlast) atomicAdd(&hrow[last_le(thr, m, d2)], 1u);
     }
 }
 
@@ -200,12 +182,7 @@ __global__ void __launch_bounds__(256) nb_pairs_kernel(NbArgs a)
     const double nan = __longlong_as_double(0x7FF8000000000000LL), inf = __longlong_as_double(0x7FF0000000000000LL);
     const int total = a.prefix[a.B];
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
-        int lo = 0, hi = a.B;  // frame b: the last b with prefix[b] <= item (frames without items share one)
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (a.prefix[mid] <= item) lo = mid; else hi = mid;
-        }
-        const int b = lo, local = item - a.prefix[b], qt = local / S, c = local - qt * S;
+        const int b = last_le(a.prefix, a.B, item), local = item - a.prefix[b], qt = local / S, c = local - qt * S;
         const int64_t f0 = a.foff[b];
         const int32_t *st = a.sstart + (int64_t)b * (K + 2);
         const int nvalid = st[K], q0 = qt * NB_TILE, i = q0 + tid;
@@ -270,12 +247,7 @@ __global__ void __launch_bounds__(256) nb_merge_kernel(NbArgs a, const int32_t *
 {
     const int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (gi >= a.n) return;
-    int lo = 0, hi = a.B;  // frame b: the last b with foff[b] <= gi (empty frames share an offset)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.foff[mid] <= gi) lo = mid; else hi = mid;
-    }
-    const int K = a.K, b = lo;
+    const int K = a.K, b = last_le(a.foff, a.B, gi);
     const int32_t *st = a.sstart + (int64_t)b * (K + 2);
     const int i = (int)(gi - a.foff[b]);
     const int64_t o = sorig[gi];
@@ -323,50 +295,6 @@ __global__ void __launch_bounds__(256) nb_hist_finish_kernel(NbArgs a)
     row[m + 1] = n_pairs - sum;
 }
 
-__global__ void __launch_bounds__(256) nb_store_thresholds_kernel(NbThrChunk c, int k0, int cnt, double *__restrict__ thr)
-{
-    if ((int)threadIdx.x < cnt) thr[k0 + threadIdx.x] = c.v[threadIdx.x];
-}
-
-__global__ void __launch_bounds__(256) nb_pack_cells_kernel(const double *__restrict__ cells, int ncol, const long long *__restrict__ counts,
-                                                             const long long *__restrict__ offsets, ClassSlotsNb slots, int B,
-                                                             double *__restrict__ xy, int32_t *__restrict__ slot,
-                                                             int32_t *__restrict__ id, int64_t *__restrict__ foff)
-{
-    const int b = blockIdx.x;
-    const long long row0 = offsets[b * 3 + 1];
-    const int n = (int)counts[b * 3 + 1];
-    if (threadIdx.x == 0) {
-        foff[b] = row0;
-        if (b == B - 1) foff[B] = row0 + n;
-    }
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const double *r = cells + (row0 + i) * ncol;
-        xy[2 * (row0 + i)] = r[6] + 1.0;
-        xy[2 * (row0 + i) + 1] = r[5] + 1.0;
-        const int s = slots.slot[(int)r[2] & 255];
-        slot[row0 + i] = s == 255 ? -1 : s;
-        id[row0 + i] = (int32_t)r[1];
-    }
-}
-
-// d(d2) = sqrt(d2) / scale, rounded as the kernels round it
-static double nb_dist_host(double d2, double scale) { return std::sqrt(d2) / scale; }
-
-// smallest non-negative double t with d(t) >= e (d is non-decreasing in d2): a bisection over the ordered bit patterns
-// (declared in common.h: surface.hip bins its query rows with the same thresholds)
-double nb_threshold(double e, double scale)
-{
-    uint64_t lo = 0, hi = 0x7FF0000000000000ULL;  // d(+inf) = inf >= e
-    auto val = [](uint64_t u) { double d; memcpy(&d, &u, 8); return d; };
-    if (nb_dist_host(val(lo), scale) >= e) return 0.0;
-    while (hi - lo > 1) {  // d(lo) < e <= d(hi)
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (nb_dist_host(val(mid), scale) >= e) hi = mid; else lo = mid;
-    }
-    return val(hi);
-}
-
 struct NbWorkspace {
     double2 *sxy;
     int32_t *sid, *sorig, *sstart, *items, *prefix, *part_id;
@@ -407,10 +335,7 @@ int pcseg_point_neighbours(const double *xy, const int32_t *slot, const int32_t 
                            int B, int K, double scale, const double *edges, int n_edges, double *dist, int32_t *nn_id,
                            int64_t *pair_hist, void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
 {
-    bool edges_ok = n_edges == 0 ? (edges == nullptr && pair_hist == nullptr)
-                                 : (edges != nullptr && pair_hist != nullptr && n_edges >= 2 && n_edges <= NB_MAX_BINS + 1);
-    for (int k = 0; edges_ok && k < n_edges; ++k)
-        edges_ok = std::isfinite(edges[k]) && (k == 0 ? edges[0] == 0.0 : edges[k] > edges[k - 1]);
+    const bool edges_ok = n_edges == 0 ? (edges == nullptr && pair_hist == nullptr) : (hist_edges_ok(edges, n_edges) && pair_hist);
     PCSEG_REQUIRE(xy && slot && id && frame_offsets && dist && nn_id && workspace && B >= 1 && K >= 1 && K <= NB_MAX_K &&
                       n_points >= 0 && n_points < ((int64_t)1 << 24) && scale > 0.0 && std::isfinite(scale) && edges_ok,
                   "bad arguments");
@@ -428,13 +353,8 @@ int pcseg_point_neighbours(const double *xy, const int32_t *slot, const int32_t 
     a.hist = (unsigned long long *)pair_hist;
     a.n = n_points; a.B = B; a.K = K; a.S = S; a.m = m;
     if (n_edges > 0) {
-        NbThrChunk c;
-        for (int k0 = 0; k0 < n_edges; k0 += NB_THR_CHUNK) {
-            const int cnt = n_edges - k0 < NB_THR_CHUNK ? n_edges - k0 : NB_THR_CHUNK;
-            for (int k = 0; k < cnt; ++k) c.v[k] = nb_threshold(edges[k0 + k], scale);
-            PCSEG_LAUNCH(nb_store_thresholds_kernel, dim3(1), dim3(256), 0, s, c, k0, cnt, w.thr);
-            PCSEG_CHECK_LAUNCH();
-        }
+        const int rc = upload_values(s, w.thr, n_edges, [=](int k) { return d2_threshold(edges[k], scale); });
+        if (rc != PCSEG_OK) return rc;
         PCSEG_CHECK_HIP(hipMemsetAsync(pair_hist, 0, sizeof(int64_t) * (size_t)B * P * (m + 2), s));
     }
     PCSEG_LAUNCH(nb_partition_kernel, dim3(B), dim3(256), 0, s, xy, slot, id, frame_offsets, K, S, w.sxy, w.sid, w.sorig, w.sstart,
@@ -466,19 +386,8 @@ int pcseg_neighbours_pack_cells(const double *cells, int ncol, const uint8_t *cl
 {
     PCSEG_REQUIRE(cells && class_slot && table_workspace && xy && slot && id && frame_offsets && B >= 1 && ncol >= 14,
                   "bad arguments");
-    Carver cv(const_cast<void *>(table_workspace), table_workspace_bytes);
-    const long long *counts = cv.take<long long>(3 * (size_t)B);
-    const long long *offsets = cv.take<long long>(3 * (size_t)B);
-    if (!cv.ok()) {
-        set_error("neighbours_pack_cells: workspace too small (%zu < %zu)", table_workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    ClassSlotsNb slots;
-    memcpy(slots.slot, class_slot, 256);
-    PCSEG_LAUNCH(nb_pack_cells_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, cells, ncol, counts, offsets, slots, B, xy, slot, id,
-                 frame_offsets);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    return pack_cells<true>("neighbours_pack_cells", cells, ncol, class_slot, B, table_workspace, table_workspace_bytes, xy, slot, id,
+                            frame_offsets, stream);
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 //
 // pcseg_refined_layout / pcseg_refined_table_write: the `refined`, `cell_resolution` and `frames_refined` rows (one
 // block per frame, row positions by block scans as in tables.hip) and the refined points for pcseg_point_neighbours.
-#include "common.h"
+#include "table_common.h"
 
 namespace pcseg {
 
@@ -285,27 +285,7 @@ __global__ void __launch_bounds__(256) lp_final_kernel(const int *__restrict__ c
 
 // ---- tables
 
-constexpr int RF_T = 4;  // cell-type slots
-
-__device__ __forceinline__ int rf_block_scan(int v, int *total, int *wsum)
-{
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < 4; ++w) {
-        if (w < wid) base += wsum[w];
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
+constexpr int RF_T = MAX_TYPE_SLOTS;
 
 // a refined row exists for r < min(n_markers, cap) with a pixel (the `rois` rows); a refined point is such a row of kind >= 1
 __device__ __forceinline__ bool rf_row(const pcseg_refined_inputs &in, int b, int r)
@@ -321,7 +301,7 @@ __global__ void __launch_bounds__(256) rf_count_kernel(pcseg_refined_inputs in, 
     int n = 0;
     for (int r = threadIdx.x; r < m; r += 256) n += rf_row(in, b, r) && in.kind_r[(int64_t)b * in.cap + r] >= 1;
     int tot;
-    rf_block_scan(n, &tot, wsum);
+    block_scan_256(n, &tot, wsum);
     if (threadIdx.x == 0) n_points[b] = tot;
 }
 
@@ -344,7 +324,7 @@ __global__ void __launch_bounds__(64) rf_scan_kernel(const long long *__restrict
     }
 }
 
-__global__ void __launch_bounds__(256) rf_write_kernel(pcseg_refined_inputs in, const long long *__restrict__ tb_offsets,
+__global__ void __launch_bounds__(256) rf_write_kernel(pcseg_refined_inputs in, TableOffsets tb,
                                                        const long long *__restrict__ pt_offsets, int *__restrict__ acc,
                                                        double *__restrict__ refined, double *__restrict__ resolution,
                                                        double *__restrict__ frames, double *__restrict__ xy, int *__restrict__ pslot,
@@ -365,7 +345,7 @@ __global__ void __launch_bounds__(256) rf_write_kernel(pcseg_refined_inputs in, 
     __syncthreads();
     // ---- refined rows (and points)
     {
-        double *out = refined + tb_offsets[b * 3 + 0] * 11;
+        double *out = refined + tb.first(b, ROWS_ROIS) * 11;
         const long long pbase = pt_offsets[b];
         int carry = 0, pcarry = 0;
         for (int base = 0; base < m; base += 256) {
@@ -374,8 +354,8 @@ __global__ void __launch_bounds__(256) rf_write_kernel(pcseg_refined_inputs in, 
             const int k = valid ? in.kind_r[fb + r] : 0;
             const int point = valid && k >= 1;
             int total, ptotal;
-            const int pos = carry + rf_block_scan(valid, &total, wsum);
-            const int ppos = pcarry + rf_block_scan(point, &ptotal, wsum);
+            const int pos = carry + block_scan_256(valid, &total, wsum);
+            const int ppos = pcarry + block_scan_256(point, &ptotal, wsum);
             if (valid) {
                 const int64_t *st = in.ws_stats + (fb + r) * 8;
                 const double area = (double)st[0];
@@ -409,14 +389,14 @@ __global__ void __launch_bounds__(256) rf_write_kernel(pcseg_refined_inputs in, 
     __syncthreads();
     // ---- cell_resolution rows: one per `cells` row (class-map kind >= 1), in its order
     {
-        double *out = resolution + tb_offsets[b * 3 + 1] * 5;
+        double *out = resolution + tb.first(b, ROWS_CELLS) * 5;
         int carry = 0;
         for (int base = 0; base < n; base += 256) {
             const int a = base + threadIdx.x;
             const int kind = a < n ? in.kind[fb + a] : 0;
             const int valid = kind > 0;
             int total;
-            const int pos = carry + rf_block_scan(valid, &total, wsum);
+            const int pos = carry + block_scan_256(valid, &total, wsum);
             if (valid) {
                 const int ch = ld_agent(&child[a * 3]), sum = ld_agent(&child[a * 3 + 1]), neg = ld_agent(&child[a * 3 + 2]);
                 const int resolved = kind == 2 && ch >= 2;
@@ -545,8 +525,7 @@ int pcseg_refined_table_write(const pcseg_refined_inputs *in, const void *table_
                       (!points || (xy && slot && id && frame_offsets)),
                   "bad arguments");
     Carver tv(const_cast<void *>(table_workspace), table_workspace_bytes);
-    tv.take<long long>(3 * (size_t)in->B);
-    const long long *tb_offsets = tv.take<long long>(3 * (size_t)in->B);
+    const TableOffsets tb = table_offsets(tv, in->B);
     Carver cv(workspace, workspace_bytes);
     cv.take<long long>(in->B);
     const long long *pt_offsets = cv.take<long long>((size_t)in->B + 1);
@@ -555,7 +534,7 @@ int pcseg_refined_table_write(const pcseg_refined_inputs *in, const void *table_
         set_error("refined_table_write: workspace too small");
         return PCSEG_ERR_WORKSPACE;
     }
-    PCSEG_LAUNCH(rf_write_kernel, dim3(in->B), dim3(256), 0, (hipStream_t)stream, *in, tb_offsets, pt_offsets, acc, refined, resolution,
+    PCSEG_LAUNCH(rf_write_kernel, dim3(in->B), dim3(256), 0, (hipStream_t)stream, *in, tb, pt_offsets, acc, refined, resolution,
                  frames, xy, slot, id, (long long *)frame_offsets);
     PCSEG_CHECK_LAUNCH();
     return PCSEG_OK;

@@ -23,28 +23,14 @@
 //   sf_shell_kernel       D2 of every pixel against integer thresholds: LDS histogram per block and side, one 64-bit
 //                         global atomic per non-zero bin
 //   sf_hist_finish_kernel column 0 of every histogram row = sum of its bins and overflow
-#include <cmath>
-
-#include "common.h"
+#include "table_common.h"
 
 // each product and the sum of d2 rounded on their own (no FMA), everywhere in this file
 #pragma clang fp contract(off)
 
 namespace pcseg {
 
-constexpr int SF_MAX_BINS = 1024;
-constexpr int SF_MAX_K = 4;
-constexpr int SF_CHUNK = 256;  // thresholds handed to the device per launch, as a kernel argument
 constexpr double SF_QUERY_LIMIT = 16777216.0;  // |coordinate| above 2^24 (or NaN): no distance (d2 stays far below 2^53)
-
-template <typename T>
-struct SfChunk {
-    T v[SF_CHUNK];
-};
-
-struct SfClassSlots {
-    uint8_t slot[256];
-};
 
 __global__ void __launch_bounds__(256) sf_mask_bits_kernel(const uint8_t *__restrict__ in, unsigned long long value_bits,
                                                             uint32_t *__restrict__ mbits, int64_t rows, int W, int WW)
@@ -215,12 +201,7 @@ __global__ void __launch_bounds__(256) sf_search_kernel(SfSearchArgs a)
     const int lane = lane_id();
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= a.n) return;  // wave-uniform
-    int lo = 0, hi = a.B;  // frame b: the last b with foff[b] <= q (empty frames share an offset)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.foff[mid] <= q) lo = mid; else hi = mid;
-    }
-    const int b = lo, H = a.H, W = a.W, WW = a.WW;
+    const int b = last_le(a.foff, a.B, q), H = a.H, W = a.W, WW = a.WW;
     const double qr = a.rc[2 * q], qc = a.rc[2 * q + 1];
     const double inf = __longlong_as_double(0x7FF0000000000000LL), nan = __longlong_as_double(0x7FF8000000000000LL);
     const bool ok = fabs(qr) <= SF_QUERY_LIMIT && fabs(qc) <= SF_QUERY_LIMIT && (a.counts == nullptr || a.counts[b] > 0);
@@ -306,11 +287,7 @@ __global__ void __launch_bounds__(256) sf_search_kernel(SfSearchArgs a)
     if (a.thr && found) {
         const int s = a.slot[q];
         if (s >= 0 && s < a.K) {
-            int klo = 0, khi = a.m + 1;  // thr[klo] <= d2 < thr[khi] (thr[0] = 0; khi = m + 1: no upper bound)
-            while (khi - klo > 1) {
-                const int mid = (klo + khi) >> 1;
-                if (a.thr[mid] <= best) klo = mid; else khi = mid;
-            }
+            const int klo = last_le(a.thr, a.m + 1, best);  // thr[klo] <= d2 < thr[klo + 1] (thr[0] = 0; klo = m: no upper bound)
             atomicAdd(&a.hist[(((int64_t)b * 2 + side) * a.K + s) * (a.m + 2) + 1 + klo], 1ull);
         }
     }
@@ -324,12 +301,6 @@ __global__ void __launch_bounds__(256) sf_hist_finish_kernel(unsigned long long 
     unsigned long long sum = 0;
     for (int k = 0; k <= m; ++k) sum += row[1 + k];
     row[0] = sum;
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256) sf_put_kernel(SfChunk<T> c, int k0, int cnt, T *__restrict__ out)
-{
-    if ((int)threadIdx.x < cnt) out[k0 + threadIdx.x] = c.v[threadIdx.x];
 }
 
 __global__ void __launch_bounds__(256) sf_zero_image_kernel(const uint32_t *__restrict__ bits, uint8_t *__restrict__ img, int64_t rows,
@@ -359,16 +330,7 @@ __global__ void __launch_bounds__(256) sf_shell_kernel(const int32_t *__restrict
     const uint8_t *fm = mask + (int64_t)b * HW;
     for (int p = blockIdx.x * 256 + tid; p < HW; p += gridDim.x * 256) {
         const int side = fm[p] != 0;
-        int k = m;
-        if (!empty) {
-            const long long v = fd[p];
-            int klo = 0, khi = m + 1;  // thr[klo] <= v < thr[khi]
-            while (khi - klo > 1) {
-                const int mid = (klo + khi) >> 1;
-                if (s_thr[mid] <= v) klo = mid; else khi = mid;
-            }
-            k = klo;
-        }
+        const int k = empty ? m : last_le(s_thr, m + 1, (long long)fd[p]);  // thr[k] <= d2 < thr[k + 1]
         atomicAdd(&s_hist[side * (m + 1) + k], 1u);
     }
     __syncthreads();
@@ -379,72 +341,24 @@ __global__ void __launch_bounds__(256) sf_shell_kernel(const int32_t *__restrict
     }
 }
 
-__global__ void __launch_bounds__(256) sf_pack_cells_kernel(const double *__restrict__ cells, int ncol, const long long *__restrict__ counts,
-                                                             const long long *__restrict__ offsets, SfClassSlots slots, int B,
-                                                             double *__restrict__ rc, int32_t *__restrict__ slot,
-                                                             int32_t *__restrict__ id, int64_t *__restrict__ foff)
-{
-    const int b = blockIdx.x;
-    const long long row0 = offsets[b * 3 + 1];
-    const int n = (int)counts[b * 3 + 1];
-    if (threadIdx.x == 0) {
-        foff[b] = row0;
-        if (b == B - 1) foff[B] = row0 + n;
-    }
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const double *r = cells + (row0 + i) * ncol;
-        rc[2 * (row0 + i)] = r[5];
-        rc[2 * (row0 + i) + 1] = r[6];
-        const int s = slots.slot[(int)r[2] & 255];
-        slot[row0 + i] = s == 255 ? -1 : s;
-        id[row0 + i] = (int32_t)r[1];
-    }
-}
-
 // refined points (label id, frame by frame) -> their centroids as the `refined` table prints them: sum / area
 __global__ void __launch_bounds__(256) sf_pack_refined_kernel(const int64_t *__restrict__ ws_stats, int cap, const int32_t *__restrict__ id,
                                                                const int64_t *__restrict__ foff, int64_t n, int B, double *__restrict__ rc)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (foff[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int b = last_le(foff, B, i);
     const int r = id[i] - 1;
     const double nan = __longlong_as_double(0x7FF8000000000000LL);
     double crow = nan, ccol = nan;
     if (r >= 0 && r < cap) {
-        const int64_t *st = ws_stats + ((int64_t)lo * cap + r) * 8;
+        const int64_t *st = ws_stats + ((int64_t)b * cap + r) * 8;
         const double area = (double)st[0];
         crow = __ddiv_rn((double)st[1], area);
         ccol = __ddiv_rn((double)st[2], area);
     }
     rc[2 * i] = crow;
     rc[2 * i + 1] = ccol;
-}
-
-static bool sf_edges_ok(const double *edges, int n_edges)
-{
-    if (!edges || n_edges < 2 || n_edges > SF_MAX_BINS + 1) return false;
-    for (int k = 0; k < n_edges; ++k)
-        if (!std::isfinite(edges[k]) || (k == 0 ? edges[0] != 0.0 : !(edges[k] > edges[k - 1]))) return false;
-    return true;
-}
-
-// smallest integer n >= 0 with sqrt((double)n) / scale >= e (INT64_MAX when no n up to 2^53 reaches it)
-static int64_t sf_threshold(double e, double scale)
-{
-    auto d = [scale](int64_t n) { return std::sqrt((double)n) / scale; };
-    if (d(0) >= e) return 0;
-    int64_t lo = 0, hi = (int64_t)1 << 53;
-    if (!(d(hi) >= e)) return INT64_MAX;
-    while (hi - lo > 1) {  // d(lo) < e <= d(hi)
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (d(mid) >= e) hi = mid; else lo = mid;
-    }
-    return hi;
 }
 
 struct SfWorkspace {
@@ -463,7 +377,7 @@ static SfWorkspace sf_carve(void *workspace, size_t bytes, int B, int H, int W)
     w.rowcnt = cv.take<int32_t>(2 * (size_t)B * H);
     w.rowarea = w.rowcnt + (size_t)B * H;
     w.rowoff = cv.take<int32_t>((size_t)B * H);
-    w.thr = cv.take<double>(SF_MAX_BINS + 1);
+    w.thr = cv.take<double>(MAX_HIST_BINS + 1);
     w.off = cv.off;
     return w;
 }
@@ -482,7 +396,7 @@ static SfShellWorkspace sf_shell_carve(void *workspace, size_t bytes, int B, int
     SfShellWorkspace w;
     w.img = cv.take<uint8_t>((size_t)B * H * W);
     w.d2 = cv.take<int32_t>((size_t)B * H * W);
-    w.thr = cv.take<long long>(SF_MAX_BINS + 1);
+    w.thr = cv.take<long long>(MAX_HIST_BINS + 1);
     w.edt_bytes = pcseg_edt_workspace_bytes(B, H, W);
     w.edt = cv.take<uint8_t>(w.edt_bytes);
     w.off = cv.off;
@@ -547,7 +461,7 @@ int pcseg_surface_distances(const double *rc, const int32_t *slot, const int64_t
                             int32_t *rows_visited, void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
 {
     const bool edges_ok = n_edges == 0 ? (edges == nullptr && hist == nullptr)
-                                       : (sf_edges_ok(edges, n_edges) && hist && slot && mask && K >= 1 && K <= SF_MAX_K);
+                                       : (hist_edges_ok(edges, n_edges) && hist && slot && mask && K >= 1 && K <= MAX_TYPE_SLOTS);
     PCSEG_REQUIRE(rc && frame_offsets && bits && dist && nearest && workspace && check_shape(B, H, W) && n_points >= 0 &&
                       n_points < ((int64_t)1 << 31) && scale > 0.0 && std::isfinite(scale) && edges_ok,
                   "bad arguments");
@@ -559,13 +473,8 @@ int pcseg_surface_distances(const double *rc, const int32_t *slot, const int64_t
     hipStream_t s = (hipStream_t)stream;
     const int m = n_edges > 0 ? n_edges - 1 : 0;
     if (n_edges > 0) {
-        SfChunk<double> c;
-        for (int k0 = 0; k0 < n_edges; k0 += SF_CHUNK) {
-            const int cnt = n_edges - k0 < SF_CHUNK ? n_edges - k0 : SF_CHUNK;
-            for (int k = 0; k < cnt; ++k) c.v[k] = nb_threshold(edges[k0 + k], scale);
-            PCSEG_LAUNCH(sf_put_kernel<double>, dim3(1), dim3(256), 0, s, c, k0, cnt, w.thr);
-            PCSEG_CHECK_LAUNCH();
-        }
+        const int rc = upload_values(s, w.thr, n_edges, [=](int k) { return d2_threshold(edges[k], scale); });
+        if (rc != PCSEG_OK) return rc;
         PCSEG_CHECK_HIP(hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)B * 2 * K * (m + 2), s));
     }
     if (n_points > 0) {
@@ -588,8 +497,8 @@ int pcseg_surface_distances(const double *rc, const int32_t *slot, const int64_t
 
 int pcseg_surface_thresholds(const double *edges, int n_edges, double scale, int64_t *out)
 {
-    PCSEG_REQUIRE(out && sf_edges_ok(edges, n_edges) && scale > 0.0 && std::isfinite(scale), "bad arguments");
-    for (int k = 0; k < n_edges; ++k) out[k] = sf_threshold(edges[k], scale);
+    PCSEG_REQUIRE(out && hist_edges_ok(edges, n_edges) && scale > 0.0 && std::isfinite(scale), "bad arguments");
+    for (int k = 0; k < n_edges; ++k) out[k] = d2_threshold_int(edges[k], scale);
     return PCSEG_OK;
 }
 
@@ -604,7 +513,7 @@ int pcseg_surface_shells(const uint32_t *bits, const int64_t *counts, const uint
                          pcseg_stream_t stream)
 {
     PCSEG_REQUIRE(bits && counts && mask && shells && workspace && check_shape(B, H, W) && B <= 65535 && scale > 0.0 &&
-                      std::isfinite(scale) && sf_edges_ok(edges, n_edges),
+                      std::isfinite(scale) && hist_edges_ok(edges, n_edges),
                   "bad arguments");
     SfShellWorkspace w = sf_shell_carve(workspace, workspace_bytes, B, H, W);
     if (w.off > workspace_bytes) {
@@ -614,17 +523,12 @@ int pcseg_surface_shells(const uint32_t *bits, const int64_t *counts, const uint
     hipStream_t s = (hipStream_t)stream;
     const int m = n_edges - 1, WW = (W + 31) / 32, HW = H * W;
     const int64_t rows = (int64_t)B * H;
-    SfChunk<long long> c;
-    for (int k0 = 0; k0 < n_edges; k0 += SF_CHUNK) {
-        const int cnt = n_edges - k0 < SF_CHUNK ? n_edges - k0 : SF_CHUNK;
-        for (int k = 0; k < cnt; ++k) c.v[k] = sf_threshold(edges[k0 + k], scale);
-        PCSEG_LAUNCH(sf_put_kernel<long long>, dim3(1), dim3(256), 0, s, c, k0, cnt, w.thr);
-        PCSEG_CHECK_LAUNCH();
-    }
+    int rc = upload_values(s, w.thr, n_edges, [=](int k) { return (long long)d2_threshold_int(edges[k], scale); });
+    if (rc != PCSEG_OK) return rc;
     PCSEG_CHECK_HIP(hipMemsetAsync(shells, 0, sizeof(int64_t) * (size_t)B * 2 * (m + 2), s));
     PCSEG_LAUNCH(sf_zero_image_kernel, dim3((unsigned)((rows * W + 255) / 256)), dim3(256), 0, s, bits, w.img, rows, W, WW);
     PCSEG_CHECK_LAUNCH();
-    const int rc = pcseg_edt_sq_u8(w.img, w.d2, B, H, W, -1, w.edt, w.edt_bytes, stream);
+    rc = pcseg_edt_sq_u8(w.img, w.d2, B, H, W, -1, w.edt, w.edt_bytes, stream);
     if (rc != PCSEG_OK) return rc;
     int per_frame = (HW + 256 * 16 - 1) / (256 * 16);
     per_frame = per_frame > 128 ? 128 : per_frame;
@@ -644,19 +548,8 @@ int pcseg_surface_pack_cells(const double *cells, int ncol, const uint8_t *class
 {
     PCSEG_REQUIRE(cells && class_slot && table_workspace && rc && slot && id && frame_offsets && B >= 1 && ncol >= 14,
                   "bad arguments");
-    Carver cv(const_cast<void *>(table_workspace), table_workspace_bytes);
-    const long long *counts = cv.take<long long>(3 * (size_t)B);
-    const long long *offsets = cv.take<long long>(3 * (size_t)B);
-    if (!cv.ok()) {
-        set_error("surface_pack_cells: workspace too small (%zu < %zu)", table_workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    SfClassSlots slots;
-    memcpy(slots.slot, class_slot, 256);
-    PCSEG_LAUNCH(sf_pack_cells_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, cells, ncol, counts, offsets, slots, B, rc, slot, id,
-                 frame_offsets);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    return pack_cells<false>("surface_pack_cells", cells, ncol, class_slot, B, table_workspace, table_workspace_bytes, rc, slot, id,
+                             frame_offsets, stream);
 }
 
 int pcseg_surface_pack_refined(const int64_t *ws_stats, int cap, const int32_t *id, const int64_t *frame_offsets, int64_t n_points,

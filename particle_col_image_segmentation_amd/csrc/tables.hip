@@ -9,35 +9,11 @@
 //           round(x, 5) of that function are Python's decimal rounding and stay a B-row host epilogue
 // Row order is the reference's: frames in batch order, labels ascending.  Three launches: per-frame row counts,
 // one-block scan over the frames, per-frame writers (block scan over the frame's rows gives every row its slot).
-#include "common.h"
+#include "table_common.h"
 
 namespace pcseg {
 
 constexpr int TB_SLOTS = 5;  // CLS_T cell-type slots + the "combined" list
-
-struct ClassSlots {
-    uint8_t slot[256];  // class value -> cell-type slot, 255 = not a cell type
-};
-
-__device__ __forceinline__ int tb_block_scan(int v, int *total, int *wsum)
-{
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < 4; ++w) {
-        if (w < wid) base += wsum[w];
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
 
 // counts[b] = {roi rows, cell rows, group rows}
 __global__ void __launch_bounds__(256) table_count_kernel(pcseg_table_inputs in, long long *__restrict__ counts)
@@ -49,15 +25,15 @@ __global__ void __launch_bounds__(256) table_count_kernel(pcseg_table_inputs in,
     for (int r = threadIdx.x; r < m; r += 256) n_roi += in.ws_stats[((int64_t)b * in.cap + r) * 8] > 0;
     for (int r = threadIdx.x; r < n; r += 256) n_cell += in.kind[(int64_t)b * in.cap + r] > 0;
     int tot_roi, tot_cell;
-    tb_block_scan(n_roi, &tot_roi, wsum);
-    tb_block_scan(n_cell, &tot_cell, wsum);
+    block_scan_256(n_roi, &tot_roi, wsum);
+    block_scan_256(n_cell, &tot_cell, wsum);
     if (threadIdx.x == 0) {
         long long g = 0;
         for (int s = 0; s < TB_SLOTS; ++s)
             if (in.n_groups[s]) g += in.n_groups[s][b];
-        counts[b * 3 + 0] = tot_roi;
-        counts[b * 3 + 1] = tot_cell;
-        counts[b * 3 + 2] = g;
+        counts[b * ROW_KINDS + ROWS_ROIS] = tot_roi;
+        counts[b * ROW_KINDS + ROWS_CELLS] = tot_cell;
+        counts[b * ROW_KINDS + ROWS_GROUPS] = g;
     }
 }
 
@@ -68,11 +44,11 @@ __global__ void __launch_bounds__(64) table_scan_kernel(pcseg_table_inputs in, c
                                                          long long *__restrict__ offsets, long long *__restrict__ totals, int B)
 {
     const int t = threadIdx.x;
-    if (t < 3) {
+    if (t < ROW_KINDS) {
         long long acc = 0;
         for (int b = 0; b < B; ++b) {
-            offsets[b * 3 + t] = acc;
-            acc += counts[b * 3 + t];
+            offsets[b * ROW_KINDS + t] = acc;
+            acc += counts[b * ROW_KINDS + t];
         }
         totals[t] = acc;
     } else if (t < 6) {
@@ -112,14 +88,14 @@ __global__ void __launch_bounds__(256) table_write_kernel(pcseg_table_inputs in,
     // ---- rois
     {
         const int ncol = 5 + C + nr;
-        double *out = rois + offsets[b * 3 + 0] * ncol;
+        double *out = rois + offsets[b * ROW_KINDS + ROWS_ROIS] * ncol;
         int carry = 0;
         for (int base = 0; base < m; base += 256) {
             const int r = base + threadIdx.x;
             const int64_t *st = in.ws_stats + ((int64_t)b * cap + (r < m ? r : 0)) * 8;
             const int valid = r < m && st[0] > 0;
             int total;
-            const int pos = carry + tb_block_scan(valid, &total, wsum);
+            const int pos = carry + block_scan_256(valid, &total, wsum);
             if (valid) {
                 double *row = out + (int64_t)pos * ncol;
                 const double a = (double)st[0];
@@ -151,13 +127,13 @@ __global__ void __launch_bounds__(256) table_write_kernel(pcseg_table_inputs in,
     // ---- cells
     {
         const int ncol = 14 + C + nr;
-        double *out = cells + offsets[b * 3 + 1] * ncol;
+        double *out = cells + offsets[b * ROW_KINDS + ROWS_CELLS] * ncol;
         int carry = 0;
         for (int base = 0; base < n; base += 256) {
             const int r = base + threadIdx.x;
             const int valid = r < n && in.kind[(int64_t)b * cap + r] > 0;
             int total;
-            const int pos = carry + tb_block_scan(valid, &total, wsum);
+            const int pos = carry + block_scan_256(valid, &total, wsum);
             if (valid) {
                 const int64_t *st = in.stats + ((int64_t)b * cap + r) * 8;
                 double *row = out + (int64_t)pos * ncol;
@@ -176,7 +152,7 @@ __global__ void __launch_bounds__(256) table_write_kernel(pcseg_table_inputs in,
     }
     // ---- groups: slots in the order the reference's dict holds them (types, then "combined")
     {
-        double *out = groups + offsets[b * 3 + 2] * 11;
+        double *out = groups + offsets[b * ROW_KINDS + ROWS_GROUPS] * 11;
         int done = 0;
         for (int s = 0; s < TB_SLOTS; ++s) {
             if (!in.n_groups[s]) continue;
@@ -224,14 +200,13 @@ __global__ void __launch_bounds__(256) table_write_kernel(pcseg_table_inputs in,
 // and the sum rounded on their own (no fused multiply-add), then / (512 / raster).  One block per frame; a frame lists a
 // few hundred rows, every thread scans the frame's rows of the other type.  NaN marks a row that has no entry in the
 // distance table (another type, or a frame in which one of the two types is absent).
-__global__ void __launch_bounds__(256) cell_distance_kernel(const double *__restrict__ cells, int ncol, const long long *__restrict__ counts,
-                                                             const long long *__restrict__ offsets, ClassSlots slots, double scale,
-                                                             double *__restrict__ dist)
+__global__ void __launch_bounds__(256) cell_distance_kernel(const double *__restrict__ cells, int ncol, TableOffsets to, ClassSlots slots,
+                                                             double scale, double *__restrict__ dist)
 {
     __shared__ int s_n[2];
     const int b = blockIdx.x;
-    const long long row0 = offsets[b * 3 + 1];
-    const int n = (int)counts[b * 3 + 1];
+    const long long row0 = to.first(b, ROWS_CELLS);
+    const int n = (int)to.count(b, ROWS_CELLS);
     const double *rows = cells + row0 * ncol;
     if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
     __syncthreads();
@@ -244,7 +219,7 @@ __global__ void __launch_bounds__(256) cell_distance_kernel(const double *__rest
     const double nan = __longlong_as_double(0x7FF8000000000000LL);
     for (int i = threadIdx.x; i < n; i += 256) {
         const double *ri = rows + (int64_t)i * ncol;
-        const int sl = slots.slot[(int)ri[2] & 255];
+        const int sl = slots.slot[(int)ri[2] & 255];  // (the table's own bytes: only slots 0 and 1 matter here, 255 is neither)
         double out = nan;
         if (both && sl < 2) {
             const double x = ri[6] + 1.0, y = ri[5] + 1.0;
@@ -286,16 +261,17 @@ int pcseg_table_layout(const pcseg_table_inputs *in, int64_t *totals, void *work
 {
     PCSEG_REQUIRE(table_check(in) && totals && workspace, "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    long long *counts = cv.take<long long>(3 * (size_t)in->B);
-    long long *offsets = cv.take<long long>(3 * (size_t)in->B);
+    const TableOffsets to = table_offsets(cv, in->B);
     if (!cv.ok()) {
         set_error("table_layout: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    PCSEG_LAUNCH(table_count_kernel, dim3(in->B), dim3(256), 0, s, *in, counts);
+    // (the one writer of the workspace's head)
+    PCSEG_LAUNCH(table_count_kernel, dim3(in->B), dim3(256), 0, s, *in, const_cast<long long *>(to.counts));
     PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(table_scan_kernel, dim3(1), dim3(64), 0, s, *in, (const long long *)counts, offsets, (long long *)totals, in->B);
+    PCSEG_LAUNCH(table_scan_kernel, dim3(1), dim3(64), 0, s, *in, to.counts, const_cast<long long *>(to.offsets), (long long *)totals,
+                 in->B);
     PCSEG_CHECK_LAUNCH();
     return PCSEG_OK;
 }
@@ -305,16 +281,15 @@ int pcseg_table_write(const pcseg_table_inputs *in, double *rois, double *cells,
 {
     PCSEG_REQUIRE(table_check(in) && rois && cells && groups && frames && workspace, "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    cv.take<long long>(3 * (size_t)in->B);
-    long long *offsets = cv.take<long long>(3 * (size_t)in->B);
+    const TableOffsets to = table_offsets(cv, in->B);
     int *own = cv.take<int>((size_t)in->B * in->cap);
     int *comb = cv.take<int>((size_t)in->B * in->cap);
     if (!cv.ok()) {
         set_error("table_write: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
-    PCSEG_LAUNCH(table_write_kernel, dim3(in->B), dim3(256), 0, (hipStream_t)stream, *in, (const long long *)offsets, rois, cells,
-                 groups, (long long *)frames, own, comb);
+    PCSEG_LAUNCH(table_write_kernel, dim3(in->B), dim3(256), 0, (hipStream_t)stream, *in, to.offsets, rois, cells, groups,
+                 (long long *)frames, own, comb);
     PCSEG_CHECK_LAUNCH();
     return PCSEG_OK;
 }
@@ -325,16 +300,13 @@ int pcseg_cell_distances(const double *cells, int64_t n_rows, int ncol, const ui
     PCSEG_REQUIRE(cells && class_slot && dist && workspace && B >= 1 && ncol >= 14 && n_rows >= 0 && raster > 0.0 && size > 0.0,
                   "bad arguments");
     Carver cv(const_cast<void *>(workspace), workspace_bytes);
-    const long long *counts = cv.take<long long>(3 * (size_t)B);
-    const long long *offsets = cv.take<long long>(3 * (size_t)B);
+    const TableOffsets to = table_offsets(cv, B);
     if (!cv.ok()) {
         set_error("cell_distances: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
-    ClassSlots slots;
-    memcpy(slots.slot, class_slot, 256);
-    PCSEG_LAUNCH(cell_distance_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, cells, ncol, counts, offsets, slots, size / raster,
-                 dist);
+    PCSEG_LAUNCH(cell_distance_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, cells, ncol, to, ClassSlots(class_slot),
+                 size / raster, dist);
     PCSEG_CHECK_LAUNCH();
     return PCSEG_OK;
 }

@@ -11,6 +11,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .pipeline import OPTIONAL_TABLES, FramePipeline
+
 
 def shard_frames(n_frames, rank, world_size):
     """Round-robin frame ownership: frame i -> rank i mod world (BASELINE config 3)."""
@@ -86,9 +88,8 @@ def all_gather_table(table, group=None, sort_cols=(0, 1), presorted=False, chunk
 TABLE_KEYS = ("cells", "rois", "frames", "groups", "distances")
 # key columns per table.  `distances`: frame only -- a frame lives on one rank and the sort is stable, so the rows of a
 # frame keep the order their rank made them in (type slot 0 first, then slot 1), with any number of ranks
-_SORT_COLS = {"frames": (0,), "frames_rec": (0,), "groups": (0, 1, 2), "distances": (0,), "pair_hist": (0, 1, 2),
-              "refined_pair_hist": (0, 1, 2), "frames_surface": (0,), "surface_hist": (0, 1, 2), "surface_shells": (0, 1),
-              "refined_surface_hist": (0, 1, 2)}
+# (the optional tables' keys stand in their schema, pipeline.OPTIONAL_TABLES; any other table: (frame, label))
+_SORT_COLS = {"frames": (0,), "frames_rec": (0,), "groups": (0, 1, 2), "distances": (0,), **{t.name: t.key for t in OPTIONAL_TABLES}}
 
 
 def gather_tables(tables, device=None, group=None, presorted=False, chunk_bytes=None):
@@ -185,8 +186,9 @@ def run_sharded(n_frames, make_batch, pipe, batch=64, group=None, device=None, p
     the host epilogue (``pipe.host_tables``) then runs on the gathered rows.  A rank that owns no frame
     (``n_frames < world``) contributes ``pipe.empty_device_tables``, so that every rank enters the same collectives with
     the same column counts.  The plane count comes from the data (the first batch a rank makes; ranks agree on it with one
-    all-reduce), ``planes`` only overrides it.  ``table_kwargs`` (ratios, distances, raster, neighbours, pair_edges,
-    refined, surface, surface_edges) go to ``tables_device`` and ``host_tables``, each only when the caller gives it.
+    all-reduce), ``planes`` only overrides it.  ``table_kwargs`` (ratios, distances, raster and the switches of the
+    optional tables) go to ``tables_device``, ``host_tables`` and ``empty_device_tables`` as
+    ``FramePipeline.table_kwargs`` sorts them, each only when the caller gives it.
 
     ``force_gather``: one rank normally streams its rows to pinned host memory batch by batch (``_HostRows``: there is
     nothing to gather); with this switch it takes the route every rank of a larger world takes -- device tables
@@ -200,8 +202,8 @@ def run_sharded(n_frames, make_batch, pipe, batch=64, group=None, device=None, p
     rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     mine = shard_frames(n_frames, rank, world)
-    ratio_kw = {k: table_kwargs[k] for k in ("ratios", "distances", "raster", "neighbours", "pair_edges", "refined", "surface",
-                                             "surface_edges") if k in table_kwargs}
+    ratio_kw = FramePipeline.table_kwargs("tables_device", table_kwargs)
+    host_kw = FramePipeline.table_kwargs("host_tables", table_kwargs)
     parts = []
     n_batches = (len(mine) + batch - 1) // batch
     host_rows = None  # one rank: the rows go to the host as the batches finish (see _HostRows)
@@ -242,15 +244,13 @@ def run_sharded(n_frames, make_batch, pipe, batch=64, group=None, device=None, p
         planes = _agree_planes(seen_planes, group, device) or 5
     if host_rows is not None:
         # (one rank's rows come out of the batches in frame order, labels ascending: that IS the gathered order)
-        return pipe.host_tables(host_rows.finish(), planes, **table_kwargs)
+        return pipe.host_tables(host_rows.finish(), planes, **host_kw)
     if parts:
         merged = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
     else:
-        merged = pipe.empty_device_tables(planes, device=device, **{k: ratio_kw[k] for k in ("ratios", "neighbours", "pair_edges",
-                                                                                        "refined", "surface", "surface_edges")
-                                                                     if k in ratio_kw})
+        merged = pipe.empty_device_tables(planes, device=device, **FramePipeline.table_kwargs("empty_device_tables", table_kwargs))
     # (a rank's own rows come out of the batches in frame order, labels ascending: with one rank that IS the gathered
     # order and the sort is skipped)
     gathered = gather_tables(merged, device=device, group=group, presorted=world == 1 and mine == sorted(mine),
                              chunk_bytes=chunk_bytes)
-    return pipe.host_tables(gathered, planes, **table_kwargs)
+    return pipe.host_tables(gathered, planes, **host_kw)

@@ -5,7 +5,9 @@ its outputs and workspace through torch's caching allocator and enqueues the
 libpcseg kernels on torch's current stream.  PyTorch is plumbing here (device
 memory + streams); all arithmetic is in ``csrc/*.hip``.
 """
+import collections
 import ctypes
+import functools
 
 import torch
 
@@ -537,20 +539,37 @@ def classify_regions(stats, cls_out, counts, tables):
     return out
 
 
-def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
-                 n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None):
-    """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device).  ``distance_slots``: the
-    class value -> type slot table (uint8[256] numpy); with it the result carries ``cell_dist`` (one value per row of
-    ``cells``, NaN = no entry) of pcseg_cell_distances.  ``neighbour_slots`` (the same kind of table) with ``n_types``
-    slots: the result also carries ``cell_nn`` = (dist, nn_id, pair_hist) of :func:`point_neighbours` over the rows of
-    ``cells`` (packed on the device by pcseg_neighbours_pack_cells), at the scale of ``cell_dist``; ``pair_hist`` is
-    None unless ``pair_edges`` is given.  ``refined`` (a :class:`ClassTables`): also the outputs of
-    :func:`refined_tables`, and with ``refined_points`` ``refined_nn`` = :func:`point_neighbours` over the refined
-    rows of kind >= 1 (same scale and edges as ``cell_nn``) followed by the points (xy, slot, ids, frame_offsets).
-    ``surface`` (a :class:`ClassTables`; .m:271-309): ``cell_sf`` = the dict of :func:`_surface_rows` over the rows of
-    ``cells`` against the surface of ``binary_fill_holes(res["recreated"] == Particle)``, at the scale of ``cell_dist``,
-    plus ``surface_px`` / ``filled_area`` (B,) and with ``surface_edges`` ``hist`` and ``shells``
-    (:func:`surface_shells`); with ``refined`` also ``refined_sf``, the same over the refined rows of kind >= 1."""
+Points = collections.namedtuple("Points", "coords slot ids frame_offsets")
+Points.__doc__ = """A packed point set on the device: ``coords`` (n, 2) float64, ``slot`` (n,) int32 type slot (-1: none),
+``ids`` (n,) int32 labels and ``frame_offsets`` (B + 1,) int64, the points of a frame contiguous."""
+
+
+def _alloc_points(n, B, device):
+    """Buffers for ``n`` points of ``B`` frames, one spare row each (an empty set still has non-null pointers): hand the
+    buffers to the library, then keep ``_head(points, n)``."""
+    return Points(torch.empty((n + 1, 2), dtype=torch.float64, device=device), torch.empty((n + 1,), dtype=torch.int32, device=device),
+                  torch.empty((n + 1,), dtype=torch.int32, device=device), torch.empty((B + 1,), dtype=torch.int64, device=device))
+
+
+def _head(points, n):
+    return Points(points.coords[:n], points.slot[:n], points.ids[:n], points.frame_offsets)
+
+
+def _addr(keep, what, t, dtype, shape):
+    """Address of a checked tensor for a field of a ctypes struct; ``keep`` holds the tensor until the kernels are enqueued."""
+    t = _req(t, dtype, len(shape))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s input of shape %s, expected %s" % (what, tuple(t.shape), tuple(shape)))
+    keep.append(t)
+    return t.data_ptr()
+
+
+# the dense tables of a batch as the optional stages need them: `cells` with its spare row, row counts, table workspace
+_Dense = collections.namedtuple("_Dense", "cells n_roi n_cell ws B")
+
+
+def _dense_tables(res, groups, frame_ids, C, ratios, check):
+    """pcseg_table_layout + pcseg_table_write: (dict of ``rois`` / ``cells`` / ``groups`` / ``frames``, :class:`_Dense`)."""
     lib = _lib.load()
     B, cap = res["stats"].shape[0], res["stats"].shape[1]
     dev = res["stats"].device
@@ -559,14 +578,7 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
     ti = _lib.TableInputs()
     ti.B, ti.cap, ti.C, ti.n_ratios = B, cap, C, len(ratios)
     keep = []  # tensors referenced by raw pointers until the kernels are enqueued
-
-    def ptr(t, dtype, shape):
-        t = _req(t, dtype, len(shape))
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError("table input of shape %s, expected %s" % (tuple(t.shape), tuple(shape)))
-        keep.append(t)
-        return t.data_ptr()
-
+    ptr = functools.partial(_addr, keep, "table")
     ti.frame_ids = ptr(frame_ids, torch.int64, (B,))
     ti.counts = ptr(res["counts"], torch.int32, (B,))
     ti.stats = ptr(res["stats"], torch.int64, (B, cap, 8))
@@ -614,57 +626,82 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
     _lib.check(lib.pcseg_table_write(ctypes.byref(ti), _ptr(rois), _ptr(cells), _ptr(grp), _ptr(frames), _ptr(ws), nbytes,
                                      _stream()), "table_write")
     out = {"rois": rois[:n_roi], "cells": cells[:n_cell], "groups": grp[:n_group], "frames": frames, "frame_ids": frame_ids}
+    return out, _Dense(cells, n_roi, n_cell, ws, B)
+
+
+def _cell_distances(d, slots, raster):
+    """pcseg_cell_distances: one value per row of ``cells``, NaN = no entry."""
+    dist = torch.empty((d.n_cell + 1,), dtype=torch.float64, device=d.cells.device)
+    _lib.check(_lib.load().pcseg_cell_distances(_ptr(d.cells), d.n_cell, d.cells.shape[1], ctypes.c_void_p(slots.ctypes.data),
+                                                float(raster), 512.0, _ptr(dist), d.B, _ptr(d.ws), d.ws.numel(), _stream()),
+               "cell_distances")
+    return dist[:d.n_cell]
+
+
+def _pack_cells(name, d, slots):
+    """pcseg_<name>: the rows of ``cells`` as :class:`Points` (``slots``: class value -> type slot, uint8[256] numpy)."""
+    pts = _alloc_points(d.n_cell, d.B, d.cells.device)
+    _lib.check(getattr(_lib.load(), "pcseg_" + name)(_ptr(d.cells), d.cells.shape[1], ctypes.c_void_p(slots.ctypes.data), d.B,
+                                                     _ptr(d.ws), d.ws.numel(), *[_ptr(t) for t in pts], _stream()), name)
+    return _head(pts, d.n_cell)
+
+
+def _neighbours(points, K, scale, edges):
+    dist, nn_id, hist = point_neighbours(*points, K, scale, edges)
+    return {"dist": dist, "nn_id": nn_id, "hist": hist, "points": points}
+
+
+def _surface_rows(points, surface, mask, scale, K, edges):
+    """:func:`surface_distances` of packed query rows, with what a table of them needs: dict of ``dist``, ``nearest``,
+    ``inside``, ``hist`` (None without ``edges``) and ``points``."""
+    dist, nearest, inside, hist = surface_distances(points.coords, points.frame_offsets, surface, scale, mask=mask,
+                                                    slot=points.slot, n_types=K, edges=edges)
+    return {"dist": dist, "nearest": nearest, "inside": inside, "hist": hist, "points": points}
+
+
+def _refined_surface(res, points, surface, mask, scale, K, edges):
+    """:func:`_surface_rows` of the refined points, at their centroids (pcseg_surface_pack_refined)."""
+    B, cap, n = res["stats"].shape[0], res["stats"].shape[1], points.ids.shape[0]
+    rc = torch.empty((n + 1, 2), dtype=torch.float64, device=points.ids.device)
+    _lib.check(_lib.load().pcseg_surface_pack_refined(_ptr(_req(res["ws_stats"], torch.int64, 3)), cap, _ptr(points.ids),
+                                                      _ptr(points.frame_offsets), n, B, _ptr(rc), _stream()), "surface_pack_refined")
+    return _surface_rows(points._replace(coords=rc[:n]), surface, mask, scale, K, edges)
+
+
+def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
+                 n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None):
+    """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device), then one stage per switch, in
+    this order.  ``distance_slots`` (the class value -> type slot table, uint8[256] numpy): ``cell_dist``, one value
+    per row of ``cells`` (NaN = no entry).  ``neighbour_slots`` (the same kind of table) with ``n_types`` slots:
+    ``cell_nn`` = dict of ``dist`` / ``nn_id`` / ``hist`` of :func:`point_neighbours` (``hist`` None without
+    ``pair_edges``) and the ``points`` (:class:`Points`) it ran over, the rows of ``cells``, at the scale of
+    ``cell_dist``.  ``surface`` (a :class:`ClassTables`; .m:271-309): ``cell_sf`` = the dict of :func:`_surface_rows`
+    over the rows of ``cells`` against the surface of ``binary_fill_holes(res["recreated"] == Particle)``, plus
+    ``surface_px`` / ``filled_area`` (B,) and with ``surface_edges`` ``hist`` and ``shells`` (:func:`surface_shells`).
+    ``refined`` (a :class:`ClassTables`): the outputs of :func:`refined_tables`, with ``refined_points``
+    ``refined_nn`` and with ``surface`` ``refined_sf``: the same two dicts over the refined rows of kind >= 1."""
+    out, d = _dense_tables(res, groups, frame_ids, C, ratios, check)
+    scale = 512.0 / float(raster)
     if distance_slots is not None:
-        dist = torch.empty((n_cell + 1,), dtype=torch.float64, device=dev)
-        _lib.check(lib.pcseg_cell_distances(_ptr(cells), n_cell, cells.shape[1], ctypes.c_void_p(distance_slots.ctypes.data),
-                                            float(raster), 512.0, _ptr(dist), B, _ptr(ws), nbytes, _stream()), "cell_distances")
-        out["cell_dist"] = dist[:n_cell]
+        out["cell_dist"] = _cell_distances(d, distance_slots, raster)
     if neighbour_slots is not None:
-        xy = torch.empty((n_cell + 1, 2), dtype=torch.float64, device=dev)
-        slot = torch.empty((n_cell + 1,), dtype=torch.int32, device=dev)
-        ids = torch.empty((n_cell + 1,), dtype=torch.int32, device=dev)
-        foff = torch.empty((B + 1,), dtype=torch.int64, device=dev)
-        _lib.check(lib.pcseg_neighbours_pack_cells(_ptr(cells), cells.shape[1], ctypes.c_void_p(neighbour_slots.ctypes.data), B,
-                                                   _ptr(ws), nbytes, _ptr(xy), _ptr(slot), _ptr(ids), _ptr(foff), _stream()),
-                   "neighbours_pack_cells")
-        out["cell_nn"] = point_neighbours(xy[:n_cell], slot[:n_cell], ids[:n_cell], foff, n_types, 512.0 / float(raster),
-                                          pair_edges)
-    sf = None
+        out["cell_nn"] = _neighbours(_pack_cells("neighbours_pack_cells", d, neighbour_slots), n_types, scale, pair_edges)
     if surface is not None:
-        K, scale = max(len(surface.slot_names), 1), 512.0 / float(raster)
+        K = max(len(surface.slot_names), 1)
         mask, sf = particle_surface(res["recreated"], surface.particle_value)
-        rc = torch.empty((n_cell + 1, 2), dtype=torch.float64, device=dev)
-        slot = torch.empty((n_cell + 1,), dtype=torch.int32, device=dev)
-        ids = torch.empty((n_cell + 1,), dtype=torch.int32, device=dev)
-        foff = torch.empty((B + 1,), dtype=torch.int64, device=dev)
-        _lib.check(lib.pcseg_surface_pack_cells(_ptr(cells), cells.shape[1], ctypes.c_void_p(surface.slot.ctypes.data), B, _ptr(ws),
-                                                nbytes, _ptr(rc), _ptr(slot), _ptr(ids), _ptr(foff), _stream()), "surface_pack_cells")
-        out["cell_sf"] = _surface_rows(rc[:n_cell], slot[:n_cell], ids[:n_cell], foff, sf, mask, scale, K, surface_edges)
+        out["cell_sf"] = _surface_rows(_pack_cells("surface_pack_cells", d, surface.slot), sf, mask, scale, K, surface_edges)
         out["cell_sf"].update(surface_px=sf["counts"], filled_area=sf["area"])
         if surface_edges is not None:
             out["cell_sf"]["shells"] = surface_shells(sf, mask, surface_edges, scale)
     if refined is not None:
-        want_points = refined_points or sf is not None
-        out.update(refined_tables(res, frame_ids, refined, ws, (n_roi, n_cell), check=check, points=want_points))
-        if want_points:
-            pts = out.pop("points")
+        want_points = refined_points or surface is not None
+        out.update(refined_tables(res, frame_ids, refined, d.ws, (d.n_roi, d.n_cell), check=check, points=want_points))
+        pts = out.pop("points", None)
         if refined_points:
-            out["refined_nn"] = point_neighbours(*pts, n_types, 512.0 / float(raster), pair_edges) + pts
-        if sf is not None:
-            _, pslot, pids, pfoff = pts
-            n_pts = pids.shape[0]
-            rc = torch.empty((n_pts + 1, 2), dtype=torch.float64, device=dev)
-            _lib.check(lib.pcseg_surface_pack_refined(_ptr(_req(res["ws_stats"], torch.int64, 3)), cap, _ptr(pids), _ptr(pfoff), n_pts,
-                                                      B, _ptr(rc), _stream()), "surface_pack_refined")
-            out["refined_sf"] = _surface_rows(rc[:n_pts], pslot, pids, pfoff, sf, mask, scale, K, surface_edges)
+            out["refined_nn"] = _neighbours(pts, n_types, scale, pair_edges)
+        if surface is not None:
+            out["refined_sf"] = _refined_surface(res, pts, sf, mask, scale, K, surface_edges)
     return out
-
-
-def _surface_rows(rc, slot, ids, foff, surface, mask, scale, K, edges):
-    """:func:`surface_distances` of packed query rows, with what a table of them needs: dict of ``dist``, ``nearest``,
-    ``inside``, ``hist`` (None without ``edges``), ``slot``, ``ids`` and ``frame_offsets``."""
-    dist, nearest, inside, hist = surface_distances(rc, foff, surface, scale, mask=mask, slot=slot, n_types=K, edges=edges)
-    return {"dist": dist, "nearest": nearest, "inside": inside, "hist": hist, "slot": slot, "ids": ids, "frame_offsets": foff}
 
 
 def label_parent(labels_a, labels_r, counts_r, cls_a=None, cap=None, stats_r=None, return_spilled=False):
@@ -720,14 +757,7 @@ def refined_inputs(res, lp, rc, frame_ids, n_slots):
     ri = _lib.RefinedInputs()
     ri.B, ri.cap, ri.n_slots = B, cap, int(n_slots)
     keep = []
-
-    def ptr(t, dtype, shape):
-        t = _req(t, dtype, len(shape))
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError("refined input of shape %s, expected %s" % (tuple(t.shape), tuple(shape)))
-        keep.append(t)
-        return t.data_ptr()
-
+    ptr = functools.partial(_addr, keep, "refined")
     parent, parent_px, n_overlap, cls_r, overflow = lp[:5]
     ri.frame_ids = ptr(frame_ids, torch.int64, (B,))
     ri.counts = ptr(res["counts"], torch.int32, (B,))
@@ -753,8 +783,8 @@ def refined_tables(res, frame_ids, tables, table_ws, table_rows, check=False, po
     """Goal 2 of refine_boundaries.py:1-12 for one batch whose dense tables :func:`build_tables` has just written
     (``table_ws``: its workspace, ``table_rows``: its (rois, cells) row counts): :func:`label_parent` of the refined
     ROIs, :func:`classify_regions` on them with their parent's class, then ``refined`` / ``cell_resolution`` /
-    ``frames_refined`` (float64, see include/pcseg.h).  ``points``: also ``points`` = (xy, slot, ids, frame_offsets) of
-    the refined rows of kind >= 1 for :func:`point_neighbours`.  ``check``: raise where a parent label exceeds cap."""
+    ``frames_refined`` (float64, see include/pcseg.h).  ``points``: also ``points`` = the refined rows of kind >= 1 as
+    :class:`Points` for :func:`point_neighbours`.  ``check``: raise where a parent label exceeds cap."""
     B, cap = res["stats"].shape[0], res["stats"].shape[1]
     dev = res["stats"].device
     lp = label_parent(res["labels"], res["ws_labels"], res["n_markers"], cls_a=res["cls_out"], cap=cap, stats_r=res["ws_stats"])
@@ -773,17 +803,14 @@ def refined_tables(res, frame_ids, tables, table_ws, table_rows, check=False, po
     refined = torch.empty((n_roi + 1, 11), dtype=torch.float64, device=dev)
     resolution = torch.empty((n_cell + 1, 5), dtype=torch.float64, device=dev)
     frames = torch.empty((B, 2 + 5 * K), dtype=torch.float64, device=dev)
-    pts = [None] * 4
-    if points:
-        pts = [torch.empty((n_pts + 1, 2), dtype=torch.float64, device=dev), torch.empty((n_pts + 1,), dtype=torch.int32, device=dev),
-               torch.empty((n_pts + 1,), dtype=torch.int32, device=dev), torch.empty((B + 1,), dtype=torch.int64, device=dev)]
+    pts = _alloc_points(n_pts, B, dev) if points else Points(None, None, None, None)
     _lib.check(lib.pcseg_refined_table_write(ctypes.byref(ri), _ptr(table_ws), table_ws.numel(), _ptr(refined), _ptr(resolution),
                                              _ptr(frames), *[_ptr(t) for t in pts], _ptr(ws), nbytes, _stream()),
                "refined_table_write")
     out = {"refined": refined[:n_roi], "cell_resolution": resolution[:n_cell], "frames_refined": frames,
            "parent_overflow": lp[4], "refined_nan_flag": rc["nan_flag"]}
     if points:
-        out["points"] = (pts[0][:n_pts], pts[1][:n_pts], pts[2][:n_pts], pts[3])
+        out["points"] = _head(pts, n_pts)
     del keep
     return out
 
@@ -803,8 +830,7 @@ def point_neighbours(xy, slot, ids, frame_offsets, K, scale, edges=None):
     n, B, K = xy.shape[0], frame_offsets.shape[0] - 1, int(K)
     if xy.shape[1] != 2 or slot.shape[0] != n or ids.shape[0] != n:
         raise ValueError("xy must be (n, 2) with n slots and ids")
-    import numpy as np
-    e = None if edges is None else np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))  # checked by the library
+    e, e_ptr, n_edges = _edges_arg(edges)
     dev = xy.device
     dist = torch.empty((n + 1, K), dtype=torch.float64, device=dev)  # (a spare row: never a null pointer)
     nn_id = torch.empty((n + 1, K), dtype=torch.int32, device=dev)
@@ -815,12 +841,10 @@ def point_neighbours(xy, slot, ids, frame_offsets, K, scale, edges=None):
     if B < 1:
         return dist[:n], nn_id[:n], (hist[:0] if hist is not None else None)
     lib = _lib.load()
-    n_edges = 0 if e is None else int(e.shape[0])
     nbytes = lib.pcseg_neighbours_workspace_bytes(n, B, K, n_edges)
     ws = _ws(nbytes, dev)
     _lib.check(lib.pcseg_point_neighbours(_ptr(xy), _ptr(slot), _ptr(ids), _ptr(frame_offsets), n, B, K, float(scale),
-                                          ctypes.c_void_p(e.ctypes.data) if e is not None else ctypes.c_void_p(0), n_edges,
-                                          _ptr(dist), _ptr(nn_id), _ptr(hist), _ptr(ws), nbytes, _stream()), "point_neighbours")
+                                          e_ptr, n_edges, _ptr(dist), _ptr(nn_id), _ptr(hist), _ptr(ws), nbytes, _stream()), "point_neighbours")
     return dist[:n], nn_id[:n], hist
 
 

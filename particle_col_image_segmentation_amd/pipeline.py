@@ -14,6 +14,8 @@ device-side tail kernels), so the whole chain of a batch can be captured once as
 (``FramePipeline(graph=True)``).  ``tables()`` downloads the result as plain numpy tables (the per-ROI table format of
 this build; the reference's CSV writers take the per-frame drop-in objects instead, see ``tiff_analysis``).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -164,10 +166,54 @@ def _lanes_for(device, lanes):
     return _LANES[key]
 
 
-# optional tables of tables_device, in schema order (table_columns names each only when its keyword asks for it)
-_EXTRA_TABLES = ("neighbours", "pair_hist", "refined", "cell_resolution", "frames_refined", "refined_neighbours",
-                 "refined_pair_hist", "surface", "frames_surface", "surface_hist", "surface_shells", "refined_surface",
-                 "refined_surface_hist")
+class TableSwitches(collections.namedtuple("TableSwitches", "neighbours pair_edges refined surface surface_edges")):
+    """The switches of the optional tables, as ``tables`` / ``tables_device`` / ``host_tables`` / ``table_columns`` /
+    ``empty_device_tables`` take them (see :meth:`FramePipeline.tables_device`)."""
+
+
+TableSwitches.__new__.__defaults__ = (False, None, False, False, None)
+
+# THE schema of the optional tables, in the order table_columns names them: name, on(switches), columns(type names,
+# switches), key columns of the gather's sort (distributed._SORT_COLS) and rows(pipeline, frame ids, ops.build_tables
+# result) -> the device table.  The refined_* tables are their namesakes over the refined rows of kind >= 1.
+_Table = collections.namedtuple("_Table", "name on columns key rows")
+_bins = lambda edges: ["bin_%d" % k for k in range(len(edges) - 1)] + ["over"]
+_per_type = lambda names, *fmts: [f % n for n in names for f in fmts]
+_nn_cols = lambda names, o: ["frame", "label", "slot"] + _per_type(names, "nn_um_%s") + _per_type(names, "nn_label_%s")
+_pair_cols = lambda names, o: ["frame", "slot_a", "slot_b", "n_pairs"] + _bins(o.pair_edges)
+_sf_cols = lambda names, o: ["frame", "label", "slot", "inside", "surface_um", "nearest_row", "nearest_col"]
+_sf_hist_cols = lambda names, o: ["frame", "side", "slot", "n"] + _bins(o.surface_edges)
+_sf_rows = lambda p, fid, sf: p._point_rows(fid, sf["points"], sf["inside"], sf["dist"], sf["nearest"])
+_pairs, _shells = (lambda o: o.pair_edges is not None), (lambda o: o.surface_edges is not None)
+OPTIONAL_TABLES = (
+    _Table("neighbours", lambda o: o.neighbours, _nn_cols, (0, 1),
+           lambda p, fid, raw: p._neighbour_rows(raw["cells"], raw["cell_nn"]["dist"], raw["cell_nn"]["nn_id"])),
+    _Table("pair_hist", _pairs, _pair_cols, (0, 1, 2), lambda p, fid, raw: p._pair_rows(fid, raw["cell_nn"]["hist"])),
+    _Table("refined", lambda o: o.refined, lambda names, o: ["frame", "label", "parent", "parent_px", "n_overlap", "class", "kind",
+                                                             "cells", "area", "centroid_row", "centroid_col"], (0, 1),
+           lambda p, fid, raw: raw["refined"]),
+    _Table("cell_resolution", lambda o: o.refined, lambda names, o: ["frame", "label", "children", "resolved", "cells_integrated"],
+           (0, 1), lambda p, fid, raw: raw["cell_resolution"]),
+    _Table("frames_refined", lambda o: o.refined,
+           lambda names, o: ["frame", "refined_nan_flag"] + _per_type(names, "%s_refined_cells", "%s_refined_clusters", "%s_resolved",
+                                                                      "%s_residual", "%s_count_integrated"),
+           (0, 1), lambda p, fid, raw: raw["frames_refined"]),
+    _Table("refined_neighbours", lambda o: o.refined and o.neighbours, _nn_cols, (0, 1),
+           lambda p, fid, raw: p._point_rows(fid, raw["refined_nn"]["points"], raw["refined_nn"]["dist"], raw["refined_nn"]["nn_id"])),
+    _Table("refined_pair_hist", lambda o: o.refined and _pairs(o), _pair_cols, (0, 1, 2),
+           lambda p, fid, raw: p._pair_rows(fid, raw["refined_nn"]["hist"])),
+    _Table("surface", lambda o: o.surface, _sf_cols, (0, 1), lambda p, fid, raw: _sf_rows(p, fid, raw["cell_sf"])),
+    _Table("frames_surface", lambda o: o.surface, lambda names, o: ["frame", "surface_px", "filled_area"], (0,),
+           lambda p, fid, raw: torch.stack([fid, raw["cell_sf"]["surface_px"], raw["cell_sf"]["filled_area"]], dim=1).to(torch.float64)),
+    _Table("surface_hist", _shells, _sf_hist_cols, (0, 1, 2), lambda p, fid, raw: p._side_rows(fid, raw["cell_sf"]["hist"])),
+    _Table("surface_shells", _shells, lambda names, o: ["frame", "side", "n_px"] + _bins(o.surface_edges), (0, 1),
+           lambda p, fid, raw: p._side_rows(fid, raw["cell_sf"]["shells"])),
+    _Table("refined_surface", lambda o: o.refined and o.surface, _sf_cols, (0, 1),
+           lambda p, fid, raw: _sf_rows(p, fid, raw["refined_sf"])),
+    _Table("refined_surface_hist", lambda o: o.refined and _shells(o), _sf_hist_cols, (0, 1, 2),
+           lambda p, fid, raw: p._side_rows(fid, raw["refined_sf"]["hist"])),
+)
+_EXTRA_TABLES = tuple(t.name for t in OPTIONAL_TABLES)
 
 
 def _download(tables):
@@ -513,6 +559,10 @@ class FramePipeline:
         ``refined_pair_hist``), ``surface`` its ``surface`` / ``frames_surface`` tables, ``surface_edges`` its
         ``surface_hist`` / ``surface_shells`` tables (and with ``refined`` ``refined_surface`` /
         ``refined_surface_hist``)."""
+        return self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
+                                                        surface_edges=surface_edges))
+
+    def _columns(self, C, ratios, switches):
         tb = self.tables_
         rn = [r[0] for r in ratios]
         cols = {
@@ -520,40 +570,26 @@ class FramePipeline:
                       "max_row1", "max_col1", "cells", "group", "group_combined"] + ["S%d" % k for k in range(C)] + rn,
             "rois": ["frame", "label", "area", "centroid_row", "centroid_col"] + ["S%d" % k for k in range(C)] + rn,
             "frames": ["frame", "n_labels", "n_rois", "particle_area", "particle_area_recreated", "tie_flag"]
-                      + [c % n for n in tb.slot_names for c in ("%s_present", "%s_count", "%s_density", "%s_area_ratio")],
+                      + _per_type(tb.slot_names, "%s_present", "%s_count", "%s_density", "%s_area_ratio"),
             "distances": ["frame", "label", "nearest_other_type_um"],
             "groups": ["frame", "slot", "group", "area", "centroid_row", "centroid_col", "min_row", "min_col",
                        "max_row1", "max_col1", "members"],
         }
-        if neighbours:
-            cols["neighbours"] = (["frame", "label", "slot"] + ["nn_um_%s" % n for n in tb.slot_names]
-                                  + ["nn_label_%s" % n for n in tb.slot_names])
-        if pair_edges is not None:
-            cols["pair_hist"] = (["frame", "slot_a", "slot_b", "n_pairs"] + ["bin_%d" % k for k in range(len(pair_edges) - 1)]
-                                 + ["over"])
-        if refined:
-            cols["refined"] = ["frame", "label", "parent", "parent_px", "n_overlap", "class", "kind", "cells", "area",
-                               "centroid_row", "centroid_col"]
-            cols["cell_resolution"] = ["frame", "label", "children", "resolved", "cells_integrated"]
-            cols["frames_refined"] = (["frame", "refined_nan_flag"]
-                                      + [c % n for n in tb.slot_names for c in ("%s_refined_cells", "%s_refined_clusters",
-                                                                                "%s_resolved", "%s_residual",
-                                                                                "%s_count_integrated")])
-            for k in ("neighbours", "pair_hist"):
-                if k in cols:
-                    cols["refined_" + k] = list(cols[k])
-        if surface:
-            cols["surface"] = ["frame", "label", "slot", "inside", "surface_um", "nearest_row", "nearest_col"]
-            cols["frames_surface"] = ["frame", "surface_px", "filled_area"]
-        if surface_edges is not None:
-            bins = ["bin_%d" % k for k in range(len(surface_edges) - 1)] + ["over"]
-            cols["surface_hist"] = ["frame", "side", "slot", "n"] + bins
-            cols["surface_shells"] = ["frame", "side", "n_px"] + bins
-        if refined:
-            for k in ("surface", "surface_hist"):
-                if k in cols:
-                    cols["refined_" + k] = list(cols[k])
+        cols.update((t.name, t.columns(tb.slot_names, switches)) for t in OPTIONAL_TABLES if t.on(switches))
         return cols
+
+    # which of run_sharded's table keywords each method takes
+    _TABLE_KEYWORDS = {"tables_device": ("ratios", "distances", "raster") + TableSwitches._fields,
+                       "host_tables": ("ratios", "distances", "raster") + TableSwitches._fields,
+                       "empty_device_tables": ("ratios",) + TableSwitches._fields}
+
+    @classmethod
+    def table_kwargs(cls, method, given):
+        """The entries of ``given`` (a caller's table keywords) that ``method`` takes: each keyword only when given."""
+        unknown = set(given) - set(cls._TABLE_KEYWORDS["tables_device"])
+        if unknown:
+            raise TypeError("unknown table keyword(s): %s" % ", ".join(sorted(unknown)))
+        return {k: given[k] for k in cls._TABLE_KEYWORDS[method] if k in given}
 
     def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0, neighbours=False,
                       pair_edges=None, refined=False, surface=False, surface_edges=None):
@@ -609,45 +645,19 @@ class FramePipeline:
             else:
                 fid = torch.tensor(ids, dtype=torch.int64).to(dev)
             groups = (res.get("groups") or {}) if self.merged else {}
-            dt = ops.build_tables(res, groups, fid, C, ratios, check=check,  # raises what BatchResult.check() raises
-                                  distance_slots=self.tables_.slot if distances else None, raster=raster,
-                                  neighbour_slots=self.tables_.slot if neighbours or pair_edges is not None else None,
-                                  n_types=len(self.tables_.slot_names), pair_edges=pair_edges,
-                                  refined=self.tables_ if refined else None,
-                                  refined_points=refined and (neighbours or pair_edges is not None),
-                                  surface=self.tables_ if surface or surface_edges is not None else None,
-                                  surface_edges=surface_edges)
-            dt["frames_rec"] = torch.cat([fid[:, None].to(torch.float64), dt.pop("frames").to(torch.float64)], dim=1)
-            del dt["frame_ids"]
-            dt["distances"] = self._distance_rows(dt["cells"], dt.pop("cell_dist", None))
-            nn = dt.pop("cell_nn", None)
-            if neighbours:
-                dt["neighbours"] = self._neighbour_rows(dt["cells"], nn[0], nn[1])
-            if pair_edges is not None:
-                dt["pair_hist"] = self._pair_rows(fid, nn[2])
-            for k in ("parent_overflow", "refined_nan_flag"):
-                dt.pop(k, None)
-            rn = dt.pop("refined_nn", None)
-            if rn is not None:
-                dist, nn_id, hist, _, slot, ids, foff = rn
-                if neighbours:
-                    frame = torch.repeat_interleave(fid.to(torch.float64), foff[1:] - foff[:-1], output_size=ids.shape[0])
-                    dt["refined_neighbours"] = torch.cat([frame[:, None], ids.to(torch.float64)[:, None],
-                                                          slot.to(torch.float64)[:, None], dist, nn_id.to(torch.float64)], dim=1)
-                if pair_edges is not None:
-                    dt["refined_pair_hist"] = self._pair_rows(fid, hist)
-            csf, rsf = dt.pop("cell_sf", None), dt.pop("refined_sf", None)
-            for name, sf in (("surface", csf), ("refined_surface", rsf)):
-                if sf is None:
-                    continue
-                if surface:
-                    dt[name] = self._surface_rows(fid, sf)
-                if surface_edges is not None:
-                    dt[name + "_hist"] = self._side_rows(fid, sf["hist"])
-            if surface:
-                dt["frames_surface"] = torch.stack([fid, csf["surface_px"], csf["filled_area"]], dim=1).to(torch.float64)
-            if surface_edges is not None:
-                dt["surface_shells"] = self._side_rows(fid, csf["shells"])
+            o = TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
+                              surface_edges=surface_edges)
+            want_nn, want_sf = neighbours or pair_edges is not None, surface or surface_edges is not None
+            raw = ops.build_tables(res, groups, fid, C, ratios, check=check,  # raises what BatchResult.check() raises
+                                   distance_slots=self.tables_.slot if distances else None, raster=raster,
+                                   neighbour_slots=self.tables_.slot if want_nn else None,
+                                   n_types=len(self.tables_.slot_names), pair_edges=pair_edges,
+                                   refined=self.tables_ if refined else None, refined_points=refined and want_nn,
+                                   surface=self.tables_ if want_sf else None, surface_edges=surface_edges)
+            dt = {k: raw[k] for k in ("rois", "cells", "groups")}
+            dt["frames_rec"] = torch.cat([fid[:, None].to(torch.float64), raw["frames"].to(torch.float64)], dim=1)
+            dt["distances"] = self._distance_rows(dt["cells"], raw.get("cell_dist"))
+            dt.update((t.name, t.rows(self, fid, raw)) for t in OPTIONAL_TABLES if t.on(o))
             if res._slot is not None:  # graph mode: the lane may overwrite this result once the tables are out
                 res._check_alive()
                 res._slot.release = torch.cuda.Event()
@@ -687,13 +697,12 @@ class FramePipeline:
         return torch.cat([fid.to(torch.float64)[:, None, None].expand(B, P, 1), ab[None].expand(B, P, 2),
                           hist.to(torch.float64)], dim=2).reshape(B * P, -1)
 
-    def _surface_rows(self, fid, sf):
-        """``[frame, label, slot, inside, surface_um, nearest_row, nearest_col]`` for every packed query row."""
-        foff, ids = sf["frame_offsets"], sf["ids"]
+    def _point_rows(self, fid, points, *columns):
+        """``[frame, label, slot, columns..]`` for every point of a packed point set (``ops.Points``)."""
+        foff, ids = points.frame_offsets, points.ids
         frame = torch.repeat_interleave(fid.to(torch.float64), foff[1:] - foff[:-1], output_size=ids.shape[0])
-        f64 = lambda t: t.to(torch.float64)
-        return torch.cat([frame[:, None], f64(ids)[:, None], f64(sf["slot"])[:, None], f64(sf["inside"])[:, None],
-                          sf["dist"][:, None], f64(sf["nearest"])], dim=1)
+        f64 = lambda t: t.to(torch.float64) if t.dim() == 2 else t.to(torch.float64)[:, None]
+        return torch.cat([f64(frame), f64(ids), f64(points.slot)] + [f64(c) for c in columns], dim=1)
 
     def _side_rows(self, fid, hist):
         """(B, 2, m + 2) or (B, 2, K, m + 2) counts -> ``[frame, side, (slot,) n, bins.., over]`` rows, (side, slot) order."""
@@ -707,7 +716,8 @@ class FramePipeline:
     def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None, refined=False,
                             surface=False, surface_edges=None):
         """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset)."""
-        cols = self.table_columns(C, ratios, neighbours, pair_edges, refined, surface, surface_edges)
+        cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
+                                                        surface_edges=surface_edges))
         mk = lambda n: torch.zeros((0, n), dtype=torch.float64, device=device)
         out = {"rois": mk(len(cols["rois"])), "cells": mk(len(cols["cells"])), "groups": mk(len(cols["groups"])),
                "frames_rec": mk(18), "distances": mk(3)}
@@ -723,7 +733,8 @@ class FramePipeline:
         (tiff_analysis.py:1018-1038; Python's decimal rounding, a handful of numbers per frame).  Every table's width
         must be the one :meth:`table_columns` names for ``C`` planes and these ``ratios``."""
         host = _download(dt)
-        cols = self.table_columns(C, ratios, neighbours, pair_edges, refined, surface, surface_edges)
+        cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
+                                                        surface_edges=surface_edges))
         tb = self.tables_
         out = {k: host[k] for k in ("cells", "rois", "groups")}
         for k in out:
@@ -766,6 +777,6 @@ class FramePipeline:
         cluster statistics).  ``neighbours`` / ``pair_edges`` / ``refined``: the ``neighbours`` / ``pair_hist`` and
         refined tables of :meth:`tables_device`; ``surface`` / ``surface_edges``: its surface-distance tables."""
         C = res["shape"][1]
-        dt = self.tables_device(res, frame_ids, ratios, check, distances, raster, neighbours, pair_edges, refined, surface,
-                                surface_edges)
-        return self.host_tables(dt, C, ratios, distances, raster, neighbours, pair_edges, refined, surface, surface_edges)
+        kw = dict(ratios=ratios, distances=distances, raster=raster, neighbours=neighbours, pair_edges=pair_edges, refined=refined,
+                  surface=surface, surface_edges=surface_edges)
+        return self.host_tables(self.tables_device(res, frame_ids, check=check, **kw), C, **kw)
