@@ -19,8 +19,8 @@ def _stale():
 
 
 def build(force=False, verbose=False, out_dir=None, extra_flags=None):
-    """``out_dir`` / ``extra_flags``: an A/B variant of the library (``-D`` tunables) built beside the product's, e.g. into
-    ``ab/<name>/libpcseg.so`` -- loaded with ``PCSEG_LIB=<path>`` (``_lib.load``), see profiles/r04/make_ab.sh."""
+    """``out_dir`` / ``extra_flags``: this tree's library built beside the product's, e.g. into ``ab/<name>/libpcseg.so``
+    (with other compiler flags if wanted) -- loaded with ``PCSEG_LIB=<path>`` (``_lib.load``): how two trees are A/B-ed."""
     lib_path = LIB if out_dir is None else os.path.join(out_dir, "libpcseg.so")
     if out_dir is None and not force and not _stale():
         return LIB
@@ -33,7 +33,7 @@ def build(force=False, verbose=False, out_dir=None, extra_flags=None):
     for src in SOURCES:
         obj = os.path.join(obj_dir, src.replace(".hip", ".o"))
         cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"] + flags + [
-            "-c", os.path.join(CSRC, src), "-o", obj]  # PCSEG_EXTRA_FLAGS: -D tunables for A/B builds (profiles/ab_compare.sh)
+            "-c", os.path.join(CSRC, src), "-o", obj]  # PCSEG_EXTRA_FLAGS: compiler flags of an A/B build
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -461,13 +461,6 @@ struct CclWs {
     int *corrupt;  // [B], cleared by ccl_roots / the callers that bring their own parents
 };
 
-static size_t ccl_ws_bytes(int B, int H, int W)
-{
-    int64_t n = (int64_t)H * W;
-    int nblk = (int)((n + SCAN_PIX - 1) / SCAN_PIX);
-    return align_up(sizeof(int) * (size_t)B * n) + align_up(sizeof(int) * (size_t)B * nblk) + align_up(sizeof(int) * (size_t)B);
-}
-
 static CclWs ccl_carve(Carver &cv, int B, int H, int W)
 {
     int64_t n = (int64_t)H * W;
@@ -476,6 +469,62 @@ static CclWs ccl_carve(Carver &cv, int B, int H, int W)
     ws.parent = cv.take<int>((size_t)B * n);
     ws.blockcount = cv.take<int>((size_t)B * ws.nblk);
     ws.corrupt = cv.take<int>((size_t)B);
+    return ws;
+}
+
+// the workspaces of the entry points below: what a CCL needs, then the entry point's own arrays
+struct DilateCclWs {
+    unsigned *bits, *dil;  // [B][ceil(H / 32)][W] column words: the selected classes, and their dilation
+};
+static DilateCclWs dilate_ccl_carve(Carver &cv, int B, int H, int W)
+{
+    const size_t words = (size_t)B * ((H + 31) / 32) * W;
+    DilateCclWs ws;
+    ws.bits = cv.take<unsigned>(words);
+    ws.dil = cv.take<unsigned>(words);
+    return ws;
+}
+// (the run-based path dilates into the caller's array: only the undilated words; B counts masks * frames for the multi form)
+static unsigned *dilate_ccl_runs_carve(Carver &cv, int B, int H, int W) { return cv.take<unsigned>((size_t)B * ((H + 31) / 32) * W); }
+
+struct FillHolesWs : CclWs {
+    uint8_t *flag;
+};
+static FillHolesWs fill_holes_carve(Carver &cv, int B, int H, int W)
+{
+    FillHolesWs ws;
+    static_cast<CclWs &>(ws) = ccl_carve(cv, B, H, W);
+    ws.flag = cv.take<uint8_t>((size_t)B * H * W);
+    return ws;
+}
+
+struct LocmaxWs : CclWs {
+    size_t nwords;              // 64-pixel words of the whole batch
+    unsigned long long *cbits;  // [nwords + 1] candidate bits
+    uint8_t *bad;
+    int *nonconst;  // [B]
+};
+static LocmaxWs locmax_carve(Carver &cv, int B, int H, int W)
+{
+    const size_t total = (size_t)B * H * W;
+    LocmaxWs ws;
+    static_cast<CclWs &>(ws) = ccl_carve(cv, B, H, W);
+    ws.nwords = (total + 63) / 64;
+    ws.cbits = cv.take<unsigned long long>(ws.nwords + 1);
+    ws.bad = cv.take<uint8_t>(total);
+    ws.nonconst = cv.take<int>(B);
+    return ws;
+}
+
+struct OverlapWs : CclWs {
+    int *area, *ov;
+};
+static OverlapWs overlap_carve(Carver &cv, int B, int H, int W)
+{
+    OverlapWs ws;
+    static_cast<CclWs &>(ws) = ccl_carve(cv, B, H, W);
+    ws.area = cv.take<int>((size_t)B * H * W);
+    ws.ov = cv.take<int>((size_t)B * H * W);
     return ws;
 }
 
@@ -987,11 +1036,7 @@ __global__ void __launch_bounds__(256) locmax_candidates_kernel(const int *__res
         uint8_t state = 2;
         if (r >= 0 && r < H && c >= 0 && c < W) {
             const int *up = tile + i - LM_SW, *dn = tile + i + LM_SW;
-#if defined(PCSEG_EXP_LOCMAX) && (PCSEG_EXP_LOCMAX & 4)
-            const int m = max(up[0], dn[0]) + 40;
-#else
             const int m = max(max(max(up[-1], up[0]), max(up[1], tile[i - 1])), max(max(tile[i + 1], dn[-1]), max(dn[0], dn[1])));
-#endif
             // 1: higher than all eight (nothing equal around it: neither a spoilt plateau nor a link), 3: a plateau pixel
             state = m < v ? 1 : (m == v ? 3 : 0);  // (OUTSIDE = INT_MIN is never higher)
             any_differs = any_differs || v != first_value;
@@ -1016,11 +1061,7 @@ __global__ void __launch_bounds__(256) locmax_candidates_kernel(const int *__res
             const uint8_t st = cand[j];
             const bool is_cand = (st & 1) != 0;
             bool touches = false;
-#if defined(PCSEG_EXP_LOCMAX) && (PCSEG_EXP_LOCMAX & 1)  // (ablation builds, profiles/r04/time_ops.py locmax: the pass without a phase)
-            if (false) {
-#else
             if (st == 3) {
-#endif
 #pragma unroll
                 for (int dr = -1; dr <= 1; ++dr)
 #pragma unroll
@@ -1057,7 +1098,6 @@ __global__ void __launch_bounds__(256) locmax_candidates_kernel(const int *__res
     // of this kernel's 256, profiles/r04/ab_logs/r4n_*)
     for (int i = threadIdx.x; i < CCL_TILE; i += 256) par[i] = i;
     __syncthreads();
-#if !(defined(PCSEG_EXP_LOCMAX) && (PCSEG_EXP_LOCMAX & 2))
     if (links) {
 #pragma unroll
         for (int kk = 0; kk < LM_TH * LM_TW / 256; ++kk) {
@@ -1071,7 +1111,6 @@ __global__ void __launch_bounds__(256) locmax_candidates_kernel(const int *__res
         }
     }
     __syncthreads();
-#endif
     // tile-local roots -> frame-wide parent entries, candidates only
     for (int i = threadIdx.x; i < CCL_TILE; i += 256) {
         const int r = r0 + i / CCL_TW, c = c0 + i % CCL_TW;
@@ -1214,7 +1253,9 @@ extern "C" {
 size_t pcseg_ccl_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    return ccl_ws_bytes(B, H, W);
+    Carver cv(nullptr, 0);
+    ccl_carve(cv, B, H, W);
+    return cv.off;
 }
 
 int pcseg_ccl8_equal_u8(const uint8_t *in, int32_t *labels, int32_t *counts, int B, int H, int W, void *workspace,
@@ -1241,8 +1282,9 @@ int pcseg_ccl4_bool(const uint8_t *in, int32_t *labels, int32_t *counts, int B, 
 size_t pcseg_dilate_ccl_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    int nch = (H + 31) / 32;
-    return 2 * align_up(sizeof(unsigned) * (size_t)B * nch * W);
+    Carver cv(nullptr, 0);
+    dilate_ccl_carve(cv, B, H, W);
+    return cv.off;
 }
 
 int pcseg_dilate_ccl_roots_u8(const uint8_t *in, uint64_t value_bits, int radius, int32_t *roots, int B, int H, int W,
@@ -1252,8 +1294,8 @@ int pcseg_dilate_ccl_roots_u8(const uint8_t *in, uint64_t value_bits, int radius
     hipStream_t s = (hipStream_t)stream;
     const int nch = (H + 31) / 32;
     Carver cv(workspace, workspace_bytes);
-    unsigned *bits = cv.take<unsigned>((size_t)B * nch * W);
-    unsigned *dil = cv.take<unsigned>((size_t)B * nch * W);
+    const DilateCclWs ws = dilate_ccl_carve(cv, B, H, W);
+    unsigned *bits = ws.bits, *dil = ws.dil;
     if (!cv.ok()) {
         set_error("dilate_ccl_roots: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -1275,8 +1317,9 @@ int pcseg_dilate_ccl_roots_u8(const uint8_t *in, uint64_t value_bits, int radius
 size_t pcseg_dilate_ccl_runs_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    int nch = (H + 31) / 32;
-    return align_up(sizeof(unsigned) * (size_t)B * nch * W);
+    Carver cv(nullptr, 0);
+    dilate_ccl_runs_carve(cv, B, H, W);
+    return cv.off;
 }
 
 int pcseg_dilate_ccl_runs_u8(const uint8_t *in, uint64_t value_bits, int radius, uint32_t *dilated_bits, int32_t *run_parent,
@@ -1287,7 +1330,7 @@ int pcseg_dilate_ccl_runs_u8(const uint8_t *in, uint64_t value_bits, int radius,
     hipStream_t s = (hipStream_t)stream;
     const int nch = (H + 31) / 32;
     Carver cv(workspace, workspace_bytes);
-    unsigned *bits = cv.take<unsigned>((size_t)B * nch * W);
+    unsigned *bits = dilate_ccl_runs_carve(cv, B, H, W);
     if (!cv.ok()) {
         set_error("dilate_ccl_runs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -1323,7 +1366,7 @@ int pcseg_dilate_ccl_runs_multi_u8(const uint8_t *in, const uint64_t *value_bits
     const int nch = (H + 31) / 32;
     const int BM = B * n_masks;
     Carver cv(workspace, workspace_bytes);
-    unsigned *bits = cv.take<unsigned>((size_t)BM * nch * W);
+    unsigned *bits = dilate_ccl_runs_carve(cv, BM, H, W);
     if (!cv.ok() || ((uintptr_t)bits & 15)) {
         set_error("dilate_ccl_runs_multi: workspace too small or misaligned (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -1369,7 +1412,9 @@ int pcseg_compact_labels(const int32_t *roots, int32_t *labels, int32_t *counts,
 size_t pcseg_fill_holes_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    return ccl_ws_bytes(B, H, W) + align_up((size_t)B * H * W);
+    Carver cv(nullptr, 0);
+    fill_holes_carve(cv, B, H, W);
+    return cv.off;
 }
 
 int pcseg_fill_holes(const uint8_t *mask, uint8_t *out, int B, int H, int W, void *workspace, size_t workspace_bytes,
@@ -1379,8 +1424,8 @@ int pcseg_fill_holes(const uint8_t *mask, uint8_t *out, int B, int H, int W, voi
     hipStream_t s = (hipStream_t)stream;
     int64_t n = (int64_t)H * W;
     Carver cv(workspace, workspace_bytes);
-    CclWs ws = ccl_carve(cv, B, H, W);
-    uint8_t *flag = cv.take<uint8_t>((size_t)B * n);
+    const FillHolesWs ws = fill_holes_carve(cv, B, H, W);
+    uint8_t *flag = ws.flag;
     if (!cv.ok()) {
         set_error("fill_holes: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -1401,8 +1446,9 @@ int pcseg_fill_holes(const uint8_t *mask, uint8_t *out, int B, int H, int W, voi
 size_t pcseg_local_maxima_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    size_t n = (size_t)H * W;
-    return ccl_ws_bytes(B, H, W) + align_up(8 * (((size_t)B * n + 63) / 64 + 1)) + align_up((size_t)B * n) + align_up(sizeof(int) * B);
+    Carver cv(nullptr, 0);
+    locmax_carve(cv, B, H, W);
+    return cv.off;
 }
 
 int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers, int32_t *counts, int B, int H, int W,
@@ -1413,12 +1459,12 @@ int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers
     hipStream_t s = (hipStream_t)stream;
     int64_t n = (int64_t)H * W;
     const int64_t total = (int64_t)B * n;
-    const size_t nwords = (size_t)((total + 63) / 64);
     Carver cv(workspace, workspace_bytes);
-    CclWs ws = ccl_carve(cv, B, H, W);
-    unsigned long long *cbits = cv.take<unsigned long long>(nwords + 1);
-    uint8_t *bad = cv.take<uint8_t>((size_t)B * n);
-    int *nonconst = cv.take<int>(B);
+    const LocmaxWs ws = locmax_carve(cv, B, H, W);
+    const size_t nwords = ws.nwords;
+    unsigned long long *cbits = ws.cbits;
+    uint8_t *bad = ws.bad;
+    int *nonconst = ws.nonconst;
     if (!cv.ok()) {
         set_error("local_maxima: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -1459,8 +1505,9 @@ int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers
 size_t pcseg_overlap_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    size_t n = (size_t)H * W;
-    return ccl_ws_bytes(B, H, W) + 2 * align_up(sizeof(int) * B * n);
+    Carver cv(nullptr, 0);
+    overlap_carve(cv, B, H, W);
+    return cv.off;
 }
 
 int pcseg_remove_overlapping(const uint8_t *dapi, const uint8_t *other, double threshold, uint8_t *out, int B, int H, int W,
@@ -1470,9 +1517,8 @@ int pcseg_remove_overlapping(const uint8_t *dapi, const uint8_t *other, double t
     hipStream_t s = (hipStream_t)stream;
     int64_t n = (int64_t)H * W;
     Carver cv(workspace, workspace_bytes);
-    CclWs ws = ccl_carve(cv, B, H, W);
-    int *area = cv.take<int>((size_t)B * n);
-    int *ov = cv.take<int>((size_t)B * n);
+    const OverlapWs ws = overlap_carve(cv, B, H, W);
+    int *area = ws.area, *ov = ws.ov;
     if (!cv.ok()) {
         set_error("remove_overlapping: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;

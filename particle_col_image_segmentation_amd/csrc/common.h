@@ -64,7 +64,9 @@ inline int check_shape(int B, int H, int W)
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// carve typed regions out of the caller's workspace
+// carve typed regions out of the caller's workspace.  A workspace's layout is written ONCE, as the function that takes its
+// regions: run on a null base it takes nothing (every region comes back null) and only adds up `off` -- which is what the
+// pcseg_*_workspace_bytes queries return
 struct Carver {
     char *base;
     size_t off = 0;
@@ -74,7 +76,7 @@ struct Carver {
     T *take(size_t n)
     {
         size_t bytes = align_up(n * sizeof(T));
-        T *p = (T *)(base + off);
+        T *p = base ? (T *)(base + off) : nullptr;
         off += bytes;
         return p;
     }

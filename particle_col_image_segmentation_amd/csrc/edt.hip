@@ -18,16 +18,7 @@
 namespace pcseg {
 
 constexpr int EDT_CH = 32;          // rows per bit word
-#ifndef PCSEG_EDT_REACH_ROWS
-#define PCSEG_EDT_REACH_ROWS 8
-#endif
-#ifndef PCSEG_EDT_REACH_BITS
-#define PCSEG_EDT_REACH_BITS 1  // 0 (A/B builds): every threshold epilogue takes the row-block pass (edt_reach_kernel)
-#endif
-#ifndef PCSEG_EDT_REACH_OCC
-#define PCSEG_EDT_REACH_OCC 1
-#endif
-constexpr int EDT_RB = PCSEG_EDT_REACH_ROWS;  // rows per block of the threshold pass (a divisor of the 32-row word)
+constexpr int EDT_RB = 8;           // rows per block of the threshold pass (a divisor of the 32-row word)
 static_assert(EDT_CH % EDT_RB == 0, "a block's rows lie in one bit word");
 constexpr unsigned G_INF = 0xFFFFu;  // "no zero pixel in this column"
 constexpr int EDT_STAGE_TRIPS = 4;   // column words a thread fetches as one batch when it stages a row block
@@ -378,7 +369,7 @@ __device__ __forceinline__ int reach_halfwidth(unsigned g, int R2)
 }
 
 template <typename Epi>
-__global__ void __launch_bounds__(256, PCSEG_EDT_REACH_OCC) edt_reach_kernel(const unsigned *__restrict__ bits, const uint16_t *__restrict__ up,
+__global__ void __launch_bounds__(256, 1) edt_reach_kernel(const unsigned *__restrict__ bits, const uint16_t *__restrict__ up,
                                                          const uint16_t *__restrict__ dn, const int *__restrict__ any_bg,
                                                          Epi epi, unsigned long long *__restrict__ count, int H, int W, int nch)
 {
@@ -431,22 +422,14 @@ __global__ void __launch_bounds__(256, PCSEG_EDT_REACH_OCC) edt_reach_kernel(con
 #pragma unroll
                 for (int j = 0; j < EDT_RB; ++j)
                     if (j < nrows) {
-#if defined(PCSEG_EXP_REACH) && (PCSEG_EXP_REACH & 2)  // (... without the bit scans of its staging)
-                        const unsigned v = ((wordv[t] >> (j0 + j)) & 1u) ? min(uv[t] + dv[t], 0x7FFFu) : 0u;
-#else
                         const unsigned v = min(vdist(wordv[t], valid, j0 + j, uv[t], dv[t], rows_in_word), 0x7FFFu);
-#endif
                         g[j * W4 + c] = (uint16_t)v;  // bit 15 stays free
                         near = near || v <= gmax;
                     }
             }
         }
     }
-#if defined(PCSEG_EXP_REACH) && (PCSEG_EXP_REACH & 1)  // (ablation builds, profiles/r04/time_ops.py: the pass without its scans)
-    const bool any_near = __syncthreads_or(near) && false;
-#else
     const bool any_near = __syncthreads_or(near);
-#endif
     const bool anybg = any_bg[b] != 0;
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int nchunks = (W + WAVE - 1) / WAVE;
@@ -645,14 +628,6 @@ struct EdtWs {
     int nch;
 };
 
-static size_t edt_ws_bytes(int B, int H, int W)
-{
-    int nch = (H + EDT_CH - 1) / EDT_CH;
-    size_t words = (size_t)B * nch * W;
-    return align_up(words * 4) + 2 * align_up(words * 2) + align_up(sizeof(int) * B) +
-           align_up(sizeof(unsigned long long) * B * ((H + EDT_RB - 1) / EDT_RB));
-}
-
 static EdtWs edt_carve(Carver &cv, int B, int H, int W)
 {
     EdtWs ws;
@@ -693,7 +668,7 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
         int D = (int)sqrt((double)R2);
         while (D * D > R2) --D;
         while ((D + 1) * (D + 1) <= R2) ++D;
-        if (PCSEG_EDT_REACH_BITS && D <= RBIT_MAXD) {
+        if (D <= RBIT_MAXD) {
             bit_path = true;
             tab.D = D;
             tab.nslots = 0;
@@ -759,14 +734,9 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
         };
         const size_t per_row = (size_t)(W + 2 * EDT_GUARD) * sizeof(unsigned);
         int rc;
-#ifndef PCSEG_EDT_ROWS
-#define PCSEG_EDT_ROWS 4
-#endif
         // rows per block: the search is a chain of dependent LDS reads, so occupancy beats amortising the staging --
         // 4 rows (17 KB at W = 1024, 8+ blocks per CU) measured 20 % faster than 8, 2 rows were tried too
-        if (PCSEG_EDT_ROWS == 8 && 8 * per_row <= 64 * 1024) rc = launch_rows(std::integral_constant<int, 8>());
-        else if (PCSEG_EDT_ROWS == 2 && 2 * per_row <= 160 * 1024) rc = launch_rows(std::integral_constant<int, 2>());
-        else if (4 * per_row <= 160 * 1024) rc = launch_rows(std::integral_constant<int, 4>());
+        if (4 * per_row <= 160 * 1024) rc = launch_rows(std::integral_constant<int, 4>());
         else rc = launch_rows(std::integral_constant<int, 1>());
         if (rc) return rc;
     }
@@ -783,7 +753,9 @@ extern "C" {
 size_t pcseg_edt_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    return edt_ws_bytes(B, H, W);
+    Carver cv(nullptr, 0);
+    edt_carve(cv, B, H, W);
+    return cv.off;
 }
 
 int pcseg_edt_sq_u8(const uint8_t *mask, int32_t *d2, int B, int H, int W, int cap, void *workspace, size_t workspace_bytes,

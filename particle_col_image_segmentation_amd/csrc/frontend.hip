@@ -43,11 +43,10 @@ __device__ __forceinline__ unsigned class1(const float *__restrict__ fr, int C, 
     return arg;
 }
 
+// (tried: asking the register allocator for eight waves per SIMD gives 64 registers with 20 bytes of scratch instead of 67
+// registers and seven waves; the plain bound stays)
 template <int CT>
-#ifndef PCSEG_FRONTEND_OCC
-#define PCSEG_FRONTEND_OCC 1  // A/B: 8 = 64 registers (20 bytes of scratch) and eight waves per SIMD instead of 67 and seven
-#endif
-__global__ void __launch_bounds__(256, PCSEG_FRONTEND_OCC) classmap_median_ccl_kernel(const float *__restrict__ stack, int C, uint8_t *__restrict__ z,
+__global__ void __launch_bounds__(256, 1) classmap_median_ccl_kernel(const float *__restrict__ stack, int C, uint8_t *__restrict__ z,
                                                                    int *__restrict__ parent, int H, int W)
 {
     // the histogram words are dead once the medians are out: the union-find parents take their place (18 KB per block
@@ -115,11 +114,7 @@ __global__ void __launch_bounds__(256, PCSEG_FRONTEND_OCC) classmap_median_ccl_k
         const int lr = 2 * (s / (MED_TW / 4)), lc = (s % (MED_TW / 4)) * 4;
         const int c = c0 + lc;
         uint32_t med[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-#if defined(PCSEG_EXP_FRONTEND) && (PCSEG_EXP_FRONTEND & 1)  // (ablation builds, profiles/r04/time_ops.py: the kernel's time without a phase)
-        for (int j = 0; j < 4; ++j) med[0][j] = med[1][j] = 1 + ((lr + lc) & 1);
-#else
         if (r0 + lr < H && c < W) median5_hot6_strip2(hot, lr, lc, med[0], med[1]);
-#endif
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int r = r0 + lr + half;
@@ -137,13 +132,16 @@ __global__ void __launch_bounds__(256, PCSEG_FRONTEND_OCC) classmap_median_ccl_k
     }
     __syncthreads();
     // (3) tile pass of the equal-value 8-connected labelling
-#if defined(PCSEG_EXP_FRONTEND) && (PCSEG_EXP_FRONTEND & 2)
-    for (int i = threadIdx.x; i < CCL_TILE; i += 256) par[i] = i;
-    __syncthreads();
-#else
     ccl_tile_unions<true>(key, par);
-#endif
     ccl_tile_store(key, par, parent, (int64_t)b * n, r0, c0, H, W);
+}
+
+// the workspace of the labelling (a whole pcseg_ccl_workspace_bytes block in front: ccl_plan and pcseg_ccl8_equal_u8 carve it
+// themselves), then a raw class map for the unfused path
+static uint8_t *classmap_label_carve(Carver &cv, size_t ccl_bytes, int B, int H, int W)
+{
+    cv.take<uint8_t>(ccl_bytes);
+    return cv.take<uint8_t>((size_t)B * H * W);
 }
 
 }  // namespace pcseg
@@ -155,7 +153,9 @@ extern "C" {
 size_t pcseg_classmap_label_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    return pcseg_ccl_workspace_bytes(B, H, W) + align_up((size_t)B * H * W);  // + a raw class map for the unfused path
+    Carver cv(nullptr, 0);
+    classmap_label_carve(cv, pcseg_ccl_workspace_bytes(B, H, W), B, H, W);
+    return cv.off;
 }
 
 int pcseg_classmap_label_f32(const float *stack, int C, uint8_t *denoised, int32_t *labels, int32_t *counts, int B, int H, int W,
@@ -165,10 +165,11 @@ int pcseg_classmap_label_f32(const float *stack, int C, uint8_t *denoised, int32
     static_assert(MED_TW == CCL_TW && MED_TH == CCL_TH, "one tile shape for the median and the union-find");
     hipStream_t s = (hipStream_t)stream;
     const size_t ccl_bytes = pcseg_ccl_workspace_bytes(B, H, W);
-    PCSEG_REQUIRE(workspace_bytes >= ccl_bytes + align_up((size_t)B * H * W), "workspace too small");
+    Carver cv(workspace, workspace_bytes);
+    uint8_t *raw = classmap_label_carve(cv, ccl_bytes, B, H, W);
+    PCSEG_REQUIRE(cv.ok(), "workspace too small");
     if (C > 5) {
         // more than five planes: class values above 5 do not fit the one-hot histogram words -- the separate kernels
-        uint8_t *raw = (uint8_t *)workspace + ccl_bytes;
         int rc = pcseg_argmax_planes_f32(stack, raw, B, C, H, W, stream);
         if (rc) return rc;
         rc = pcseg_median5_u8(raw, denoised, B, H, W, stream);

@@ -9,27 +9,10 @@
 // fallback walks rows: one wave per 64-pixel row segment, label runs from a ballot, closed-form run sums.
 #include "common.h"
 
-#ifndef PCSEG_SUMS_NT_LOADS
-// A/B (profiles/r04/ab_logs/r5a_*): the fused sums pass 378 us with non-temporal plane loads against 389-394 with plain ones; the
-// front end, whose tiles share halo rows through L2, lost a quarter with them (526 us against 426) and keeps plain loads
-#define PCSEG_SUMS_NT_LOADS 1
-#endif
-#ifndef PCSEG_LABELS_NT_LOADS
-#define PCSEG_LABELS_NT_LOADS 0  // A/B: the label images of the region passes (each read once per pass) as non-temporal loads too
-#endif
 namespace pcseg {
-__device__ __forceinline__ int4 ld_labels4(const int *p)
-{
-#if PCSEG_LABELS_NT_LOADS
-    typedef int i4v __attribute__((ext_vector_type(4)));
-    const i4v t = __builtin_nontemporal_load(reinterpret_cast<const i4v *>(p));
-    return make_int4(t.x, t.y, t.z, t.w);
-#else
-    return *reinterpret_cast<const int4 *>(p);
-#endif
-}
-}  // namespace pcseg
-namespace pcseg {
+
+// four labels of a row as one 16-byte load
+__device__ __forceinline__ int4 ld_labels4(const int *p) { return *reinterpret_cast<const int4 *>(p); }
 
 constexpr int RED_SLOTS = 256;
 constexpr int RED_MAXC = 8;
@@ -258,17 +241,11 @@ __device__ __forceinline__ void landed(unsigned q) { asm volatile("" ::"v"(q) : 
 // Column-run variant (W % 4 == 0): a lane owns 4 adjacent columns and walks DOWN COL_ROWS rows; it accumulates the
 // vertical run of equal labels in registers (area, row sum, plane sums in float64) and commits when the label
 // changes.  No cross-lane traffic at all; loads are int4 / float4 and coalesced along the row.
-#ifndef PCSEG_COL_ROWS
-#define PCSEG_COL_ROWS 32
-#endif
-constexpr int COL_ROWS = PCSEG_COL_ROWS;
+constexpr int COL_ROWS = 32;
 
-#ifndef PCSEG_RED_WAVES
-#define PCSEG_RED_WAVES 2
-#endif
 // (NC == 0 is kept for completeness; the pipeline's plane-free pass is region_stats_col_kernel below)
 template <int NC>
-__global__ void __launch_bounds__(256, NC > 0 ? PCSEG_RED_WAVES : 4) region_reduce_col_kernel(const int *__restrict__ labels, const float *__restrict__ planes,
+__global__ void __launch_bounds__(256, NC > 0 ? 2 : 4) region_reduce_col_kernel(const int *__restrict__ labels, const float *__restrict__ planes,
                                                                  const uint8_t *__restrict__ cls, unsigned long long sel, int C,
                                                                  int H, int W, int cap, long long *__restrict__ stats,
                                                                  double *__restrict__ sums, int *__restrict__ overflow)
@@ -457,10 +434,7 @@ __global__ void __launch_bounds__(256, NC > 0 ? PCSEG_RED_WAVES : 4) region_redu
 // few dozen pixels wide is eight lanes -- and only the first lane of each segment goes to the LDS table.
 // (measured on the way: a four- and an eight-row load ring on the old form, 180 and 197 us against 179 -- not the loads;
 // parking alone, every lane still committing for itself at the end: 200 us against 185 -- the atomics, not the branch.)
-#ifndef PCSEG_STATS_ROWS
-#define PCSEG_STATS_ROWS 32
-#endif
-constexpr int STATS_ROWS = PCSEG_STATS_ROWS;  // rows per block of the plane-free pass (block partials must fit 32 bits: <= 64)
+constexpr int STATS_ROWS = 32;  // rows per block of the plane-free pass (block partials must fit 32 bits: <= 64)
 static_assert(STATS_ROWS <= 64, "block-local sums are 32-bit");
 
 struct RunSum {
@@ -508,10 +482,7 @@ __device__ __forceinline__ void wave_commit(const RegionSlots &ls, long long *gs
     if (head && a.label > 0) run_commit(ls, gst, overflow, b, cap, a);
 }
 
-#ifndef PCSEG_STATS_OCC
-#define PCSEG_STATS_OCC 4
-#endif
-__global__ void __launch_bounds__(256, PCSEG_STATS_OCC) region_stats_col_kernel(const int *__restrict__ labels, int H, int W, int cap,
+__global__ void __launch_bounds__(256, 4) region_stats_col_kernel(const int *__restrict__ labels, int H, int W, int cap,
                                                                    long long *__restrict__ stats, int *__restrict__ overflow)
 {
     __shared__ int tags[RED_SLOTS];
@@ -698,17 +669,15 @@ __global__ void __launch_bounds__(256, (NC <= 5 && !STATS_B) ? 3 : 2) region_sum
                 b4n = ld_labels4(lb + at);
                 cwn = *reinterpret_cast<const unsigned *>(cbytes + at);
 #pragma unroll
-                for (int k = 0; k < NC; ++k)
-#if PCSEG_SUMS_NT_LOADS  // the planes are read once by this pass and not again: non-temporal loads (no reuse to keep in the caches)
-                    {
-                        typedef float f4v __attribute__((ext_vector_type(4)));
-                        f4v t = {0.f, 0.f, 0.f, 0.f};
-                        if (EXACT || k < C) t = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(pl + (int64_t)k * n + at));
-                        vn[k] = make_float4(t.x, t.y, t.z, t.w);
-                    }
-#else
-                    vn[k] = (EXACT || k < C) ? *reinterpret_cast<const float4 *>(pl + (int64_t)k * n + at) : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
+                for (int k = 0; k < NC; ++k) {
+                    // the planes are read once by this pass and not again: non-temporal loads (no reuse to keep in the
+                    // caches).  378 us against 389-394 with plain ones (profiles/r04/ab_logs/r5a_*); the front end, whose
+                    // tiles share halo rows through L2, lost a quarter with them (526 us against 426) and keeps plain loads
+                    typedef float f4v __attribute__((ext_vector_type(4)));
+                    f4v t = {0.f, 0.f, 0.f, 0.f};
+                    if (EXACT || k < C) t = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(pl + (int64_t)k * n + at));
+                    vn[k] = make_float4(t.x, t.y, t.z, t.w);
+                }
                 at += W;
             }
         };
@@ -1355,10 +1324,25 @@ int pcseg_region_sums2(const int32_t *labels_a, const uint8_t *cls, uint64_t sum
     return PCSEG_OK;
 }
 
+// scratch of the grouping kernels (B counts masks * frames for the fused form)
+struct MergeGroupsWs {
+    int *key, *gid, *first;
+};
+static MergeGroupsWs merge_groups_carve(Carver &cv, size_t B, int list_cap)
+{
+    MergeGroupsWs ws;
+    ws.key = cv.take<int>(B * list_cap);
+    ws.gid = cv.take<int>(B * list_cap);
+    ws.first = cv.take<int>(B * (list_cap + 1));
+    return ws;
+}
+
 size_t pcseg_merge_groups_workspace_bytes(int B, int list_cap)
 {
     if (B < 1 || list_cap < 1) return 0;
-    return align_up(sizeof(int) * (size_t)B * list_cap) * 2 + align_up(sizeof(int) * (size_t)B * (list_cap + 1));
+    Carver cv(nullptr, 0);
+    merge_groups_carve(cv, (size_t)B, list_cap);
+    return cv.off;
 }
 
 int pcseg_merge_groups(const int32_t *dilated_labels, int keys_are_roots, const int64_t *stats, const int32_t *region_list,
@@ -1369,9 +1353,8 @@ int pcseg_merge_groups(const int32_t *dilated_labels, int keys_are_roots, const 
                       list_cap >= 1 && check_shape(B, H, W),
                   "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    int *key = cv.take<int>((size_t)B * list_cap);
-    int *gid = cv.take<int>((size_t)B * list_cap);
-    int *first = cv.take<int>((size_t)B * (list_cap + 1));
+    const MergeGroupsWs ws = merge_groups_carve(cv, (size_t)B, list_cap);
+    int *key = ws.key, *gid = ws.gid, *first = ws.first;
     if (!cv.ok()) {
         set_error("merge_groups: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -1392,9 +1375,8 @@ int pcseg_merge_groups_runs(const uint32_t *dilated_bits, const int32_t *run_par
                       list_cap >= 1 && check_shape(B, H, W),
                   "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    int *key = cv.take<int>((size_t)B * list_cap);
-    int *gid = cv.take<int>((size_t)B * list_cap);
-    int *first = cv.take<int>((size_t)B * (list_cap + 1));
+    const MergeGroupsWs ws = merge_groups_carve(cv, (size_t)B, list_cap);
+    int *key = ws.key, *gid = ws.gid, *first = ws.first;
     if (!cv.ok()) {
         set_error("merge_groups_runs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -1423,9 +1405,8 @@ int pcseg_merge_groups_fused_multi(const uint32_t *dilated_bits, const int32_t *
     const int list_cap = cap;
     const size_t BM = (size_t)B * n_masks;
     Carver cv(workspace, workspace_bytes);
-    int *key = cv.take<int>(BM * list_cap);
-    int *gid = cv.take<int>(BM * list_cap);
-    int *first = cv.take<int>(BM * (list_cap + 1));
+    const MergeGroupsWs ws = merge_groups_carve(cv, BM, list_cap);
+    int *key = ws.key, *gid = ws.gid, *first = ws.first;
     if (!cv.ok()) {
         set_error("merge_groups_fused: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;

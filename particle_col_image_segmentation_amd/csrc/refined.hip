@@ -428,6 +428,36 @@ __global__ void __launch_bounds__(256) rf_write_kernel(pcseg_refined_inputs in, 
     }
 }
 
+struct LabelParentWs {
+    int *cand;                   // [B * cap][LP_SLOTS] (parent, pixels) pairs
+    int *spilled, *spill_list;   // [B * cap]
+    int *n_spill;                // [1]
+};
+static LabelParentWs label_parent_carve(Carver &cv, size_t rows)
+{
+    LabelParentWs ws;
+    ws.cand = cv.take<int>(2 * LP_SLOTS * rows);
+    ws.spilled = cv.take<int>(rows);
+    ws.spill_list = cv.take<int>(rows);
+    ws.n_spill = cv.take<int>(1);
+    return ws;
+}
+
+// pcseg_refined_layout writes the head, pcseg_refined_table_write reads it and uses the accumulators
+struct RefinedWs {
+    long long *n_points;  // [B]
+    long long *offsets;   // [B + 1]
+    int *acc;             // [B][cap][3]
+};
+static RefinedWs refined_carve(Carver &cv, int B, int cap)
+{
+    RefinedWs ws;
+    ws.n_points = cv.take<long long>(B);
+    ws.offsets = cv.take<long long>((size_t)B + 1);
+    ws.acc = cv.take<int>(3 * (size_t)B * cap);
+    return ws;
+}
+
 }  // namespace pcseg
 
 using namespace pcseg;
@@ -437,8 +467,9 @@ extern "C" {
 size_t pcseg_label_parent_workspace_bytes(int B, int H, int W, int cap)
 {
     if (!check_shape(B, H, W) || cap < 1) return 0;
-    const size_t rows = (size_t)B * cap;
-    return align_up(sizeof(int) * 2 * LP_SLOTS * rows) + 2 * align_up(sizeof(int) * rows) + align_up(sizeof(int));
+    Carver cv(nullptr, 0);
+    label_parent_carve(cv, (size_t)B * cap);
+    return cv.off;
 }
 
 int pcseg_label_parent(const int32_t *labels_a, const int32_t *labels_r, const int32_t *counts_r, const int64_t *stats_r,
@@ -451,10 +482,8 @@ int pcseg_label_parent(const int32_t *labels_a, const int32_t *labels_r, const i
                   "bad arguments");
     const size_t rows = (size_t)B * cap;
     Carver cv(workspace, workspace_bytes);
-    int *cand = cv.take<int>(2 * LP_SLOTS * rows);
-    int *spilled = cv.take<int>(rows);
-    int *spill_list = cv.take<int>(rows);
-    int *n_spill = cv.take<int>(1);
+    const LabelParentWs ws = label_parent_carve(cv, rows);
+    int *cand = ws.cand, *spilled = ws.spilled, *spill_list = ws.spill_list, *n_spill = ws.n_spill;
     if (!cv.ok()) {
         set_error("label_parent: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -484,8 +513,9 @@ int pcseg_label_parent(const int32_t *labels_a, const int32_t *labels_r, const i
 size_t pcseg_refined_workspace_bytes(int B, int cap)
 {
     if (B < 1 || cap < 1) return 0;
-    return align_up(sizeof(long long) * (size_t)B) + align_up(sizeof(long long) * ((size_t)B + 1)) +
-           align_up(sizeof(int) * 3 * (size_t)B * cap);
+    Carver cv(nullptr, 0);
+    refined_carve(cv, B, cap);
+    return cv.off;
 }
 
 static int refined_check(const pcseg_refined_inputs *in)
@@ -500,9 +530,8 @@ int pcseg_refined_layout(const pcseg_refined_inputs *in, int64_t *totals, void *
 {
     PCSEG_REQUIRE(refined_check(in) && totals && workspace, "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    long long *n_points = cv.take<long long>(in->B);
-    long long *offsets = cv.take<long long>((size_t)in->B + 1);
-    cv.take<int>(3 * (size_t)in->B * in->cap);
+    const RefinedWs ws = refined_carve(cv, in->B, in->cap);
+    long long *n_points = ws.n_points, *offsets = ws.offsets;
     if (!cv.ok()) {
         set_error("refined_layout: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -527,9 +556,9 @@ int pcseg_refined_table_write(const pcseg_refined_inputs *in, const void *table_
     Carver tv(const_cast<void *>(table_workspace), table_workspace_bytes);
     const TableOffsets tb = table_offsets(tv, in->B);
     Carver cv(workspace, workspace_bytes);
-    cv.take<long long>(in->B);
-    const long long *pt_offsets = cv.take<long long>((size_t)in->B + 1);
-    int *acc = cv.take<int>(3 * (size_t)in->B * in->cap);
+    const RefinedWs ws = refined_carve(cv, in->B, in->cap);
+    const long long *pt_offsets = ws.offsets;
+    int *acc = ws.acc;
     if (!tv.ok() || !cv.ok()) {
         set_error("refined_table_write: workspace too small");
         return PCSEG_ERR_WORKSPACE;

@@ -237,6 +237,21 @@ __global__ void __launch_bounds__(256) cell_distance_kernel(const double *__rest
     }
 }
 
+// the table workspace: the row counts and offsets in front (all that a reader of the workspace looks at: table_offsets),
+// then the writer's scratch
+struct TableWs {
+    TableOffsets to;
+    int *own, *comb;  // [B][cap]
+};
+static TableWs table_carve(Carver &cv, int B, int cap)
+{
+    TableWs ws;
+    ws.to = table_offsets(cv, B);
+    ws.own = cv.take<int>((size_t)B * cap);
+    ws.comb = cv.take<int>((size_t)B * cap);
+    return ws;
+}
+
 }  // namespace pcseg
 
 using namespace pcseg;
@@ -246,7 +261,9 @@ extern "C" {
 size_t pcseg_table_workspace_bytes(int B, int cap)
 {
     if (B < 1 || cap < 1) return 0;
-    return 2 * align_up(sizeof(long long) * 3 * (size_t)B) + 2 * align_up(sizeof(int) * (size_t)B * cap);
+    Carver cv(nullptr, 0);
+    table_carve(cv, B, cap);
+    return cv.off;
 }
 
 static int table_check(const pcseg_table_inputs *in)
@@ -281,15 +298,13 @@ int pcseg_table_write(const pcseg_table_inputs *in, double *rois, double *cells,
 {
     PCSEG_REQUIRE(table_check(in) && rois && cells && groups && frames && workspace, "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    const TableOffsets to = table_offsets(cv, in->B);
-    int *own = cv.take<int>((size_t)in->B * in->cap);
-    int *comb = cv.take<int>((size_t)in->B * in->cap);
+    const TableWs ws = table_carve(cv, in->B, in->cap);
     if (!cv.ok()) {
         set_error("table_write: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
-    PCSEG_LAUNCH(table_write_kernel, dim3(in->B), dim3(256), 0, (hipStream_t)stream, *in, to.offsets, rois, cells, groups,
-                 (long long *)frames, own, comb);
+    PCSEG_LAUNCH(table_write_kernel, dim3(in->B), dim3(256), 0, (hipStream_t)stream, *in, ws.to.offsets, rois, cells, groups,
+                 (long long *)frames, ws.own, ws.comb);
     PCSEG_CHECK_LAUNCH();
     return PCSEG_OK;
 }

@@ -63,35 +63,6 @@ __global__ void __launch_bounds__(256) ws_init_kernel(const float *__restrict__ 
 }
 
 template <typename T>
-__device__ __forceinline__ void ws_load_tile(T *s, const T *__restrict__ g, int r0, int c0, int H, int W, T fill)
-{
-    for (int i = threadIdx.x; i < WS_S * WS_S; i += 256) {
-        int lr = i / WS_S, lc = i % WS_S;
-        int r = r0 + lr - 1, c = c0 + lc - 1;
-        s[lr * WS_P + lc] = (r >= 0 && r < H && c >= 0 && c < W) ? g[rowoff(r, W) + c] : fill;
-    }
-}
-
-// The tile fixed points below are run as DIRECTIONAL SWEEPS: wave 0 sweeps the 64 rows left->right (one row per
-// lane), wave 1 right->left, wave 2 the 64 columns top->bottom, wave 3 bottom->top, all at once.  Every update is
-// monotone (min / 0->label), so concurrent sweeps may read each other's half-finished values: a stale read only
-// costs another outer iteration.  One sweep carries information across the whole tile, so the number of outer
-// iterations is the number of direction changes of the dependency paths, not their length.
-struct SweepLine {
-    int start, step;  // LDS index of the halo element in front of the line, and the index step along the line
-};
-__device__ __forceinline__ SweepLine ws_line()
-{
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    SweepLine s;
-    if (w == 0) { s.start = (lane + 1) * WS_P; s.step = 1; }
-    else if (w == 1) { s.start = (lane + 1) * WS_P + WS_S - 1; s.step = -1; }
-    else if (w == 2) { s.start = lane + 1; s.step = WS_P; }
-    else { s.start = (WS_S - 1) * WS_P + lane + 1; s.step = -WS_P; }
-    return s;
-}
-
-template <typename T>
 __device__ __forceinline__ void ws_store_tile(const T *s, T *__restrict__ g, int r0, int c0, int H, int W)
 {
     for (int i = threadIdx.x; i < WS_T * WS_T; i += blockDim.x) {
@@ -127,120 +98,29 @@ __device__ __forceinline__ void ws_mark_changed_edges(const T *s, const T *__res
 // y = value): a sweep step is ONE ds_read_b64 instead of two ds_read_b32 -- the kernel is bound by LDS-array cycles, and
 // the b64 form moves twice the bytes per cycle (odd pitch: conflict-free for row and column sweeps alike).
 //
-// Geometry of a relaxation tile of edge T (64 or 128; PCSEG_WS_RELAX_TILE picks, 64 is the default).  T = 128 fills the
-// 160 KB LDS of a CDNA4 CU -- the tile with its halo is 130 x 131 x 8 B = 133 KB, ONE workgroup of 16 waves per CU (as
+// Geometry of a relaxation tile of edge T = 64: four tiles (4 x 36 KB of LDS) and sixteen waves per CU.  A 128-pixel tile
+// fills the 160 KB LDS of a CDNA4 CU -- with its halo it is 130 x 131 x 8 B = 133 KB, ONE workgroup of 16 waves per CU (as
 // many waves as four 64-tiles bring), the four 64 x 64 quadrants exchange their rims through LDS inside one iteration
 // -- and MEASURED SLOWER on the benchmark batch (3.30 ms of relaxation per step against 2.16 ms, rounds 1133 / 1121 /
 // 533 / 240 us against 742 / 606 / 327 / 175 us): with one workgroup per CU nothing runs under a tile's load, store and
 // 16-wave barriers, the shifted tiling has 81 tiles per 1024^2 frame instead of 64 (+27 %) where 64-tiles have 289
 // instead of 256 (+13 %), and the number of rounds hardly drops because levels travel along winding paths, not tile
 // diameters.
-#ifndef PCSEG_WS_SWEEP_MASKS
-// change tracking of the quadrant sweep (A/B builds): 0 = per-lane xor / or, every cell of a changed batch goes through its
-// LDS atomic (round 2); 1 = scalar lane masks from one v_cmp per step; 2 = 1 + only the lanes that lowered a cell issue
-// the atomic.  Same box, relaxation us per launch / overlapped ms per step (profiles/r03/ab_run.sh): 0: 119.7 / 5.85-5.93,
-// 1: 116.7 / 5.83-5.84, 2: 124.1 / 6.09-6.31 -- an exec-masked ds_min costs the LDS what a full one does, and the eight
-// scalar branches per batch come on top: 1 stays
-#define PCSEG_WS_SWEEP_MASKS 1
-#endif
-#ifndef PCSEG_WS_FSM
-#define PCSEG_WS_FSM 1  // 1: quadrant (raster-order wavefront) sweeps, 0: line sweeps -- see ws_quadrant_sweep
-#endif
 template <int T>
 struct RelaxGeom {
-    static_assert(T == 64 || T == 128, "relaxation tiles are 64 or 128 pixels wide");
+    static_assert(T == 64, "relaxation tiles are 64 pixels wide: one wave per sweep quadrant");
     static constexpr int S = T + 2;        // with halo
-    // LDS row pitch in elements.  Line sweeps (one row or column per lane) want it odd; the wavefront sweeps of the
-    // quadrant scheme walk lane l along row l at column (step - l), i.e. lanes are P - 1 or P + 1 elements apart: even P
-    static constexpr int P = (PCSEG_WS_FSM && T == 64) ? T + 4 : T + 3;
+    // LDS row pitch in elements.  The wavefront sweeps of the quadrant scheme walk lane l along row l at column
+    // (step - l), i.e. lanes are P - 1 or P + 1 elements apart: even P
+    static constexpr int P = T + 4;
     static constexpr int PAD = 8;          // elements in front of and behind the tile (wavefront lanes read past their row's ends)
     static constexpr int N = S * P + 2 * PAD;  // LDS elements
-    static constexpr int G = T / 64;       // 64-line groups per direction, and 64-cell segments per line
-    static constexpr int THREADS = 4 * G * G * 64;  // one wave per (direction, line group, segment)
+    static constexpr int THREADS = 4 * 64;  // one wave per sweep quadrant
     static constexpr int HE = T / 2;       // cells of a half edge
     static constexpr size_t LDS_BYTES = sizeof(uint2) * N;
 };
 
-// one directional sweep of a 64-cell segment of a line: L(i) = min(L(i), max(value(i), L(previous cell))).  Eight cells
-// are fetched before any of them is updated: the reads of a batch carry no dependency on the batch's writes (a cell is
-// written only when it is processed), and what another wave writes meanwhile is picked up an iteration later, which
-// the monotone update tolerates.  The batch loop is NOT unrolled: four direction-specific bodies have to stay resident
-// in the I-cache.
-#ifndef WS_BATCH
-#define WS_BATCH 8
-#endif
-#ifndef PCSEG_WS_ASM_READ
-#define PCSEG_WS_ASM_READ 1
-#endif
-template <int STEP>
-__device__ __forceinline__ bool ws_sweep(uint2 *sLV, int start)
-{
-    unsigned *sLw = reinterpret_cast<unsigned *>(sLV);  // the L half of element i is word 2 * i
-    unsigned diff = 0;  // != 0 once a cell of this line was lowered
-    unsigned prev = sLV[start].x;
-    int base = start + STEP;
-#pragma unroll 1
-    for (int k0 = 0; k0 < 64; k0 += WS_BATCH, base += WS_BATCH * STEP) {
-        uint2 lv[WS_BATCH];
-#if PCSEG_WS_ASM_READ
-        // The eight reads are written as ds_read_b64 by hand: the compiler pairs neighbouring reads into ds_read2_b64,
-        // which the LDS serves at HALF the bytes per clock of ds_read_b64 (MI355X_MICROARCH.md, LDS table: 8 cycles
-        // for 2 x 512 B against 2 cycles per 512 B), and this kernel is bound by LDS-array cycles.  Offsets are
-        // unsigned: a batch is addressed from its lowest cell.
-        {
-            static_assert(WS_BATCH == 8 || WS_BATCH == 16, "the hand-written batch read is eight or sixteen wide");
-            typedef unsigned u2v __attribute__((ext_vector_type(2)));
-            constexpr int A = STEP < 0 ? -STEP : STEP;
-            const int low = STEP < 0 ? base + (WS_BATCH - 1) * STEP : base;
-            const unsigned addr = (unsigned)(uintptr_t)(sLV + low);
-            u2v t[WS_BATCH];
-#define PCSEG_DS_READ(j) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(t[j]) : "v"(addr), "n"(8 * A * (STEP < 0 ? WS_BATCH - 1 - (j) : (j))))
-            PCSEG_DS_READ(0); PCSEG_DS_READ(1); PCSEG_DS_READ(2); PCSEG_DS_READ(3);
-            PCSEG_DS_READ(4); PCSEG_DS_READ(5); PCSEG_DS_READ(6); PCSEG_DS_READ(7);
-#if WS_BATCH == 16
-            PCSEG_DS_READ(8); PCSEG_DS_READ(9); PCSEG_DS_READ(10); PCSEG_DS_READ(11);
-            PCSEG_DS_READ(12); PCSEG_DS_READ(13); PCSEG_DS_READ(14); PCSEG_DS_READ(15);
-            asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]));
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]), "+v"(t[15]));
-#else
-            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]));
-#endif
-#undef PCSEG_DS_READ
-#pragma unroll
-            for (int j = 0; j < WS_BATCH; ++j) lv[j] = make_uint2(t[j].x, t[j].y);
-        }
-#else
-#pragma unroll
-        for (int j = 0; j < WS_BATCH; ++j) lv[j] = sLV[base + j * STEP];
-#endif
-        // the running values come from registers alone; the LDS updates of a batch are skipped as a whole when no lane
-        // lowered anything in it (late iterations, converged neighbourhoods): one ballot instead of eight atomics
-        unsigned nw[WS_BATCH];
-        unsigned batch_diff = 0;
-#pragma unroll
-        for (int j = 0; j < WS_BATCH; ++j) {
-            // value <= L holds for every cell (seeds start at their value, everything else at +inf, and a level never
-            // drops below its cell's value), so min(L, max(value, prev)) is the MEDIAN of the three: one v_med3_u32 on
-            // the serial chain instead of v_max followed by v_min
-            const unsigned cur = lv[j].x, v = lv[j].y;
-            nw[j] = min(max(v, prev), max(min(v, prev), cur));
-            batch_diff |= cur ^ nw[j];
-            prev = nw[j];
-        }
-        if (__any(batch_diff != 0)) {
-            // unconditional LDS atomic min per cell: nothing under an exec mask (compare + store to the cell or to a pad
-            // word measured 13 % slower, a compare + masked store 10 %), and still monotone when another wave lowered
-            // the cell since the batch was read
-#pragma unroll
-            for (int j = 0; j < WS_BATCH; ++j) atomicMin(&sLw[2 * (base + j * STEP)], nw[j]);
-            diff |= batch_diff;
-        }
-    }
-    return diff != 0;
-}
-
-// QUADRANT SWEEPS (fast-sweeping order; PCSEG_WS_FSM, the default).  A line sweep carries a level along one axis only,
+// QUADRANT SWEEPS (fast-sweeping order).  A line sweep carries a level along one axis only,
 // so a minimax path that turns costs an iteration per turn -- and the paths of a noisy probability map turn every few
 // pixels: isolated 64 x 64 tiles of the benchmark frames need 14 iterations of the four line sweeps on average (35 at
 // worst).  A raster-order Gauss-Seidel sweep
@@ -299,6 +179,9 @@ __device__ __forceinline__ bool ws_quadrant_sweep(uint2 *sLV, int lane)
         // scalar mask (one VALU operation each, no per-lane compare).
         const unsigned base_a = DC > 0 ? a0 + 8u * (unsigned)ub : a0 - 8u * (unsigned)ub - 56u;
         const unsigned base_b = DC > 0 ? base_a - 512u : base_a + 512u;
+        // The reads are written as ds_read_b64 by hand: the compiler pairs neighbouring reads into ds_read2_b64, which the
+        // LDS serves at HALF the bytes per clock of ds_read_b64 (MI355X_MICROARCH.md, LDS table: 8 cycles for 2 x 512 B
+        // against 2 cycles per 512 B).
         unsigned ba[8];
         u2v t[8];
 #define PCSEG_DS_READ(k)                                                                                                   \
@@ -312,11 +195,7 @@ __device__ __forceinline__ bool ws_quadrant_sweep(uint2 *sLV, int lane)
 #undef PCSEG_DS_READ
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]));
         unsigned wr[8];
-        bool lowered[8];  // per lane "this step lowered its cell": lives as a lane mask in an SGPR pair (the v_cmp's result)
         unsigned long long batch_diff = 0;
-#if PCSEG_WS_SWEEP_MASKS == 0
-        unsigned lane_diff = 0;
-#endif
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             // lane l takes lane l - 1's result of the previous step; lane 0 has no row above (wave_shr:1, `old` = +inf)
@@ -326,28 +205,23 @@ __device__ __forceinline__ bool ws_quadrant_sweep(uint2 *sLV, int lane)
             asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(lf) : "v"(left), "v"(halo), "s"(at0));
             const unsigned cur = t[k].x, v = t[k].y;
             const unsigned m = min(up, lf);
-            const unsigned cand = min(max(v, m), max(min(v, m), cur));  // median(value, m, cur) = min(cur, max(value, m))
+            // value <= L holds for every cell (seeds start at their value, everything else at +inf, and a level never
+            // drops below its cell's value), so min(cur, max(value, m)) is the MEDIAN of the three: one v_med3_u32 on
+            // the serial chain instead of v_max followed by v_min
+            const unsigned cand = min(max(v, m), max(min(v, m), cur));
             wr[k] = cand;
-#if PCSEG_WS_SWEEP_MASKS == 0
-            lane_diff |= cur ^ cand;
-            lowered[k] = true;
-#else
-            lowered[k] = cur != cand;
-            batch_diff |= __ballot(lowered[k]);
-#endif
+            batch_diff |= __ballot(cur != cand);
             left = cand;
             prev = cand;
         }
-#if PCSEG_WS_SWEEP_MASKS == 0
-        batch_diff = __ballot(lane_diff != 0);
-#endif
         if (batch_diff != 0) {
-            // unconditional LDS atomic min per cell of a changed batch (variant 2 predicates it per lane: measured slower);
-            // still monotone when another wave lowered the cell since the batch was read.  (The level is the first word of
-            // the cell: the read's address and offset serve the atomic as they are.)
+            // unconditional LDS atomic min per cell of a changed batch: issuing it only from the lanes that lowered their cell
+            // measured slower (relaxation 124.1 us per launch against 116.7, profiles/r03/ab_run.sh) -- an exec-masked ds_min
+            // costs the LDS what a full one does, and the eight scalar branches per batch come on top.  Still monotone when
+            // another wave lowered the cell since the batch was read.  (The level is the first word of the cell: the read's
+            // address and offset serve the atomic as they are.)
 #define PCSEG_DS_MIN(k)                                                                                                             \
-            if (PCSEG_WS_SWEEP_MASKS < 2 || lowered[k])                                                                                 \
-                asm volatile("ds_min_u32 %0, %1 offset:%2" : : "v"(ba[k]), "v"(wr[k]), "n"(DC > 0 ? 8 * (k) : 8 * (7 - (k))) : "memory");
+            asm volatile("ds_min_u32 %0, %1 offset:%2" : : "v"(ba[k]), "v"(wr[k]), "n"(DC > 0 ? 8 * (k) : 8 * (7 - (k))) : "memory");
             PCSEG_DS_MIN(0) PCSEG_DS_MIN(1) PCSEG_DS_MIN(2) PCSEG_DS_MIN(3)
             PCSEG_DS_MIN(4) PCSEG_DS_MIN(5) PCSEG_DS_MIN(6) PCSEG_DS_MIN(7)
 #undef PCSEG_DS_MIN
@@ -404,7 +278,7 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
     }
     // 64 x 64 units actually processed (measurement: bench.py roofline), spread over 16 cache lines: one counter would
     // make every block of the launch queue on the same line
-    if (tid == 0) atomicAdd(any_changed + WS_CNT0 + WS_CNT_STRIDE * ((tx + 5 * ty + 3 * b) & 15), G::G * G::G);
+    if (tid == 0) atomicAdd(any_changed + WS_CNT0 + WS_CNT_STRIDE * ((tx + 5 * ty + 3 * b) & 15), 1);
     const int r0 = ty * T - cur.off, c0 = tx * T - cur.off;
     const int64_t fbase = (int64_t)b * H * W;
     // (L, value) of a pixel before any relaxation
@@ -474,15 +348,7 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
                 const unsigned key = msk ? ws_key(hf) : WS_INF;
                 sLV[h_lr * P + h_lc] = make_uint2(msk && hm != 0 ? key : WS_INF, key);
             }
-        } else
-#ifdef PCSEG_EXP_RELAX_LOADS  // sensitivity build: a revisited tile is fetched this many times (what do its loads cost?)
-#pragma unroll 1
-        for (int load_rep = 0; load_rep < PCSEG_EXP_RELAX_LOADS; ++load_rep)
-#endif
-        {
-#ifdef PCSEG_EXP_RELAX_LOADS
-            asm volatile("" ::: "memory");
-#endif
+        } else {
             uint4 l4[TRIPS], v4[TRIPS];
 #pragma unroll
             for (int t = 0; t < TRIPS; ++t) {
@@ -539,30 +405,18 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
     const int rim_lr = e < 4 ? (qy ? T : 1) : qy * G::HE + ej + 1;
     const int rim_lc = e < 4 ? qx * G::HE + ej + 1 : (qx ? T : 1);
     const unsigned rim_before = rim_thread ? sLV[rim_lr * P + rim_lc].x : 0u;
-    // wave = (direction, group of 64 lines, 64-cell segment of the lines): the segments of a line are swept at the same
-    // time, each starting from the cell in front of it -- its neighbour segment's last cell, or the halo
-    const int wave = tid >> 6, lane = tid & 63;
-    const int dir = wave & 3, seg = wave >> 2;
-    const int line = 1 + (seg % G::G) * 64 + lane, along = (seg / G::G) * 64;
-    const int start = dir == 0 ? line * P + along : dir == 1 ? line * P + (S - 1) - along
-                    : dir == 2 ? along * P + line : ((S - 1) - along) * P + line;
+    // wave = sweep quadrant (row direction, column direction)
+    const int dir = (tid >> 6) & 3, lane = tid & 63;
     bool changed_any = false;
     bool capped = true;  // left before the tile's fixed point (round 0 stops after max_iter sweeps per direction)
     for (int iter = 0; iter < max_iter; ++iter) {
-        // one code path per direction: the step is a compile-time constant there, so the LDS addresses of a batch are
+        // one code path per quadrant: the steps are compile-time constants there, so the LDS addresses of a batch are
         // base + constant
         bool changed;
-        if constexpr (PCSEG_WS_FSM && T == 64) {
-            if (dir == 0) changed = ws_quadrant_sweep<1, 1, P>(sLV, lane);
-            else if (dir == 1) changed = ws_quadrant_sweep<1, -1, P>(sLV, lane);
-            else if (dir == 2) changed = ws_quadrant_sweep<-1, 1, P>(sLV, lane);
-            else changed = ws_quadrant_sweep<-1, -1, P>(sLV, lane);
-        } else {
-            if (dir == 0) changed = ws_sweep<1>(sLV, start);
-            else if (dir == 1) changed = ws_sweep<-1>(sLV, start);
-            else if (dir == 2) changed = ws_sweep<P>(sLV, start);
-            else changed = ws_sweep<-P>(sLV, start);
-        }
+        if (dir == 0) changed = ws_quadrant_sweep<1, 1, P>(sLV, lane);
+        else if (dir == 1) changed = ws_quadrant_sweep<1, -1, P>(sLV, lane);
+        else if (dir == 2) changed = ws_quadrant_sweep<-1, 1, P>(sLV, lane);
+        else changed = ws_quadrant_sweep<-1, -1, P>(sLV, lane);
         if (!__syncthreads_or(changed)) { capped = false; break; }
         changed_any = true;
     }
@@ -574,7 +428,7 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
         bool ch = rim_thread && capped;
         if (rim_thread && !capped && r >= 0 && r < H && c >= 0 && c < W) ch = sLV[rim_lr * P + rim_lc].x != rim_before;
         // the lanes of this thread's half edge inside its wave
-        const unsigned long long mine = G::HE >= 64 ? ~0ull : (((1ull << (G::HE & 63)) - 1ull) << ((tid & 63) / G::HE * G::HE));
+        const unsigned long long mine = ((1ull << G::HE) - 1ull) << ((tid & 63) / G::HE * G::HE);
         const unsigned long long edge_changed = __ballot(ch) & mine;
         if (rim_thread && edge_changed && ej == 0) {
             // the tile of the other tiling that holds this corner quadrant (rows r0 + qy * T / 2 .., cols c0 + qx * T / 2 ..)
@@ -595,11 +449,6 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
     }
     __syncthreads();
     if (in.vec) {
-#ifdef PCSEG_EXP_RELAX_STORES  // sensitivity build: a tile's levels are written this many times
-#pragma unroll 1
-        for (int store_rep = 0; store_rep < PCSEG_EXP_RELAX_STORES; ++store_rep) {
-            asm volatile("" ::: "memory");
-#endif
 #pragma unroll
         for (int t = 0; t < T * QW / NT; ++t) {
             const int idx = tid + NT * t, lr = idx / QW, q = idx % QW;
@@ -608,9 +457,6 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
             if (r >= 0 && r < H && c >= 0 && c < W)
                 *reinterpret_cast<uint4 *>(L + fbase + rowoff(r, W) + c) = make_uint4(src[0].x, src[1].x, src[2].x, src[3].x);
         }
-#ifdef PCSEG_EXP_RELAX_STORES
-        }
-#endif
         return;
     }
     for (int i = tid; i < T * T; i += NT) {
@@ -637,10 +483,7 @@ __global__ void __launch_bounds__(RelaxGeom<T>::THREADS) ws_relax_kernel(WsInput
 // byte and leave -- each of which first has to be given 36 KB of LDS and four wave slots on a CU that seven other batches'
 // kernels are using (see WsTileList: the empty grids of the second level cost the STEP 3 %).  From round WS_LIST_FROM on a
 // round is a fixed small grid walking the list of tiles the round before marked (appended by the first marker of a tile).
-#ifndef PCSEG_WS_LIST_FROM
-#define PCSEG_WS_LIST_FROM 4  // first list-walking round (12 = never)
-#endif
-constexpr int WS_LIST_FROM = PCSEG_WS_LIST_FROM, WS_LIST_GRID = 1024;
+constexpr int WS_LIST_FROM = 4, WS_LIST_GRID = 1024;  // first list-walking round; blocks of a list-walking launch
 
 template <int T>
 __global__ void __launch_bounds__(RelaxGeom<T>::THREADS) ws_relax_list_kernel(WsInputs in, unsigned *__restrict__ val, unsigned *__restrict__ L,
@@ -989,9 +832,7 @@ __device__ __forceinline__ void ws_uf_tile_frame(KeyT *sK, int *par, uint8_t *sM
             const bool same_run = (m & 2) || (ml & 4), same_run_up = (mu & 2) || (mul & 4), left_vertical = (ml & 1) || (mul & 8);
             if (same_run && same_run_up && left_vertical) continue;
         }
-#if !defined(PCSEG_EXP_UFTILE) || !(PCSEG_EXP_UFTILE & 1)  // (ablation builds: wrong labels, the pass's time without a phase)
         vunite_lds(par, par[t], par[t - UF_TW]);
-#endif
     }
     __syncthreads();
     for (int t = threadIdx.x; t < UF_TH * UF_TW; t += 256) {
@@ -999,11 +840,7 @@ __device__ __forceinline__ void ws_uf_tile_frame(KeyT *sK, int *par, uint8_t *sM
         if (r >= H || c >= W) continue;
         int v = -1;
         if (par[t] >= 0) {
-#if defined(PCSEG_EXP_UFTILE) && (PCSEG_EXP_UFTILE & 2)
-            const int root = par[t];
-#else
             const int root = vfind_lds(par, par[t]);
-#endif
             const int lt = root & (UF_LNS - 1);
             v = ((r0 + lt / UF_TW) * W + c0 + lt % UF_TW) | (root >= UF_LNS ? UF_NS : 0);
         }
@@ -1196,10 +1033,7 @@ __global__ void __launch_bounds__(256) ws_uf_label_tiles_kernel(WsTileList tiles
 // pixels further on) and walks their chains -- parent entry, root, the root's label -- in lockstep: a lane with one
 // chain waits a memory latency per step (89 % of this kernel's wave cycles were waits).  A quad's chain belongs to its
 // first reachable pixel; a pixel with another parent entry walks on its own afterwards.
-#ifndef PCSEG_LABEL4_Q
-#define PCSEG_LABEL4_Q 3  // quads a lane carries (3 x 2 lockstep chains): 78 scalar / 55 vector registers, 194 us; 4: 94 / 69, 216 us
-#endif
-constexpr int LABEL4_Q = PCSEG_LABEL4_Q;
+constexpr int LABEL4_Q = 3;  // quads a lane carries (3 x 2 lockstep chains): 78 scalar / 55 vector registers, 194 us; 4: 94 / 69, 216 us
 
 // NCH chains in lockstep: root[q] (-1 = none) walks to its root, lab[q] becomes the root's label (0: no seed)
 // The fence of these chains costs two vector instructions a step and no compare of its own: every load goes to a CLAMPED index
@@ -1244,13 +1078,11 @@ __device__ __forceinline__ void label4_chains(const int *par, const int *F, int6
         lab[q] = (root[q] >= 0 && root[q] < seeds_end) ? F[fbase + root[q]] : 0;  // roots are labelled pixels, never changed by this pass
 }
 
-#ifndef PCSEG_LABEL4_OCC
 // workgroups per CU the register allocator is asked for.  With four quads a lane: 7 = 94 scalar / 69 vector registers, 217 us a
 // launch; 8 = 78 / 64 with 28 bytes of scratch, 254 us; without the argument 106 / 67 = six workgroups, 265 us.  With THREE quads
 // a lane eight workgroups fit without scratch: 194 us (profiles/r04/ab_logs/r4i_*, r4j_*)
-#define PCSEG_LABEL4_OCC 8
-#endif
-__global__ void __launch_bounds__(256, PCSEG_LABEL4_OCC) ws_uf_label4_kernel(const int *__restrict__ parent, const uint8_t *__restrict__ minmask,
+constexpr int LABEL4_OCC = 8;
+__global__ void __launch_bounds__(256, LABEL4_OCC) ws_uf_label4_kernel(const int *__restrict__ parent, const uint8_t *__restrict__ minmask,
                                                             int *F, uint8_t *__restrict__ bad, int *__restrict__ tie_flags,
                                                             int64_t n, int *__restrict__ exact_flags)
 {
@@ -1752,13 +1584,7 @@ __global__ void ws_set_flags_kernel(int *flags, int B, int v)
 // larger calls, where throughput comes from the number of frames in flight -- the flood of a frame is sequential by
 // definition, so a batch of N frames uses N waves whatever else is done, and 16+ of them fit a CU once the LDS share
 // is small.  Both sizes keep every six-level window entirely in LDS or entirely in the workspace.
-#ifndef PCSEG_EX_SMALL_LDS
-#define PCSEG_EX_SMALL_LDS 128
-#endif
-#ifndef PCSEG_EX_SMALL_D
-#define PCSEG_EX_SMALL_D 6
-#endif
-constexpr int EX_LDS_BIG = 8192, EX_LDS_SMALL = PCSEG_EX_SMALL_LDS, EX_D_BIG = 6, EX_D_SMALL = PCSEG_EX_SMALL_D;
+constexpr int EX_LDS_BIG = 8192, EX_LDS_SMALL = 128, EX_D_BIG = 6, EX_D_SMALL = 6;
 static_assert((EX_LDS_SMALL & (EX_LDS_SMALL - 1)) == 0 && EX_LDS_SMALL >= (2 << EX_D_SMALL), "the first window must fit the LDS share");
 
 // (the LDS halves are typed by address space: with four generic pointers the compiler folds `d < lds ? lk[d] : gk[d]` into
@@ -1875,7 +1701,7 @@ __device__ __forceinline__ void ex_children(const ExactHeap &h, long long d, uns
 // A deeper window saves memory round trips and loads more entries that are not on the path; a shallower one the
 // reverse.  Quantised benchmark frames (heaps of 2^16..2^17 entries), 1024 frames per call, Mpixels/s: D = 3 (LDS 2^10)
 // 271, D = 4 (2^9) 295, D = 5 (2^11) 327, D = 6 (2^7) 324, D = 8 (2^9: the whole heap in two windows) 213 -- the
-// memory system is loaded by the entries as much as the waves wait for them, and 6 stays (PCSEG_EX_SMALL_D / _LDS).
+// memory system is loaded by the entries as much as the waves wait for them, and 6 stays (EX_D_SMALL / EX_LDS_SMALL).
 template <int D>
 __device__ __forceinline__ void ex_pop(ExactHeap &h)
 {
@@ -2024,21 +1850,7 @@ using namespace pcseg;
 // batch, relaxation per launch -- line sweeps: round 0 at 16 is 4.6 % better than no limit (8 -> 1 %, 6 -> none), later
 // rounds no limit 179.9 us, 32 -> 177.5, 16 -> 170.5, 8 -> 175.1 plus 122 us of tail kernel; quadrant sweeps (which
 // need about a third of the iterations): 4 / 6 -> 136 us, 3 / 4 -> 134, 5 / 5 -> 137, 4 / 16 -> 139, 16 / 16 -> 154.
-#ifndef PCSEG_WS_ROUND0_SWEEPS
-#define PCSEG_WS_ROUND0_SWEEPS (PCSEG_WS_FSM ? 4 : 16)
-#endif
-#ifndef PCSEG_WS_ROUND_SWEEPS
-#define PCSEG_WS_ROUND_SWEEPS (PCSEG_WS_FSM ? 6 : 16)
-#endif
-#ifndef PCSEG_WS_RELAX_TILE
-#define PCSEG_WS_RELAX_TILE 64
-#endif
-constexpr int WS_ROUND0_SWEEPS = PCSEG_WS_ROUND0_SWEEPS;
-#ifndef PCSEG_WS_RELAX_LDS_PAD
-// A/B aid: extra dynamic LDS per relaxation block.  0 = four tiles per CU (4 x 36 KB); 16384 -> three, 40960 -> two: fewer of a
-// CU's waves belong to the relaxation and more of its LDS is left to the kernels of the other batches in flight
-#define PCSEG_WS_RELAX_LDS_PAD 0
-#endif
+constexpr int WS_ROUND0_SWEEPS = 4, WS_ROUND_SWEEPS = 6;
 
 // the watershed may be called from several host threads at once (FramePipeline's lanes)
 static std::atomic<long long> g_ws_counters[4];  // [0] unused (lives on the device), relax launches, calls, -
@@ -2057,6 +1869,59 @@ static unsigned long long *ws_dev_tiles()
         g_ws_dev_tiles[dev] = p;
     }
     return g_ws_dev_tiles[dev];
+}
+
+constexpr int WS_GRID_ROUNDS = 12, WS_K2_GRID_ROUNDS = 4;
+
+struct WsWorkspace {
+    unsigned *val, *L;
+    uint8_t *dirtyA, *dirtyB;  // tile marks of the two tilings (the half-tile-shifted one has one more tile per axis)
+    uint8_t *active_tiles;
+    int *changed;  // [6] "a tail kernel gave up", [WS_CNT0 + 32 i] tile counters
+    int *flags, *flags2;
+    int *frame_list;      // [0] = number of flagged frames (stays on the device), the frames behind it
+    int *round_count;     // [r] = tiles listed for relaxation round r (see ws_relax_list_kernel)
+    int *tile_list;       // [0] = number of the second level's active tiles, the tiles behind it
+    int *round_list[2];
+    unsigned long long *heap_key;  // doubles as K64 of the second-level pass
+    unsigned *heap_idx;            // doubles as K2
+    int *uf_parent;
+    uint8_t *uf_bad1, *uf_bad2;  // roots of components the first / second level cannot resolve
+    uint8_t *uf_mask;
+};
+
+// ORDER MATTERS from dirtyA to tile_list: pcseg_watershed4_f32 clears everything that starts at zero -- both mark buffers,
+// the active-tile set, the counters, both flag arrays, the frame list, the round counts and the first word of tile_list
+// (its length) -- with ONE fill from dirtyA up to the first entry of tile_list, and later both mark buffers with one fill from dirtyA to the
+// end of dirtyB.  Whatever is carved between them is zeroed by those fills; nothing that must survive them may sit there.
+static WsWorkspace ws_carve(Carver &cv, int B, int H, int W)
+{
+    const size_t n = (size_t)B * H * W;
+    const int tilesX = (W + WS_T - 1) / WS_T, tilesY = (H + WS_T - 1) / WS_T;
+    const size_t ntiles = (size_t)B * tilesX * tilesY;
+    const size_t ntiles_max = (size_t)B * (tilesX + 1) * (tilesY + 1);
+    WsWorkspace ws;
+    ws.val = cv.take<unsigned>(n);
+    ws.L = cv.take<unsigned>(n);
+    ws.dirtyA = cv.take<uint8_t>(ntiles_max);
+    ws.dirtyB = cv.take<uint8_t>(ntiles_max);
+    ws.active_tiles = cv.take<uint8_t>(ntiles);
+    ws.changed = cv.take<int>(WS_CHANGED_INTS);
+    ws.flags = cv.take<int>(B);
+    ws.flags2 = cv.take<int>(B);
+    ws.frame_list = cv.take<int>(B + 1);
+    static_assert(WS_GRID_ROUNDS < 16, "one counter per grid round");
+    ws.round_count = cv.take<int>(16);
+    ws.tile_list = cv.take<int>(ntiles + 1);
+    ws.round_list[0] = cv.take<int>(ntiles_max);
+    ws.round_list[1] = cv.take<int>(ntiles_max);
+    ws.heap_key = cv.take<unsigned long long>(n);
+    ws.heap_idx = cv.take<unsigned>(n);
+    ws.uf_parent = cv.take<int>(n);
+    ws.uf_bad1 = cv.take<uint8_t>(n);
+    ws.uf_bad2 = cv.take<uint8_t>(n);
+    ws.uf_mask = cv.take<uint8_t>(n);
+    return ws;
 }
 
 extern "C" {
@@ -2082,22 +1947,15 @@ void pcseg_watershed_counters(int64_t *out, int reset)
 size_t pcseg_watershed_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    size_t n = (size_t)B * H * W;
-    int tilesX = (W + WS_T - 1) / WS_T, tilesY = (H + WS_T - 1) / WS_T;
-    return 3 * align_up(n * 4) + 3 * align_up(n) + 2 * align_up((size_t)B * (tilesX + 1) * (tilesY + 1)) + align_up((size_t)B * tilesX * tilesY) + align_up(sizeof(int) * WS_CHANGED_INTS) + 2 * align_up(sizeof(int) * B) + align_up(sizeof(int) * ((size_t)B + 1)) +
-           align_up(n * 8) + align_up(n * 4) + align_up(sizeof(int) * ((size_t)B * tilesX * tilesY + 1)) +
-           align_up(sizeof(int) * 16) + 2 * align_up(sizeof(int) * (size_t)B * (tilesX + 1) * (tilesY + 1));
+    Carver cv(nullptr, 0);
+    ws_carve(cv, B, H, W);
+    return cv.off;
 }
 
 // grid rounds enqueued before the per-frame tail kernels take over (see ws_relax_tail_kernel): the benchmark batch needs
 // 10 relaxation rounds; a round without marks costs a few microseconds.  The second level sees a few dozen tiles of a
 // few frames (benchmark batch: 31 tiles in 7 frames; rounds of 127 / 60 / 25 / 18 us -- the first is one winding lake's
 // fixed point); with two grid rounds the per-frame tail kernel walks the rest one tile at a time (177 us against 43)
-#ifndef PCSEG_WS_K2_ROUNDS
-#define PCSEG_WS_K2_ROUNDS 4
-#endif
-constexpr int WS_GRID_ROUNDS = 12, WS_K2_GRID_ROUNDS = PCSEG_WS_K2_ROUNDS;
-
 int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *markers, const uint8_t *mask, int32_t *out,
                          int32_t *tie_flags, int B, int H, int W, int mode, void *workspace, size_t workspace_bytes,
                          pcseg_stream_t stream)
@@ -2113,28 +1971,19 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * H * W;
     const int tilesX = (W + WS_T - 1) / WS_T, tilesY = (H + WS_T - 1) / WS_T;
-    const size_t ntiles = (size_t)B * tilesX * tilesY;
     const size_t ntiles_max = (size_t)B * (tilesX + 1) * (tilesY + 1);  // the half-tile-shifted tiling has one more per axis
     Carver cv(workspace, workspace_bytes);
-    unsigned *val = cv.take<unsigned>(n);
-    unsigned *L = cv.take<unsigned>(n);
-    uint8_t *dirtyA = cv.take<uint8_t>(ntiles_max);
-    uint8_t *dirtyB = cv.take<uint8_t>(ntiles_max);
-    uint8_t *active_tiles = cv.take<uint8_t>(ntiles);
-    int *changed = cv.take<int>(WS_CHANGED_INTS);  // [6] "a tail kernel gave up", [WS_CNT0 + 32 i] tile counters
-    int *flags = cv.take<int>(B);
-    int *flags2 = cv.take<int>(B);
-    int *frame_list = cv.take<int>(B + 1) + 1;  // frame_list[-1] = number of flagged frames (stays on the device)
-    int *round_count = cv.take<int>(16);            // [r] = tiles listed for relaxation round r (see ws_relax_list_kernel)
-    int *tile_list = cv.take<int>(ntiles + 1) + 1;  // the second level's active tiles, tile_list[-1] = their number
-    int *round_list[2] = {cv.take<int>(ntiles_max), cv.take<int>(ntiles_max)};
-    static_assert(WS_GRID_ROUNDS < 16, "one counter per grid round");
-    unsigned long long *heap_key = cv.take<unsigned long long>(n);  // doubles as K64 of the second-level pass
-    unsigned *heap_idx = cv.take<unsigned>(n);                      // doubles as K2
-    int *uf_parent = cv.take<int>(n);
-    uint8_t *uf_bad1 = cv.take<uint8_t>(n);  // roots of components the first / second level cannot resolve
-    uint8_t *uf_bad2 = cv.take<uint8_t>(n);
-    uint8_t *uf_mask = cv.take<uint8_t>(n);
+    const WsWorkspace ws = ws_carve(cv, B, H, W);
+    unsigned *val = ws.val, *L = ws.L;
+    uint8_t *dirtyA = ws.dirtyA, *dirtyB = ws.dirtyB, *active_tiles = ws.active_tiles;
+    int *changed = ws.changed, *flags = ws.flags, *flags2 = ws.flags2;
+    int *frame_list = ws.frame_list + 1, *tile_list = ws.tile_list + 1;  // list[-1] = the list's length
+    int *round_count = ws.round_count;
+    int *const *round_list = ws.round_list;
+    unsigned long long *heap_key = ws.heap_key;
+    unsigned *heap_idx = ws.heap_idx;
+    int *uf_parent = ws.uf_parent;
+    uint8_t *uf_bad1 = ws.uf_bad1, *uf_bad2 = ws.uf_bad2, *uf_mask = ws.uf_mask;
     if (!cv.ok()) {
         set_error("watershed: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
@@ -2161,23 +2010,11 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
                          ((uintptr_t)mask & 3) == 0;
         const WsInputs inputs{img, frame_stride, markers, mask, out, vec};
         // minimax relaxation over alternating tilings
-        constexpr int RT = PCSEG_WS_RELAX_TILE;  // edge of a relaxation tile (the later stages keep their 64 x 64 tiles)
+        constexpr int RT = WS_T;  // edge of a relaxation tile
         using RG = RelaxGeom<RT>;
         const WsTiling tilings[2] = {{0, (W + RT - 1) / RT, (H + RT - 1) / RT},
                                      {RT / 2, (W + RT / 2 + RT - 1) / RT, (H + RT / 2 + RT - 1) / RT}};
-        static std::atomic<bool> lds_attr_set[64];
-        {
-            int dev = 0;
-            if (RG::LDS_BYTES + PCSEG_WS_RELAX_LDS_PAD > 64 * 1024 && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !lds_attr_set[dev].load()) {
-                PCSEG_CHECK_HIP(hipFuncSetAttribute((const void *)ws_relax_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    (int)(RG::LDS_BYTES + PCSEG_WS_RELAX_LDS_PAD)));
-                PCSEG_CHECK_HIP(hipFuncSetAttribute((const void *)ws_relax_list_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    (int)(RG::LDS_BYTES + PCSEG_WS_RELAX_LDS_PAD)));
-                PCSEG_CHECK_HIP(hipFuncSetAttribute((const void *)ws_relax_tail_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    (int)RG::LDS_BYTES));
-                lds_attr_set[dev].store(true);
-            }
-        }
+        static_assert(RG::LDS_BYTES <= 64 * 1024, "dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize");
         // (frame flags and mark buffers: cleared by the one fill above -- the tail kernels may raise flags2 for a fixed point
         // they had to abandon)
         {
@@ -2187,13 +2024,13 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
                 // (a round's marks go into the next round's list once that round walks a list)
                 const bool lists_next = round + 1 >= WS_LIST_FROM && round + 1 < WS_GRID_ROUNDS;
                 int *lout = lists_next ? round_list[(round + 1) & 1] : nullptr, *cout = lists_next ? round_count + round + 1 : nullptr;
-                if (round >= WS_LIST_FROM)
-                    PCSEG_LAUNCH(ws_relax_list_kernel<RT>, dim3(WS_LIST_GRID), dim3(RG::THREADS), RG::LDS_BYTES + PCSEG_WS_RELAX_LDS_PAD, s, inputs,
-                                 val, L, din, dout, changed, H, W, cur, nxt, PCSEG_WS_ROUND_SWEEPS, (const int *)round_list[round & 1],
-                                 (const int *)(round_count + round), lout, cout);
+                if (round < WS_LIST_FROM)
+                    PCSEG_LAUNCH(ws_relax_kernel<RT>, dim3(cur.nx, cur.ny, B), dim3(RG::THREADS), RG::LDS_BYTES, s, inputs, round == 0, val,
+                                 L, din, dout, changed, H, W, cur, nxt, round == 0 ? WS_ROUND0_SWEEPS : WS_ROUND_SWEEPS, lout, cout);
                 else
-                PCSEG_LAUNCH(ws_relax_kernel<RT>, dim3(cur.nx, cur.ny, B), dim3(RG::THREADS), RG::LDS_BYTES + PCSEG_WS_RELAX_LDS_PAD, s, inputs, round == 0, val,
-                             L, din, dout, changed, H, W, cur, nxt, round == 0 ? WS_ROUND0_SWEEPS : PCSEG_WS_ROUND_SWEEPS, lout, cout);
+                    PCSEG_LAUNCH(ws_relax_list_kernel<RT>, dim3(WS_LIST_GRID), dim3(RG::THREADS), RG::LDS_BYTES, s, inputs,
+                                 val, L, din, dout, changed, H, W, cur, nxt, WS_ROUND_SWEEPS, (const int *)round_list[round & 1],
+                                 (const int *)(round_count + round), lout, cout);
                 PCSEG_CHECK_LAUNCH();
                 ++relax_launches;
                 uint8_t *t = din; din = dout; dout = t;
