@@ -488,6 +488,35 @@ int pcseg_surface_pack_cells(const double *cells, int ncol, const uint8_t *class
 int pcseg_surface_pack_refined(const int64_t *ws_stats, int cap, const int32_t *id, const int64_t *frame_offsets, int64_t n_points,
                                int B, double *rc, pcseg_stream_t stream);
 
+/* ---- per-ROI shape: what RegionProperties offers beyond the fields the reference reads itself (every public function
+ * hands such objects back: tiff_analysis.py:742-883, 1018; HCN_nanosims_rois_activity_distance_5iso_YG.m:104, 173 asks for
+ * regionprops(red, 'all')) -- second moments, axes, eccentricity, orientation, perimeter; scikit-image 0.18.3 conventions.
+ * pcseg_region_shape: labels device int32 (B, H, W), any width and alignment (the class-map components or the refined
+ * ROIs); counts device int32 (B).  shape_out device int64 (B, cap, 8), rows l = 1 .. min(counts[b], cap) (row l - 1; the
+ * others stay untouched), all exact integers over the label's pixels, absolute image coordinates:
+ *   0, 1, 2  sum r^2, sum r c, sum c^2
+ *   3, 4, 5  n_1, n_sqrt2, n_mid: border pixels by the weight class of skimage.measure.perimeter(region.image, 4)
+ *   6        n_border: all border pixels;  7: 0
+ * border pixel: a pixel of the label with a 4-neighbour of another label (outside the image counts as another label);
+ * its value v = 1 + 2 #(4-neighbours that are border pixels OF THE SAME LABEL) + 10 #(such diagonal neighbours);
+ * v in {5,7,15,17,25,27} -> n_1, {21,33} -> n_sqrt2, {13,23} -> n_mid.  Labels above min(counts[b], cap) are skipped;
+ * overflow[b] (device int32 (B), may be NULL) is cleared and then set when a label exceeds cap.  B <= 65535.
+ * pcseg_shape_properties: stats device int64 (B, cap, 8) (pcseg_region_col rows of the same labels), shape as above; out
+ * device float64 (B, cap, 12), rows below min(counts[b], cap); NaN for a label without pixel.  With A the area, P = (A sum
+ * r^2 - (sum r)^2) / A^2, Q the same in c, R = (A sum r c - sum r sum c) / A^2 (numerators exact in 128-bit integers):
+ *   0, 1, 2  inertia tensor [[a, b], [b, c]] = [[Q, -R], [-R, P]]
+ *   3, 4     l1, l2 = ((P + Q) +- sqrt((P - Q)^2 + 4 R^2)) / 2, l2 clipped at 0
+ *   5, 6     major, minor axis length = 4 sqrt(l1), 4 sqrt(l2);  7: eccentricity = l1 == 0 ? 0 : sqrt(1 - l2 / l1)
+ *   8        orientation = a - c == 0 ? (b < 0 ? -pi/4 : pi/4) : atan2(-2 b, c - a) / 2
+ *   9        equivalent diameter = sqrt(4 A / pi);  10: extent = A / bounding-box area
+ *   11       perimeter = n_1 + n_sqrt2 sqrt 2 + n_mid (1 + sqrt 2) / 2
+ * in pixels; every operation rounded on its own (no FMA). */
+size_t pcseg_region_shape_workspace_bytes(int B, int H, int W);
+int pcseg_region_shape(const int32_t *labels, const int32_t *counts, int64_t *shape_out, int32_t *overflow, int B, int H, int W,
+                       int cap, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_shape_properties(const int64_t *stats, const int64_t *shape, const int32_t *counts, double *out, int B, int cap,
+                           pcseg_stream_t stream);
+
 /* ---- X1 (north_star extension; refine_boundaries.py:22 imports skimage.filters and never calls it): the library
  * SURVEY.md 8a names is the oracle -- skimage.filters.threshold_otsu(float32 image, nbins=256), pinned by
  * tests/golden/extensions.npz.  pcseg_otsu_f32: threshold[b] (device float64 (B,), the value is the float32 bin

@@ -88,7 +88,10 @@ SIGNATURES = {
     "pcseg_surface_shells": (c_int, [_P, _P, _P, _I, _I, _I, c_double, _P, _I, _P, _P, c_size_t, _P]),
     "pcseg_surface_pack_cells": (c_int, [_P, _I, _P, _I, _P, c_size_t, _P, _P, _P, _P, _P]),
     "pcseg_surface_pack_refined": (c_int, [_P, _I, _P, _P, c_int64, _I, _P, _P]),
-    "pcseg_otsu_hist_f32": (c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    "pcseg_region_shape_workspace_bytes": (c_size_t, [_I, _I, _I]),
+    "pcseg_region_shape": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, c_size_t, _P]),
+    "pcseg_shape_properties": (c_int, [_P, _P, _P, _P, _I, _I, _P]),
+    "pcseg_otsu_hist_f32":(c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "pcseg_otsu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "pcseg_morph3x3": (c_int, [_P, _P, _I, _I, _I, _I, _P]),
 }

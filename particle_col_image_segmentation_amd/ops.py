@@ -195,6 +195,55 @@ def region_reduce(labels, counts=None, cls=None, planes=None, cap=None, sum_clas
     return stats, cls_out, sums, overflow
 
 
+SHAPE_COLUMNS = ("a", "b", "c", "l1", "l2", "major", "minor", "eccentricity", "orientation", "equivalent_diameter", "extent",
+                 "perimeter")
+
+
+def region_shape(labels, counts, cap=None):
+    """The integer shape table of a label batch (csrc/shape.hip, include/pcseg.h): ``labels`` (B, H, W) int32 CUDA tensor
+    of any width and alignment, ``counts`` (B,) int32.  Returns ``(shape, overflow)``: int64 (B, cap, 8) = sum r^2, sum
+    r c, sum c^2, n_1, n_sqrt2, n_mid, n_border, 0 for the labels 1 .. min(counts[b], cap) (rows beyond are not
+    initialised) and int32 (B,) set where a label exceeds ``cap`` (default: max(counts))."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("labels must be an int32 (B, H, W) tensor")
+    if not labels.is_contiguous():  # (a contiguous view keeps its base address: unaligned images are taken as they are)
+        labels = labels.contiguous()
+    counts = _req(counts, torch.int32, 1)
+    B, H, W = labels.shape
+    if counts.shape[0] != B:
+        raise ValueError("counts must have one entry per frame")
+    if cap is None:
+        cap = max(1, int(counts.max().item()))
+    cap = int(cap)
+    dev = labels.device
+    shape = torch.empty((B, cap, 8), dtype=torch.int64, device=dev)
+    overflow = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.pcseg_region_shape_workspace_bytes(B, H, W)
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.pcseg_region_shape(_ptr(labels), _ptr(counts), _ptr(shape), _ptr(overflow), B, H, W, cap, _ptr(ws), nbytes,
+                                      _stream()), "region_shape")
+    return shape, overflow
+
+
+def shape_properties(stats, shape, counts):
+    """The derived shape columns (scikit-image 0.18.3 conventions, pixels): ``stats`` int64 (B, cap, 8) of
+    :func:`region_reduce` and ``shape`` of :func:`region_shape` over the same labels -> float64 (B, cap, 12) in the order of
+    ``SHAPE_COLUMNS``, rows below min(counts[b], cap); NaN for a label without pixel."""
+    stats = _req(stats, torch.int64, 3)
+    shape = _req(shape, torch.int64, 3)
+    counts = _req(counts, torch.int32, 1)
+    B, cap = stats.shape[0], stats.shape[1]
+    if tuple(stats.shape) != (B, cap, 8) or tuple(shape.shape) != (B, cap, 8) or counts.shape[0] != B:
+        raise ValueError("stats and shape must both be (B, cap, 8), counts (B,)")
+    out = torch.empty((B, cap, len(SHAPE_COLUMNS)), dtype=torch.float64, device=stats.device)
+    _lib.check(_lib.load().pcseg_shape_properties(_ptr(stats), _ptr(shape), _ptr(counts), _ptr(out), B, cap, _stream()),
+               "shape_properties")
+    return out
+
+
 def threshold_lt(img, threshold):
     """binary_mask = boundary_map < threshold (refine_boundaries.py:44-45)."""
     img = _req(img, torch.float32, 3)
@@ -668,8 +717,29 @@ def _refined_surface(res, points, surface, mask, scale, K, edges):
     return _surface_rows(points._replace(coords=rc[:n]), surface, mask, scale, K, edges)
 
 
+def _shape_rows(labels, counts, stats, live, slot_of, frame_ids, scale):
+    """The ``shapes`` table of one label batch: :func:`region_shape` + :func:`shape_properties` on the whole batch, then
+    the rows ``live`` ((B, cap) bool) in (frame, label) order as ``[frame, label, slot, n_border, n_1, n_sqrt2, n_mid, mu_rr,
+    mu_rc, mu_cc, major_um, minor_um, eccentricity, orientation, equivalent_diameter_um, extent, perimeter_um]``
+    (lengths / ``scale``; the second central moments stay in pixels)."""
+    cap = stats.shape[1]
+    shape, _ = region_shape(labels, counts, cap=cap)
+    props = shape_properties(stats, shape, counts)
+    b, l = torch.nonzero(live, as_tuple=True)
+    sh, pr = shape[b, l].to(torch.float64), props[b, l]
+    slot = slot_of[b, l].to(torch.int64)
+    slot = torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
+    um = lambda k: pr[:, k] / scale
+    return torch.stack([frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), slot, sh[:, 6], sh[:, 3], sh[:, 4], sh[:, 5],
+                        pr[:, 2], -pr[:, 1], pr[:, 0], um(5), um(6), pr[:, 7], pr[:, 8], um(9), pr[:, 10], um(11)], dim=1)
+
+
+def _rows_below(counts, cap):
+    return torch.arange(cap, device=counts.device)[None, :] < counts[:, None]
+
+
 def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
-                 n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None):
+                 n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None, shape=False):
     """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device), then one stage per switch, in
     this order.  ``distance_slots`` (the class value -> type slot table, uint8[256] numpy): ``cell_dist``, one value
     per row of ``cells`` (NaN = no entry).  ``neighbour_slots`` (the same kind of table) with ``n_types`` slots:
@@ -679,9 +749,15 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
     over the rows of ``cells`` against the surface of ``binary_fill_holes(res["recreated"] == Particle)``, plus
     ``surface_px`` / ``filled_area`` (B,) and with ``surface_edges`` ``hist`` and ``shells`` (:func:`surface_shells`).
     ``refined`` (a :class:`ClassTables`): the outputs of :func:`refined_tables`, with ``refined_points``
-    ``refined_nn`` and with ``surface`` ``refined_sf``: the same two dicts over the refined rows of kind >= 1."""
+    ``refined_nn`` and with ``surface`` ``refined_sf``: the same two dicts over the refined rows of kind >= 1.
+    ``shape``: ``shapes`` = :func:`_shape_rows` over the rows of ``cells`` and, with ``refined``, ``refined_shapes`` over
+    the refined rows of kind >= 1."""
     out, d = _dense_tables(res, groups, frame_ids, C, ratios, check)
     scale = 512.0 / float(raster)
+    cap = res["stats"].shape[1]
+    if shape:
+        out["shapes"] = _shape_rows(res["labels"], res["counts"], res["stats"], (res["kind"] >= 1) & _rows_below(res["counts"], cap),
+                                    res["slot_of"], frame_ids, scale)
     if distance_slots is not None:
         out["cell_dist"] = _cell_distances(d, distance_slots, raster)
     if neighbour_slots is not None:
@@ -701,6 +777,10 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
             out["refined_nn"] = _neighbours(pts, n_types, scale, pair_edges)
         if surface is not None:
             out["refined_sf"] = _refined_surface(res, pts, sf, mask, scale, K, surface_edges)
+        if shape:
+            live = (out["kind_r"] >= 1) & (res["ws_stats"][:, :, 0] > 0) & _rows_below(res["n_markers"], cap)
+            out["refined_shapes"] = _shape_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"], frame_ids,
+                                                scale)
     return out
 
 
@@ -808,7 +888,7 @@ def refined_tables(res, frame_ids, tables, table_ws, table_rows, check=False, po
                                              _ptr(frames), *[_ptr(t) for t in pts], _ptr(ws), nbytes, _stream()),
                "refined_table_write")
     out = {"refined": refined[:n_roi], "cell_resolution": resolution[:n_cell], "frames_refined": frames,
-           "parent_overflow": lp[4], "refined_nan_flag": rc["nan_flag"]}
+           "parent_overflow": lp[4], "refined_nan_flag": rc["nan_flag"], "kind_r": rc["kind"], "slot_r": rc["slot_of"]}
     if points:
         out["points"] = _head(pts, n_pts)
     del keep

@@ -63,11 +63,26 @@ def _back(t, was_tensor, dtype=None):
 
 
 class _LabelImage:
-    """Device label image of one frame with a lazily fetched host copy (for Region.coords)."""
+    """Device label image of one frame with a lazily fetched host copy (for Region.coords) and, shared by the frame's
+    regions, the lazily computed shape columns (``stats``: the frame's (1, cap, 8) region table on the device, ``n``: its
+    label count)."""
 
-    def __init__(self, dev_labels):
+    def __init__(self, dev_labels, stats=None, n=0):
         self.dev = dev_labels
         self._host = None
+        self._stats, self._n, self._shape = stats, int(n), None
+
+    @property
+    def shape_columns(self):
+        """(n, 12) float64 in the order of ``ops.SHAPE_COLUMNS``: ONE device call for the whole frame, at the first
+        access to a shape attribute of any of its regions."""
+        if self._shape is None:
+            if self._stats is None:
+                raise AttributeError("this region carries no label image to take its shape from")
+            counts = torch.full((1,), self._n, dtype=torch.int32, device=self.dev.device)
+            table, _ = ops.region_shape(self.dev[None], counts, cap=self._stats.shape[1])
+            self._shape = ops.shape_properties(self._stats, table, counts)[0, :self._n].cpu().numpy()
+        return self._shape
 
     @property
     def host(self):
@@ -80,7 +95,13 @@ class Region:
     """Duck type of skimage RegionProperties restricted to what the reference touches:
     .label (:270), .area (:275, 769-781, 855, 1031, 1055), ["area"] (:1033), .centroid (:406, 844, 1054),
     .bbox (:860-863, 912), .coords[0] (:1042), dynamically added .cells (:781, 1029, 1063); refined regions
-    (get_refined_cell_positions_and_areas) also carry .parent, the class-map label they lie in."""
+    (get_refined_cell_positions_and_areas) also carry .parent, the class-map label they lie in.
+
+    What a cell looks like, under scikit-image 0.18.3's names and conventions and in pixels: .inertia_tensor,
+    .inertia_tensor_eigvals, .major_axis_length, .minor_axis_length, .eccentricity, .orientation, .equivalent_diameter,
+    .extent, .perimeter.  They are lazy: the regions of a frame share one holder, the first access to any of them costs
+    one device call for the whole frame (csrc/shape.hip), a caller that never asks pays nothing.  Any other
+    RegionProperties attribute raises AttributeError."""
 
     __slots__ = ("label", "area", "centroid", "bbox", "first", "sum_row", "sum_col", "cells", "parent", "_im")
 
@@ -102,6 +123,28 @@ class Region:
         if self._im is None:
             return np.array([self.first])
         return np.argwhere(self._im.host == self.label)
+
+    def _shape(self, k):
+        if self._im is None:
+            raise AttributeError("this region carries no label image to take its shape from")
+        return self._im.shape_columns[self.label - 1, k]
+
+    @property
+    def inertia_tensor(self):
+        a, b, c = (self._shape(k) for k in range(3))
+        return np.array([[a, b], [b, c]])
+
+    @property
+    def inertia_tensor_eigvals(self):
+        return [self._shape(3), self._shape(4)]
+
+    major_axis_length = property(lambda self: self._shape(5))
+    minor_axis_length = property(lambda self: self._shape(6))
+    eccentricity = property(lambda self: self._shape(7))
+    orientation = property(lambda self: self._shape(8))
+    equivalent_diameter = property(lambda self: self._shape(9))
+    extent = property(lambda self: self._shape(10))
+    perimeter = property(lambda self: self._shape(11))
 
     def __getitem__(self, key):
         return getattr(self, key)
@@ -129,7 +172,7 @@ def _regions_of(z_dev):
     labels, counts = ops.label_equal8(z_dev)
     n = int(counts[0].item())
     stats, cls_out, _, _ = ops.region_reduce(labels, counts, cls=z_dev, cap=max(n, 1))
-    holder = _LabelImage(labels[0])
+    holder = _LabelImage(labels[0], stats, n)
     st = stats[0, :n].cpu().numpy()
     cl = cls_out[0, :n].cpu().numpy()
     width = z_dev.shape[2]
@@ -146,7 +189,7 @@ def regionprops(label_im):
     n = int(lab.max().item()) if lab.numel() else 0
     stats, _, _, _ = ops.region_reduce(lab, cap=max(n, 1))
     st = stats[0, :n].cpu().numpy()
-    holder = _LabelImage(lab[0])
+    holder = _LabelImage(lab[0], stats, n)
     return [Region(i + 1, st[i], lab.shape[2], holder) for i in range(n) if st[i][0] > 0]
 
 
@@ -239,7 +282,7 @@ def get_refined_cell_positions_and_areas(z_slice, boundary_map, cell_types, thre
     order = sorted((int(first_region[t]), t) for t in range(len(tables.slot_names)) if first_region[t] != 0x7FFFFFFF)
     cell_pos = {tables.slot_names[t]: [] for _, t in order}
     cell_clusters = {tables.slot_names[t]: [] for _, t in order}
-    r_holder = _LabelImage(ws_labels[0])
+    r_holder = _LabelImage(ws_labels[0], ws_stats, m)
     for i in np.nonzero(r_kind)[0]:
         reg = Region(i + 1, wst[i], z_dev.shape[2], r_holder)
         reg.parent = int(r_parent[i])
