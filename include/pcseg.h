@@ -517,6 +517,33 @@ int pcseg_region_shape(const int32_t *labels, const int32_t *counts, int64_t *sh
 int pcseg_shape_properties(const int64_t *stats, const int64_t *shape, const int32_t *counts, double *out, int B, int cap,
                            pcseg_stream_t stream);
 
+/* ---- per-ROI convexity: is this blob one cell or a clump (tiff_analysis.py:776-781 counts a cluster's cells as area //
+ * mean cell area; refine_boundaries.py:5-7 expects clusters the watershed does not split) -- convex area, solidity, Feret
+ * diameter, Euler number; scikit-image 0.18.3 conventions, every value exact.
+ * pcseg_region_hull: labels device int32 (B, H, W), any width and alignment; counts device int32 (B); stats device int64
+ * (B, cap, 8), the pcseg_region_col rows of the same labels (area and bounding box are read: a ROI is looked for inside
+ * the box its row names, held to the frame, and nowhere else -- a row that does not belong to the image gives a wrong
+ * answer, never an access outside it).  hull_out device int64 (B, cap, 4), rows l = 1 .. min(counts[b], cap) (row l - 1; the
+ * others stay untouched; zeros for a label without pixel).  In doubled coordinates a pixel (r, c) owns the four points
+ * (2r +- 1, 2c), (2r, 2c +- 1) (convex_hull_image(offset_coordinates=True)):
+ *   0  convex_area: the pixel centres (2r, 2c) in the CLOSED convex hull of the points of the label's pixels (a centre on a
+ *      hull edge counts; pixels of other labels count); these pixels are the convex image
+ *   1  feret_sq4: the largest squared distance between points of the pixels OF THE CONVEX IMAGE (which reaches further than
+ *      the hull of the label's own points); feret_diameter_max = sqrt(feret_sq4 / 4)
+ *   2  euler number, 8-connectivity: (Q1 - Q3 - 2 QD) / 4 over all 2 x 2 windows of the zero-padded indicator of the label
+ *      (one, three, exactly the two diagonal pixels set; windows over the frame's edge count)
+ *   3  0
+ * Labels need not be connected.  overflow[b] (device int32 (B), may be NULL) = counts[b] > cap: the image is not searched
+ * for labels, a label above min(counts[b], cap) is never looked at.  B <= 65535.  Asynchronous, nothing is allocated.
+ * pcseg_hull_properties: out device float64 (B, cap, 4), rows below min(counts[b], cap); NaN for a label without pixel:
+ *   0  convex_area;  1  solidity = area / convex_area (one division);  2  feret_diameter_max = sqrt(feret_sq4 / 4.0), in
+ *   pixels;  3  euler_number */
+size_t pcseg_region_hull_workspace_bytes(int B, int H, int W, int cap);
+int pcseg_region_hull(const int32_t *labels, const int32_t *counts, const int64_t *stats, int64_t *hull_out, int32_t *overflow, int B,
+                      int H, int W, int cap, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_hull_properties(const int64_t *stats, const int64_t *hull, const int32_t *counts, double *out, int B, int cap,
+                          pcseg_stream_t stream);
+
 /* ---- X1 (north_star extension; refine_boundaries.py:22 imports skimage.filters and never calls it): the library
  * SURVEY.md 8a names is the oracle -- skimage.filters.threshold_otsu(float32 image, nbins=256), pinned by
  * tests/golden/extensions.npz.  pcseg_otsu_f32: threshold[b] (device float64 (B,), the value is the float32 bin

@@ -91,6 +91,9 @@ SIGNATURES = {
     "pcseg_region_shape_workspace_bytes": (c_size_t, [_I, _I, _I]),
     "pcseg_region_shape": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, c_size_t, _P]),
     "pcseg_shape_properties": (c_int, [_P, _P, _P, _P, _I, _I, _P]),
+    "pcseg_region_hull_workspace_bytes": (c_size_t, [_I, _I, _I, _I]),
+    "pcseg_region_hull": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, c_size_t, _P]),
+    "pcseg_hull_properties": (c_int, [_P, _P, _P, _P, _I, _I, _P]),
     "pcseg_otsu_hist_f32":(c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "pcseg_otsu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "pcseg_morph3x3": (c_int, [_P, _P, _I, _I, _I, _I, _P]),

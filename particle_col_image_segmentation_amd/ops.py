@@ -244,6 +244,58 @@ def shape_properties(stats, shape, counts):
     return out
 
 
+HULL_COLUMNS = ("convex_area", "solidity", "feret_diameter_max", "euler_number")
+
+
+def region_hull(labels, counts, stats, cap=None):
+    """The integer convexity table of a label batch (csrc/hull.hip, include/pcseg.h): ``labels`` (B, H, W) int32 CUDA
+    tensor of any width and alignment, ``counts`` (B,) int32, ``stats`` int64 (B, cap, 8) of :func:`region_reduce` over the
+    same labels (a ROI is looked for inside the bounding box its row names).  Returns ``(hull, overflow)``: int64 (B, cap,
+    4) = convex_area, feret_sq4, euler number, 0 for the labels 1 .. min(counts[b], cap) (rows beyond are not initialised)
+    and int32 (B,) set where ``counts[b]`` exceeds ``cap`` (default: the height of ``stats``)."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("labels must be an int32 (B, H, W) tensor")
+    if not labels.is_contiguous():  # (a contiguous view keeps its base address: unaligned images are taken as they are)
+        labels = labels.contiguous()
+    counts = _req(counts, torch.int32, 1)
+    stats = _req(stats, torch.int64, 3)
+    B, H, W = labels.shape
+    if counts.shape[0] != B:
+        raise ValueError("counts must have one entry per frame")
+    if cap is None:
+        cap = stats.shape[1]
+    cap = int(cap)
+    if tuple(stats.shape) != (B, cap, 8):
+        raise ValueError("stats must be (B, cap, 8)")
+    dev = labels.device
+    hull = torch.empty((B, cap, 4), dtype=torch.int64, device=dev)
+    overflow = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.pcseg_region_hull_workspace_bytes(B, H, W, cap)
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.pcseg_region_hull(_ptr(labels), _ptr(counts), _ptr(stats), _ptr(hull), _ptr(overflow), B, H, W, cap, _ptr(ws),
+                                     nbytes, _stream()), "region_hull")
+    return hull, overflow
+
+
+def hull_properties(stats, hull, counts):
+    """The derived convexity columns (scikit-image 0.18.3 conventions, pixels): ``stats`` int64 (B, cap, 8) of
+    :func:`region_reduce` and ``hull`` of :func:`region_hull` over the same labels -> float64 (B, cap, 4) in the order of
+    ``HULL_COLUMNS``, rows below min(counts[b], cap); NaN for a label without pixel."""
+    stats = _req(stats, torch.int64, 3)
+    hull = _req(hull, torch.int64, 3)
+    counts = _req(counts, torch.int32, 1)
+    B, cap = stats.shape[0], stats.shape[1]
+    if tuple(stats.shape) != (B, cap, 8) or tuple(hull.shape) != (B, cap, 4) or counts.shape[0] != B:
+        raise ValueError("stats must be (B, cap, 8), hull (B, cap, 4), counts (B,)")
+    out = torch.empty((B, cap, len(HULL_COLUMNS)), dtype=torch.float64, device=stats.device)
+    _lib.check(_lib.load().pcseg_hull_properties(_ptr(stats), _ptr(hull), _ptr(counts), _ptr(out), B, cap, _stream()),
+               "hull_properties")
+    return out
+
+
 def threshold_lt(img, threshold):
     """binary_mask = boundary_map < threshold (refine_boundaries.py:44-45)."""
     img = _req(img, torch.float32, 3)
@@ -734,12 +786,30 @@ def _shape_rows(labels, counts, stats, live, slot_of, frame_ids, scale):
                         pr[:, 2], -pr[:, 1], pr[:, 0], um(5), um(6), pr[:, 7], pr[:, 8], um(9), pr[:, 10], um(11)], dim=1)
 
 
+def _hull_rows(labels, counts, stats, live, slot_of, frame_ids, scale):
+    """The ``convexity`` table of one label batch: :func:`region_hull` + :func:`hull_properties` on the whole batch, then
+    the rows ``live`` ((B, cap) bool) in (frame, label) order as ``[frame, label, slot, convex_area, solidity, feret_um,
+    euler_number, convex_area_um2]`` (the length / ``scale``, the area / ``scale`` ^ 2, each ONE correctly rounded division)."""
+    hull, _ = region_hull(labels, counts, stats, cap=stats.shape[1])
+    props = hull_properties(stats, hull, counts)
+    b, l = torch.nonzero(live, as_tuple=True)
+    pr = props[b, l]
+    slot = slot_of[b, l].to(torch.int64)
+    slot = torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
+    # tensor divisors: a correctly rounded division per element (a Python scalar divisor is turned into a multiplication by
+    # its reciprocal on the device, one ulp off for some values -- the columns are promised equal to numpy's quotient)
+    per_um, per_um2 = torch.full_like(pr[:, 0], scale), torch.full_like(pr[:, 0], scale * scale)
+    return torch.stack([frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), slot, pr[:, 0], pr[:, 1], pr[:, 2] / per_um, pr[:, 3],
+                        pr[:, 0] / per_um2], dim=1)
+
+
 def _rows_below(counts, cap):
     return torch.arange(cap, device=counts.device)[None, :] < counts[:, None]
 
 
 def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
-                 n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None, shape=False):
+                 n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None, convex=False,
+                 shape=False):
     """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device), then one stage per switch, in
     this order.  ``distance_slots`` (the class value -> type slot table, uint8[256] numpy): ``cell_dist``, one value
     per row of ``cells`` (NaN = no entry).  ``neighbour_slots`` (the same kind of table) with ``n_types`` slots:
@@ -751,10 +821,14 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
     ``refined`` (a :class:`ClassTables`): the outputs of :func:`refined_tables`, with ``refined_points``
     ``refined_nn`` and with ``surface`` ``refined_sf``: the same two dicts over the refined rows of kind >= 1.
     ``shape``: ``shapes`` = :func:`_shape_rows` over the rows of ``cells`` and, with ``refined``, ``refined_shapes`` over
-    the refined rows of kind >= 1."""
+    the refined rows of kind >= 1.  ``convex``: ``convexity`` = :func:`_hull_rows` and ``refined_convexity``, over the same
+    rows."""
     out, d = _dense_tables(res, groups, frame_ids, C, ratios, check)
     scale = 512.0 / float(raster)
     cap = res["stats"].shape[1]
+    if convex:
+        out["convexity"] = _hull_rows(res["labels"], res["counts"], res["stats"], (res["kind"] >= 1) & _rows_below(res["counts"], cap),
+                                      res["slot_of"], frame_ids, scale)
     if shape:
         out["shapes"] = _shape_rows(res["labels"], res["counts"], res["stats"], (res["kind"] >= 1) & _rows_below(res["counts"], cap),
                                     res["slot_of"], frame_ids, scale)
@@ -777,8 +851,12 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
             out["refined_nn"] = _neighbours(pts, n_types, scale, pair_edges)
         if surface is not None:
             out["refined_sf"] = _refined_surface(res, pts, sf, mask, scale, K, surface_edges)
-        if shape:
+        if convex or shape:
             live = (out["kind_r"] >= 1) & (res["ws_stats"][:, :, 0] > 0) & _rows_below(res["n_markers"], cap)
+        if convex:
+            out["refined_convexity"] = _hull_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"], frame_ids,
+                                                  scale)
+        if shape:
             out["refined_shapes"] = _shape_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"], frame_ids,
                                                 scale)
     return out

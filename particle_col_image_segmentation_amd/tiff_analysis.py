@@ -70,7 +70,7 @@ class _LabelImage:
     def __init__(self, dev_labels, stats=None, n=0):
         self.dev = dev_labels
         self._host = None
-        self._stats, self._n, self._shape = stats, int(n), None
+        self._stats, self._n, self._shape, self._hull = stats, int(n), None, None
 
     @property
     def shape_columns(self):
@@ -83,6 +83,18 @@ class _LabelImage:
             table, _ = ops.region_shape(self.dev[None], counts, cap=self._stats.shape[1])
             self._shape = ops.shape_properties(self._stats, table, counts)[0, :self._n].cpu().numpy()
         return self._shape
+
+    @property
+    def hull_columns(self):
+        """(n, 4) float64 in the order of ``ops.HULL_COLUMNS``: ONE device call for the whole frame, at the first
+        :func:`get_cell_convexity` that meets one of its regions."""
+        if self._hull is None:
+            if self._stats is None:
+                raise AttributeError("this region carries no label image to take its shape from")
+            counts = torch.full((1,), self._n, dtype=torch.int32, device=self.dev.device)
+            table, _ = ops.region_hull(self.dev[None], counts, self._stats)
+            self._hull = ops.hull_properties(self._stats, table, counts)[0, :self._n].cpu().numpy()
+        return self._hull
 
     @property
     def host(self):
@@ -355,6 +367,27 @@ def get_cell_neighbour_distances(cell_pos, px_to_um=PX_TO_UM_CONV, edges=None):
     pairs = [(a, b) for a in range(K) for b in range(a, K)]
     return out, {(names[a], names[b]): {"n_pairs": int(h[p, 0]), "bins": h[p, 1:-1], "over": int(h[p, -1])}
                  for p, (a, b) in enumerate(pairs) if b < len(names)}
+
+
+def get_cell_convexity(cell_pos, px_to_um=PX_TO_UM_CONV):
+    """One cell or a clump, for the regions of ``cell_pos`` (strain -> regions, as get_cell_positions_and_areas returns
+    ``cell_pos`` or ``cell_clusters``): per strain a dict with ``labels`` (the regions' labels in list order) and, in the
+    same order, ``convex_area`` (pixels of the convex hull image), ``solidity`` (area / convex_area: 1 for a convex cell,
+    lower for a clump), ``feret_um`` (``feret_diameter_max / px_to_um``) and ``euler_number`` (8-connectivity), all equal to
+    scikit-image 0.18.3's ``regionprops`` values.  Lazy like the shape attributes: the regions of a frame share one
+    holder, the first call costs one device call for the frame (csrc/hull.hip), later ones none.  The regions themselves
+    gain no attribute."""
+    out = {}
+    for name, regs in cell_pos.items():
+        rows = []
+        for r in regs:
+            if r._im is None:
+                raise AttributeError("this region carries no label image to take its shape from")
+            rows.append(r._im.hull_columns[r.label - 1])
+        t = np.array(rows, np.float64).reshape(-1, 4)
+        out[name] = {"labels": np.array([int(r.label) for r in regs], np.int32), "convex_area": t[:, 0], "solidity": t[:, 1],
+                     "feret_um": t[:, 2] / px_to_um, "euler_number": t[:, 3]}
+    return out
 
 
 def get_cell_surface_distances(z_slice, cell_types, cell_pos=None, cell_clusters=None, px_to_um=PX_TO_UM_CONV, edges=None):
