@@ -2,19 +2,16 @@
 // region classification / cluster cell counts (A3/A4 tail) and the proximity
 // merge grouping (A6 tail).
 //
-// Main kernel (W % 4 == 0): a lane owns 4 adjacent columns and walks down 32 rows, accumulating each vertical run
-// of equal labels in registers (int4 / float4 loads, no cross-lane traffic) and committing it when the label
-// changes.  All table columns are integers, so the result does not depend on the order of the atomics; a 256-slot
-// direct-mapped LDS table absorbs the hot labels (background, particle) and is flushed once per block.  The generic
-// fallback walks rows: one wave per 64-pixel row segment, label runs from a ballot, closed-form run sums.
-#include "common.h"
+// Main kernels: a lane owns 4 adjacent columns and walks down 32 rows, accumulating each vertical run of equal labels in
+// registers (int4 / float4 loads, no cross-lane traffic) and committing it when the label changes.  All table columns are
+// integers, so the result does not depend on the order of the atomics; a 256-slot direct-mapped LDS table absorbs the hot
+// labels (background, particle) and is flushed once per block.  The walk of the plane-free pass, the slot table and the
+// segmented wave reduction are label_reduce.h's.  Frames with planes whose width or base address rules out 16-byte loads
+// take the row fallback: one wave per 64-pixel row segment, label runs from a ballot, closed-form run sums.
+#include "label_reduce.h"
 
 namespace pcseg {
 
-// four labels of a row as one 16-byte load
-__device__ __forceinline__ int4 ld_labels4(const int *p) { return *reinterpret_cast<const int4 *>(p); }
-
-constexpr int RED_SLOTS = 256;
 constexpr int RED_MAXC = 8;
 constexpr int RED_ROWS = 16;  // rows per block
 
@@ -35,27 +32,27 @@ __global__ void __launch_bounds__(256) region_init_kernel(long long *__restrict_
     if (sums && f < C) sums[((int64_t)b * cap + l) * C + f] = 0.0;
 }
 
-template <bool HAS_PLANES>
+// the fallback for frames WITH planes whose width or base address rules out 16-byte loads (plane-free frames of any width
+// and alignment go through region_stats_col_kernel)
 __global__ void __launch_bounds__(256) region_reduce_kernel(const int *__restrict__ labels, const float *__restrict__ planes,
                                                              const uint8_t *__restrict__ cls, unsigned long long sel, int C, int H,
                                                              int W, int cap, long long *__restrict__ stats,
                                                              double *__restrict__ sums, int *__restrict__ overflow)
 {
-    __shared__ int tags[RED_SLOTS];
-    __shared__ long long lstat[RED_SLOTS][8];
-    __shared__ double lsum[HAS_PLANES ? RED_SLOTS : 1][RED_MAXC];
+    __shared__ int tags[LABEL_SLOTS];
+    __shared__ long long lstat[LABEL_SLOTS][8];
+    __shared__ double lsum[LABEL_SLOTS][RED_MAXC];
     const int b = blockIdx.y;
     const int64_t n = (int64_t)H * W;
     const int *lab = labels + (int64_t)b * n;
-    const float *pl = HAS_PLANES ? planes + (int64_t)b * C * n : nullptr;
+    const float *pl = planes + (int64_t)b * C * n;
     long long *gst = stats + (int64_t)b * cap * 8;
-    double *gsum = HAS_PLANES ? sums + (int64_t)b * cap * C : nullptr;
-    for (int i = threadIdx.x; i < RED_SLOTS; i += 256) {
+    double *gsum = sums + (int64_t)b * cap * C;
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
         tags[i] = 0;
         lstat[i][0] = 0; lstat[i][1] = 0; lstat[i][2] = 0; lstat[i][3] = H; lstat[i][4] = W; lstat[i][5] = 0; lstat[i][6] = 0;
         lstat[i][7] = 0x7FFFFFFFFFFFFFFFLL;
-        if (HAS_PLANES)
-            for (int k = 0; k < RED_MAXC; ++k) lsum[i][k] = 0.0;
+        for (int k = 0; k < RED_MAXC; ++k) lsum[i][k] = 0.0;
     }
     __syncthreads();
     const int lane = lane_id(), wid = threadIdx.x >> 6;
@@ -68,63 +65,42 @@ __global__ void __launch_bounds__(256) region_reduce_kernel(const int *__restric
         const int c = (item % segs) * 64 + lane;
         const bool inb = c < W;
         const int l = inb ? lab[rowoff(r, W) + c] : 0;
-        float v[RED_MAXC];
-        if (HAS_PLANES) {
-            // sel != 0: plane sums only where the class map holds one of the selected values
-            bool want = inb && l > 0;
-            if (want && sel) {
-                const unsigned cv = cls[(int64_t)b * n + rowoff(r, W) + c];
-                want = cv < 64 && ((sel >> cv) & 1ull);
-            }
-#pragma unroll
-            for (int k = 0; k < RED_MAXC; ++k) v[k] = (k < C && want) ? pl[(int64_t)k * n + rowoff(r, W) + c] : 0.f;
+        // sel != 0: plane sums only where the class map holds one of the selected values
+        bool want = inb && l > 0;
+        if (want && sel) {
+            const unsigned cv = cls[(int64_t)b * n + rowoff(r, W) + c];
+            want = cv < 64 && ((sel >> cv) & 1ull);
         }
-        const int lprev = __shfl_up(l, 1);
-        const bool head = (lane == 0) || (l != lprev);
-        const unsigned long long heads = __ballot(head);
-        // run end: next head after this lane (exclusive), 64 if none
-        unsigned long long after = lane == 63 ? 0ull : (heads >> (lane + 1));
-        const int len = after ? (__ffsll((long long)after)) : (64 - lane);
-        // segmented (per run) float64 sums of the channel values: suffix sums inside the run
-        double acc[RED_MAXC];
-        if (HAS_PLANES) {
+        struct Acc {
+            double v[RED_MAXC];
+        } acc;
 #pragma unroll
-            for (int k = 0; k < RED_MAXC; ++k) acc[k] = (double)v[k];
-            // distance to the end of the run for this lane
-            unsigned long long after_me = lane == 63 ? 0ull : (heads >> (lane + 1));
-            int remain = after_me ? (__ffsll((long long)after_me) - 1) : (63 - lane);  // lanes after me in my run
-            for (int off = 1; off < 64; off <<= 1) {
+        for (int k = 0; k < RED_MAXC; ++k) acc.v[k] = (k < C && want) ? (double)pl[(int64_t)k * n + rowoff(r, W) + c] : 0.0;
+        // label runs of the row segment; per run the float64 sums of the channel values (suffix sums inside the run)
+        const WaveSeg seg = wave_segment(l);
+        const int len = seg.remain + 1;
+        segment_reduce(
+            acc, seg.remain,
+            [](const Acc &a, int off) {
+                Acc o;
 #pragma unroll
-                for (int k = 0; k < RED_MAXC; ++k) {
-                    double t = __shfl_down(acc[k], off);
-                    if (k < C && off <= remain) acc[k] += t;
-                }
-            }
-        }
-        if (head && l > 0) {
+                for (int k = 0; k < RED_MAXC; ++k) o.v[k] = __shfl_down(a.v[k], off);
+                return o;
+            },
+            [C](Acc &a, const Acc &o) {
+#pragma unroll
+                for (int k = 0; k < RED_MAXC; ++k)
+                    if (k < C) a.v[k] += o.v[k];
+            });
+        if (seg.head && l > 0) {
             if (l > cap) {
                 if (overflow) overflow[b] = 1;
             } else {
                 const long long L = len, c0 = c, c1 = c + len - 1;
                 const long long s_area = L, s_r = (long long)r * L, s_c = (c0 + c1) * L / 2;
                 const long long first = (long long)r * W + c0;
-                const int slot = l & (RED_SLOTS - 1);
-                int tag = atomicCAS(&tags[slot], 0, l);
-                if (tag == 0 || tag == l) {
-                    atomicAdd((unsigned long long *)&lstat[slot][0], (unsigned long long)s_area);
-                    atomicAdd((unsigned long long *)&lstat[slot][1], (unsigned long long)s_r);
-                    atomicAdd((unsigned long long *)&lstat[slot][2], (unsigned long long)s_c);
-                    atomic_min_i64(&lstat[slot][3], (long long)r);
-                    atomic_min_i64(&lstat[slot][4], c0);
-                    atomic_max_i64(&lstat[slot][5], (long long)r + 1);
-                    atomic_max_i64(&lstat[slot][6], c1 + 1);
-                    atomic_min_i64(&lstat[slot][7], first);
-                    if (HAS_PLANES)
-#pragma unroll
-                        for (int k = 0; k < RED_MAXC; ++k)
-                            if (k < C) atomicAdd(&lsum[slot][k], acc[k]);
-                } else {
-                    long long *t = gst + (int64_t)(l - 1) * 8;
+                // the same adds on the slot's row in LDS or on the label's row in global memory (there zero sums are skipped)
+                auto add = [&](long long *t, double *ts, bool skip_zero) {
                     atomicAdd((unsigned long long *)&t[0], (unsigned long long)s_area);
                     atomicAdd((unsigned long long *)&t[1], (unsigned long long)s_r);
                     atomicAdd((unsigned long long *)&t[2], (unsigned long long)s_c);
@@ -133,16 +109,18 @@ __global__ void __launch_bounds__(256) region_reduce_kernel(const int *__restric
                     atomic_max_i64(&t[5], (long long)r + 1);
                     atomic_max_i64(&t[6], c1 + 1);
                     atomic_min_i64(&t[7], first);
-                    if (HAS_PLANES)
 #pragma unroll
-                        for (int k = 0; k < RED_MAXC; ++k)
-                            if (k < C && acc[k] != 0.0) atomicAdd(&gsum[(int64_t)(l - 1) * C + k], acc[k]);
-                }
+                    for (int k = 0; k < RED_MAXC; ++k)
+                        if (k < C && !(skip_zero && acc.v[k] == 0.0)) atomicAdd(&ts[k], acc.v[k]);
+                };
+                const int slot = slot_claim(tags, l);
+                if (slot >= 0) add(lstat[slot], lsum[slot], false);
+                else add(gst + (int64_t)(l - 1) * 8, gsum + (int64_t)(l - 1) * C, true);
             }
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < RED_SLOTS; i += 256) {
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
         const int l = tags[i];
         if (l == 0) continue;
         long long *t = gst + (int64_t)(l - 1) * 8;
@@ -154,8 +132,7 @@ __global__ void __launch_bounds__(256) region_reduce_kernel(const int *__restric
         atomic_max_i64(&t[5], lstat[i][5]);
         atomic_max_i64(&t[6], lstat[i][6]);
         atomic_min_i64(&t[7], lstat[i][7]);
-        if (HAS_PLANES)
-            for (int k = 0; k < C; ++k) atomicAdd(&gsum[(int64_t)(l - 1) * C + k], lsum[i][k]);
+        for (int k = 0; k < C; ++k) atomicAdd(&gsum[(int64_t)(l - 1) * C + k], lsum[i][k]);
     }
 }
 
@@ -186,6 +163,14 @@ __device__ __forceinline__ void region_slots_flush(const int *s, long long *t)
     atomic_min_i64(&t[7], (long long)s[7]);
 }
 
+// column f of a slot's row into the label's row t: the three adds, the three mins, the two maxes
+__device__ __forceinline__ void region_slots_flush_word(int v, long long *t, int f)
+{
+    if (f < 3) atomicAdd((unsigned long long *)&t[f], (unsigned long long)(unsigned)v);
+    else if (f == 5 || f == 6) atomic_max_i64(&t[f], (long long)v);
+    else atomic_min_i64(&t[f], (long long)v);
+}
+
 template <int NC>
 __device__ __forceinline__ void region_commit(const RegionSlots &ls, long long *gst, double *gsum, int *overflow, int b, int cap,
                                               int C, int l, int s_area, int s_r, int s_c, int rmin, int rmax1, int c0, int c1,
@@ -195,12 +180,8 @@ __device__ __forceinline__ void region_commit(const RegionSlots &ls, long long *
         if (overflow) overflow[b] = 1;
         return;
     }
-    // (direct-mapped on purpose.  Linear probing over eight slots keeps more labels in the block's LDS table, and measured
-    // SLOWER where it matters: the float64 plane sums of a colliding label then queue at an LDS float64 atomic instead of
-    // going to the memory-side one -- the fused sums pass 540 us against 407; the integer pass did not move, 197 against 202)
-    const int slot = l & (RED_SLOTS - 1);
-    const int tag = atomicCAS(&ls.tags[slot], 0, l);
-    if (tag == 0 || tag == l) {
+    const int slot = slot_claim(ls.tags, l);
+    if (slot >= 0) {
         int *t = ls.lstat[slot];
         atomicAdd((unsigned *)&t[0], (unsigned)s_area);
         atomicAdd((unsigned *)&t[1], (unsigned)s_r);
@@ -229,15 +210,6 @@ __device__ __forceinline__ void region_commit(const RegionSlots &ls, long long *
     }
 }
 
-// The row walks below fetch row r + 1 before they process row r.  The compiler's wait-count pass cannot count loads across
-// the loop's back edge: left alone it puts `s_waitcnt vmcnt(0)` at the first USE of row r -- after the loads of row r + 1
-// went out -- and every step then waits a full memory latency (the plane-free pass ran at 1.3 TB/s for that reason).
-// "Using" row r's registers in an empty asm ahead of the fetch moves that wait to the top of the step, where only row
-// r's loads are outstanding.
-__device__ __forceinline__ void landed(const int4 &q) { asm volatile("" ::"v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w) : "memory"); }
-__device__ __forceinline__ void landed(const float4 &q) { asm volatile("" ::"v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w) : "memory"); }
-__device__ __forceinline__ void landed(unsigned q) { asm volatile("" ::"v"(q) : "memory"); }
-
 // Column-run variant (W % 4 == 0): a lane owns 4 adjacent columns and walks DOWN COL_ROWS rows; it accumulates the
 // vertical run of equal labels in registers (area, row sum, plane sums in float64) and commits when the label
 // changes.  No cross-lane traffic at all; loads are int4 / float4 and coalesced along the row.
@@ -250,9 +222,9 @@ __global__ void __launch_bounds__(256, NC > 0 ? 2 : 4) region_reduce_col_kernel(
                                                                  int H, int W, int cap, long long *__restrict__ stats,
                                                                  double *__restrict__ sums, int *__restrict__ overflow)
 {
-    __shared__ int tags[RED_SLOTS];
-    __shared__ int lstat[RED_SLOTS][8];
-    __shared__ double lsum[NC > 0 ? RED_SLOTS : 1][RED_MAXC];
+    __shared__ int tags[LABEL_SLOTS];
+    __shared__ int lstat[LABEL_SLOTS][8];
+    __shared__ double lsum[NC > 0 ? LABEL_SLOTS : 1][RED_MAXC];
     const TileIndex ti = xcd_tile_index();  // (a frame's blocks on one XCD: their atomics on the frame's tables meet in one L2)
     const int b = ti.z;
     const int64_t n = (int64_t)H * W;
@@ -260,7 +232,7 @@ __global__ void __launch_bounds__(256, NC > 0 ? 2 : 4) region_reduce_col_kernel(
     const float *pl = NC > 0 ? planes + (int64_t)b * C * n : nullptr;
     long long *gst = stats + (int64_t)b * cap * 8;
     double *gsum = NC > 0 ? sums + (int64_t)b * cap * C : nullptr;
-    for (int i = threadIdx.x; i < RED_SLOTS; i += 256) {
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
         tags[i] = 0;
         region_slots_clear(lstat[i], H, W);
         if (NC > 0)
@@ -411,169 +383,76 @@ __global__ void __launch_bounds__(256, NC > 0 ? 2 : 4) region_reduce_col_kernel(
         }
     }
     __syncthreads();
-    // flush, eight lanes per slot (see region_stats_col_kernel): one per column of the integer row, one per plane sum
-    for (int base = 0; base < RED_SLOTS; base += 32) {
-        const int i = base + (int)(threadIdx.x >> 3), f = threadIdx.x & 7;
-        const int l = tags[i];
-        if (l == 0) continue;
-        long long *t = gst + (int64_t)(l - 1) * 8 + f;
-        const int v = lstat[i][f];
-        if (f < 3) atomicAdd((unsigned long long *)t, (unsigned long long)(unsigned)v);
-        else if (f == 5 || f == 6) atomic_max_i64(t, (long long)v);
-        else atomic_min_i64(t, (long long)v);
+    // flush: one lane per column of the integer row, one per plane sum
+    slots_flush8(tags, [&](int i, int l, int f) {
+        region_slots_flush_word(lstat[i][f], gst + (int64_t)(l - 1) * 8, f);
         if (NC > 0 && f < C) atomicAdd(&gsum[(int64_t)(l - 1) * C + f], lsum[i][f]);
-    }
+    });
 }
 
-// ---- the plane-free pass (area, centroid sums, bounding box, first pixel): 4 bytes per pixel.
-// Same column walk, but a vertical run is just (label, first row, end row) -- its area, row sum and column sum follow --
-// and what bounds the pass is not the walk (64 us with the commits taken out: 4.2 TB/s) but the LDS atomics of the
-// commits, eight per run and column, most of them aimed at the slot the neighbouring lanes aim at too (72 us), and the
-// block's flush to the frame's table (55 us).  So a finished run is PARKED in two registers, and at the end of the block
-// the wave adds up the runs of ADJACENT LANES THAT CARRY THE SAME LABEL with a segmented shuffle reduction -- a region a
-// few dozen pixels wide is eight lanes -- and only the first lane of each segment goes to the LDS table.
-// (measured on the way: a four- and an eight-row load ring on the old form, 180 and 197 us against 179 -- not the loads;
-// parking alone, every lane still committing for itself at the end: 200 us against 185 -- the atomics, not the branch.)
-constexpr int STATS_ROWS = 32;  // rows per block of the plane-free pass (block partials must fit 32 bits: <= 64)
-static_assert(STATS_ROWS <= 64, "block-local sums are 32-bit");
-
+// ---- the plane-free pass (area, centroid sums, bounding box, first pixel): 4 bytes per pixel, frames of any width and
+// alignment.  The column-run walk of label_reduce.h: a vertical run is just (label, first row, end row) -- its area, row sum
+// and column sum follow.  What bounds the pass is not the walk (64 us with the commits taken out: 4.2 TB/s) but the LDS
+// atomics of the commits, eight per run and column (72 us), and the block's flush to the frame's table (55 us): hence the
+// walk's parking and its segmented reduction over the lanes.
 struct RunSum {
-    int label;  // 0 = none
+    int key;  // the label; 0 = none
     int area, srow, scol, rmin, rmax1, cmin, cmax, first;
 };
 
-__device__ __forceinline__ RunSum run_sum(int label, int start, int end, int col, int W)
-{
-    const int area = end - start;
-    return RunSum{label, area, __mul24(area, start) + ((area * (area - 1)) >> 1), __mul24(col, area), start, end, col, col,
-                  __mul24(start, W) + col};
-}
-
-__device__ __forceinline__ void run_merge(RunSum &a, const RunSum &o)
-{
-    a.area += o.area; a.srow += o.srow; a.scol += o.scol;
-    a.rmin = min(a.rmin, o.rmin); a.rmax1 = max(a.rmax1, o.rmax1);
-    a.cmin = min(a.cmin, o.cmin); a.cmax = max(a.cmax, o.cmax); a.first = min(a.first, o.first);
-}
-
-__device__ __forceinline__ void run_commit(const RegionSlots &ls, long long *gst, int *overflow, int b, int cap, const RunSum &a)
-{
-    region_commit<0>(ls, gst, nullptr, overflow, b, cap, 0, a.label, a.area, a.srow, a.scol, a.rmin, a.rmax1, a.cmin, a.cmax, a.first,
-                     nullptr);
-}
-
-// all 64 lanes call this (label 0 = nothing to add): lanes next to each other with the same label are summed into the
-// first of them, which commits
-__device__ __forceinline__ void wave_commit(const RegionSlots &ls, long long *gst, int *overflow, int b, int cap, RunSum a)
-{
-    const int lane = lane_id();
-    const int left = __shfl_up(a.label, 1);
-    const bool head = lane == 0 || a.label != left;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int remain = after ? __ffsll((long long)after) - 1 : 63 - lane;  // lanes after this one in its segment
-    for (int off = 1; off < 64; off <<= 1) {
-        RunSum o;
-        o.area = __shfl_down(a.area, off); o.srow = __shfl_down(a.srow, off); o.scol = __shfl_down(a.scol, off);
-        o.rmin = __shfl_down(a.rmin, off); o.rmax1 = __shfl_down(a.rmax1, off); o.cmin = __shfl_down(a.cmin, off);
-        o.cmax = __shfl_down(a.cmax, off); o.first = __shfl_down(a.first, off);
-        if (off <= remain) run_merge(a, o);
+template <bool VEC>
+struct StatsWalk : LabelRows<VEC> {
+    using Run = RunSum;
+    RegionSlots ls;
+    long long *gst;
+    int *overflow;
+    int b, cap;
+    __device__ __forceinline__ Run run(int label, int start, int end, int col) const
+    {
+        const int area = end - start;
+        return Run{label, area, __mul24(area, start) + ((area * (area - 1)) >> 1), __mul24(col, area), start, end, col, col,
+                   __mul24(start, this->W) + col};
     }
-    if (head && a.label > 0) run_commit(ls, gst, overflow, b, cap, a);
-}
+    static __device__ __forceinline__ Run shfl(const Run &a, int off)
+    {
+        return Run{a.key, __shfl_down(a.area, off), __shfl_down(a.srow, off), __shfl_down(a.scol, off), __shfl_down(a.rmin, off),
+                   __shfl_down(a.rmax1, off), __shfl_down(a.cmin, off), __shfl_down(a.cmax, off), __shfl_down(a.first, off)};
+    }
+    static __device__ __forceinline__ void merge(Run &a, const Run &o)
+    {
+        a.area += o.area; a.srow += o.srow; a.scol += o.scol;
+        a.rmin = min(a.rmin, o.rmin); a.rmax1 = max(a.rmax1, o.rmax1);
+        a.cmin = min(a.cmin, o.cmin); a.cmax = max(a.cmax, o.cmax); a.first = min(a.first, o.first);
+    }
+    __device__ __forceinline__ void commit(const Run &a) const
+    {
+        region_commit<0>(ls, gst, nullptr, overflow, b, cap, 0, a.key, a.area, a.srow, a.scol, a.rmin, a.rmax1, a.cmin, a.cmax, a.first,
+                         nullptr);
+    }
+};
 
+template <bool VEC>
 __global__ void __launch_bounds__(256, 4) region_stats_col_kernel(const int *__restrict__ labels, int H, int W, int cap,
                                                                    long long *__restrict__ stats, int *__restrict__ overflow)
 {
-    __shared__ int tags[RED_SLOTS];
-    __shared__ int lstat[RED_SLOTS][8];
+    __shared__ int tags[LABEL_SLOTS];
+    __shared__ int lstat[LABEL_SLOTS][8];
     // every block of a frame adds to the same few lines of the frame's table (the background's, the particle's): with a
     // frame's blocks on ONE XCD those atomics meet in one L2 instead of bouncing the line between eight
     const TileIndex ti = xcd_tile_index();
     const int b = ti.z;
-    const int64_t n = (int64_t)H * W;
-    const int *lab = labels + (int64_t)b * n;
     long long *gst = stats + (int64_t)b * cap * 8;
-    for (int i = threadIdx.x; i < RED_SLOTS; i += 256) {
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
         tags[i] = 0;
         region_slots_clear(lstat[i], H, W);
     }
     __syncthreads();
-    const RegionSlots ls{tags, lstat, nullptr};
     const int c = (ti.x * 256 + threadIdx.x) * 4;
-    const int r0 = ti.y * STATS_ROWS, r1 = min(H, r0 + STATS_ROWS);
-    // (lanes beyond the frame's width walk zeros: the reductions at the end want all 64 lanes)
-    const bool inside = c < W;
-    int cur[4] = {0, 0, 0, 0}, start[4] = {0, 0, 0, 0};
-    int parked_label[4] = {0, 0, 0, 0}, parked_rows[4] = {0, 0, 0, 0};  // first row | end row << 16 (rows < 2^15)
-    const int *at = lab + rowoff(r0, W) + (inside ? c : 0);
-    int4 l4n = inside ? ld_labels4(at) : make_int4(0, 0, 0, 0);
-    for (int r = r0; r < r1; ++r) {
-        const int4 l4 = l4n;
-        landed(l4);
-        at += W;
-        if (inside && r + 1 < r1) l4n = ld_labels4(at);
-        const int ll[4] = {l4.x, l4.y, l4.z, l4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (ll[j] != cur[j]) {
-                if (cur[j] > 0) {
-                    // (a column seldom ends two runs inside one block)
-                    if (parked_label[j])
-                        run_commit(ls, gst, overflow, b, cap,
-                                   run_sum(parked_label[j], parked_rows[j] & 0xFFFF, parked_rows[j] >> 16, c + j, W));
-                    parked_label[j] = cur[j];
-                    parked_rows[j] = start[j] | (r << 16);
-                }
-                cur[j] = ll[j];
-                start[j] = r;
-            }
-        }
-    }
-    // end of the block: the open runs and the parked ones, each folded over the lane's four columns first (they usually sit
-    // in the same region), then over the lanes
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        RunSum q[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            q[j] = pass == 0 ? run_sum(cur[j], start[j], r1, c + j, W)
-                             : run_sum(parked_label[j], parked_rows[j] & 0xFFFF, parked_rows[j] >> 16, c + j, W);
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-#pragma unroll
-            for (int i = 0; i < j; ++i)
-                if (q[j].label > 0 && q[j].label == q[i].label) {
-                    run_merge(q[i], q[j]);
-                    q[j].label = 0;
-                }
-        // a lane whose first column carries no label hands another column's run to the lane reduction instead
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (q[0].label <= 0 && q[j].label > 0) {
-                q[0] = q[j];
-                q[j].label = 0;
-            }
-        if (q[0].label < 0) q[0].label = 0;
-        wave_commit(ls, gst, overflow, b, cap, q[0]);
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (q[j].label > 0) run_commit(ls, gst, overflow, b, cap, q[j]);
-    }
+    const int r0 = ti.y * RUN_ROWS;
+    column_run_walk(StatsWalk<VEC>{{labels + (int64_t)b * H * W, c, W}, RegionSlots{tags, lstat, nullptr}, gst, overflow, b, cap}, c, r0,
+                    min(H, r0 + RUN_ROWS));
     __syncthreads();
-    // flush: EIGHT LANES PER SLOT, one per column of the table row, so that one atomic instruction carries up to eight
-    // neighbouring 8-byte words of a row's 64-byte line (the three adds, the three mins, the two maxes) instead of 64 lanes
-    // aiming at 64 different lines eight times over
-    for (int base = 0; base < RED_SLOTS; base += 32) {
-        const int i = base + (int)(threadIdx.x >> 3), f = threadIdx.x & 7;
-        const int l = tags[i];
-        if (l == 0) continue;
-        long long *t = gst + (int64_t)(l - 1) * 8 + f;
-        const int v = lstat[i][f];
-        if (f < 3) atomicAdd((unsigned long long *)t, (unsigned long long)(unsigned)v);
-        else if (f == 5 || f == 6) atomic_max_i64(t, (long long)v);
-        else atomic_min_i64(t, (long long)v);
-    }
+    slots_flush8(tags, [&](int i, int l, int f) { region_slots_flush_word(lstat[i][f], gst + (int64_t)(l - 1) * 8, f); });
 }
 
 // ---- plane sums of TWO label images in one pass over the planes (M1 for the class-map components and for the refined
@@ -595,9 +474,8 @@ __device__ __forceinline__ void sums_commit(const SumSlots &ls, double *gsum, in
 #pragma unroll
     for (int k = 0; k < NC; ++k) any = any || acc[k] != 0.0;
     if (!any) return;  // (regions outside the class selection, runs of zero-valued planes)
-    const int slot = l & (RED_SLOTS - 1);
-    const int tag = atomicCAS(&ls.tags[slot], 0, l);
-    if (tag == 0 || tag == l) {
+    const int slot = slot_claim(ls.tags, l);
+    if (slot >= 0) {
 #pragma unroll
         for (int k = 0; k < NC; ++k)
             if (k < C && acc[k] != 0.0) atomicAdd(&ls.lsum[slot][k], acc[k]);
@@ -621,9 +499,9 @@ __global__ void __launch_bounds__(256, (NC <= 5 && !STATS_B) ? 3 : 2) region_sum
                                                                   int cap_b, double *__restrict__ sums_a, double *__restrict__ sums_b,
                                                                   long long *__restrict__ stats_b, int *__restrict__ overflow_b)
 {
-    __shared__ int tags_a[RED_SLOTS], tags_b[RED_SLOTS];
-    __shared__ double lsum_a[RED_SLOTS][RED_MAXC], lsum_b[RED_SLOTS][RED_MAXC];
-    __shared__ int lstat_b[STATS_B ? RED_SLOTS : 1][8];
+    __shared__ int tags_a[LABEL_SLOTS], tags_b[LABEL_SLOTS];
+    __shared__ double lsum_a[LABEL_SLOTS][RED_MAXC], lsum_b[LABEL_SLOTS][RED_MAXC];
+    __shared__ int lstat_b[STATS_B ? LABEL_SLOTS : 1][8];
     const TileIndex ti = xcd_tile_index();  // (a frame's blocks on one XCD: their atomics on the frame's tables meet in one L2)
     const int b = ti.z;
     const int64_t n = (int64_t)H * W;
@@ -631,7 +509,7 @@ __global__ void __launch_bounds__(256, (NC <= 5 && !STATS_B) ? 3 : 2) region_sum
     const float *pl = planes + (int64_t)b * C * n;
     double *ga = sums_a + (int64_t)b * cap_a * C, *gb = sums_b + (int64_t)b * cap_b * C;
     long long *gst_b = STATS_B ? stats_b + (int64_t)b * cap_b * 8 : nullptr;
-    for (int i = threadIdx.x; i < RED_SLOTS; i += 256) {
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
         tags_a[i] = 0;
         tags_b[i] = 0;
         for (int k = 0; k < RED_MAXC; ++k) { lsum_a[i][k] = 0.0; lsum_b[i][k] = 0.0; }
@@ -746,16 +624,15 @@ __global__ void __launch_bounds__(256, (NC <= 5 && !STATS_B) ? 3 : 2) region_sum
         }
     }
     __syncthreads();
-    // flush: eight lanes per slot, one per plane, so that one atomic instruction carries a row's neighbouring sums (merged per
-    // 64-byte line by the hardware) instead of 64 lanes aiming at 64 different rows once per plane
+    // flush: one lane per plane (a row's neighbouring sums are merged per 64-byte line by the hardware)
     static_assert(RED_MAXC == 8, "eight lanes per slot");
-    for (int base = 0; base < RED_SLOTS; base += 32) {
-        const int i = base + (int)(threadIdx.x >> 3), k = threadIdx.x & 7;
-        const int l1 = tags_a[i], l2 = tags_b[i];
-        if (l1 && k < C && lsum_a[i][k] != 0.0) atomicAdd(&ga[(int64_t)(l1 - 1) * C + k], lsum_a[i][k]);
-        if (l2 && k < C && lsum_b[i][k] != 0.0) atomicAdd(&gb[(int64_t)(l2 - 1) * C + k], lsum_b[i][k]);
-        if (STATS_B && l2 && k == 0) region_slots_flush(lstat_b[i], gst_b + (int64_t)(l2 - 1) * 8);
-    }
+    slots_flush8(tags_a, [&](int i, int l, int k) {
+        if (k < C && lsum_a[i][k] != 0.0) atomicAdd(&ga[(int64_t)(l - 1) * C + k], lsum_a[i][k]);
+    });
+    slots_flush8(tags_b, [&](int i, int l, int k) {
+        if (k < C && lsum_b[i][k] != 0.0) atomicAdd(&gb[(int64_t)(l - 1) * C + k], lsum_b[i][k]);
+        if (STATS_B && k == 0) region_slots_flush(lstat_b[i], gst_b + (int64_t)(l - 1) * 8);
+    });
 }
 
 __global__ void __launch_bounds__(256) region_class_kernel(const long long *__restrict__ stats, const uint8_t *__restrict__ cls,
@@ -1012,7 +889,7 @@ __global__ void __launch_bounds__(MG_THREADS) merge_fused_kernel(const unsigned 
     __syncthreads();  // (group ids and the zeroed rows of this block's groups: written above, used below by the same block)
     // (4) members take their leader's id; every listed region adds itself to its group's row (tiff_analysis.py:855-872)
     // (eight lanes per member, one per column of the row: the reads are one 64-byte line per member and the atomics of an
-    // instruction that fall into one line travel together -- see region_stats_col_kernel's flush)
+    // instruction that fall into one line travel together -- see slots_flush8, label_reduce.h)
     for (int idx = threadIdx.x; idx < R * 8; idx += MG_THREADS) {
         const int k = idx >> 3, f = idx & 7;
         int g = 0;
@@ -1252,21 +1129,20 @@ int pcseg_region_reduce_sel(const int32_t *labels, const int32_t *counts, const 
     const bool vec = (W % 4) == 0 && ((uintptr_t)labels % 16) == 0 && (!planes || ((uintptr_t)planes % 16) == 0) &&
                      (!sel || ((uintptr_t)cls % 4) == 0);
     const dim3 cgrid((W / 4 + 255) / 256, (H + COL_ROWS - 1) / COL_ROWS, B);
+    const dim3 sgrid((W + 1023) / 1024, (H + RUN_ROWS - 1) / RUN_ROWS, B);  // the plane-free pass: any width
     if (vec && planes && C <= 5)
         PCSEG_LAUNCH(region_reduce_col_kernel<5>, cgrid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats, sums,
                      overflow);
     else if (vec && planes)
         PCSEG_LAUNCH(region_reduce_col_kernel<8>, cgrid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats, sums,
                      overflow);
-    else if (vec)
-        PCSEG_LAUNCH(region_stats_col_kernel, dim3(cgrid.x, (H + STATS_ROWS - 1) / STATS_ROWS, B), dim3(256), 0, s, labels, H, W, cap,
-                     (long long *)stats, overflow);
     else if (planes)
-        PCSEG_LAUNCH(region_reduce_kernel<true>, grid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats,
-                           sums, overflow);
+        PCSEG_LAUNCH(region_reduce_kernel, grid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats, sums,
+                     overflow);
+    else if (vec)
+        PCSEG_LAUNCH(region_stats_col_kernel<true>, sgrid, dim3(256), 0, s, labels, H, W, cap, (long long *)stats, overflow);
     else
-        PCSEG_LAUNCH(region_reduce_kernel<false>, grid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap,
-                           (long long *)stats, sums, overflow);
+        PCSEG_LAUNCH(region_stats_col_kernel<false>, sgrid, dim3(256), 0, s, labels, H, W, cap, (long long *)stats, overflow);
     PCSEG_CHECK_LAUNCH();
     if (cls) {
         PCSEG_LAUNCH(region_class_kernel, gi, dim3(256), 0, s, (const long long *)stats, cls, counts, cls_out, cap,

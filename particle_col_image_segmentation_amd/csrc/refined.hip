@@ -4,9 +4,9 @@
 // pcseg_label_parent: for every refined ROI r of a frame, the class-map component a that shares the most pixels with it
 // (ties: the smallest a), that overlap, and the number of distinct components it touches.  Three passes, all on the
 // device, all exact (integer counts: any atomic order gives the same result):
-//   1. lp_count_kernel   the column-run walk of region_stats_col_kernel (reduce.hip) over BOTH label images: a lane owns
-//                        4 columns of a 32-row block, a run is a vertical stretch of constant (r, a), runs of adjacent
-//                        lanes with the same pair are summed by a segmented shuffle, and a finished run goes into r's
+//   1. lp_count_kernel   the column-run walk of label_reduce.h over BOTH label images: a lane owns 4 columns of a 32-row
+//                        block, a run is a vertical stretch of constant (r, a), runs of adjacent lanes with the same
+//                        pair are summed by a segmented shuffle, and a finished run goes into r's
 //                        candidate table: LP_SLOTS (label, count) slots, a slot claimed by atomicCAS on its label word.
 //                        An r that finds every slot taken by other labels is marked spilled and listed (once).
 //   2. lp_spill_kernel   one block per spilled r: scans r's bounding box, counting a in a direct-indexed LDS array over
@@ -16,12 +16,12 @@
 //
 // pcseg_refined_layout / pcseg_refined_table_write: the `refined`, `cell_resolution` and `frames_refined` rows (one
 // block per frame, row positions by block scans as in tables.hip) and the refined points for pcseg_point_neighbours.
+#include "label_reduce.h"
 #include "table_common.h"
 
 namespace pcseg {
 
 constexpr int LP_SLOTS = 16;  // candidate (label, count) slots per refined ROI: one 128-byte line
-constexpr int LP_ROWS = 32;   // rows per block of the count pass
 constexpr int LP_WIN = 4096;  // label window of the spill pass (16 KiB of LDS)
 
 __global__ void __launch_bounds__(256) lp_clear_kernel(const int *__restrict__ counts_r, int B, int cap, int *__restrict__ cand,
@@ -57,26 +57,46 @@ __device__ __forceinline__ void lp_commit(int *cand, int *spilled, int *spill_li
 }
 
 struct LpRun {
-    int r, a, n;  // r == 0: nothing
+    long long key;  // r << 32 | a; 0 = nothing
+    int n;
 };
 
-// all 64 lanes call this: lanes next to each other with the same pair are summed into the first of them, which commits
-__device__ __forceinline__ void lp_wave_commit(int *cand, int *spilled, int *spill_list, int *n_spill, int64_t rowbase, LpRun q)
-{
-    const int lane = lane_id();
-    const int left_r = __shfl_up(q.r, 1), left_a = __shfl_up(q.a, 1);
-    const bool head = lane == 0 || q.r != left_r || q.a != left_a;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int remain = after ? __ffsll((long long)after) - 1 : 63 - lane;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_down(q.n, off);
-        if (off <= remain) q.n += o;
-    }
-    if (head && q.r > 0) lp_commit(cand, spilled, spill_list, n_spill, rowbase + q.r - 1, q.a, q.n);
-}
+struct LpRaw {
+    int4 r, a;
+};
+__device__ __forceinline__ void landed(const LpRaw &q) { landed(q.r); landed(q.a); }
 
-// VEC: W % 4 == 0 and both images 16-byte aligned (int4 loads); otherwise four scalar loads per row
+// the walk's key is the pair (refined label, class-map label) of a pixel.
+// VEC: W % 4 == 0 and both images 16-byte aligned (int4 loads); otherwise four guarded loads per row and image
+template <bool VEC>
+struct LpWalk {
+    using Key = long long;
+    using Raw = LpRaw;
+    using Run = LpRun;
+    const int *pa, *pr;  // the frame's two images
+    int c, W, nr;
+    int *cand, *spilled, *spill_list, *n_spill;
+    int64_t rowbase;
+    __device__ __forceinline__ Raw load(int y) const
+    {
+        return Raw{row_labels4<VEC>(pr + rowoff(y, W), c, W), row_labels4<VEC>(pa + rowoff(y, W), c, W)};
+    }
+    __device__ __forceinline__ void keys(const Raw &q, Key k[4]) const
+    {
+        const int rv[4] = {q.r.x, q.r.y, q.r.z, q.r.w}, av[4] = {q.a.x, q.a.y, q.a.z, q.a.w};
+        // pixels on A = 0, on R = 0 or on an R label without a row (above min(counts_r, cap)) belong to no pair
+#pragma unroll
+        for (int j = 0; j < 4; ++j) k[j] = (rv[j] >= 1 && rv[j] <= nr && av[j] >= 1) ? ((long long)rv[j] << 32) | (unsigned)av[j] : 0;
+    }
+    __device__ __forceinline__ Run run(Key key, int start, int end, int) const { return Run{key, end - start}; }
+    static __device__ __forceinline__ Run shfl(const Run &q, int off) { return Run{q.key, __shfl_down(q.n, off)}; }
+    static __device__ __forceinline__ void merge(Run &q, const Run &o) { q.n += o.n; }
+    __device__ __forceinline__ void commit(const Run &q) const
+    {
+        lp_commit(cand, spilled, spill_list, n_spill, rowbase + (int)(q.key >> 32) - 1, (int)q.key, q.n);
+    }
+};
+
 template <bool VEC>
 __global__ void __launch_bounds__(256) lp_count_kernel(const int *__restrict__ la, const int *__restrict__ lr,
                                                        const int *__restrict__ counts_r, int H, int W, int cap, int *__restrict__ cand,
@@ -84,69 +104,12 @@ __global__ void __launch_bounds__(256) lp_count_kernel(const int *__restrict__ l
 {
     const TileIndex ti = xcd_tile_index();
     const int b = ti.z;
-    const int64_t npx = (int64_t)H * W, rowbase = (int64_t)b * cap;
-    const int nr = min(counts_r[b], cap);
-    const int *pa = la + b * npx, *pr = lr + b * npx;
+    const int64_t npx = (int64_t)H * W;
     const int c = (ti.x * 256 + threadIdx.x) * 4;
-    const int r0 = ti.y * LP_ROWS, r1 = min(H, r0 + LP_ROWS);
-    int cr[4] = {0, 0, 0, 0}, ca[4] = {0, 0, 0, 0}, start[4] = {0, 0, 0, 0};
-    LpRun parked[4] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    for (int y = r0; y < r1; ++y) {
-        int rv[4] = {0, 0, 0, 0}, av[4] = {0, 0, 0, 0};
-        const int64_t o = rowoff(y, W) + c;
-        if (VEC) {
-            if (c < W) {
-                const int4 r4 = *reinterpret_cast<const int4 *>(pr + o), a4 = *reinterpret_cast<const int4 *>(pa + o);
-                rv[0] = r4.x; rv[1] = r4.y; rv[2] = r4.z; rv[3] = r4.w;
-                av[0] = a4.x; av[1] = a4.y; av[2] = a4.z; av[3] = a4.w;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (c + j < W) { rv[j] = pr[o + j]; av[j] = pa[o + j]; }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // pixels on A = 0, on R = 0 or on an R label without a row (above min(counts_r, cap)) belong to no pair
-            const bool ok = rv[j] >= 1 && rv[j] <= nr && av[j] >= 1;
-            const int rr = ok ? rv[j] : 0, aa = ok ? av[j] : 0;
-            if (rr != cr[j] || aa != ca[j]) {
-                if (cr[j] > 0) {
-                    // (a column seldom ends two runs inside one block)
-                    if (parked[j].r > 0) lp_commit(cand, spilled, spill_list, n_spill, rowbase + parked[j].r - 1, parked[j].a, parked[j].n);
-                    parked[j] = LpRun{cr[j], ca[j], y - start[j]};
-                }
-                cr[j] = rr;
-                ca[j] = aa;
-                start[j] = y;
-            }
-        }
-    }
-    // end of the block: the open runs, then the parked ones, each folded over the lane's four columns, then over the lanes
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        LpRun q[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) q[j] = pass == 0 ? LpRun{cr[j], ca[j], r1 - start[j]} : parked[j];
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-#pragma unroll
-            for (int i = 0; i < j; ++i)
-                if (q[j].r > 0 && q[j].r == q[i].r && q[j].a == q[i].a) {
-                    q[i].n += q[j].n;
-                    q[j].r = 0;
-                }
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (q[0].r <= 0 && q[j].r > 0) {
-                q[0] = q[j];
-                q[j].r = 0;
-            }
-        lp_wave_commit(cand, spilled, spill_list, n_spill, rowbase, q[0]);
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (q[j].r > 0) lp_commit(cand, spilled, spill_list, n_spill, rowbase + q[j].r - 1, q[j].a, q[j].n);
-    }
+    const int r0 = ti.y * RUN_ROWS;
+    column_run_walk(LpWalk<VEC>{la + b * npx, lr + b * npx, c, W, min(counts_r[b], cap), cand, spilled, spill_list, n_spill,
+                                (int64_t)b * cap},
+                    c, r0, min(H, r0 + RUN_ROWS));
 }
 
 // block-wide (sum, max, min) over 256 threads
@@ -492,7 +455,7 @@ int pcseg_label_parent(const int32_t *labels_a, const int32_t *labels_r, const i
     const int grid = (int)((rows + 255) / 256 < 4096 ? (rows + 255) / 256 : 4096);
     PCSEG_LAUNCH(lp_clear_kernel, dim3(grid), dim3(256), 0, s, counts_r, B, cap, cand, spilled, n_spill, overflow);
     PCSEG_CHECK_LAUNCH();
-    const dim3 cgrid((unsigned)((W + 1023) / 1024), (unsigned)((H + LP_ROWS - 1) / LP_ROWS), (unsigned)B);
+    const dim3 cgrid((unsigned)((W + 1023) / 1024), (unsigned)((H + RUN_ROWS - 1) / RUN_ROWS), (unsigned)B);
     const bool vec = W % 4 == 0 && ((uintptr_t)labels_a % 16) == 0 && ((uintptr_t)labels_r % 16) == 0;
     if (vec)
         PCSEG_LAUNCH(lp_count_kernel<true>, cgrid, dim3(256), 0, s, labels_a, labels_r, counts_r, H, W, cap, cand, spilled, spill_list,

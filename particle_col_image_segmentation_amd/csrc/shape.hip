@@ -7,25 +7,22 @@
 //
 // Launches (asynchronous, no host read):
 //   shape_init_kernel       rows below min(counts[b], cap) zeroed, the frame's label bound and overflow flag set
-//   shape_moments_kernel    the column-run walk of region_stats_col_kernel (reduce.hip): a lane owns 4 columns x 32 rows,
-//                           a vertical run [r0, r1) in column c adds S2(r1 - 1) - S2(r0 - 1), c * sum r and n c^2 in closed
-//                           form (no per-pixel work); finished runs are parked, same-label neighbouring lanes are summed by a
-//                           segmented shuffle, then a 256-slot LDS table of 64-bit partials (the sum of r^2 of one block in
-//                           absolute rows does not fit 32 bits) and an eight-lanes-per-row flush
+//   shape_moments_kernel    the column-run walk of label_reduce.h (a lane owns 4 columns x 32 rows, same-label neighbouring
+//                           lanes are summed by a segmented shuffle): a vertical run [r0, r1) in column c adds S2(r1 - 1) -
+//                           S2(r0 - 1), c * sum r and n c^2 in closed form (no per-pixel work), into a slot table of 64-bit
+//                           partials (the sum of r^2 of one block in absolute rows does not fit 32 bits) with an
+//                           eight-lanes-per-row flush
 //   shape_perimeter_kernel  skimage.measure.perimeter(region.image, 4) on integers: a 64 x 32 label tile with a 2-pixel halo
 //                           in LDS, border bits of the tile plus a 1-pixel ring in LDS, the class of a border pixel from three
 //                           constant 64-bit masks indexed by its neighbourhood value; a lane walks 8 rows of one column, the
 //                           wave sums same-label neighbouring lanes, then one LDS table and integer global atomics
 //   shape_properties_kernel one thread per row: the derived float64 columns
-#include "common.h"
+#include "label_reduce.h"
 
 // every product, quotient and sum of the derived columns rounded on its own (no FMA), as neighbours.hip and surface.hip
 #pragma clang fp contract(off)
 
 namespace pcseg {
-
-constexpr int SH_SLOTS = 256;
-constexpr int SH_ROWS = 32;  // rows per block of the moments pass
 
 struct ShWorkspace {
     int *nrows;  // [B] min(counts[b], cap): the label bound of both passes (labels above it own no initialised row)
@@ -57,167 +54,79 @@ __global__ void __launch_bounds__(256) shape_init_kernel(long long *__restrict__
 
 // ---- moments
 struct RunMom {
-    int label;  // 0 = none
+    int key;  // the label; 0 = none
     unsigned long long rr, rc, cc;
 };
 
 // sum of i^2 for i = 0..x (x >= -1)
 __device__ __forceinline__ long long sum_squares(long long x) { return x * (x + 1) * (2 * x + 1) / 6; }
 
-__device__ __forceinline__ RunMom run_mom(int label, int start, int end, int col)
-{
-    const long long n = end - start;
-    const long long sr = n * (start + end - 1) / 2;
-    return RunMom{label, (unsigned long long)(sum_squares(end - 1) - sum_squares(start - 1)), (unsigned long long)(sr * col),
-                  (unsigned long long)(n * col * col)};
-}
-
-__device__ __forceinline__ void mom_merge(RunMom &a, const RunMom &o) { a.rr += o.rr; a.rc += o.rc; a.cc += o.cc; }
-
-struct MomSlots {
+// VEC: W % 4 == 0 and a 16-byte aligned image: one 16-byte load per row; otherwise four guarded 4-byte loads
+template <bool VEC>
+struct MomentsWalk : LabelRows<VEC> {
+    using Run = RunMom;
     int *tags;
     unsigned long long (*lm)[4];
+    long long *gout;
+    int *overflow;
+    int b, nl, cap;
+    __device__ __forceinline__ Run run(int label, int start, int end, int col) const
+    {
+        const long long n = end - start;
+        const long long sr = n * (start + end - 1) / 2;
+        return Run{label, (unsigned long long)(sum_squares(end - 1) - sum_squares(start - 1)), (unsigned long long)(sr * col),
+                   (unsigned long long)(n * col * col)};
+    }
+    static __device__ __forceinline__ Run shfl(const Run &a, int off)
+    {
+        return Run{a.key, __shfl_down(a.rr, off), __shfl_down(a.rc, off), __shfl_down(a.cc, off)};
+    }
+    static __device__ __forceinline__ void merge(Run &a, const Run &o) { a.rr += o.rr; a.rc += o.rc; a.cc += o.cc; }
+    __device__ __forceinline__ void commit(const Run &a) const
+    {
+        if (a.key > nl) {
+            if (a.key > cap && overflow) overflow[b] = 1;
+            return;
+        }
+        const int slot = slot_claim(tags, a.key);
+        if (slot >= 0) {
+            atomicAdd(&lm[slot][0], a.rr);
+            atomicAdd(&lm[slot][1], a.rc);
+            atomicAdd(&lm[slot][2], a.cc);
+        } else {
+            unsigned long long *t = (unsigned long long *)(gout + (int64_t)(a.key - 1) * 8);
+            atomicAdd(&t[0], a.rr);
+            atomicAdd(&t[1], a.rc);
+            atomicAdd(&t[2], a.cc);
+        }
+    }
 };
 
-__device__ __forceinline__ void mom_commit(const MomSlots &ls, long long *gout, int *overflow, int b, int nl, int cap, const RunMom &a)
-{
-    if (a.label > nl) {
-        if (a.label > cap && overflow) overflow[b] = 1;
-        return;
-    }
-    const int slot = a.label & (SH_SLOTS - 1);
-    const int tag = atomicCAS(&ls.tags[slot], 0, a.label);
-    if (tag == 0 || tag == a.label) {
-        atomicAdd(&ls.lm[slot][0], a.rr);
-        atomicAdd(&ls.lm[slot][1], a.rc);
-        atomicAdd(&ls.lm[slot][2], a.cc);
-    } else {
-        unsigned long long *t = (unsigned long long *)(gout + (int64_t)(a.label - 1) * 8);
-        atomicAdd(&t[0], a.rr);
-        atomicAdd(&t[1], a.rc);
-        atomicAdd(&t[2], a.cc);
-    }
-}
-
-// all 64 lanes call this (label 0 = nothing to add): lanes next to each other with the same label are summed into the
-// first of them, which commits
-__device__ __forceinline__ void mom_wave_commit(const MomSlots &ls, long long *gout, int *overflow, int b, int nl, int cap, RunMom a)
-{
-    const int lane = lane_id();
-    const int left = __shfl_up(a.label, 1);
-    const bool head = lane == 0 || a.label != left;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int remain = after ? __ffsll((long long)after) - 1 : 63 - lane;  // lanes after this one in its segment
-    for (int off = 1; off < 64; off <<= 1) {
-        RunMom o;
-        o.rr = __shfl_down(a.rr, off); o.rc = __shfl_down(a.rc, off); o.cc = __shfl_down(a.cc, off);
-        if (off <= remain) mom_merge(a, o);
-    }
-    if (head && a.label > 0) mom_commit(ls, gout, overflow, b, nl, cap, a);
-}
-
-__device__ __forceinline__ void shape_landed(const int4 &q) { asm volatile("" ::"v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w) : "memory"); }
-
-// VEC: W % 4 == 0 and a 16-byte aligned image: one 16-byte load per row; otherwise four guarded 4-byte loads
 template <bool VEC>
 __global__ void __launch_bounds__(256, 4) shape_moments_kernel(const int *__restrict__ labels, const int *__restrict__ nrows, int H,
                                                                 int W, int cap, long long *__restrict__ out,
                                                                 int *__restrict__ overflow)
 {
-    __shared__ int tags[SH_SLOTS];
-    __shared__ unsigned long long lm[SH_SLOTS][4];
+    __shared__ int tags[LABEL_SLOTS];
+    __shared__ unsigned long long lm[LABEL_SLOTS][4];
     const TileIndex ti = xcd_tile_index();  // (a frame's blocks on one XCD: their atomics on the frame's table meet in one L2)
     const int b = ti.z;
     const int nl = nrows[b];
-    const int *lab = labels + (int64_t)b * H * W;
     long long *gout = out + (int64_t)b * cap * 8;
-    for (int i = threadIdx.x; i < SH_SLOTS; i += 256) {
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
         tags[i] = 0;
         lm[i][0] = 0; lm[i][1] = 0; lm[i][2] = 0;
     }
     __syncthreads();
-    const MomSlots ls{tags, lm};
     const int c = (ti.x * 256 + threadIdx.x) * 4;
-    const int r0 = ti.y * SH_ROWS, r1 = min(H, r0 + SH_ROWS);
-    // (lanes beyond the frame's width walk zeros: the reductions at the end want all 64 lanes)
-    auto load4 = [&](int r) {
-        int4 q = make_int4(0, 0, 0, 0);
-        if (c < W) {
-            const int *at = lab + rowoff(r, W) + c;
-            if (VEC) {
-                q = *reinterpret_cast<const int4 *>(at);
-            } else {
-                q.x = at[0];
-                if (c + 1 < W) q.y = at[1];
-                if (c + 2 < W) q.z = at[2];
-                if (c + 3 < W) q.w = at[3];
-            }
-        }
-        return q;
-    };
-    int cur[4] = {0, 0, 0, 0}, start[4] = {0, 0, 0, 0};
-    int parked_label[4] = {0, 0, 0, 0}, parked_rows[4] = {0, 0, 0, 0};  // first row | end row << 16 (rows < 2^15)
-    int4 l4n = load4(r0);
-    for (int r = r0; r < r1; ++r) {
-        const int4 l4 = l4n;
-        shape_landed(l4);
-        if (r + 1 < r1) l4n = load4(r + 1);
-        const int ll[4] = {l4.x, l4.y, l4.z, l4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (ll[j] != cur[j]) {
-                if (cur[j] > 0) {
-                    // (a column seldom ends two runs inside one block)
-                    if (parked_label[j])
-                        mom_commit(ls, gout, overflow, b, nl, cap,
-                                   run_mom(parked_label[j], parked_rows[j] & 0xFFFF, parked_rows[j] >> 16, c + j));
-                    parked_label[j] = cur[j];
-                    parked_rows[j] = start[j] | (r << 16);
-                }
-                cur[j] = ll[j];
-                start[j] = r;
-            }
-        }
-    }
-    // end of the block: the open runs and the parked ones, each folded over the lane's four columns first, then over the lanes
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        RunMom q[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            q[j] = pass == 0 ? run_mom(cur[j], start[j], r1, c + j)
-                             : run_mom(parked_label[j], parked_rows[j] & 0xFFFF, parked_rows[j] >> 16, c + j);
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-#pragma unroll
-            for (int i = 0; i < j; ++i)
-                if (q[j].label > 0 && q[j].label == q[i].label) {
-                    mom_merge(q[i], q[j]);
-                    q[j].label = 0;
-                }
-        // a lane whose first column carries no label hands another column's run to the lane reduction instead
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (q[0].label <= 0 && q[j].label > 0) {
-                q[0] = q[j];
-                q[j].label = 0;
-            }
-        if (q[0].label < 0) q[0].label = 0;
-        mom_wave_commit(ls, gout, overflow, b, nl, cap, q[0]);
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (q[j].label > 0) mom_commit(ls, gout, overflow, b, nl, cap, q[j]);
-    }
+    const int r0 = ti.y * RUN_ROWS;
+    column_run_walk(MomentsWalk<VEC>{{labels + (int64_t)b * H * W, c, W}, tags, lm, gout, overflow, b, nl, cap}, c, r0,
+                    min(H, r0 + RUN_ROWS));
     __syncthreads();
-    // flush, eight lanes per slot: one atomic instruction carries the three neighbouring words of a row's 64-byte line
-    for (int base = 0; base < SH_SLOTS; base += 32) {
-        const int i = base + (int)(threadIdx.x >> 3), f = threadIdx.x & 7;
-        const int l = tags[i];
-        if (l == 0 || f >= 3) continue;
-        const unsigned long long v = lm[i][f];
-        if (v) atomicAdd((unsigned long long *)(gout + (int64_t)(l - 1) * 8 + f), v);
-    }
+    // flush: one atomic instruction carries the three neighbouring words of a row's 64-byte line
+    slots_flush8(tags, [&](int i, int l, int f) {
+        if (f < 3 && lm[i][f]) atomicAdd((unsigned long long *)(gout + (int64_t)(l - 1) * 8 + f), lm[i][f]);
+    });
 }
 
 // ---- perimeter
@@ -244,9 +153,8 @@ __device__ __forceinline__ void per_commit(const PerSlots &ls, long long *gout, 
         return;
     }
     const unsigned v[4] = {lo & 0xFFFFu, lo >> 16, hi & 0xFFFFu, hi >> 16};
-    const int slot = l & (SH_SLOTS - 1);
-    const int tag = atomicCAS(&ls.tags[slot], 0, l);
-    if (tag == 0 || tag == l) {
+    const int slot = slot_claim(ls.tags, l);
+    if (slot >= 0) {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (v[k]) atomicAdd((unsigned *)&ls.cnt[slot][k], v[k]);
@@ -264,15 +172,15 @@ __global__ void __launch_bounds__(256) shape_perimeter_kernel(const int *__restr
 {
     __shared__ int lab[PL_H][PL_W];
     __shared__ uint8_t bb[PB_H][PB_W + 2];
-    __shared__ int tags[SH_SLOTS];
-    __shared__ int cnt[SH_SLOTS][4];
+    __shared__ int tags[LABEL_SLOTS];
+    __shared__ int cnt[LABEL_SLOTS][4];
     const TileIndex ti = xcd_tile_index();  // (neighbouring tiles share their halo lines in one L2)
     const int b = ti.z;
     const int nl = nrows[b];
     const int *g = labels + (int64_t)b * H * W;
     long long *gout = out + (int64_t)b * cap * 8;
     const int R0 = ti.y * PT_H, C0 = ti.x * PT_W;
-    for (int i = threadIdx.x; i < SH_SLOTS; i += 256) {
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
         tags[i] = 0;
         cnt[i][0] = 0; cnt[i][1] = 0; cnt[i][2] = 0; cnt[i][3] = 0;
     }
@@ -314,24 +222,15 @@ __global__ void __launch_bounds__(256) shape_perimeter_kernel(const int *__restr
     }
     if (!(lo | hi)) cur = 0;
     // lanes next to each other with the same label are summed into the first of them
-    {
-        const int left = __shfl_up(cur, 1);
-        const bool head = lane == 0 || cur != left;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int remain = after ? __ffsll((long long)after) - 1 : 63 - lane;
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned olo = __shfl_down(lo, off), ohi = __shfl_down(hi, off);
-            if (off <= remain) {
-                lo += olo;
-                hi += ohi;
-            }
-        }
-        if (head && cur > 0) per_commit(ls, gout, overflow, b, nl, cap, cur, lo, hi);
-    }
+    const WaveSeg seg = wave_segment(cur);
+    uint2 cnt2 = make_uint2(lo, hi);
+    segment_reduce(
+        cnt2, seg.remain, [](const uint2 &a, int off) { return make_uint2(__shfl_down(a.x, off), __shfl_down(a.y, off)); },
+        [](uint2 &a, const uint2 &o) { a.x += o.x; a.y += o.y; });
+    if (seg.head && cur > 0) per_commit(ls, gout, overflow, b, nl, cap, cur, cnt2.x, cnt2.y);
     __syncthreads();
     // flush, four lanes per slot (columns 3..6 of the row)
-    for (int base = 0; base < SH_SLOTS; base += 64) {
+    for (int base = 0; base < LABEL_SLOTS; base += 64) {
         const int i = base + (int)(threadIdx.x >> 2), f = threadIdx.x & 3;
         const int l = tags[i];
         if (l == 0) continue;
@@ -410,7 +309,7 @@ int pcseg_region_shape(const int32_t *labels, const int32_t *counts, int64_t *sh
     PCSEG_LAUNCH(shape_init_kernel, dim3((unsigned)(((int64_t)cap * 8 + 255) / 256), B), dim3(256), 0, s, out, counts, w.nrows,
                  overflow, cap);
     PCSEG_CHECK_LAUNCH();
-    const dim3 mgrid((W + 1023) / 1024, (H + SH_ROWS - 1) / SH_ROWS, B);
+    const dim3 mgrid((W + 1023) / 1024, (H + RUN_ROWS - 1) / RUN_ROWS, B);
     if (W % 4 == 0 && ((uintptr_t)labels & 15) == 0)
         PCSEG_LAUNCH(shape_moments_kernel<true>, mgrid, dim3(256), 0, s, labels, (const int *)w.nrows, H, W, cap, out, overflow);
     else
