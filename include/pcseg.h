@@ -181,7 +181,9 @@ int pcseg_dilate_ccl_runs_u8(const uint8_t *in, uint64_t value_bits, int radius,
 /* the same for n_masks (<= 4) masks of one class map at once -- get_cell_clusters_from_distances dilates and labels one
  * mask per cell type plus the union of all types (tiff_analysis.py:806-822): the map is read once, every pass behind the
  * bit planes is ONE launch over n_masks * B frames.  value_bits: HOST array [n_masks]; dilated_bits (n_masks, B,
- * ceil(H/32), W); run_parent (n_masks, B, H, W).  W % 4 == 0.  Workspace: pcseg_dilate_ccl_runs_workspace_bytes(B * n_masks, H, W). */
+ * ceil(H/32), W); run_parent (n_masks, B, H, W).  Any width and alignment (W % 4 == 0 with a 4-byte aligned map and a
+ * 16-byte aligned workspace takes the fast bit setter; pcseg_dilate_ccl_runs_u8 is this call with one mask).
+ * Workspace: pcseg_dilate_ccl_runs_workspace_bytes(B * n_masks, H, W). */
 int pcseg_dilate_ccl_runs_multi_u8(const uint8_t *in, const uint64_t *value_bits, int n_masks, int radius,
                                    uint32_t *dilated_bits, int32_t *run_parent, int B, int H, int W,
                                    void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
@@ -246,7 +248,12 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
  * group_of[b][k] = group id or 0 (centroid on a zero pixel -> dropped, :848).
  * region_list / group_of: int32 (B, list_cap); n_list / n_groups: int32[B].
  * keys_are_roots != 0: `dilated_labels` is the parent image of pcseg_dilate_ccl_roots_u8 (no numbering pass needed,
- * groups only need "same component"). */
+ * groups only need "same component").
+ * An entry outside [0, cap), a region of area 0 and a region whose centroid lies outside the frame get group 0 too;
+ * entries of group_of at or beyond n_list[b] are not written.
+ * Every grouping entry point below is ONE launch of the same kernel, one block per frame (and mask): they differ in
+ * where a key comes from (label image, parent image, run components) and in whether the member sums are wanted.
+ * The workspace is only touched by frames that list more than 4096 regions (shorter lists are grouped in LDS). */
 size_t pcseg_merge_groups_workspace_bytes(int B, int list_cap);
 int pcseg_merge_groups(const int32_t *dilated_labels, int keys_are_roots, const int64_t *stats,
                        const int32_t *region_list, const int32_t *n_list, int32_t *group_of, int32_t *n_groups,
@@ -263,7 +270,7 @@ int pcseg_merge_groups_runs(const uint32_t *dilated_bits, const int32_t *run_par
  * computes, with the list of type slot `slot` read in place from the (B, n_slots, cap) region lists and (B, n_slots)
  * list lengths pcseg_classify_regions writes (list capacity = cap).  group_of int32 (B, cap): every entry below the
  * list length is written; n_groups int32[B]; group_stats int64 (B, cap, 8): rows below n_groups[b] are written.
- * Workspace: pcseg_merge_groups_workspace_bytes(B, cap) (only touched by frames that list more than 4096 regions). */
+ * Workspace: pcseg_merge_groups_workspace_bytes(B, cap). */
 int pcseg_merge_groups_fused(const uint32_t *dilated_bits, const int32_t *run_parent, const int64_t *stats,
                              const int32_t *region_lists, const int32_t *n_lists, int slot, int n_slots,
                              int32_t *group_of, int32_t *n_groups, int64_t *group_stats, int B, int H, int W, int cap,
@@ -278,8 +285,9 @@ int pcseg_merge_groups_fused_multi(const uint32_t *dilated_bits, const int32_t *
                                    int n_slots, int32_t *group_of, int32_t *n_groups, int64_t *group_stats, int B, int H,
                                    int W, int cap, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
 
-/* member sums of the groups: group_stats int64 (B, list_cap, 8) = area, sum_row,
- * sum_col, min_row, min_col, max_row+1, max_col+1, members (tiff_analysis.py:855-872) */
+/* member sums of the groups of a caller's own group_of (what pcseg_merge_groups_fused adds up in its own launch):
+ * group_stats int64 (B, list_cap, 8) = area, sum_row, sum_col, min_row, min_col, max_row+1, max_col+1, members
+ * (tiff_analysis.py:855-872) */
 int pcseg_group_reduce(const int64_t *stats, const int32_t *region_list, const int32_t *n_list,
                        const int32_t *group_of, const int32_t *n_groups, int64_t *group_stats,
                        int B, int H, int W, int cap, int list_cap, pcseg_stream_t stream);

@@ -167,28 +167,6 @@ struct PredNotFlagged {  // root accepted unless flag[root] != 0 or its whole fr
     __device__ __forceinline__ bool operator()(int64_t gi) const { return flag[gi] == 0 && frame_on[gi / n] != 0; }
 };
 
-__device__ __forceinline__ int block_exclusive_scan(int v, int *total)
-{
-    // 256 threads = 4 waves; returns exclusive prefix of v, *total = block sum
-    __shared__ int wsum[4];
-    int lane = lane_id(), wid = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < 4; ++w) {
-        if (w < wid) base += wsum[w];
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 // Raster-order numbering = rank of the accepted roots.  Two pixel passes: (1) flatten, count the accepted roots of each
 // SCAN_PIX block and leave -(rank inside the block) at every accepted root; (2) after the block totals were scanned,
 // every pixel decodes its root's entry: negative = block offset - value, positive = a final label that the root's
@@ -198,6 +176,7 @@ __global__ void __launch_bounds__(256) ccl_flatten_count_kernel(int *__restrict_
                                                                  int *__restrict__ blockcount, Pred pred, int64_t n, int nblk,
                                                                  bool flatten, int *__restrict__ corrupt)
 {
+    __shared__ int wsum[4];
     const int b = blockIdx.y;
     int *par = parent + (int64_t)b * n;
     int cnt = 0;
@@ -229,7 +208,7 @@ __global__ void __launch_bounds__(256) ccl_flatten_count_kernel(int *__restrict_
         cnt += isroot[j];
     }
     int total;
-    int rank = block_exclusive_scan(cnt, &total);
+    int rank = block_exclusive_scan<256>(cnt, &total, wsum);
     for (int j = 0; j < 4; ++j)
         if (isroot[j]) labels[(int64_t)b * n + i0 + j] = -(++rank);
     if (threadIdx.x == 0) blockcount[b * nblk + blockIdx.x] = total;
@@ -239,13 +218,14 @@ __global__ void __launch_bounds__(256) ccl_flatten_count_kernel(int *__restrict_
 __global__ void __launch_bounds__(256) ccl_scan_blocks_kernel(int *__restrict__ blockcount, int *__restrict__ counts, int nblk,
                                                                const int *__restrict__ corrupt)
 {
+    __shared__ int wsum[4];
     int *bc = blockcount + (int64_t)blockIdx.x * nblk;
     int carry = 0;
     for (int base = 0; base < nblk; base += 256) {
         int i = base + threadIdx.x;
         int v = i < nblk ? bc[i] : 0;
         int total;
-        int ex = block_exclusive_scan(v, &total);
+        int ex = block_exclusive_scan<256>(v, &total, wsum);
         if (i < nblk) bc[i] = carry + ex;
         carry += total;
     }
@@ -629,80 +609,43 @@ __global__ void __launch_bounds__(256) roots_to_parent_kernel(const int *__restr
 }
 
 // ---- disk(r) dilation on the 1-bit image + components of the result, roots only (A6) -------------------------
-// set bits: 1 where ((value_bits >> in) & 1), rows beyond H are 0
-__global__ void __launch_bounds__(256) set_bits_kernel(const uint8_t *__restrict__ in, unsigned long long value_bits,
-                                                        unsigned *__restrict__ bits, int H, int W, int nch)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    const int ch = blockIdx.y, b = blockIdx.z;
-    if (c >= W) return;
-    const uint8_t *src = in + (int64_t)b * H * W;
-    unsigned word = 0;
-#pragma unroll 8
-    for (int j = 0; j < 32; ++j) {
-        int r = ch * 32 + j;
-        if (r < H) {
-            unsigned v = src[rowoff(r, W) + c];
-            if (v < 64 && ((value_bits >> v) & 1ull)) word |= 1u << j;
-        }
-    }
-    bits[((int64_t)b * nch + ch) * W + c] = word;
-}
-
-// the same for W % 4 == 0 and a 4-byte aligned input: a lane takes four adjacent columns (one 4-byte load per row)
-__global__ void __launch_bounds__(256) set_bits4_kernel(const uint8_t *__restrict__ in, unsigned long long value_bits,
-                                                         unsigned *__restrict__ bits, int H, int W, int nch)
-{
-    const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
-    const int ch = blockIdx.y, b = blockIdx.z;
-    if (c >= W) return;
-    const uint8_t *src = in + (int64_t)b * H * W + c;
-    unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-#pragma unroll 8
-    for (int j = 0; j < 32; ++j) {
-        const int r = ch * 32 + j;
-        if (r < H) {
-            const unsigned v = *reinterpret_cast<const unsigned *>(src + rowoff(r, W));
-            const unsigned a = v & 255u, bb = (v >> 8) & 255u, cc = (v >> 16) & 255u, d = v >> 24;
-            if (a < 64 && ((value_bits >> a) & 1ull)) w0 |= 1u << j;
-            if (bb < 64 && ((value_bits >> bb) & 1ull)) w1 |= 1u << j;
-            if (cc < 64 && ((value_bits >> cc) & 1ull)) w2 |= 1u << j;
-            if (d < 64 && ((value_bits >> d) & 1ull)) w3 |= 1u << j;
-        }
-    }
-    *reinterpret_cast<uint4 *>(bits + ((int64_t)b * nch + ch) * W + c) = make_uint4(w0, w1, w2, w3);
-}
-
-// several masks of one class map at once (the proximity merge wants one mask per cell type plus the union of all types):
-// the map is read ONCE, mask m goes to bits + m * (B * nch * W) -- behind it the dilation / run passes simply see
-// n_masks * B frames
+// set bits: 1 where ((mask >> in) & 1), rows beyond H are 0.  Several masks of one class map at once (the proximity merge
+// wants one mask per cell type plus the union of all types): the map is read ONCE, mask m goes to bits + m * (B * nch * W)
+// -- behind it the dilation / run passes simply see n_masks * B frames.
+// VEC (W % 4 == 0, a 4-byte aligned map, 16-byte aligned words): a lane takes four adjacent columns, one 4-byte load per
+// row and one 16-byte store per mask; otherwise one column per lane, any width and alignment.
 struct MaskSet {
     unsigned long long bits[4];
     int n;
 };
-__global__ void __launch_bounds__(256) set_bits4_multi_kernel(const uint8_t *__restrict__ in, MaskSet masks, unsigned *__restrict__ bits,
-                                                               int H, int W, int nch, int B)
+template <bool VEC>
+__global__ void __launch_bounds__(256) set_bits_kernel(const uint8_t *__restrict__ in, MaskSet masks, unsigned *__restrict__ bits,
+                                                        int H, int W, int nch, int B)
 {
-    const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+    constexpr int COLS = VEC ? 4 : 1;
+    const int c = (blockIdx.x * 256 + threadIdx.x) * COLS;
     const int ch = blockIdx.y, b = blockIdx.z;
     if (c >= W) return;
     const uint8_t *src = in + (int64_t)b * H * W + c;
-    unsigned w[4][4];
+    unsigned w[4][COLS];
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[m][j] = 0;
+        for (int j = 0; j < COLS; ++j) w[m][j] = 0;
     // eight rows' loads in flight at a time (a row test around each load made them 32 dependent round trips): rows past
     // the frame's end re-read its last row and are masked out of the words
 #pragma unroll 1
     for (int j0 = 0; j0 < 32; j0 += 8) {
         unsigned v8[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v8[j] = *reinterpret_cast<const unsigned *>(src + rowoff(min(ch * 32 + j0 + j, H - 1), W));
+        for (int j = 0; j < 8; ++j) {
+            const uint8_t *at = src + rowoff(min(ch * 32 + j0 + j, H - 1), W);
+            v8[j] = VEC ? *reinterpret_cast<const unsigned *>(at) : (unsigned)*at;
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
+            for (int q = 0; q < COLS; ++q) {
                 const unsigned a = (v8[j] >> (8 * q)) & 255u;
                 const unsigned long long sel = a < 64 ? (1ull << a) : 0ull;
 #pragma unroll
@@ -717,13 +660,16 @@ __global__ void __launch_bounds__(256) set_bits4_multi_kernel(const uint8_t *__r
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) w[m][q] &= valid;
+            for (int q = 0; q < COLS; ++q) w[m][q] &= valid;
     }
     const int64_t plane = (int64_t)B * nch * W;
 #pragma unroll
     for (int m = 0; m < 4; ++m)
-        if (m < masks.n)
-            *reinterpret_cast<uint4 *>(bits + m * plane + ((int64_t)b * nch + ch) * W + c) = make_uint4(w[m][0], w[m][1], w[m][2], w[m][3]);
+        if (m < masks.n) {
+            unsigned *out = bits + m * plane + ((int64_t)b * nch + ch) * W + c;
+            if constexpr (VEC) *reinterpret_cast<uint4 *>(out) = make_uint4(w[m][0], w[m][1], w[m][2], w[m][3]);
+            else *out = w[m][0];
+        }
 }
 
 // out = dilate(in, disk(radius)): for every row offset dy the columns within half(dy) = floor(sqrt(r^2 - dy^2)) are
@@ -1287,31 +1233,58 @@ size_t pcseg_dilate_ccl_workspace_bytes(int B, int H, int W)
     return cv.off;
 }
 
+// the dilated bit planes of masks.n masks of a class map: dil[m * B + b] = dilate(mask m of frame b, disk(radius));
+// `bits` is scratch of the same size.  Everything behind the bit setter sees masks.n * B independent frames.
+static int dilated_bit_planes(const uint8_t *in, const MaskSet &masks, int radius, unsigned *bits, unsigned *dil, int B, int H, int W,
+                              hipStream_t s)
+{
+    const int nch = (H + 31) / 32;
+    if ((W & 3) == 0 && ((uintptr_t)in & 3) == 0 && ((uintptr_t)bits & 15) == 0)
+        PCSEG_LAUNCH(set_bits_kernel<true>, dim3((W / 4 + 255) / 256, nch, B), dim3(256), 0, s, in, masks, bits, H, W, nch, B);
+    else
+        PCSEG_LAUNCH(set_bits_kernel<false>, dim3((W + 255) / 256, nch, B), dim3(256), 0, s, in, masks, bits, H, W, nch, B);
+    PCSEG_CHECK_LAUNCH();
+    const dim3 g((W + 255) / 256, nch, B * masks.n);
+    if (radius == 2) PCSEG_LAUNCH(dilate_bits_disk2_kernel, g, dim3(256), 0, s, (const unsigned *)bits, dil, H, W, nch);
+    else PCSEG_LAUNCH(dilate_bits_kernel, g, dim3(256), 0, s, (const unsigned *)bits, dil, radius, H, W, nch);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+// union-find over the vertical runs of B bit-plane frames: tile pass, then the links across tile edges
+static int bitrun_components(const unsigned *dil, int *run_parent, int B, int H, int W, hipStream_t s)
+{
+    const int nch = (H + 31) / 32;
+    PCSEG_LAUNCH(bitrun_tile_kernel, dim3((W + BR_TW - 1) / BR_TW, (nch + BR_CH - 1) / BR_CH, B), dim3(256), 0, s, dil, run_parent, H,
+                 W, nch);
+    PCSEG_CHECK_LAUNCH();
+    PCSEG_LAUNCH(bitrun_border_kernel, dim3((W + 255) / 256, nch, B), dim3(256), 0, s, dil, run_parent, H, W, nch);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+static MaskSet mask_set(const uint64_t *value_bits, int n_masks)
+{
+    MaskSet masks;
+    masks.n = n_masks;
+    for (int m = 0; m < 4; ++m) masks.bits[m] = m < n_masks ? (unsigned long long)value_bits[m] : 0ull;
+    return masks;
+}
+
 int pcseg_dilate_ccl_roots_u8(const uint8_t *in, uint64_t value_bits, int radius, int32_t *roots, int B, int H, int W,
                               void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
 {
     PCSEG_REQUIRE(in && roots && workspace && radius >= 0 && radius <= 15 && check_shape(B, H, W), "bad arguments (radius <= 15)");
     hipStream_t s = (hipStream_t)stream;
-    const int nch = (H + 31) / 32;
     Carver cv(workspace, workspace_bytes);
     const DilateCclWs ws = dilate_ccl_carve(cv, B, H, W);
-    unsigned *bits = ws.bits, *dil = ws.dil;
     if (!cv.ok()) {
         set_error("dilate_ccl_roots: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
-    dim3 g((W + 255) / 256, nch, B);
-    if ((W & 3) == 0 && ((uintptr_t)in & 3) == 0 && ((uintptr_t)bits & 15) == 0) {
-        PCSEG_LAUNCH(set_bits4_kernel, dim3((W / 4 + 255) / 256, g.y, g.z), dim3(256), 0, s, in, (unsigned long long)value_bits, bits, H,
-                     W, nch);
-    } else {
-        PCSEG_LAUNCH(set_bits_kernel, g, dim3(256), 0, s, in, (unsigned long long)value_bits, bits, H, W, nch);
-    }
-    PCSEG_CHECK_LAUNCH();
-    if (radius == 2) PCSEG_LAUNCH(dilate_bits_disk2_kernel, g, dim3(256), 0, s, (const unsigned *)bits, dil, H, W, nch);
-    else PCSEG_LAUNCH(dilate_bits_kernel, g, dim3(256), 0, s, (const unsigned *)bits, dil, radius, H, W, nch);
-    PCSEG_CHECK_LAUNCH();
-    return ccl_roots<KeyBits, true>(KeyBits{dil, W, nch}, roots, B, H, W, s);
+    const int rc = dilated_bit_planes(in, mask_set(&value_bits, 1), radius, ws.bits, ws.dil, B, H, W, s);
+    if (rc) return rc;
+    return ccl_roots<KeyBits, true>(KeyBits{ws.dil, W, (H + 31) / 32}, roots, B, H, W, s);
 }
 
 size_t pcseg_dilate_ccl_runs_workspace_bytes(int B, int H, int W)
@@ -1322,38 +1295,6 @@ size_t pcseg_dilate_ccl_runs_workspace_bytes(int B, int H, int W)
     return cv.off;
 }
 
-int pcseg_dilate_ccl_runs_u8(const uint8_t *in, uint64_t value_bits, int radius, uint32_t *dilated_bits, int32_t *run_parent,
-                             int B, int H, int W, void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
-{
-    PCSEG_REQUIRE(in && dilated_bits && run_parent && workspace && radius >= 0 && radius <= 15 && check_shape(B, H, W),
-                  "bad arguments (radius <= 15)");
-    hipStream_t s = (hipStream_t)stream;
-    const int nch = (H + 31) / 32;
-    Carver cv(workspace, workspace_bytes);
-    unsigned *bits = dilate_ccl_runs_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("dilate_ccl_runs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    dim3 g((W + 255) / 256, nch, B);
-    if ((W & 3) == 0 && ((uintptr_t)in & 3) == 0 && ((uintptr_t)bits & 15) == 0) {
-        PCSEG_LAUNCH(set_bits4_kernel, dim3((W / 4 + 255) / 256, g.y, g.z), dim3(256), 0, s, in, (unsigned long long)value_bits, bits, H,
-                     W, nch);
-    } else {
-        PCSEG_LAUNCH(set_bits_kernel, g, dim3(256), 0, s, in, (unsigned long long)value_bits, bits, H, W, nch);
-    }
-    PCSEG_CHECK_LAUNCH();
-    if (radius == 2) PCSEG_LAUNCH(dilate_bits_disk2_kernel, g, dim3(256), 0, s, (const unsigned *)bits, (unsigned *)dilated_bits, H, W, nch);
-    else PCSEG_LAUNCH(dilate_bits_kernel, g, dim3(256), 0, s, (const unsigned *)bits, (unsigned *)dilated_bits, radius, H, W, nch);
-    PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(bitrun_tile_kernel, dim3((W + BR_TW - 1) / BR_TW, (nch + BR_CH - 1) / BR_CH, B), dim3(256), 0, s,
-                 (const unsigned *)dilated_bits, (int *)run_parent, H, W, nch);
-    PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(bitrun_border_kernel, g, dim3(256), 0, s, (const unsigned *)dilated_bits, (int *)run_parent, H, W, nch);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
-}
-
 int pcseg_dilate_ccl_runs_multi_u8(const uint8_t *in, const uint64_t *value_bits, int n_masks, int radius, uint32_t *dilated_bits,
                                    int32_t *run_parent, int B, int H, int W, void *workspace, size_t workspace_bytes,
                                    pcseg_stream_t stream)
@@ -1361,32 +1302,24 @@ int pcseg_dilate_ccl_runs_multi_u8(const uint8_t *in, const uint64_t *value_bits
     PCSEG_REQUIRE(in && value_bits && dilated_bits && run_parent && workspace && n_masks >= 1 && n_masks <= 4 && radius >= 0 &&
                       radius <= 15 && check_shape(B, H, W) && check_shape(B * n_masks, H, W),
                   "bad arguments (1..4 masks, radius <= 15)");
-    PCSEG_REQUIRE((W & 3) == 0 && ((uintptr_t)in & 3) == 0, "W must be a multiple of 4 (use pcseg_dilate_ccl_runs_u8 per mask otherwise)");
     hipStream_t s = (hipStream_t)stream;
-    const int nch = (H + 31) / 32;
     const int BM = B * n_masks;
     Carver cv(workspace, workspace_bytes);
     unsigned *bits = dilate_ccl_runs_carve(cv, BM, H, W);
-    if (!cv.ok() || ((uintptr_t)bits & 15)) {
-        set_error("dilate_ccl_runs_multi: workspace too small or misaligned (%zu < %zu)", workspace_bytes, cv.off);
+    if (!cv.ok()) {
+        set_error("dilate_ccl_runs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
-    MaskSet masks;
-    masks.n = n_masks;
-    for (int m = 0; m < 4; ++m) masks.bits[m] = m < n_masks ? (unsigned long long)value_bits[m] : 0ull;
-    PCSEG_LAUNCH(set_bits4_multi_kernel, dim3((W / 4 + 255) / 256, nch, B), dim3(256), 0, s, in, masks, bits, H, W, nch, B);
-    PCSEG_CHECK_LAUNCH();
-    // everything behind the bit planes sees n_masks * B independent frames
-    dim3 g((W + 255) / 256, nch, BM);
-    if (radius == 2) PCSEG_LAUNCH(dilate_bits_disk2_kernel, g, dim3(256), 0, s, (const unsigned *)bits, (unsigned *)dilated_bits, H, W, nch);
-    else PCSEG_LAUNCH(dilate_bits_kernel, g, dim3(256), 0, s, (const unsigned *)bits, (unsigned *)dilated_bits, radius, H, W, nch);
-    PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(bitrun_tile_kernel, dim3((W + BR_TW - 1) / BR_TW, (nch + BR_CH - 1) / BR_CH, BM), dim3(256), 0, s,
-                 (const unsigned *)dilated_bits, (int *)run_parent, H, W, nch);
-    PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(bitrun_border_kernel, g, dim3(256), 0, s, (const unsigned *)dilated_bits, (int *)run_parent, H, W, nch);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    const int rc = dilated_bit_planes(in, mask_set(value_bits, n_masks), radius, bits, (unsigned *)dilated_bits, B, H, W, s);
+    if (rc) return rc;
+    return bitrun_components((const unsigned *)dilated_bits, (int *)run_parent, BM, H, W, s);
+}
+
+int pcseg_dilate_ccl_runs_u8(const uint8_t *in, uint64_t value_bits, int radius, uint32_t *dilated_bits, int32_t *run_parent,
+                             int B, int H, int W, void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
+{
+    return pcseg_dilate_ccl_runs_multi_u8(in, &value_bits, 1, radius, dilated_bits, run_parent, B, H, W, workspace, workspace_bytes,
+                                          stream);
 }
 
 int pcseg_compact_labels(const int32_t *roots, int32_t *labels, int32_t *counts, int B, int H, int W, void *workspace,

@@ -116,6 +116,39 @@ __device__ __forceinline__ int wave_prefix_max(int x) { return wave_prefix_extre
 __device__ __forceinline__ int wave_prefix_min(int x) { return wave_prefix_extreme<false>(x); }
 __device__ __forceinline__ int wave_last_lane(int x) { return __builtin_amdgcn_readlane(x, WAVE - 1); }
 
+// ---- prefix sums (the only copies: every count -> offset step of the library goes through these two)
+// inclusive prefix sum over the 64 lanes of a wave
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_sum(T v)
+{
+    const int lane = lane_id();
+    for (int off = 1; off < WAVE; off <<= 1) {
+        const T t = __shfl_up(v, off);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+
+// exclusive prefix of v over the THREADS threads of a block, *total = the block's sum.  wsum: THREADS / 64 values of LDS,
+// free for the next scan when the call returns (two barriers: every thread of the block must call)
+template <int THREADS, typename T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T *total, T *wsum)
+{
+    static_assert(THREADS % WAVE == 0, "whole waves");
+    const int wid = threadIdx.x / WAVE;
+    const T inc = wave_inclusive_sum(v);
+    if (lane_id() == WAVE - 1) wsum[wid] = inc;
+    __syncthreads();
+    T base = 0, tot = 0;
+    for (int w = 0; w < THREADS / WAVE; ++w) {
+        if (w < wid) base += wsum[w];
+        tot += wsum[w];
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
+
 // XCD-aware tile order for kernels whose blocks read a halo of their neighbours' pixels.  Workgroups are dealt
 // round-robin over the 8 XCDs (blocks b and b + 8 share one; MI355X_MICROARCH.md, "Workgroup dispatch"), each XCD with
 // an L2 of its own: with the plain blockIdx -> tile map the left / right neighbour of a tile runs on ANOTHER XCD, so

@@ -112,21 +112,13 @@ __global__ void __launch_bounds__(256) nb_items_scan_kernel(const int32_t *__res
     const int per = (B + 255) / 256, lo = min(B, (int)threadIdx.x * per), hi = min(B, lo + per);
     int v = 0;
     for (int b = lo; b < hi; ++b) v += items[b];
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int acc = inc - v;
-    for (int w = 0; w < wid; ++w) acc += wsum[w];
+    int total;
+    int acc = block_exclusive_scan<256>(v, &total, wsum);
     for (int b = lo; b < hi; ++b) {
         prefix[b] = acc;
         acc += items[b];
     }
-    if (threadIdx.x == 255) prefix[B] = acc;
+    if (threadIdx.x == 0) prefix[B] = total;
 }
 
 struct NbArgs {

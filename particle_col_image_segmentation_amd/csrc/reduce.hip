@@ -647,98 +647,99 @@ __global__ void __launch_bounds__(256) region_class_kernel(const long long *__re
     cls_out[(int64_t)b * cap + l] = (first >= 0 && first < n) ? cls[(int64_t)b * n + first] : 0;
 }
 
-// ---- A6 tail: grouping by dilated label at the truncated centroid ------------
-__device__ __forceinline__ int block_exclusive_scan256(int v, int *total, int *wsum)
+// ---- A6 tail (tiff_analysis.py:843-878): centroid keys, grouping in order of the first member and, if wanted, the member
+// sums of every group, in ONE launch per merge.  One 1024-thread block per frame and mask: a frame lists a few hundred
+// regions, so every entry has a thread of its own and the union-find chain walks of the key look-ups (pure latency) all
+// run at once; the hash table of the grouping lives in LDS (in global memory every probe of a block's dependent chain
+// was a memory round trip: 117 us per launch against a handful).  Lists longer than MG_LDS entries fall back to the
+// caller's global scratch, same code.
+constexpr int MG_THREADS = 1024, MG_LDS = 4096;
+
+// Where the key of a pixel comes from: key(fb, y, x) of pixel (y, x) of frame fb (masks * frames for the batched form);
+// 0 = clear pixel, equal positive keys = same dilated component.
+struct LabelKeys {  // a label image
+    const int *lab;
+    __device__ __forceinline__ int key(int fb, long long y, long long x, int H, int W) const
+    {
+        return lab[(int64_t)fb * H * W + y * W + x];
+    }
+};
+struct RootKeys {  // the parent image of a union-find (-1 = background): walk to the root
+    const int *parent;
+    __device__ __forceinline__ int key(int fb, long long y, long long x, int H, int W) const
+    {
+        const int *par = parent + (int64_t)fb * H * W;
+        int k = par[y * W + x];
+        if (k >= 0) k = (unsigned)k < (unsigned)(H * W) ? walk_root(par, k) : -1;  // fenced (common.h, walk_ok)
+        return k + 1;
+    }
+};
+struct RunRoots {  // components by vertical runs (pcseg_dilate_ccl_runs_u8): the node of a set pixel is the top pixel of its
+                   // run inside the 32-row word; only those entries of the parent array exist
+    const unsigned *bits;
+    const int *parent;
+    __device__ __forceinline__ int key(int fb, long long y, long long x, int H, int W) const
+    {
+        const int nch = (H + 31) / 32;
+        const unsigned word = bits[((int64_t)fb * nch + (int)(y >> 5)) * W + x];
+        const int j = (int)(y & 31);
+        if (!((word >> j) & 1u)) return 0;
+        const unsigned below = ~word & ((1u << j) - 1u);
+        const int start = below ? 32 - __clz(below) : 0;
+        return walk_root(parent + (int64_t)fb * H * W, (int)((y - j + start) * W + x)) + 1;  // fenced (common.h, walk_ok)
+    }
+};
+
+// key of list entry r (tiff_analysis.py:844-848): the dilated component at (int(cy), int(cx)) of region r of the frame's
+// table `st`; exact with integer floor division.  0: not a region, an empty one, or its centroid on a clear pixel -> dropped
+template <typename Source>
+__device__ __forceinline__ int centroid_key(const Source &src, const long long *st, int r, int fb, int H, int W, int cap)
 {
-    int lane = lane_id(), wid = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < 4; ++w) {
-        if (w < wid) base += wsum[w];
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
+    if (r < 0 || r >= cap) return 0;
+    const long long a = st[(int64_t)r * 8 + 0];
+    if (a <= 0) return 0;
+    const long long y = st[(int64_t)r * 8 + 1] / a, x = st[(int64_t)r * 8 + 2] / a;
+    if (y < 0 || y >= H || x < 0 || x >= W) return 0;
+    return src.key(fb, y, x, H, W);
 }
 
-// keys (tiff_analysis.py:844-848): dilated label at (int(cy), int(cx)); exact with integer floor division.  One thread
-// per list entry over the whole batch: the look-up walks a union-find chain in global memory, which is pure latency --
-// it wants many blocks in flight, not the one block per frame of the grouping kernel below.
-__global__ void __launch_bounds__(256) merge_keys_kernel(const int *__restrict__ dl, const long long *__restrict__ stats,
-                                                          const int *__restrict__ region_list, const int *__restrict__ n_list,
-                                                          int *__restrict__ key_ws, int H, int W, int cap, int list_cap,
-                                                          int keys_are_roots, const unsigned *__restrict__ run_bits)
+// a group's row: (area, sum_row, sum_col, bbox(4), members)
+__device__ __forceinline__ void group_row_clear(long long *t, int H, int W)
 {
-    const int b = blockIdx.y;
-    const int R = min(n_list[b], list_cap);
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= R) return;
-    const int64_t n = (int64_t)H * W;
-    const int *dlab = dl + (int64_t)b * n;
-    const long long *st = stats + (int64_t)b * cap * 8;
-    int key_k = 0;
-    const int r = region_list[(int64_t)b * list_cap + k];
-    if (r >= 0 && r < cap) {
-        const long long a = st[(int64_t)r * 8 + 0];
-        if (a > 0) {
-            const long long y = st[(int64_t)r * 8 + 1] / a, x = st[(int64_t)r * 8 + 2] / a;
-            if (y >= 0 && y < H && x >= 0 && x < W) {
-                if (run_bits) {
-                    // components by vertical runs (pcseg_dilate_ccl_runs_u8): the node of a set pixel is the top
-                    // pixel of its run inside the 32-row word; only those entries of the parent array exist
-                    const int nch = (H + 31) / 32;
-                    const unsigned word = run_bits[((int64_t)b * nch + (int)(y >> 5)) * W + x];
-                    const int j = (int)(y & 31);
-                    if ((word >> j) & 1u) {
-                        const unsigned below = ~word & ((1u << j) - 1u);
-                        const int start = below ? 32 - __clz(below) : 0;
-                        key_k = walk_root(dlab, (int)((y - j + start) * W + x)) + 1;  // fenced (common.h, walk_ok)
-                    }
-                } else {
-                    key_k = dlab[y * W + x];
-                    if (keys_are_roots) {  // parent image of a union-find (-1 = background): walk to the root
-                        if (key_k >= 0) key_k = (unsigned)key_k < (unsigned)(H * W) ? walk_root(dlab, key_k) : -1;  // fenced
-                        key_k += 1;
-                    }
-                }
-            }
-        }
-    }
-    key_ws[(int64_t)b * list_cap + k] = key_k;
+    t[0] = 0; t[1] = 0; t[2] = 0; t[3] = H; t[4] = W; t[5] = 0; t[6] = 0; t[7] = 0;
+}
+// column f of a member's row s into its group's row t: columns 0-2 add, 3-4 min, 5-6 max, 7 counts members
+__device__ __forceinline__ void group_row_add(long long *t, const long long *s, int f)
+{
+    if (f < 3) atomicAdd((unsigned long long *)&t[f], (unsigned long long)s[f]);
+    else if (f < 5) atomicMin(&t[f], s[f]);
+    else if (f < 7) atomicMax(&t[f], s[f]);
+    else atomicAdd((unsigned long long *)&t[f], 1ull);
 }
 
-// grouping of one frame's list by key (one block per frame; keys from merge_keys_kernel)
-__global__ void __launch_bounds__(256) merge_groups_kernel(const int *__restrict__ n_list, int *__restrict__ group_of,
-                                                            int *__restrict__ n_groups, int *__restrict__ key_ws,
-                                                            int *__restrict__ first_ws, int *__restrict__ gid_ws, int list_cap)
+// scratch of the grouping (in LDS or in the caller's workspace): key[R], gid[R], first[R + 1]
+struct GroupTables {
+    int *key, *gid, *first;
+};
+
+// Groups the R entries of a list by key[] (<= 0: dropped), block-wide with THREADS threads: gof[k] = group id of entry k
+// (0 = dropped), ids in order of the first member; returns the number of groups.  Keys are arbitrary positive numbers:
+// they are remapped through the list itself -- a slot table (open addressing over R slots) whose first[] holds the LIST
+// POSITION of the first entry seen with the slot's key.  SUMS: every member also adds its row of `st` to its group's row
+// of `gs` (tiff_analysis.py:855-872).  The caller has filled key[], zeroed gid[0..R), set first[0..R] to INT_MAX and
+// passed a barrier.
+template <int THREADS, bool SUMS>
+__device__ __forceinline__ int group_by_key(const GroupTables &t, int R, int *gof, int *wsum, const int *lst, const long long *st,
+                                            long long *gs, int H, int W)
 {
-    __shared__ int wsum[4];
-    const int b = blockIdx.x;
-    const int R = min(n_list[b], list_cap);
-    int *key = key_ws + (int64_t)b * list_cap;
-    int *first = first_ws + (int64_t)b * (list_cap + 1);
-    int *gid = gid_ws + (int64_t)b * list_cap;
-    int *gof = group_of + (int64_t)b * list_cap;
-    // dilated labels are arbitrary in 1..K (K may exceed the list length): remap through the list itself --
-    // first[] is indexed by the LIST POSITION of the first entry seen with that key, found by a tiny hash on key
-    // (open addressing over list_cap + 1 slots, keys stored in gid as scratch)
-    for (int k = threadIdx.x; k <= R; k += 256) first[k] = 0x7FFFFFFF;
-    for (int k = threadIdx.x; k < R; k += 256) gid[k] = 0;
-    __syncthreads();
-    // slot table: gid[slot] holds the key owning the slot (0 = free), first[slot] the smallest list position
-    for (int k = threadIdx.x; k < R; k += 256) {
-        int kk = key[k];
+    int *key = t.key, *gid = t.gid, *first = t.first;
+    // slot table: gid[slot] = key owning the slot (0 = free), first[slot] = smallest list position
+    for (int k = threadIdx.x; k < R; k += THREADS) {
+        const int kk = key[k];
         if (kk <= 0) continue;
         unsigned slot = ((unsigned)kk * 2654435761u) % (unsigned)R;
         for (;;) {
-            int owner = atomicCAS(&gid[slot], 0, kk);
+            const int owner = atomicCAS(&gid[slot], 0, kk);
             if (owner == 0 || owner == kk) break;
             slot = slot + 1 == (unsigned)R ? 0 : slot + 1;
         }
@@ -746,164 +747,70 @@ __global__ void __launch_bounds__(256) merge_groups_kernel(const int *__restrict
         key[k] = -(int)slot - 1;  // remember the slot (negative marks "resolved")
     }
     __syncthreads();
+    // group ids in order of the first member: leaders are the list positions k with first[slot(k)] == k
     int carry = 0;
-    // group ids in order of the first member: leaders are list positions k with first[slot(k)] == k
-    for (int base = 0; base < R; base += 256) {
-        int k = base + threadIdx.x;
-        int leader = 0;
-        if (k < R && key[k] < 0) leader = first[-key[k] - 1] == k;
-        int total;
-        int ex = block_exclusive_scan256(leader, &total, wsum);
-        if (leader) gof[k] = carry + ex + 1;
-        carry += total;
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < R; k += 256) {
-        if (key[k] >= 0) gof[k] = 0;
-        else {
-            int f = first[-key[k] - 1];
-            if (f != k) gof[k] = gof[f];  // leaders were written before the barrier; members only read leaders
-        }
-    }
-    if (threadIdx.x == 0) n_groups[b] = carry;
-}
-
-// ---- A6 tail in ONE launch per merge (tiff_analysis.py:843-878): centroid keys, grouping in order of the first member
-// and the member sums of every group.  One 1024-thread block per frame: a frame lists a few hundred regions, so every
-// entry has a thread of its own and the union-find chain walks of the key look-ups (pure latency) all run at once; the
-// hash table of the grouping lives in LDS (the three separate kernels kept it in global memory, where every probe of
-// a block's dependent chain was a memory round trip: 117 us per launch against a handful).  Lists longer than MG_LDS
-// entries fall back to the caller's global scratch, same code.  region_list / n_list are addressed in place inside the
-// (B, n_slots, cap) / (B, n_slots) arrays of pcseg_classify_regions (no per-slot copies).
-constexpr int MG_THREADS = 1024, MG_LDS = 4096;
-
-__device__ __forceinline__ int block_exclusive_scan1024(int v, int *total, int *wsum)
-{
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < MG_THREADS / 64; ++w) {
-        if (w < wid) base += wsum[w];
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
-// (blockIdx.y = mask: the bit planes / run parents / outputs of mask m sit m * B frames further, its list is slot_of_mask[m])
-struct MergeSlots {
-    int slot[4];
-};
-__global__ void __launch_bounds__(MG_THREADS) merge_fused_kernel(const unsigned *__restrict__ run_bits_all, const int *__restrict__ run_parent_all,
-                                                                 const long long *__restrict__ stats, const int *__restrict__ region_list,
-                                                                 const int *__restrict__ n_list, MergeSlots slot_of_mask, int n_slots,
-                                                                 int *__restrict__ group_of_all, int *__restrict__ n_groups_all,
-                                                                 long long *__restrict__ gstats_all, int *__restrict__ key_ws_all,
-                                                                 int *__restrict__ first_ws_all, int *__restrict__ gid_ws_all, int H, int W, int cap,
-                                                                 int list_cap)
-{
-    __shared__ int s_key[MG_LDS], s_first[MG_LDS + 1], s_gid[MG_LDS];
-    __shared__ int wsum[MG_THREADS / 64];
-    const int b = blockIdx.x;
-    const int mask = blockIdx.y, B = gridDim.x, slot = slot_of_mask.slot[mask];
-    const int64_t mf = (int64_t)mask * B;  // frames in front of this mask's arrays
-    const unsigned *run_bits = run_bits_all + mf * ((H + 31) / 32) * W;
-    const int *run_parent = run_parent_all + mf * H * W;
-    int *group_of = group_of_all + mf * list_cap, *n_groups = n_groups_all + mf;
-    long long *gstats = gstats_all + mf * list_cap * 8;
-    int *key_ws = key_ws_all + mf * list_cap, *first_ws = first_ws_all + mf * (list_cap + 1), *gid_ws = gid_ws_all + mf * list_cap;
-    const int R = min(n_list[b * n_slots + slot], list_cap);
-    const int *lst = region_list + ((int64_t)b * n_slots + slot) * cap;
-    const bool in_lds = R <= MG_LDS;  // block-uniform
-    int *key = in_lds ? s_key : key_ws + (int64_t)b * list_cap;
-    int *first = in_lds ? s_first : first_ws + (int64_t)b * (list_cap + 1);
-    int *gid = in_lds ? s_gid : gid_ws + (int64_t)b * list_cap;
-    int *gof = group_of + (int64_t)b * list_cap;
-    long long *gs = gstats + (int64_t)b * list_cap * 8;
-    const int64_t n = (int64_t)H * W;
-    const int *par = run_parent + (int64_t)b * n;
-    const long long *st = stats + (int64_t)b * cap * 8;
-    const int nch = (H + 31) / 32;
-    // (1) keys: the run component under the truncated centroid (0: centroid on a clear pixel -> dropped, :848)
-    for (int k = threadIdx.x; k < R; k += MG_THREADS) {
-        int key_k = 0;
-        const int r = lst[k];
-        if (r >= 0 && r < cap) {
-            const long long a = st[(int64_t)r * 8 + 0];
-            if (a > 0) {
-                const long long y = st[(int64_t)r * 8 + 1] / a, x = st[(int64_t)r * 8 + 2] / a;
-                if (y >= 0 && y < H && x >= 0 && x < W) {
-                    const unsigned word = run_bits[((int64_t)b * nch + (int)(y >> 5)) * W + x];
-                    const int j = (int)(y & 31);
-                    if ((word >> j) & 1u) {
-                        const unsigned below = ~word & ((1u << j) - 1u);
-                        const int start = below ? 32 - __clz(below) : 0;
-                        key_k = walk_root(par, (int)((y - j + start) * W + x)) + 1;  // fenced (common.h, walk_ok)
-                    }
-                }
-            }
-        }
-        key[k] = key_k;
-        gid[k] = 0;
-    }
-    for (int k = threadIdx.x; k <= R; k += MG_THREADS) first[k] = 0x7FFFFFFF;
-    __syncthreads();
-    // (2) slot table (open addressing over R slots): gid[slot] = key owning the slot, first[slot] = smallest list position
-    for (int k = threadIdx.x; k < R; k += MG_THREADS) {
-        const int kk = key[k];
-        if (kk <= 0) continue;
-        unsigned slot_i = ((unsigned)kk * 2654435761u) % (unsigned)R;
-        for (;;) {
-            const int owner = atomicCAS(&gid[slot_i], 0, kk);
-            if (owner == 0 || owner == kk) break;
-            slot_i = slot_i + 1 == (unsigned)R ? 0 : slot_i + 1;
-        }
-        atomicMin(&first[slot_i], k);
-        key[k] = -(int)slot_i - 1;  // remember the slot (negative marks "resolved")
-    }
-    __syncthreads();
-    // (3) group ids in order of the first member: leaders are the list positions k with first[slot(k)] == k
-    int carry = 0;
-    for (int base = 0; base < R; base += MG_THREADS) {
+    for (int base = 0; base < R; base += THREADS) {
         const int k = base + threadIdx.x;
         int leader = 0;
         if (k < R && key[k] < 0) leader = first[-key[k] - 1] == k;
         int total;
-        const int ex = block_exclusive_scan1024(leader, &total, wsum);
+        const int ex = block_exclusive_scan<THREADS>(leader, &total, wsum);
         if (leader) {
             const int g = carry + ex + 1;
             gof[k] = g;
             gid[-key[k] - 1] = g;  // the slot's key is not needed any more: it now holds the group id for the members
-            long long *t = gs + (int64_t)(g - 1) * 8;
-            t[0] = 0; t[1] = 0; t[2] = 0; t[3] = H; t[4] = W; t[5] = 0; t[6] = 0; t[7] = 0;
+            if (SUMS) group_row_clear(gs + (int64_t)(g - 1) * 8, H, W);
         }
         carry += total;
     }
     __syncthreads();  // (group ids and the zeroed rows of this block's groups: written above, used below by the same block)
-    // (4) members take their leader's id; every listed region adds itself to its group's row (tiff_analysis.py:855-872)
+    // members take their leader's id; with SUMS every listed region adds itself to its group's row
     // (eight lanes per member, one per column of the row: the reads are one 64-byte line per member and the atomics of an
     // instruction that fall into one line travel together -- see slots_flush8, label_reduce.h)
-    for (int idx = threadIdx.x; idx < R * 8; idx += MG_THREADS) {
-        const int k = idx >> 3, f = idx & 7;
+    constexpr int LANES = SUMS ? 8 : 1;
+    for (int idx = threadIdx.x; idx < R * LANES; idx += THREADS) {
+        const int k = idx / LANES, f = idx % LANES;
         int g = 0;
         if (key[k] < 0) g = gid[-key[k] - 1];
         if (f == 0) gof[k] = g;
-        if (g <= 0) continue;
-        const long long v = st[(int64_t)lst[k] * 8 + f];
-        long long *t = gs + (int64_t)(g - 1) * 8 + f;
-        if (f < 3) atomicAdd((unsigned long long *)t, (unsigned long long)v);
-        else if (f < 5) atomicMin(t, v);
-        else if (f < 7) atomicMax(t, v);
-        else atomicAdd((unsigned long long *)t, 1ull);
+        if (SUMS && g > 0) group_row_add(gs + (int64_t)(g - 1) * 8, st + (int64_t)lst[k] * 8, f);
     }
-    if (threadIdx.x == 0) n_groups[b] = carry;
+    return carry;
+}
+
+// (blockIdx.y = mask: the key source / outputs / scratch of mask m sit m * B frames further, its list is slot_of_mask[m].
+// The list of frame b is addressed in place inside (B, n_slots, list_cap) / (B, n_slots) arrays -- those of
+// pcseg_classify_regions, no per-slot copies; a plain (B, list_cap) list is n_slots = 1, slot 0)
+struct MergeSlots {
+    int slot[4];
+};
+template <typename Source, bool SUMS>
+__global__ void __launch_bounds__(MG_THREADS) merge_groups_kernel(Source src, const long long *__restrict__ stats,
+                                                                  const int *__restrict__ region_list, const int *__restrict__ n_list,
+                                                                  MergeSlots slot_of_mask, int n_slots, int *__restrict__ group_of,
+                                                                  int *__restrict__ n_groups, long long *__restrict__ gstats,
+                                                                  GroupTables ws, int H, int W, int cap, int list_cap)
+{
+    __shared__ int s_key[MG_LDS], s_first[MG_LDS + 1], s_gid[MG_LDS];
+    __shared__ int wsum[MG_THREADS / 64];
+    const int b = blockIdx.x;
+    const int slot = slot_of_mask.slot[blockIdx.y];
+    const int fb = blockIdx.y * gridDim.x + b;  // this mask's frame b among masks * frames
+    const int R = min(n_list[b * n_slots + slot], list_cap);
+    const int *lst = region_list + ((int64_t)b * n_slots + slot) * list_cap;
+    const bool in_lds = R <= MG_LDS;  // block-uniform
+    const GroupTables t{in_lds ? s_key : ws.key + (int64_t)fb * list_cap, in_lds ? s_gid : ws.gid + (int64_t)fb * list_cap,
+                        in_lds ? s_first : ws.first + (int64_t)fb * (list_cap + 1)};
+    const long long *st = stats + (int64_t)b * cap * 8;
+    for (int k = threadIdx.x; k < R; k += MG_THREADS) {
+        t.key[k] = centroid_key(src, st, lst[k], fb, H, W, cap);
+        t.gid[k] = 0;
+    }
+    for (int k = threadIdx.x; k <= R; k += MG_THREADS) t.first[k] = 0x7FFFFFFF;
+    __syncthreads();
+    const int G = group_by_key<MG_THREADS, SUMS>(t, R, group_of + (int64_t)fb * list_cap, wsum, lst, st,
+                                                 SUMS ? gstats + (int64_t)fb * list_cap * 8 : nullptr, H, W);
+    if (threadIdx.x == 0) n_groups[fb] = G;
 }
 
 // ---- A3 tail + A4: the reference's per-region loop (tiff_analysis.py:754-781) and the region lists that
@@ -1048,7 +955,8 @@ __global__ void __launch_bounds__(CLS_THREADS) classify_regions_kernel(const lon
     }
 }
 
-// group table of pcseg_merge_groups: (B, list_cap, 8) = area, sum_row, sum_col, bbox(4), members
+// group table of pcseg_merge_groups: (B, list_cap, 8) = area, sum_row, sum_col, bbox(4), members -- the member sums of
+// merge_groups_kernel for a caller's own group_of (eight lanes per member, as there)
 __global__ void __launch_bounds__(256) group_reduce_kernel(const long long *__restrict__ stats, const int *__restrict__ region_list,
                                                             const int *__restrict__ n_list, const int *__restrict__ group_of,
                                                             const int *__restrict__ n_groups, long long *__restrict__ gstats,
@@ -1057,24 +965,13 @@ __global__ void __launch_bounds__(256) group_reduce_kernel(const long long *__re
     const int b = blockIdx.x;
     const int R = min(n_list[b], list_cap), G = n_groups[b];
     long long *gs = gstats + (int64_t)b * list_cap * 8;
-    for (int g = threadIdx.x; g < G; g += 256) {
-        long long *t = gs + (int64_t)g * 8;
-        t[0] = 0; t[1] = 0; t[2] = 0; t[3] = H; t[4] = W; t[5] = 0; t[6] = 0; t[7] = 0;
-    }
+    for (int g = threadIdx.x; g < G; g += 256) group_row_clear(gs + (int64_t)g * 8, H, W);
     __syncthreads();
-    for (int k = threadIdx.x; k < R; k += 256) {
-        int g = group_of[(int64_t)b * list_cap + k];
+    for (int idx = threadIdx.x; idx < R * 8; idx += 256) {
+        const int k = idx >> 3;
+        const int g = group_of[(int64_t)b * list_cap + k];
         if (g <= 0) continue;
-        const long long *s = stats + ((int64_t)b * cap + region_list[(int64_t)b * list_cap + k]) * 8;
-        long long *t = gs + (int64_t)(g - 1) * 8;
-        atomicAdd((unsigned long long *)&t[0], (unsigned long long)s[0]);
-        atomicAdd((unsigned long long *)&t[1], (unsigned long long)s[1]);
-        atomicAdd((unsigned long long *)&t[2], (unsigned long long)s[2]);
-        atomicMin(&t[3], s[3]);
-        atomicMin(&t[4], s[4]);
-        atomicMax(&t[5], s[5]);
-        atomicMax(&t[6], s[6]);
-        atomicAdd((unsigned long long *)&t[7], 1ull);
+        group_row_add(gs + (int64_t)(g - 1) * 8, stats + ((int64_t)b * cap + region_list[(int64_t)b * list_cap + k]) * 8, idx & 7);
     }
 }
 
@@ -1092,6 +989,36 @@ __global__ void __launch_bounds__(256) nearest_kernel(const double *__restrict__
         best = d2 < best ? d2 : best;
     }
     out[i] = sqrt(best);
+}
+
+// scratch of the grouping kernel (B counts masks * frames for the batched form)
+static GroupTables merge_groups_carve(Carver &cv, size_t B, int list_cap)
+{
+    GroupTables ws;
+    ws.key = cv.take<int>(B * list_cap);
+    ws.gid = cv.take<int>(B * list_cap);
+    ws.first = cv.take<int>(B * (list_cap + 1));
+    return ws;
+}
+
+// carve + launch of one grouping: n_masks masks (their lists: `slots`) of B frames each
+template <typename Source, bool SUMS>
+static int merge_groups_launch(const char *who, Source src, const int64_t *stats, const int32_t *region_list, const int32_t *n_list,
+                               const MergeSlots &slots, int n_masks, int n_slots, int32_t *group_of, int32_t *n_groups,
+                               int64_t *group_stats, int B, int H, int W, int cap, int list_cap, void *workspace,
+                               size_t workspace_bytes, pcseg_stream_t stream)
+{
+    Carver cv(workspace, workspace_bytes);
+    const GroupTables ws = merge_groups_carve(cv, (size_t)B * n_masks, list_cap);
+    if (!cv.ok()) {
+        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
+        return PCSEG_ERR_WORKSPACE;
+    }
+    PCSEG_LAUNCH((merge_groups_kernel<Source, SUMS>), dim3(B, n_masks), dim3(MG_THREADS), 0, (hipStream_t)stream, src,
+                 (const long long *)stats, (const int *)region_list, (const int *)n_list, slots, n_slots, (int *)group_of,
+                 (int *)n_groups, (long long *)group_stats, ws, H, W, cap, list_cap);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
 }
 
 }  // namespace pcseg
@@ -1200,19 +1127,6 @@ int pcseg_region_sums2(const int32_t *labels_a, const uint8_t *cls, uint64_t sum
     return PCSEG_OK;
 }
 
-// scratch of the grouping kernels (B counts masks * frames for the fused form)
-struct MergeGroupsWs {
-    int *key, *gid, *first;
-};
-static MergeGroupsWs merge_groups_carve(Carver &cv, size_t B, int list_cap)
-{
-    MergeGroupsWs ws;
-    ws.key = cv.take<int>(B * list_cap);
-    ws.gid = cv.take<int>(B * list_cap);
-    ws.first = cv.take<int>(B * (list_cap + 1));
-    return ws;
-}
-
 size_t pcseg_merge_groups_workspace_bytes(int B, int list_cap)
 {
     if (B < 1 || list_cap < 1) return 0;
@@ -1228,19 +1142,11 @@ int pcseg_merge_groups(const int32_t *dilated_labels, int keys_are_roots, const 
     PCSEG_REQUIRE(dilated_labels && stats && region_list && n_list && group_of && n_groups && workspace && cap >= 1 &&
                       list_cap >= 1 && check_shape(B, H, W),
                   "bad arguments");
-    Carver cv(workspace, workspace_bytes);
-    const MergeGroupsWs ws = merge_groups_carve(cv, (size_t)B, list_cap);
-    int *key = ws.key, *gid = ws.gid, *first = ws.first;
-    if (!cv.ok()) {
-        set_error("merge_groups: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    PCSEG_LAUNCH(merge_keys_kernel, dim3((list_cap + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, dilated_labels,
-                 (const long long *)stats, region_list, n_list, key, H, W, cap, list_cap, keys_are_roots, (const unsigned *)nullptr);
-    PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(merge_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, n_list, group_of, n_groups, key, first, gid, list_cap);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    if (keys_are_roots)
+        return merge_groups_launch<RootKeys, false>("merge_groups", RootKeys{dilated_labels}, stats, region_list, n_list, MergeSlots{}, 1, 1,
+                                                    group_of, n_groups, nullptr, B, H, W, cap, list_cap, workspace, workspace_bytes, stream);
+    return merge_groups_launch<LabelKeys, false>("merge_groups", LabelKeys{dilated_labels}, stats, region_list, n_list, MergeSlots{}, 1, 1,
+                                                 group_of, n_groups, nullptr, B, H, W, cap, list_cap, workspace, workspace_bytes, stream);
 }
 
 int pcseg_merge_groups_runs(const uint32_t *dilated_bits, const int32_t *run_parent, const int64_t *stats,
@@ -1250,19 +1156,9 @@ int pcseg_merge_groups_runs(const uint32_t *dilated_bits, const int32_t *run_par
     PCSEG_REQUIRE(dilated_bits && run_parent && stats && region_list && n_list && group_of && n_groups && workspace && cap >= 1 &&
                       list_cap >= 1 && check_shape(B, H, W),
                   "bad arguments");
-    Carver cv(workspace, workspace_bytes);
-    const MergeGroupsWs ws = merge_groups_carve(cv, (size_t)B, list_cap);
-    int *key = ws.key, *gid = ws.gid, *first = ws.first;
-    if (!cv.ok()) {
-        set_error("merge_groups_runs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    PCSEG_LAUNCH(merge_keys_kernel, dim3((list_cap + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, run_parent,
-                 (const long long *)stats, region_list, n_list, key, H, W, cap, list_cap, 1, (const unsigned *)dilated_bits);
-    PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(merge_groups_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, n_list, group_of, n_groups, key, first, gid, list_cap);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    return merge_groups_launch<RunRoots, false>("merge_groups_runs", RunRoots{dilated_bits, run_parent}, stats, region_list, n_list,
+                                                MergeSlots{}, 1, 1, group_of, n_groups, nullptr, B, H, W, cap, list_cap, workspace,
+                                                workspace_bytes, stream);
 }
 
 int pcseg_merge_groups_fused_multi(const uint32_t *dilated_bits, const int32_t *run_parent, const int64_t *stats,
@@ -1278,20 +1174,9 @@ int pcseg_merge_groups_fused_multi(const uint32_t *dilated_bits, const int32_t *
         ms.slot[m] = m < n_masks ? slots[m] : 0;
         PCSEG_REQUIRE(ms.slot[m] >= 0 && ms.slot[m] < n_slots, "list slot out of range");
     }
-    const int list_cap = cap;
-    const size_t BM = (size_t)B * n_masks;
-    Carver cv(workspace, workspace_bytes);
-    const MergeGroupsWs ws = merge_groups_carve(cv, BM, list_cap);
-    int *key = ws.key, *gid = ws.gid, *first = ws.first;
-    if (!cv.ok()) {
-        set_error("merge_groups_fused: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    PCSEG_LAUNCH(merge_fused_kernel, dim3(B, n_masks), dim3(MG_THREADS), 0, (hipStream_t)stream, (const unsigned *)dilated_bits,
-                 (const int *)run_parent, (const long long *)stats, (const int *)region_lists, (const int *)n_lists, ms, n_slots,
-                 (int *)group_of, (int *)n_groups, (long long *)group_stats, key, first, gid, H, W, cap, list_cap);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    return merge_groups_launch<RunRoots, true>("merge_groups_fused", RunRoots{dilated_bits, run_parent}, stats, region_lists, n_lists, ms,
+                                               n_masks, n_slots, group_of, n_groups, group_stats, B, H, W, cap, cap, workspace,
+                                               workspace_bytes, stream);
 }
 
 int pcseg_merge_groups_fused(const uint32_t *dilated_bits, const int32_t *run_parent, const int64_t *stats,

@@ -264,7 +264,7 @@ __global__ void __launch_bounds__(256) rf_count_kernel(pcseg_refined_inputs in, 
     int n = 0;
     for (int r = threadIdx.x; r < m; r += 256) n += rf_row(in, b, r) && in.kind_r[(int64_t)b * in.cap + r] >= 1;
     int tot;
-    block_scan_256(n, &tot, wsum);
+    block_exclusive_scan<256>(n, &tot, wsum);
     if (threadIdx.x == 0) n_points[b] = tot;
 }
 
@@ -317,8 +317,8 @@ __global__ void __launch_bounds__(256) rf_write_kernel(pcseg_refined_inputs in, 
             const int k = valid ? in.kind_r[fb + r] : 0;
             const int point = valid && k >= 1;
             int total, ptotal;
-            const int pos = carry + block_scan_256(valid, &total, wsum);
-            const int ppos = pcarry + block_scan_256(point, &ptotal, wsum);
+            const int pos = carry + block_exclusive_scan<256>(valid, &total, wsum);
+            const int ppos = pcarry + block_exclusive_scan<256>(point, &ptotal, wsum);
             if (valid) {
                 const int64_t *st = in.ws_stats + (fb + r) * 8;
                 const double area = (double)st[0];
@@ -359,7 +359,7 @@ __global__ void __launch_bounds__(256) rf_write_kernel(pcseg_refined_inputs in, 
             const int kind = a < n ? in.kind[fb + a] : 0;
             const int valid = kind > 0;
             int total;
-            const int pos = carry + block_scan_256(valid, &total, wsum);
+            const int pos = carry + block_exclusive_scan<256>(valid, &total, wsum);
             if (valid) {
                 const int ch = ld_agent(&child[a * 3]), sum = ld_agent(&child[a * 3 + 1]), neg = ld_agent(&child[a * 3 + 2]);
                 const int resolved = kind == 2 && ch >= 2;

@@ -94,23 +94,16 @@ __global__ void __launch_bounds__(256) sf_row_scan_kernel(const int32_t *__restr
     const int per = (H + 255) / 256, lo = min(H, (int)threadIdx.x * per), hi = min(H, lo + per);
     int v = 0;
     for (int r = lo; r < hi; ++r) v += cnt[r];
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int acc = inc - v;
-    for (int w = 0; w < wid; ++w) acc += wsum[w];
+    int total;
+    int acc = block_exclusive_scan<256>(v, &total, wsum);  // (its barriers also order the adds to s_area before the read below)
     for (int r = lo; r < hi; ++r) {
         off[r] = acc;
         acc += cnt[r];
     }
-    if (threadIdx.x == 255) counts[b] = acc;
-    __syncthreads();
-    if (area && threadIdx.x == 0) area[b] = (int64_t)s_area;
+    if (threadIdx.x == 0) {
+        counts[b] = total;
+        if (area) area[b] = (int64_t)s_area;
+    }
 }
 
 // offsets[b] = exclusive sum of counts[0..b), offsets[B] = total
@@ -120,21 +113,13 @@ __global__ void __launch_bounds__(256) sf_frame_scan_kernel(const int64_t *__res
     const int per = (B + 255) / 256, lo = min(B, (int)threadIdx.x * per), hi = min(B, lo + per);
     long long v = 0;
     for (int b = lo; b < hi; ++b) v += counts[b];
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    long long inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    long long acc = inc - v;
-    for (int w = 0; w < wid; ++w) acc += wsum[w];
+    long long total;
+    long long acc = block_exclusive_scan<256>(v, &total, wsum);
     for (int b = lo; b < hi; ++b) {
         offsets[b] = acc;
         acc += counts[b];
     }
-    if (threadIdx.x == 255) offsets[B] = acc;
+    if (threadIdx.x == 0) offsets[B] = total;
 }
 
 __global__ void __launch_bounds__(256) sf_points_kernel(const uint32_t *__restrict__ bits, const int32_t *__restrict__ rowcnt,
@@ -151,11 +136,7 @@ __global__ void __launch_bounds__(256) sf_points_kernel(const uint32_t *__restri
             const int w = w0 + lane;
             uint32_t s = w < WW ? bits[row * WW + w] : 0u;
             const int c = __popc(s);
-            int inc = c;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(inc, o);
-                if (lane >= o) inc += t;
-            }
+            const int inc = wave_inclusive_sum(c);
             int64_t pos = base + inc - c;
             while (s) {
                 const int bit = __ffs((int)s) - 1;

@@ -43,27 +43,6 @@ struct ClassSlots {
     }
 };
 
-// exclusive prefix of v over the 256 threads of a block, *total = the block's sum (wsum: 4 ints of LDS)
-__device__ __forceinline__ int block_scan_256(int v, int *total, int *wsum)
-{
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    int inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < 4; ++w) {
-        if (w < wid) base += wsum[w];
-        tot += wsum[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 // the largest index i in [0, n) with arr[i] <= v, given arr[0] <= v and arr non-decreasing: the frame (or work-item
 // owner) of a point in an offsets array -- empty frames share an offset, the last of them wins -- or the bin of a value
 // in a threshold array.  The comparison is on the caller's own types.

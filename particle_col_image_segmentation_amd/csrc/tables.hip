@@ -25,8 +25,8 @@ __global__ void __launch_bounds__(256) table_count_kernel(pcseg_table_inputs in,
     for (int r = threadIdx.x; r < m; r += 256) n_roi += in.ws_stats[((int64_t)b * in.cap + r) * 8] > 0;
     for (int r = threadIdx.x; r < n; r += 256) n_cell += in.kind[(int64_t)b * in.cap + r] > 0;
     int tot_roi, tot_cell;
-    block_scan_256(n_roi, &tot_roi, wsum);
-    block_scan_256(n_cell, &tot_cell, wsum);
+    block_exclusive_scan<256>(n_roi, &tot_roi, wsum);
+    block_exclusive_scan<256>(n_cell, &tot_cell, wsum);
     if (threadIdx.x == 0) {
         long long g = 0;
         for (int s = 0; s < TB_SLOTS; ++s)
@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(256) table_write_kernel(pcseg_table_inputs in,
             const int64_t *st = in.ws_stats + ((int64_t)b * cap + (r < m ? r : 0)) * 8;
             const int valid = r < m && st[0] > 0;
             int total;
-            const int pos = carry + block_scan_256(valid, &total, wsum);
+            const int pos = carry + block_exclusive_scan<256>(valid, &total, wsum);
             if (valid) {
                 double *row = out + (int64_t)pos * ncol;
                 const double a = (double)st[0];
@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(256) table_write_kernel(pcseg_table_inputs in,
             const int r = base + threadIdx.x;
             const int valid = r < n && in.kind[(int64_t)b * cap + r] > 0;
             int total;
-            const int pos = carry + block_scan_256(valid, &total, wsum);
+            const int pos = carry + block_exclusive_scan<256>(valid, &total, wsum);
             if (valid) {
                 const int64_t *st = in.stats + ((int64_t)b * cap + r) * 8;
                 double *row = out + (int64_t)pos * ncol;

@@ -468,10 +468,6 @@ class FramePipeline:
             return
         B, C, H, W = stack.shape
         tb = self.tables_
-        if W % 4 or res["denoised"].data_ptr() % 4:  # the batched bit pass reads the class map four bytes at a time
-            for s in slots:
-                self._merge_stage(stack, res, s)
-            return
         masks = []
         for s in slots:
             bits = 0
@@ -488,24 +484,6 @@ class FramePipeline:
             gof, ng, gst = ops.merge_groups_fused_multi(dbits, run_par, res["stats"], res["region_list"], res["n_list"], [slots[k] for k in part])
             for m, k in enumerate(part):
                 res["groups"][slots[k]] = {"group_of": gof[m], "n_groups": ng[m], "group_stats": gst[m]}
-
-    def _merge_stage(self, stack, res, s):
-        """proximity merge of one cell type (s < 4) or of all types together (s = 4) (A5, A6)"""
-        B, C, H, W = stack.shape
-        tb = self.tables_
-        if s < 4:
-            bits = 1 << tb.slot_value[s]
-        else:
-            bits = 0
-            for v in tb.slot_value:
-                bits |= 1 << v
-        if bits == 0:
-            return
-        # dilated components as a union-find over the vertical runs of the 1-bit image: grouping only needs "same
-        # component" at the centroid pixels, so no label image is ever written
-        dbits, run_par = ops.dilated_runs(res["denoised"], bits, ta.CELL_CLUSTER_DISTANCE_THRESHOLD // 2)
-        gof, ng, gst = ops.merge_groups_fused(dbits, run_par, res["stats"], res["region_list"], res["n_list"], s)
-        res["groups"][s] = {"group_of": gof, "n_groups": ng, "group_stats": gst}
 
     def _fill_stage(self, stack, res):
         """particle-area reconstruction, one fill per cell class on the previous output (A8)"""

@@ -1,10 +1,12 @@
-"""Kernel resource usage of reduce.hip, shape.hip and refined.hip, parent beside branch, as a markdown table.
+"""Kernel resource usage of some files of csrc/, parent beside branch, as a markdown table.
 
-Usage: resource_table.py PARENT_DIR BRANCH_DIR > resource_usage.md
-Each directory holds reduce.txt, shape.txt, refined.txt: the stderr of
+Usage: resource_table.py [--parent REV] [--renamed OLD=NEW ...] PARENT_DIR BRANCH_DIR [FILE ...] > resource_usage.md
+Each directory holds FILE.txt for every FILE (default: reduce shape refined): the stderr of
     hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Rpass-analysis=kernel-resource-usage -c <file>.hip
-(the flags of build.py plus the remark) on that tree.  Exit status 1 if a branch kernel breaks a condition: scratch where
-the parent had none, a lower occupancy, other LDS bytes."""
+(the flags of build.py plus the remark) on that tree.  --renamed puts the parent's kernel OLD on the row of the branch's
+kernel NEW (names as the table prints them).  Exit status 1 if a branch kernel breaks a condition: scratch where the
+parent had none, a lower occupancy, other LDS bytes."""
+import argparse
 import re
 import subprocess
 import sys
@@ -36,13 +38,17 @@ def parse(path):
     return dict(zip(demangle(names), (kernels[n] for n in names)))
 
 
-def main(parent_dir, branch_dir):
+def main(parent_dir, branch_dir, files, parent_rev, renamed):
     bad = []
-    print("# Kernel resource usage, parent (83c9388) beside branch\n")
-    print("gfx950, the flags of build.py plus `-Rpass-analysis=kernel-resource-usage`; every kernel of the three files.")
-    print("Each cell: parent -> branch (one number where they agree).  Kernels that exist on one side only are listed with `-`.\n")
-    for f in ("reduce", "shape", "refined"):
+    print("# Kernel resource usage, parent (%s) beside branch\n" % parent_rev)
+    print("gfx950, the flags of build.py plus `-Rpass-analysis=kernel-resource-usage`; every kernel of the files below.")
+    print("Each cell: parent -> branch (one number where they agree).  Kernels that exist on one side only are listed with `-`.")
+    for old, new in renamed.items():
+        print("The parent's `%s` is listed as `%s`." % (old, new))
+    print()
+    for f in files:
         a, b = parse("%s/%s.txt" % (parent_dir, f)), parse("%s/%s.txt" % (branch_dir, f))
+        a = {renamed.get(k, k): v for k, v in a.items()}
         print("## %s.hip\n" % f)
         print("| Kernel | " + " | ".join(h for _, h in FIELDS) + " |")
         print("| --- |" + " --- |" * len(FIELDS))
@@ -62,4 +68,11 @@ def main(parent_dir, branch_dir):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default="83c9388")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW")
+    ap.add_argument("parent_dir")
+    ap.add_argument("branch_dir")
+    ap.add_argument("files", nargs="*", default=["reduce", "shape", "refined"])
+    args = ap.parse_args()
+    sys.exit(main(args.parent_dir, args.branch_dir, args.files, args.parent, dict(r.split("=", 1) for r in args.renamed)))
