@@ -31,10 +31,7 @@
 
 namespace pcseg {
 
-constexpr int WS_T = 64;           // tile edge
-constexpr int WS_S = WS_T + 2;     // with halo
-constexpr int WS_P = 67;           // LDS row pitch in elements (odd: row-per-lane sweeps are bank-conflict free)
-constexpr int WS_N = WS_S * WS_P;  // LDS elements per tile array
+constexpr int WS_T = 64;  // tile edge: relaxation tiles, second-level tiles and the active-tile set alike
 constexpr unsigned WS_INF = 0xFFFFFFFFu;
 constexpr int WS_CNT0 = 32, WS_CNT_STRIDE = 32, WS_CHANGED_INTS = WS_CNT0 + 16 * WS_CNT_STRIDE;  // layout of the `changed` block
 
@@ -62,43 +59,79 @@ __global__ void __launch_bounds__(256) ws_init_kernel(const float *__restrict__ 
     out[i] = mk;
 }
 
-template <typename T>
-__device__ __forceinline__ void ws_store_tile(const T *s, T *__restrict__ g, int r0, int c0, int H, int W)
+// ---- work lists and tile marks: what the drivers below share.  Work that is a few tiles of a few frames is LISTED on the
+// device and walked by a small fixed grid: a launch over every tile retires thousands of workgroups that read one byte and
+// leave, each of which first has to find a CU with its LDS and wave slots free among the kernels of the other batches in
+// flight (2 048 blocks of 1 024 threads and 58 KB for one K2 round; same box, fewer such grid rounds made the STEP faster
+// although the serial time went up: 4.53-4.57 ms against 4.62-4.75, profiles/r04/ab_logs/r4f_*).  ONE walk serves every
+// list: entries first, first + stride, .. below the count as it is when the kernel starts.
+template <typename Body>
+__device__ __forceinline__ void ws_walk_list(const int *list, const int *count, int first, int stride, Body &&body)
 {
-    for (int i = threadIdx.x; i < WS_T * WS_T; i += blockDim.x) {
-        int lr = i / WS_T, lc = i % WS_T;
-        int r = r0 + lr, c = c0 + lc;
-        if (r < H && c < W) g[rowoff(r, W) + c] = s[(lr + 1) * WS_P + lc + 1];
+    const int n = *count;
+    for (int i = first; i < n; i += stride) body(list[i]);
+}
+
+// Frames: the second level's kernels run on the flagged frames only (frame_list[-1] = their number).  A launch over the
+// list spans WS_LIST_SPAN entries in the frame dimension of its grid and every block walks the list with that stride: a
+// launch that finds the list empty (the usual case on tie-free data) retires few blocks, a batch in which every frame is
+// listed loops.  Without a list (first level) grid index = frame.
+constexpr int WS_LIST_SPAN = 8;
+template <typename Body>
+__device__ __forceinline__ void ws_for_frames(const int *frame_list, int grid_index, int grid_size, Body &&body)
+{
+    if (!frame_list) body(grid_index);
+    else ws_walk_list(frame_list, frame_list - 1, grid_index, grid_size, body);
+}
+static inline int ws_frame_span(const int *frame_list, int B) { return frame_list ? (B < WS_LIST_SPAN ? B : WS_LIST_SPAN) : B; }
+
+// Tiles: entry = frame * tiles per frame + tile.  The second level lists its active tiles once (benchmark batch: 31 tiles in
+// 7 frames; the count sits in front of the list), the relaxation per round the tiles the round before marked, in that round's
+// tiling (ws_relax_list_kernel).  Blocks walk with the grid's stride; a body that uses LDS ends with a barrier: the next tile reuses it.
+struct WsTileList {
+    const int *list;
+    const int *count;  // number of entries
+    int ntpf, tilesX;  // tiles per frame, tiles per tile row
+};
+constexpr int WS_TILE_GRID = 512;  // blocks of a list-walking launch (two per CU: a quantised batch lists every tile)
+
+template <typename Body>
+__device__ __forceinline__ void ws_for_tiles(const WsTileList &tl, Body &&body)
+{
+    ws_walk_list(tl.list, tl.count, blockIdx.x, gridDim.x, [&](const int e) {
+        const int b = e / tl.ntpf, t = e % tl.ntpf;
+        body(b, t % tl.tilesX, t / tl.tilesX);
+    });
+}
+
+// the in-frame pixels of 64 x 64 tile (tx, ty) for a block of 256 threads: lane = column, wave w takes rows w, w + 4, ..
+template <typename Body>
+__device__ __forceinline__ void ws_for_tile_pixels(int tx, int ty, int H, int W, Body &&body)
+{
+    const int c = tx * WS_T + (threadIdx.x & 63);
+    for (int rr = threadIdx.x >> 6; rr < WS_T; rr += 4) {
+        const int r = ty * WS_T + rr;
+        if (r < H && c < W) body(r, c);
     }
 }
 
-// After a tile converged: wave e compares edge e of the tile (0 top, 1 bottom, 2 left, 3 right) with what is still in
-// global memory and marks only the neighbour that shares a CHANGED edge.  Must run BEFORE the tile is stored.
-template <typename T>
-__device__ __forceinline__ void ws_mark_changed_edges(const T *s, const T *__restrict__ g, uint8_t *dirty_out,
-                                                      int b, int tx, int ty, int tilesX, int tilesY, int r0, int c0, int H, int W)
+// Both fixed points (levels, second-level keys) keep one mark per tile, "a neighbour changed my halo", in two buffers: a
+// round reads one and writes the other.  A visited tile takes its mark down itself: the buffer is all zero again when it
+// becomes the output of the round after next, and no memset has to sit between two rounds.  Block-uniform: false = no
+// mark, the block leaves the tile; every thread has read the mark before thread 0 clears it.
+__device__ __forceinline__ bool ws_take_mark(uint8_t *mark)
 {
-    if (threadIdx.x >= 256) return;  // (wave e = edge e: the first four waves of a wider block)
-    const int e = threadIdx.x >> 6, j = threadIdx.x & 63;
-    const int lr = e == 0 ? 1 : (e == 1 ? WS_T : j + 1);
-    const int lc = e == 2 ? 1 : (e == 3 ? WS_T : j + 1);
-    const int r = r0 + lr - 1, c = c0 + lc - 1;
-    bool ch = false;
-    if (r < H && c < W) ch = s[lr * WS_P + lc] != g[rowoff(r, W) + c];
-    if (__any(ch) && j == 0) {
-        uint8_t *d = dirty_out + (int64_t)b * tilesX * tilesY;
-        if (e == 0 && ty > 0) d[(ty - 1) * tilesX + tx] = 1;
-        else if (e == 1 && ty + 1 < tilesY) d[(ty + 1) * tilesX + tx] = 1;
-        else if (e == 2 && tx > 0) d[ty * tilesX + tx - 1] = 1;
-        else if (e == 3 && tx + 1 < tilesX) d[ty * tilesX + tx + 1] = 1;
-    }
+    if (!*mark) return false;
+    __syncthreads();
+    if (threadIdx.x == 0) *mark = 0;
+    return true;
 }
 
 // (1) minimax relaxation, tile-local fixed point in LDS.  L and the pixel value share one 64-bit LDS word (x = L,
 // y = value): a sweep step is ONE ds_read_b64 instead of two ds_read_b32 -- the kernel is bound by LDS-array cycles, and
 // the b64 form moves twice the bytes per cycle (odd pitch: conflict-free for row and column sweeps alike).
 //
-// Geometry of a relaxation tile of edge T = 64: four tiles (4 x 36 KB of LDS) and sixteen waves per CU.  A 128-pixel tile
+// Geometry of a relaxation tile (edge WS_T = 64, pitch 68): four tiles (4 x 36 KB of LDS) and sixteen waves per CU.  A 128-pixel tile
 // fills the 160 KB LDS of a CDNA4 CU -- with its halo it is 130 x 131 x 8 B = 133 KB, ONE workgroup of 16 waves per CU (as
 // many waves as four 64-tiles bring), the four 64 x 64 quadrants exchange their rims through LDS inside one iteration
 // -- and MEASURED SLOWER on the benchmark batch (3.30 ms of relaxation per step against 2.16 ms, rounds 1133 / 1121 /
@@ -106,17 +139,16 @@ __device__ __forceinline__ void ws_mark_changed_edges(const T *s, const T *__res
 // 16-wave barriers, the shifted tiling has 81 tiles per 1024^2 frame instead of 64 (+27 %) where 64-tiles have 289
 // instead of 256 (+13 %), and the number of rounds hardly drops because levels travel along winding paths, not tile
 // diameters.
-template <int T>
 struct RelaxGeom {
-    static_assert(T == 64, "relaxation tiles are 64 pixels wide: one wave per sweep quadrant");
-    static constexpr int S = T + 2;        // with halo
+    static_assert(WS_T == 64, "relaxation tiles are 64 pixels wide: one wave per sweep quadrant");
+    static constexpr int S = WS_T + 2;     // with halo
     // LDS row pitch in elements.  The wavefront sweeps of the quadrant scheme walk lane l along row l at column
     // (step - l), i.e. lanes are P - 1 or P + 1 elements apart: even P
-    static constexpr int P = T + 4;
+    static constexpr int P = WS_T + 4;
     static constexpr int PAD = 8;          // elements in front of and behind the tile (wavefront lanes read past their row's ends)
     static constexpr int N = S * P + 2 * PAD;  // LDS elements
     static constexpr int THREADS = 4 * 64;  // one wave per sweep quadrant
-    static constexpr int HE = T / 2;       // cells of a half edge
+    static constexpr int HE = WS_T / 2;    // cells of a half edge
     static constexpr size_t LDS_BYTES = sizeof(uint2) * N;
 };
 
@@ -258,24 +290,16 @@ struct WsTiling {
 };
 
 // One tile of one round (block-uniform control flow: every return is taken by all threads of the block).
-template <int T>
 __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, const bool FIRST, unsigned *__restrict__ val,
                                               unsigned *__restrict__ L, uint8_t *__restrict__ dirty_in,
                                               uint8_t *__restrict__ dirty_out, int *__restrict__ any_changed, int H, int W,
                                               const WsTiling &cur, const WsTiling &nxt, int max_iter, int tx, int ty, int b,
                                               int *__restrict__ list_out = nullptr, int *__restrict__ count_out = nullptr)
 {
-    using G = RelaxGeom<T>;
-    constexpr int S = G::S, P = G::P, NT = G::THREADS, QW = T / 4;  // QW: 16-byte quads per tile row
+    using G = RelaxGeom;
+    constexpr int T = WS_T, S = G::S, P = G::P, NT = G::THREADS, QW = T / 4;  // QW: 16-byte quads per tile row
     const int tid = threadIdx.x;
-    if (!FIRST) {
-        // a visited tile takes its mark down itself: the buffer is all zero again when it becomes the output of the
-        // round after next, and no memset has to sit between two rounds
-        uint8_t *mark = dirty_in + ((int64_t)b * cur.ny + ty) * cur.nx + tx;
-        if (!*mark) return;
-        __syncthreads();
-        if (tid == 0) *mark = 0;
-    }
+    if (!FIRST && !ws_take_mark(dirty_in + ((int64_t)b * cur.ny + ty) * cur.nx + tx)) return;
     // 64 x 64 units actually processed (measurement: bench.py roofline), spread over 16 cache lines: one counter would
     // make every block of the launch queue on the same line
     if (tid == 0) atomicAdd(any_changed + WS_CNT0 + WS_CNT_STRIDE * ((tx + 5 * ty + 3 * b) & 15), 1);
@@ -466,141 +490,107 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
     }
 }
 
-template <int T>
-__global__ void __launch_bounds__(RelaxGeom<T>::THREADS) ws_relax_kernel(WsInputs in, const bool FIRST, unsigned *__restrict__ val,
+__global__ void __launch_bounds__(RelaxGeom::THREADS) ws_relax_kernel(WsInputs in, const bool FIRST, unsigned *__restrict__ val,
                                                                          unsigned *__restrict__ L, uint8_t *__restrict__ dirty_in,
                                                                          uint8_t *__restrict__ dirty_out, int *__restrict__ any_changed,
                                                                          int H, int W, WsTiling cur, WsTiling nxt, int max_iter,
                                                                          int *__restrict__ list_out, int *__restrict__ count_out)
 {
-    extern __shared__ __attribute__((aligned(16))) uint2 relax_lds[];  // RelaxGeom<T>::N cells
+    extern __shared__ __attribute__((aligned(16))) uint2 relax_lds[];  // RelaxGeom::N cells
     const TileIndex t = xcd_tile_index();  // a tile's halo is its neighbours' rim: keep them on one XCD's L2
-    ws_relax_tile<T>(relax_lds + RelaxGeom<T>::PAD, in, FIRST, val, L, dirty_in, dirty_out, any_changed, H, W, cur, nxt, max_iter, t.x, t.y,
+    ws_relax_tile(relax_lds + RelaxGeom::PAD, in, FIRST, val, L, dirty_in, dirty_out, any_changed, H, W, cur, nxt, max_iter, t.x, t.y,
                      t.z, list_out, count_out);
 }
 
-// Late rounds visit a few per cent of the tiles.  Launched over every tile they retire thousands of workgroups that read one
-// byte and leave -- each of which first has to be given 36 KB of LDS and four wave slots on a CU that seven other batches'
-// kernels are using (see WsTileList: the empty grids of the second level cost the STEP 3 %).  From round WS_LIST_FROM on a
-// round is a fixed small grid walking the list of tiles the round before marked (appended by the first marker of a tile).
+// Late rounds visit a few per cent of the tiles, and a workgroup that only reads its mark still has to be given 36 KB of LDS
+// and four wave slots first (see ws_walk_list: the empty grids of the second level cost the STEP 3 %).  From round WS_LIST_FROM
+// on a round is a fixed small grid walking the list of tiles the round before marked (appended by the first marker of a tile).
 constexpr int WS_LIST_FROM = 4, WS_LIST_GRID = 1024;  // first list-walking round; blocks of a list-walking launch
 
-template <int T>
-__global__ void __launch_bounds__(RelaxGeom<T>::THREADS) ws_relax_list_kernel(WsInputs in, unsigned *__restrict__ val, unsigned *__restrict__ L,
-                                                                              uint8_t *__restrict__ dirty_in, uint8_t *__restrict__ dirty_out,
-                                                                              int *__restrict__ any_changed, int H, int W, WsTiling cur,
-                                                                              WsTiling nxt, int max_iter, const int *__restrict__ list_in,
-                                                                              const int *__restrict__ count_in, int *__restrict__ list_out,
-                                                                              int *__restrict__ count_out)
+__global__ void __launch_bounds__(RelaxGeom::THREADS) ws_relax_list_kernel(WsInputs in, unsigned *__restrict__ val, unsigned *__restrict__ L,
+                                                                           uint8_t *__restrict__ dirty_in, uint8_t *__restrict__ dirty_out,
+                                                                           int *__restrict__ any_changed, int H, int W, WsTiling cur,
+                                                                           WsTiling nxt, int max_iter, WsTileList tiles,
+                                                                           int *__restrict__ list_out, int *__restrict__ count_out)
 {
     extern __shared__ __attribute__((aligned(16))) uint2 relax_lds[];
-    const int n = *count_in, per_frame = cur.nx * cur.ny;
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const int m = list_in[i], b = m / per_frame, t = m % per_frame;
-        ws_relax_tile<T>(relax_lds + RelaxGeom<T>::PAD, in, false, val, L, dirty_in, dirty_out, any_changed, H, W, cur, nxt, max_iter,
-                         t % cur.nx, t / cur.nx, b, list_out, count_out);
+    ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
+        ws_relax_tile(relax_lds + RelaxGeom::PAD, in, false, val, L, dirty_in, dirty_out, any_changed, H, W, cur, nxt, max_iter, tx, ty, b,
+                      list_out, count_out);
         __syncthreads();  // the next listed tile reuses the LDS tile
-    }
+    });
 }
 
-// The fixed point is driven WITHOUT the host: a fixed number of grid rounds is enqueued (a round whose tiles carry no
-// mark costs a few microseconds: every block reads one byte and leaves), and whatever is still marked after them --
-// a few tiles of a few frames, if anything -- is finished by this kernel: one block per frame walks the frame's marked
-// tiles round by round until a round marks nothing.  Rounds of one frame only depend on that frame's tiles, so the
-// block's own barrier is the only synchronisation (stores and loads of one workgroup go through the same L1).
+// The fixed points are driven WITHOUT the host: a fixed number of grid rounds is enqueued (a round that finds no mark
+// costs a few microseconds), and whatever is still marked after them -- a few tiles of a few frames, if anything -- is
+// finished by a tail kernel: one block per frame walks the frame's marked tiles round by round until a round marks
+// nothing.  Rounds of one frame only depend on that frame's tiles, so the block's own barrier is the only synchronisation
+// (stores and loads of one workgroup go through the same L1).  This is that block's loop for frame b; the two tail kernels
+// supply the tilings of even and odd rounds, counts(t) -- does marked tile t count (one that does not is never visited) --
+// and visit(cur, nxt, tx, ty, din, dout): one tile of tiling cur, takes its mark in din down, marks tiles of nxt in dout.
+// It gives up after max_rounds rounds (cannot happen for a monotone fixed point; never spin for ever): the frame's keys are
+// then no fixed point, and whatever the union-find makes of them must not be reported as exact -- the frame's tie flag is
+// raised, so the exact flood (mode 0) recomputes it and mode 2 reports it.
 constexpr int WS_TAIL_LIST = 1024;  // marked tiles a tail kernel lists per round (more: it walks every tile)
 
-template <int T>
-__global__ void __launch_bounds__(RelaxGeom<T>::THREADS) ws_relax_tail_kernel(WsInputs in, unsigned *__restrict__ val,
-                                                                              unsigned *__restrict__ L, uint8_t *__restrict__ dirtyA,
-                                                                              uint8_t *__restrict__ dirtyB, int *__restrict__ any_changed,
-                                                                              int *__restrict__ not_converged, int *__restrict__ exact_flags,
-                                                                              int H, int W, WsTiling t0, WsTiling t1, int first_round,
-                                                                              int max_rounds)
+template <int THREADS, typename Counts, typename Visit>
+__device__ __forceinline__ void ws_tail_rounds(const int b, uint8_t *din, uint8_t *dout, const int first_round, const int max_rounds,
+                                               int *__restrict__ not_converged, int *__restrict__ exact_flags, const WsTiling &t_even,
+                                               const WsTiling &t_odd, Counts &&counts, Visit &&visit)
 {
-    extern __shared__ __attribute__((aligned(16))) uint2 relax_lds[];
     __shared__ int tail_list[WS_TAIL_LIST];
     __shared__ int tail_count;
-    const int b = blockIdx.x;
-    uint8_t *din = dirtyA, *dout = dirtyB;
     for (int round = first_round;; ++round) {
-        const WsTiling cur = (round & 1) ? t1 : t0, nxt = (round & 1) ? t0 : t1;
+        const WsTiling cur = (round & 1) ? t_odd : t_even, nxt = (round & 1) ? t_even : t_odd;
         const int ntiles = cur.nx * cur.ny;
         const uint8_t *marks = din + (int64_t)b * ntiles;
         // the round's work list: the marked tiles, gathered in parallel (walking ALL tiles and letting each look at its own
         // mark costs a dependent global load per tile -- 256 round trips per round for a handful of marked tiles)
+        __syncthreads();  // (a block that walks a frame list: the frame before has read tail_count)
         if (threadIdx.x == 0) tail_count = 0;
         __syncthreads();
-        for (int t = threadIdx.x; t < ntiles; t += RelaxGeom<T>::THREADS)
-            if (marks[t] != 0) {
+        for (int t = threadIdx.x; t < ntiles; t += THREADS)
+            if (marks[t] != 0 && counts(t)) {
                 const int k = atomicAdd(&tail_count, 1);
                 if (k < WS_TAIL_LIST) tail_list[k] = t;
             }
         __syncthreads();
         const int marked = tail_count;
         if (marked == 0) return;
-        if (round - first_round >= max_rounds) {  // cannot happen for a monotone fixed point; never spin for ever
-            // L of this frame is not a fixed point: whatever the union-find makes of it must not be reported as exact --
-            // the frame's tie flag is raised, so the exact flood (mode 0) recomputes it and mode 2 reports it
+        if (round - first_round >= max_rounds) {
             if (threadIdx.x == 0) { *not_converged = 1; exact_flags[b] = 1; }
             return;
         }
         const int walk = marked <= WS_TAIL_LIST ? marked : ntiles;  // (a list that overflowed: every tile, each checks its mark)
         for (int k = 0; k < walk; ++k) {
             const int t = marked <= WS_TAIL_LIST ? tail_list[k] : k;
-            ws_relax_tile<T>(relax_lds + RelaxGeom<T>::PAD, in, false, val, L, din, dout, any_changed, H, W, cur, nxt, 100000, t % cur.nx,
-                             t / cur.nx, b);
-            __syncthreads();  // the tile's stores (L, marks) before the next tile loads its halo / the next round scans
+            visit(cur, nxt, t % cur.nx, t / cur.nx, din, dout);
+            __syncthreads();  // the tile's stores (keys, marks) before the next tile loads its halo / the next round scans
         }
         uint8_t *tmp = din; din = dout; dout = tmp;
     }
 }
 
-
-// kernels of the second level are launched over the flagged frames only: grid index -> frame id through a list
-// The list and its length (frame_list[-1]) stay on the device.  A launch over a list only spans WS_LIST_SPAN entries in
-// the frame dimension of its grid and every block walks the list with that stride: a launch that finds the list
-// empty (the usual case on tie-free data) retires few blocks, a batch in which every frame is listed loops.
-constexpr int WS_LIST_SPAN = 8;
-template <typename Body>
-__device__ __forceinline__ void ws_for_frames(const int *frame_list, int grid_index, int grid_size, Body &&body)
+// the rest of the levels' fixed point after the grid rounds (which end with round first_round - 1), one block per frame
+__global__ void __launch_bounds__(RelaxGeom::THREADS) ws_relax_tail_kernel(WsInputs in, unsigned *__restrict__ val, unsigned *__restrict__ L,
+                                                                           uint8_t *__restrict__ dirtyA, uint8_t *__restrict__ dirtyB,
+                                                                           int *__restrict__ any_changed, int *__restrict__ not_converged,
+                                                                           int *__restrict__ exact_flags, int H, int W, WsTiling t0,
+                                                                           WsTiling t1, int first_round, int max_rounds)
 {
-    if (!frame_list) {
-        body(grid_index);
-        return;
-    }
-    const int n = frame_list[-1];
-    for (int gi = grid_index; gi < n; gi += grid_size) body(frame_list[gi]);
+    extern __shared__ __attribute__((aligned(16))) uint2 relax_lds[];
+    const int b = blockIdx.x;
+    ws_tail_rounds<RelaxGeom::THREADS>(
+        b, dirtyA, dirtyB, first_round, max_rounds, not_converged, exact_flags, t0, t1, [](const int) { return true; },
+        [&](const WsTiling &cur, const WsTiling &nxt, const int tx, const int ty, uint8_t *din, uint8_t *dout) {
+            ws_relax_tile(relax_lds + RelaxGeom::PAD, in, false, val, L, din, dout, any_changed, H, W, cur, nxt, 100000, tx, ty, b);
+        });
 }
-static inline int ws_frame_span(const int *frame_list, int B) { return frame_list ? (B < WS_LIST_SPAN ? B : WS_LIST_SPAN) : B; }
 
 // stage-2 work is restricted to the 64x64 tiles that hold a pixel of an unresolved component (active == nullptr: all)
 __device__ __forceinline__ bool ws_active(const uint8_t *active, int b, int r, int c, int tilesX, int tilesY)
 {
     return active == nullptr || active[((int64_t)b * tilesY + r / WS_T) * tilesX + c / WS_T] != 0;
-}
-
-// The second level's work is a few dozen 64 x 64 tiles of a few frames (benchmark batch: 31 tiles in 7 frames).  Its passes
-// used to be launched over the worst-case grid of the listed frames -- every tile or pixel of up to eight frames, almost all
-// of whose blocks leave at once.  Alone that costs little; with eight batches in flight every such block still has to find a
-// CU with its LDS and wave slots free among the other batches' kernels (2 048 blocks of 1 024 threads and 58 KB for one
-// K2 round): same box, fewer grid rounds made the STEP faster although the serial time went up (4.53-4.57 ms against
-// 4.62-4.75, profiles/r04/ab_logs/r4f_*).  So the active tiles are listed once on the device (entry = frame * tiles per frame
-// + tile, the count in front of the list) and the second level's kernels are small fixed grids that walk the list.
-struct WsTileList {
-    const int *list;   // list[-1] = number of entries
-    int ntpf, tilesX;  // tiles per frame, tiles per tile row
-};
-constexpr int WS_TILE_GRID = 512;  // blocks of a list-walking launch (two per CU: a quantised batch lists every tile)
-
-template <typename Body>
-__device__ __forceinline__ void ws_for_tiles(const WsTileList &tl, Body &&body)
-{
-    const int n = tl.list[-1];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const int e = tl.list[i], b = e / tl.ntpf, t = e % tl.ntpf;
-        body(b, t % tl.tilesX, t / tl.tilesX);
-    }
 }
 
 __global__ void __launch_bounds__(256) ws_list_tiles_kernel(const int *__restrict__ frame_list, const uint8_t *__restrict__ active, int ntpf,
@@ -1012,13 +1002,10 @@ __global__ void __launch_bounds__(256) ws_uf_label_tiles_kernel(WsTileList tiles
                                                                  int *__restrict__ exact_flags)
 {
     ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
-        const int c = tx * WS_T + (threadIdx.x & 63);
-        for (int rr = threadIdx.x >> 6; rr < WS_T; rr += 4) {
-            const int r = ty * WS_T + rr;
-            if (r < H && c < W)
-                ws_uf_label_pixel<MODE>(b, (int64_t)r * W + c, parent, F, active, bad, markers, mask, tie_flags, nullptr, (int64_t)H * W, W,
-                                        tilesX, tilesY, exact_flags, nullptr, nullptr);
-        }
+        ws_for_tile_pixels(tx, ty, H, W, [&](const int r, const int c) {
+            ws_uf_label_pixel<MODE>(b, (int64_t)r * W + c, parent, F, active, bad, markers, mask, tie_flags, nullptr, (int64_t)H * W, W,
+                                    tilesX, tilesY, exact_flags, nullptr, nullptr);
+        });
     });
 }
 
@@ -1286,10 +1273,7 @@ __global__ void __launch_bounds__(256) ws_k2_init_kernel(WsTileList tiles, const
                                                           unsigned *__restrict__ K2, int H, int W)
 {
     ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
-    const int c = tx * WS_T + (threadIdx.x & 63);
-    for (int rr = threadIdx.x >> 6; rr < WS_T; rr += 4) {
-        const int r = ty * WS_T + rr;
-        if (r >= H || c >= W) continue;
+    ws_for_tile_pixels(tx, ty, H, W, [&](const int r, const int c) {
         const int64_t i = (int64_t)b * H * W + (int64_t)r * W + c;
         const unsigned l = L[i];
         unsigned k = WS_INF;
@@ -1303,19 +1287,55 @@ __global__ void __launch_bounds__(256) ws_k2_init_kernel(WsTileList tiles, const
             }
         }
         K2[i] = k;
-    }
+    });
     });
 }
 
 // threads per tile of the second level: its tile pass is a handful of dependent LDS phases -- with 1024 threads a thread owns
 // 4 cells of the tile (256 threads, 16 cells each: 58 us a grid round against 32; profiles/r04/ab_logs/r4d_*, r4e_*)
 constexpr int K2T = 1024;
+// the tile arrays of the second level: 66 x 66 cells (tile + halo) each, at a pitch of its own (the relaxation's is RelaxGeom's)
 struct WsK2Lds {
-    unsigned sL[WS_N];
-    unsigned sK[WS_N];
-    uint8_t sLake[WS_N];
-    int par[WS_N];
+    static constexpr int S = WS_T + 2;  // with halo
+    static constexpr int P = 67;        // LDS row pitch in elements (odd: rows and columns alike are bank-conflict free)
+    static constexpr int N = S * P;     // LDS elements per tile array
+    unsigned sL[N];
+    unsigned sK[N];
+    uint8_t sLake[N];
+    int par[N];
 };
+
+// the tile's keys back to global memory
+__device__ __forceinline__ void ws_store_tile(const unsigned *s, unsigned *__restrict__ g, int r0, int c0, int H, int W)
+{
+    for (int i = threadIdx.x; i < WS_T * WS_T; i += blockDim.x) {
+        int lr = i / WS_T, lc = i % WS_T;
+        int r = r0 + lr, c = c0 + lc;
+        if (r < H && c < W) g[rowoff(r, W) + c] = s[(lr + 1) * WsK2Lds::P + lc + 1];
+    }
+}
+
+// After a tile converged: wave e compares edge e of the tile (0 top, 1 bottom, 2 left, 3 right) with what is still in
+// global memory and marks only the neighbour that shares a CHANGED edge.  Must run BEFORE the tile is stored.
+__device__ __forceinline__ void ws_mark_changed_edges(const unsigned *s, const unsigned *__restrict__ g, uint8_t *dirty_out, int b, int tx,
+                                                      int ty, int tilesX, int tilesY, int r0, int c0, int H, int W)
+{
+    static_assert(K2T >= 4 * WAVE, "one wave per tile edge");
+    if (threadIdx.x >= 4 * WAVE) return;  // wave e = edge e: the first four of the block's K2T / 64 waves
+    const int e = threadIdx.x >> 6, j = threadIdx.x & 63;
+    const int lr = e == 0 ? 1 : (e == 1 ? WS_T : j + 1);
+    const int lc = e == 2 ? 1 : (e == 3 ? WS_T : j + 1);
+    const int r = r0 + lr - 1, c = c0 + lc - 1;
+    bool ch = false;
+    if (r < H && c < W) ch = s[lr * WsK2Lds::P + lc] != g[rowoff(r, W) + c];
+    if (__any(ch) && j == 0) {
+        uint8_t *d = dirty_out + (int64_t)b * tilesX * tilesY;
+        if (e == 0 && ty > 0) d[(ty - 1) * tilesX + tx] = 1;
+        else if (e == 1 && ty + 1 < tilesY) d[(ty + 1) * tilesX + tx] = 1;
+        else if (e == 2 && tx > 0) d[ty * tilesX + tx - 1] = 1;
+        else if (e == 3 && tx + 1 < tilesX) d[ty * tilesX + tx + 1] = 1;
+    }
+}
 
 // one tile of one second-level round (block-uniform control flow, like ws_relax_tile)
 // `in_bad` (may be null: every lake): the per-pixel mark UF_REPAIR leaves.  K2 is only ever COMPARED between the
@@ -1329,27 +1349,23 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
                                                  uint8_t *__restrict__ dirty_in, uint8_t *__restrict__ dirty_out, int H, int W,
                                                  int tilesX, int tilesY, int tx, int ty, int b, const uint8_t *__restrict__ in_bad)
 {
+    constexpr int S = WsK2Lds::S, P = WsK2Lds::P;
     unsigned *sL = lds.sL, *sK = lds.sK;
     uint8_t *sLake = lds.sLake;
     if (!active[((int64_t)b * tilesY + ty) * tilesX + tx]) return;  // K2 is only defined inside the active tiles
-    {
-        uint8_t *mark = dirty_in + ((int64_t)b * tilesY + ty) * tilesX + tx;
-        if (!*mark) return;
-        __syncthreads();
-        if (threadIdx.x == 0) *mark = 0;  // see ws_relax_tile
-    }
+    if (!ws_take_mark(dirty_in + ((int64_t)b * tilesY + ty) * tilesX + tx)) return;
     const int r0 = ty * WS_T, c0 = tx * WS_T;
     const int64_t fbase = (int64_t)b * H * W;
     {
         // the three arrays of the tile + halo as ONE batch of loads per thread (clamped addresses, no branch around a
         // load; see ws_relax_tile): a loop of dependent round trips here cost more than the sweeps
-        constexpr int TRIPS = (WS_S * WS_S + K2T - 1) / K2T;
+        constexpr int TRIPS = (S * S + K2T - 1) / K2T;
         unsigned lv[TRIPS], kv[TRIPS], vv[TRIPS];
         uint8_t bv[TRIPS];
 #pragma unroll
         for (int t = 0; t < TRIPS; ++t) {
-            const int i = min((int)threadIdx.x + K2T * t, WS_S * WS_S - 1);
-            const int r = r0 + i / WS_S - 1, c = c0 + i % WS_S - 1;
+            const int i = min((int)threadIdx.x + K2T * t, S * S - 1);
+            const int r = r0 + i / S - 1, c = c0 + i % S - 1;
             const int64_t p = fbase + rowoff(min(max(r, 0), H - 1), W) + min(max(c, 0), W - 1);
             lv[t] = L[p];
             kv[t] = K2[p];
@@ -1359,13 +1375,13 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
 #pragma unroll
         for (int t = 0; t < TRIPS; ++t) {
             const int i = (int)threadIdx.x + K2T * t;
-            if (i < WS_S * WS_S) {
-                const int lr = i / WS_S, lc = i % WS_S;
+            if (i < S * S) {
+                const int lr = i / S, lc = i % S;
                 const int r = r0 + lr - 1, c = c0 + lc - 1;
                 const bool in = r >= 0 && r < H && c >= 0 && c < W;
-                sL[lr * WS_P + lc] = in ? lv[t] : WS_INF;
-                sK[lr * WS_P + lc] = in ? kv[t] : WS_INF;
-                sLake[lr * WS_P + lc] = in && lv[t] != WS_INF && vv[t] < lv[t] && bv[t] != 0;
+                sL[lr * P + lc] = in ? lv[t] : WS_INF;
+                sK[lr * P + lc] = in ? kv[t] : WS_INF;
+                sLake[lr * P + lc] = in && lv[t] != WS_INF && vv[t] < lv[t] && bv[t] != 0;
             }
         }
     }
@@ -1383,7 +1399,7 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
     unsigned k_old[CELLS];
 #pragma unroll
     for (int q = 0; q < CELLS; ++q) {
-        const int t = threadIdx.x + K2T * q, i = (t / WS_T + 1) * WS_P + t % WS_T + 1;
+        const int t = threadIdx.x + K2T * q, i = (t / WS_T + 1) * P + t % WS_T + 1;
         par[i] = sLake[i] ? i : -1;
         k_old[q] = sK[i];
     }
@@ -1391,22 +1407,22 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
     // links between interior lake cells of one level: right and down (the other two are some cell's right / down)
 #pragma unroll
     for (int q = 0; q < CELLS; ++q) {
-        const int t = threadIdx.x + K2T * q, lr = t / WS_T + 1, lc = t % WS_T + 1, i = lr * WS_P + lc;
+        const int t = threadIdx.x + K2T * q, lr = t / WS_T + 1, lc = t % WS_T + 1, i = lr * P + lc;
         if (!sLake[i]) continue;
         const unsigned l = sL[i];
         if (lc < WS_T && sLake[i + 1] && sL[i + 1] == l) unite_lds_halving(par, i, i + 1);
-        if (lr < WS_T && sLake[i + WS_P] && sL[i + WS_P] == l) unite_lds_halving(par, i, i + WS_P);
+        if (lr < WS_T && sLake[i + P] && sL[i + P] == l) unite_lds_halving(par, i, i + P);
     }
     __syncthreads();
     // every lake cell brings its own key and the keys of the same-level cells around it that are not members (entries,
     // halo cells) to its root
 #pragma unroll
     for (int q = 0; q < CELLS; ++q) {
-        const int t = threadIdx.x + K2T * q, lr = t / WS_T + 1, lc = t % WS_T + 1, i = lr * WS_P + lc;
+        const int t = threadIdx.x + K2T * q, lr = t / WS_T + 1, lc = t % WS_T + 1, i = lr * P + lc;
         if (!sLake[i]) continue;
         const unsigned l = sL[i];
         unsigned m = k_old[q];
-        const int nb[4] = {i - WS_P, i - 1, i + 1, i + WS_P};
+        const int nb[4] = {i - P, i - 1, i + 1, i + P};
         const bool interior[4] = {lr > 1, lc > 1, lc < WS_T, lr < WS_T};
 #pragma unroll
         for (int d = 0; d < 4; ++d)
@@ -1419,19 +1435,19 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
     unsigned k_new[CELLS];
 #pragma unroll
     for (int q = 0; q < CELLS; ++q) {
-        const int t = threadIdx.x + K2T * q, i = (t / WS_T + 1) * WS_P + t % WS_T + 1;
+        const int t = threadIdx.x + K2T * q, i = (t / WS_T + 1) * P + t % WS_T + 1;
         k_new[q] = sLake[i] ? sK[find_lds_halving(par, i)] : k_old[q];
         changed = changed || k_new[q] != k_old[q];
     }
     __syncthreads();  // every root has been read before a member overwrites its own cell (a root's own write is the value it holds)
 #pragma unroll
     for (int q = 0; q < CELLS; ++q) {
-        const int t = threadIdx.x + K2T * q, i = (t / WS_T + 1) * WS_P + t % WS_T + 1;
+        const int t = threadIdx.x + K2T * q, i = (t / WS_T + 1) * P + t % WS_T + 1;
         if (k_new[q] != k_old[q]) sK[i] = k_new[q];
     }
     const bool changed_any = __syncthreads_or(changed);
     if (!changed_any) return;
-    ws_mark_changed_edges(sK, (const unsigned *)K2 + fbase, dirty_out, b, tx, ty, tilesX, tilesY, r0, c0, H, W);
+    ws_mark_changed_edges(sK, K2 + fbase, dirty_out, b, tx, ty, tilesX, tilesY, r0, c0, H, W);
     __syncthreads();
     ws_store_tile(sK, K2 + fbase, r0, c0, H, W);
 }
@@ -1448,7 +1464,7 @@ __global__ void __launch_bounds__(K2T) ws_k2_relax_kernel(WsTileList tiles, cons
     });
 }
 
-// the rest of the second-level fixed point after its grid rounds, one block per flagged frame (see ws_relax_tail_kernel)
+// the rest of the second-level fixed point after its grid rounds, one block per flagged frame (ws_tail_rounds)
 __global__ void __launch_bounds__(K2T) ws_k2_relax_tail_kernel(const int *__restrict__ frame_list, const unsigned *__restrict__ val,
                                                                 const unsigned *__restrict__ L, unsigned *__restrict__ K2,
                                                                 const uint8_t *__restrict__ active, uint8_t *__restrict__ dirtyA,
@@ -1457,38 +1473,15 @@ __global__ void __launch_bounds__(K2T) ws_k2_relax_tail_kernel(const int *__rest
                                                                 int max_rounds, const uint8_t *__restrict__ in_bad)
 {
     __shared__ WsK2Lds lds;
-    __shared__ int tail_list[WS_TAIL_LIST];
-    __shared__ int tail_count;
+    const WsTiling tiling{0, tilesX, tilesY};
     ws_for_frames(frame_list, blockIdx.x, gridDim.x, [&](const int b) {
-    uint8_t *din = dirtyA, *dout = dirtyB;
-    const int ntiles = tilesX * tilesY;
-    for (int round = 0;; ++round) {
         // (a mark on a tile outside the active set is never taken down -- such tiles are not visited -- and is no work)
-        const uint8_t *marks = din + (int64_t)b * ntiles, *act = active + (int64_t)b * ntiles;
-        // the round's work list: marked active tiles, gathered in parallel (see ws_relax_tail_kernel)
-        __syncthreads();
-        if (threadIdx.x == 0) tail_count = 0;
-        __syncthreads();
-        for (int t = threadIdx.x; t < ntiles; t += K2T)
-            if (marks[t] != 0 && act[t] != 0) {
-                const int k = atomicAdd(&tail_count, 1);
-                if (k < WS_TAIL_LIST) tail_list[k] = t;
-            }
-        __syncthreads();
-        const int marked = tail_count;
-        if (marked == 0) return;
-        if (round >= max_rounds) {
-            if (threadIdx.x == 0) { *not_converged = 1; exact_flags[b] = 1; }  // see ws_relax_tail_kernel
-            return;
-        }
-        const int walk = marked <= WS_TAIL_LIST ? marked : ntiles;
-        for (int k = 0; k < walk; ++k) {
-            const int t = marked <= WS_TAIL_LIST ? tail_list[k] : k;
-            ws_k2_relax_tile(lds, val, L, K2, active, din, dout, H, W, tilesX, tilesY, t % tilesX, t / tilesX, b, in_bad);
-            __syncthreads();
-        }
-        uint8_t *tmp = din; din = dout; dout = tmp;
-    }
+        const uint8_t *act = active + (int64_t)b * tilesX * tilesY;
+        ws_tail_rounds<K2T>(
+            b, dirtyA, dirtyB, 0, max_rounds, not_converged, exact_flags, tiling, tiling, [&](const int t) { return act[t] != 0; },
+            [&](const WsTiling &, const WsTiling &, const int tx, const int ty, uint8_t *din, uint8_t *dout) {
+                ws_k2_relax_tile(lds, val, L, K2, active, din, dout, H, W, tilesX, tilesY, tx, ty, b, in_bad);
+            });
     });
 }
 
@@ -1502,14 +1495,10 @@ __global__ void __launch_bounds__(256) ws_pack_kernel(WsTileList tiles, const un
 {
     ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
         const int64_t fbase = (int64_t)b * H * W;
-        const int c = tx * WS_T + (threadIdx.x & 63);
-        for (int rr = threadIdx.x >> 6; rr < WS_T; rr += 4) {
-            const int r = ty * WS_T + rr;
-            if (r < H && c < W) {
-                const int64_t g = fbase + (int64_t)r * W + c;
-                K64[g] = ((unsigned long long)L[g] << 32) | K2[g];
-            }
-        }
+        ws_for_tile_pixels(tx, ty, H, W, [&](const int r, const int c) {
+            const int64_t g = fbase + (int64_t)r * W + c;
+            K64[g] = ((unsigned long long)L[g] << 32) | K2[g];
+        });
         // ring: thread t < 66 -> row above (t - 1 = column offset), 66..131 -> row below, 132..195 -> left column, 196..259 -> right
         for (int t = threadIdx.x; t < 2 * (WS_T + 2) + 2 * WS_T; t += 256) {
             int r, cc;
@@ -1853,7 +1842,7 @@ using namespace pcseg;
 constexpr int WS_ROUND0_SWEEPS = 4, WS_ROUND_SWEEPS = 6;
 
 // the watershed may be called from several host threads at once (FramePipeline's lanes)
-static std::atomic<long long> g_ws_counters[4];  // [0] unused (lives on the device), relax launches, calls, -
+static std::atomic<long long> g_ws_relax_launches, g_ws_calls;  // since the last reset (pcseg_watershed_counters)
 static unsigned long long *g_ws_dev_tiles[64] = {nullptr};  // per device: relaxation tiles processed since the last reset
 static std::mutex g_ws_dev_mutex;
 
@@ -1888,6 +1877,8 @@ struct WsWorkspace {
     int *uf_parent;
     uint8_t *uf_bad1, *uf_bad2;  // roots of components the first / second level cannot resolve
     uint8_t *uf_mask;
+    int *frames() const { return frame_list + 1; }  // the lists themselves: list[-1] = the list's length
+    int *tiles() const { return tile_list + 1; }
 };
 
 // ORDER MATTERS from dirtyA to tile_list: pcseg_watershed4_f32 clears everything that starts at zero -- both mark buffers,
@@ -1924,6 +1915,181 @@ static WsWorkspace ws_carve(Carver &cv, int B, int H, int W)
     return ws;
 }
 
+// what the parts of one call share
+struct WsCall {
+    int B, H, W, tilesX, tilesY;
+    hipStream_t s;
+    WsInputs in;
+    int poison;      // test-only: the PCSEG_WS_POISON_* stage of this call (ws_poison_kernel), 0 = none
+    bool verify;     // also run the explicit per-pixel proof check (implied by the component test)
+    int max_rounds;  // after which a tail kernel gives up
+    int64_t npx() const { return (int64_t)H * W; }
+    unsigned pixel_blocks() const { return (unsigned)((npx() + 255) / 256); }
+    dim3 check_grid() const { return dim3((W + 63) / 64, (H + 3) / 4, B); }
+    // the second level's active tiles (listed by ws_list_tiles_kernel)
+    WsTileList active_list(const WsWorkspace &ws) const { return WsTileList{ws.tiles(), ws.tiles() - 1, tilesX * tilesY, tilesX}; }
+};
+
+// (1) minimax levels: WS_GRID_ROUNDS grid rounds over the two alternating tilings (the benchmark batch needs 10; a round
+// without marks costs a few microseconds), then the per-frame tail kernel.  Frame flags and mark buffers start cleared;
+// the tail kernel may raise flags2 for a fixed point it had to abandon.
+static int ws_relax_levels(const WsCall &c, const WsWorkspace &ws)
+{
+    using RG = RelaxGeom;
+    static_assert(RG::LDS_BYTES <= 64 * 1024, "dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize");
+    const WsTiling tilings[2] = {{0, c.tilesX, c.tilesY}, {WS_T / 2, (c.W + WS_T / 2 + WS_T - 1) / WS_T, (c.H + WS_T / 2 + WS_T - 1) / WS_T}};
+    uint8_t *din = ws.dirtyA, *dout = ws.dirtyB;
+    for (int round = 0; round < WS_GRID_ROUNDS; ++round) {
+        const WsTiling &cur = tilings[round & 1], &nxt = tilings[(round + 1) & 1];
+        // (a round's marks go into the next round's list once that round walks a list)
+        const bool lists_next = round + 1 >= WS_LIST_FROM && round + 1 < WS_GRID_ROUNDS;
+        int *lout = lists_next ? ws.round_list[(round + 1) & 1] : nullptr, *cout = lists_next ? ws.round_count + round + 1 : nullptr;
+        if (round < WS_LIST_FROM)
+            PCSEG_LAUNCH(ws_relax_kernel, dim3(cur.nx, cur.ny, c.B), dim3(RG::THREADS), RG::LDS_BYTES, c.s, c.in, round == 0, ws.val, ws.L, din, dout,
+                         ws.changed, c.H, c.W, cur, nxt, round == 0 ? WS_ROUND0_SWEEPS : WS_ROUND_SWEEPS, lout, cout);
+        else
+            PCSEG_LAUNCH(ws_relax_list_kernel, dim3(WS_LIST_GRID), dim3(RG::THREADS), RG::LDS_BYTES, c.s, c.in, ws.val, ws.L, din, dout, ws.changed,
+                         c.H, c.W, cur, nxt, WS_ROUND_SWEEPS, (WsTileList{ws.round_list[round & 1], ws.round_count + round, cur.nx * cur.ny, cur.nx}),
+                         lout, cout);
+        PCSEG_CHECK_LAUNCH();
+        uint8_t *t = din; din = dout; dout = t;
+    }
+    PCSEG_LAUNCH(ws_relax_tail_kernel, dim3(c.B), dim3(RG::THREADS), RG::LDS_BYTES, c.s, c.in, ws.val, ws.L, din, dout, ws.changed, ws.changed + 6,
+                 ws.flags2, c.H, c.W, tilings[0], tilings[1], WS_GRID_ROUNDS, c.max_rounds);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+static int ws_poison_at(const WsCall &c, const WsWorkspace &ws, int stage, const int *flist, const uint8_t *act)
+{
+    if (c.poison != stage) return PCSEG_OK;
+    PCSEG_LAUNCH(ws_poison_kernel, dim3((c.B + 63) / 64), dim3(64), 0, c.s, flist, ws.uf_mask, act, ws.uf_parent, c.B, c.H, c.W, c.tilesX, c.tilesY,
+                 stage == PCSEG_WS_POISON_BORDER);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+// (2) label assignment = union-find over "minimum-key neighbour" links, on the levels (first level: every frame, flist and
+// act null) or on the refined keys (second level: the listed frames' active tiles).  A component holding two marker ids
+// flags its frame in out_flags, stays unlabelled and (first level) marks its tiles active for the next level.
+template <typename KeyT>
+static int ws_assign_labels(const WsCall &c, const WsWorkspace &ws, const KeyT *keys, const int *flist, const uint8_t *act, int *out_flags,
+                            bool first_level)
+{
+    const int H = c.H, W = c.W, span = ws_frame_span(flist, c.B);  // span: frame dimension of the grids (see ws_for_frames)
+    const int64_t border_px = (int64_t)((H - 1) / UF_TH) * W + (int64_t)((W - 1) / UF_TW) * H;
+    const WsTileList tiles = c.active_list(ws);
+    uint8_t *level_bad = first_level ? ws.uf_bad1 : ws.uf_bad2;  // cleared by the tile pass, tile by tile
+    if (flist)  // second level: the listed tiles only
+        PCSEG_LAUNCH((ws_uf_tile_kernel<KeyT, true>), dim3(WS_TILE_GRID), dim3(256), 0, c.s, tiles, keys, c.in.out, act, ws.uf_parent, ws.uf_mask,
+                     level_bad, H, W, c.tilesX, c.tilesY);
+    else
+        PCSEG_LAUNCH((ws_uf_tile_kernel<KeyT, false>), dim3((W + UF_TW - 1) / UF_TW, (H + UF_TH - 1) / UF_TH, span), dim3(256), 0, c.s, tiles, keys,
+                     c.in.out, act, ws.uf_parent, ws.uf_mask, level_bad, H, W, c.tilesX, c.tilesY);
+    PCSEG_CHECK_LAUNCH();
+    if (const int e = first_level ? ws_poison_at(c, ws, PCSEG_WS_POISON_BORDER, flist, act) : PCSEG_OK) return e;
+    if (border_px > 0) {
+        PCSEG_LAUNCH(ws_uf_border_kernel, dim3((unsigned)((border_px + 255) / 256), span), dim3(256), 0, c.s, flist, ws.uf_mask, act, ws.uf_parent, H,
+                     W, c.tilesX, c.tilesY, ws.flags2);
+        PCSEG_CHECK_LAUNCH();
+    }
+    if (const int e = ws_poison_at(c, ws, first_level ? PCSEG_WS_POISON_LABEL : PCSEG_WS_POISON_LEVEL2, flist, act)) return e;
+    if (first_level && act == nullptr && flist == nullptr && (W & 3) == 0 && (((uintptr_t)c.in.out | (uintptr_t)ws.uf_parent) & 15) == 0 &&
+        ((uintptr_t)ws.uf_mask & 3) == 0) {
+        PCSEG_LAUNCH(ws_uf_label4_kernel, dim3((unsigned)((c.npx() + 1024 * LABEL4_Q - 1) / (1024 * LABEL4_Q)), c.B), dim3(256), 0, c.s, ws.uf_parent,
+                     ws.uf_mask, c.in.out, ws.uf_bad1, out_flags, c.npx(), ws.flags2);
+        PCSEG_CHECK_LAUNCH();
+    } else if (first_level) {
+        PCSEG_LAUNCH(ws_uf_label_kernel<UF_OPTIMISTIC>, dim3(c.pixel_blocks(), span), dim3(256), 0, c.s, flist, ws.uf_parent, c.in.out, act,
+                     ws.uf_bad1, c.in.markers, c.in.mask, out_flags, nullptr, c.npx(), W, c.tilesX, c.tilesY, ws.flags2);
+        PCSEG_CHECK_LAUNCH();
+    } else {
+        PCSEG_LAUNCH(ws_uf_label_tiles_kernel<UF_DETECT>, dim3(WS_TILE_GRID), dim3(256), 0, c.s, tiles, ws.uf_parent, c.in.out, act, ws.uf_bad2,
+                     c.in.markers, c.in.mask, out_flags, H, W, c.tilesX, c.tilesY, ws.flags2);
+        PCSEG_CHECK_LAUNCH();
+        PCSEG_LAUNCH(ws_uf_label_tiles_kernel<UF_ASSIGN>, dim3(WS_TILE_GRID), dim3(256), 0, c.s, tiles, ws.uf_parent, c.in.out, act, ws.uf_bad2,
+                     c.in.markers, c.in.mask, out_flags, H, W, c.tilesX, c.tilesY, ws.flags2);
+        PCSEG_CHECK_LAUNCH();
+    }
+    return PCSEG_OK;
+}
+
+// (3) the second level, for the frames the first level flagged (ws.flags): refined keys (L, K2) for the components that
+// hold two marker ids and the same union-find on them; what that cannot resolve either is flagged in flags2.  Frames and
+// active tiles are listed on the device and every kernel here is a small grid walking one of the two lists.  K2's fixed
+// point: WS_K2_GRID_ROUNDS grid rounds, then the tail kernel (benchmark batch: 31 tiles in 7 frames; rounds of 127 / 60 /
+// 25 / 18 us -- the first is one winding lake's fixed point; with two grid rounds the tail walks the rest, 177 us against 43).
+static int ws_second_level(const WsCall &c, const WsWorkspace &ws)
+{
+    unsigned *K2 = ws.heap_idx;
+    unsigned long long *K64 = ws.heap_key;
+    const int *frame_list = ws.frames();
+    const WsTileList tiles = c.active_list(ws);
+    // which frames need the second level: list and length stay on the device
+    PCSEG_LAUNCH(ws_list_flagged_kernel, dim3(1), dim3(64), 0, c.s, ws.flags, c.B, ws.frames());
+    PCSEG_CHECK_LAUNCH();
+    const int span = ws_frame_span(frame_list, c.B);
+    const dim3 lgrid(c.pixel_blocks(), span);
+    // the components that hold two marker ids go back to their seeds; their tiles are the second level's work
+    // (uf_bad2 doubles as the per-pixel "in an unresolved component" mark until the second level's tile pass clears
+    // it; the verification build checks keys over whole frames and keeps every lake)
+    uint8_t *in_bad = c.verify ? nullptr : ws.uf_bad2;
+    PCSEG_LAUNCH(ws_uf_label_kernel<UF_REPAIR>, lgrid, dim3(256), 0, c.s, frame_list, ws.uf_parent, c.in.out, nullptr, ws.uf_bad1, c.in.markers,
+                 c.in.mask, ws.flags, ws.active_tiles, c.npx(), c.W, c.tilesX, c.tilesY, ws.flags2, in_bad, ws.dirtyA);
+    PCSEG_CHECK_LAUNCH();
+    // (the repair pass writes the active set -- still all zero since the call's first fill -- and the first round's
+    // marks itself: two copies and a fill between the kernels gone)
+    if (c.verify) {
+        // whole flagged frames, so that the explicit per-pixel check of the second level sees valid keys everywhere
+        PCSEG_LAUNCH(ws_activate_frames_kernel, lgrid, dim3(256), 0, c.s, frame_list, ws.flags, ws.active_tiles, ws.dirtyA, c.in.markers, c.in.mask,
+                     c.in.out, c.npx(), c.W, c.tilesX, c.tilesY);
+        PCSEG_CHECK_LAUNCH();
+    }
+    // the active tiles as a list: everything below walks it with small fixed grids
+    PCSEG_LAUNCH(ws_list_tiles_kernel, dim3(span), dim3(256), 0, c.s, frame_list, ws.active_tiles, c.tilesX * c.tilesY, ws.tiles());
+    PCSEG_CHECK_LAUNCH();
+    PCSEG_LAUNCH(ws_k2_init_kernel, dim3(WS_TILE_GRID), dim3(256), 0, c.s, tiles, ws.val, ws.L, c.in.markers, c.in.mask, K2, c.H, c.W);
+    PCSEG_CHECK_LAUNCH();
+    // marks of the first round = the active tiles (written by the repair pass); the other buffer is empty
+    uint8_t *din = ws.dirtyA, *dout = ws.dirtyB;
+    for (int round = 0; round < WS_K2_GRID_ROUNDS; ++round) {
+        PCSEG_LAUNCH(ws_k2_relax_kernel, dim3(WS_TILE_GRID), dim3(K2T), 0, c.s, tiles, ws.val, ws.L, K2, ws.active_tiles, din, dout, c.H, c.W,
+                     c.tilesX, c.tilesY, in_bad);
+        PCSEG_CHECK_LAUNCH();
+        uint8_t *t = din; din = dout; dout = t;
+    }
+    PCSEG_LAUNCH(ws_k2_relax_tail_kernel, dim3(c.B), dim3(K2T), 0, c.s, frame_list, ws.val, ws.L, K2, ws.active_tiles, din, dout, ws.changed + 6,
+                 ws.flags2, c.H, c.W, c.tilesX, c.tilesY, c.max_rounds, in_bad);
+    PCSEG_CHECK_LAUNCH();
+    PCSEG_LAUNCH(ws_pack_kernel, dim3(WS_TILE_GRID), dim3(256), 0, c.s, tiles, ws.L, K2, ws.active_tiles, K64, c.H, c.W, c.tilesX, c.tilesY);
+    PCSEG_CHECK_LAUNCH();
+    if (const int e = ws_assign_labels(c, ws, K64, frame_list, ws.active_tiles, ws.flags2, false)) return e;
+    if (c.verify) {
+        PCSEG_LAUNCH(ws_check_kernel<unsigned long long>, c.check_grid(), dim3(256), 0, c.s, K64, c.in.out, c.in.markers, c.in.mask, ws.flags,
+                     ws.flags2, c.H, c.W);
+        PCSEG_CHECK_LAUNCH();
+    }
+    return PCSEG_OK;
+}
+
+// (4) the frames flagged in flags2 again, by the exact emulation of the reference's heap: one wave per frame
+static int ws_exact_pass(const WsCall &c, const WsWorkspace &ws)
+{
+    PCSEG_LAUNCH(ws_exact_init_kernel, dim3((unsigned)std::min<int64_t>((c.npx() + 1023) / 1024, 64), c.B), dim3(256), 0, c.s, c.in.markers,
+                 c.in.mask, c.in.out, ws.flags2, c.npx());
+    PCSEG_CHECK_LAUNCH();
+    int ncu = 256, dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    if (c.B <= ncu)
+        PCSEG_LAUNCH((ws_exact_kernel<EX_LDS_BIG, EX_D_BIG>), dim3(c.B), dim3(64), 0, c.s, ws.val, c.in.markers, c.in.mask, c.in.out, ws.flags2,
+                     ws.heap_key, ws.heap_idx, c.H, c.W);
+    else
+        PCSEG_LAUNCH((ws_exact_kernel<EX_LDS_SMALL, EX_D_SMALL>), dim3(c.B), dim3(64), 0, c.s, ws.val, c.in.markers, c.in.mask, c.in.out, ws.flags2,
+                     ws.heap_key, ws.heap_idx, c.H, c.W);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
 extern "C" {
 
 void pcseg_watershed_counters(int64_t *out, int reset)
@@ -1933,14 +2099,17 @@ void pcseg_watershed_counters(int64_t *out, int reset)
         unsigned long long tiles = 0;
         if (dev) (void)hipMemcpy(&tiles, dev, sizeof(tiles), hipMemcpyDeviceToHost);  // blocking: waits for the work queued so far
         out[0] = (int64_t)tiles;
-        for (int i = 1; i < 4; ++i) out[i] = g_ws_counters[i].load();
+        out[1] = g_ws_relax_launches.load();
+        out[2] = g_ws_calls.load();
+        out[3] = 0;
     }
     if (reset) {
         if (dev) {
             (void)hipDeviceSynchronize();
             (void)hipMemset(dev, 0, sizeof(unsigned long long));
         }
-        for (int i = 0; i < 4; ++i) g_ws_counters[i].store(0);
+        g_ws_relax_launches.store(0);
+        g_ws_calls.store(0);
     }
 }
 
@@ -1952,10 +2121,8 @@ size_t pcseg_watershed_workspace_bytes(int B, int H, int W)
     return cv.off;
 }
 
-// grid rounds enqueued before the per-frame tail kernels take over (see ws_relax_tail_kernel): the benchmark batch needs
-// 10 relaxation rounds; a round without marks costs a few microseconds.  The second level sees a few dozen tiles of a
-// few frames (benchmark batch: 31 tiles in 7 frames; rounds of 127 / 60 / 25 / 18 us -- the first is one winding lake's
-// fixed point); with two grid rounds the per-frame tail kernel walks the rest one tile at a time (177 us against 43)
+// No host round trip anywhere: the fixed points run a fixed number of grid rounds and finish in a per-frame tail kernel,
+// and the frames and tiles that need the second level are listed (and counted) on the device, where its kernels walk them.
 int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *markers, const uint8_t *mask, int32_t *out,
                          int32_t *tie_flags, int B, int H, int W, int mode, void *workspace, size_t workspace_bytes,
                          pcseg_stream_t stream)
@@ -1964,221 +2131,52 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
     PCSEG_REQUIRE(img && markers && mask && out && workspace && check_shape(B, H, W) && mode >= 0 && (mode & 3) <= 2 && mode < 64 &&
                       (poison & (poison - 1)) == 0 && !(poison && (mode & 3) == 1),
                   "bad arguments");
-    const bool verify = (mode & 4) != 0;  // also run the explicit per-pixel proof check (implied by the component test)
+    const bool verify = (mode & 4) != 0;
     mode &= 3;
     PCSEG_REQUIRE(frame_stride == 0 || frame_stride >= (int64_t)H * W, "frame_stride smaller than a frame");
     if (frame_stride == 0) frame_stride = (int64_t)H * W;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n = (size_t)B * H * W;
-    const int tilesX = (W + WS_T - 1) / WS_T, tilesY = (H + WS_T - 1) / WS_T;
-    const size_t ntiles_max = (size_t)B * (tilesX + 1) * (tilesY + 1);  // the half-tile-shifted tiling has one more per axis
     Carver cv(workspace, workspace_bytes);
     const WsWorkspace ws = ws_carve(cv, B, H, W);
-    unsigned *val = ws.val, *L = ws.L;
-    uint8_t *dirtyA = ws.dirtyA, *dirtyB = ws.dirtyB, *active_tiles = ws.active_tiles;
-    int *changed = ws.changed, *flags = ws.flags, *flags2 = ws.flags2;
-    int *frame_list = ws.frame_list + 1, *tile_list = ws.tile_list + 1;  // list[-1] = the list's length
-    int *round_count = ws.round_count;
-    int *const *round_list = ws.round_list;
-    unsigned long long *heap_key = ws.heap_key;
-    unsigned *heap_idx = ws.heap_idx;
-    int *uf_parent = ws.uf_parent;
-    uint8_t *uf_bad1 = ws.uf_bad1, *uf_bad2 = ws.uf_bad2, *uf_mask = ws.uf_mask;
     if (!cv.ok()) {
         set_error("watershed: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
-    const dim3 pgrid((W + 63) / 64, (H + 3) / 4, B);
-    // No host round trip anywhere below: fixed points run a fixed number of grid rounds and finish in a per-frame tail
-    // kernel, the frames that need the second level are listed (and counted) on the device and the second-level
-    // kernels cover the worst-case grid, from which the blocks of unlisted frames leave at once.
-    const int max_rounds = (tilesX * tilesY + 64) * 64;
+    const bool vec = (W & 3) == 0 && W >= 4 && (frame_stride & 3) == 0 && (((uintptr_t)img | (uintptr_t)markers | (uintptr_t)out |
+                                                                             (uintptr_t)ws.val | (uintptr_t)ws.L) & 15) == 0 &&
+                     ((uintptr_t)mask & 3) == 0;
+    const int tilesX = (W + WS_T - 1) / WS_T, tilesY = (H + WS_T - 1) / WS_T;
+    const WsCall c{B, H, W, tilesX, tilesY, (hipStream_t)stream, {img, frame_stride, markers, mask, out, vec}, poison, verify,
+                   (tilesX * tilesY + 64) * 64};
     // ONE fill for everything that starts at zero: the two mark buffers (round 0 visits every tile regardless), the active-tile
-    // set, the counters and both frame-flag arrays are carved next to each other (five separate fills were five launches)
-    // (... and, behind the frame list, the number of listed tiles)
-    PCSEG_CHECK_HIP(hipMemsetAsync(dirtyA, 0, (size_t)((char *)tile_list - (char *)dirtyA), s));
-    long long relax_launches = 0;
+    // set, the counters, both frame-flag arrays, the frame list, the round counts and the number of listed tiles (see ws_carve)
+    PCSEG_CHECK_HIP(hipMemsetAsync(ws.dirtyA, 0, (size_t)((char *)ws.tiles() - (char *)ws.dirtyA), c.s));
     if (mode == 1) {
-        PCSEG_LAUNCH(ws_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, frame_stride, markers, mask, val, L,
-                     out, (int64_t)H * W, (int64_t)n);
+        const int64_t n = B * c.npx();
+        PCSEG_LAUNCH(ws_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.s, img, frame_stride, markers, mask, ws.val, ws.L, out,
+                     c.npx(), n);
         PCSEG_CHECK_LAUNCH();
-        PCSEG_LAUNCH(ws_set_flags_kernel, dim3((B + 63) / 64), dim3(64), 0, s, flags2, B, 1);
+        PCSEG_LAUNCH(ws_set_flags_kernel, dim3((B + 63) / 64), dim3(64), 0, c.s, ws.flags2, B, 1);
         PCSEG_CHECK_LAUNCH();
     } else {
-        const bool vec = (W & 3) == 0 && W >= 4 && (frame_stride & 3) == 0 && (((uintptr_t)img | (uintptr_t)markers | (uintptr_t)out |
-                                                                                 (uintptr_t)val | (uintptr_t)L) & 15) == 0 &&
-                         ((uintptr_t)mask & 3) == 0;
-        const WsInputs inputs{img, frame_stride, markers, mask, out, vec};
-        // minimax relaxation over alternating tilings
-        constexpr int RT = WS_T;  // edge of a relaxation tile
-        using RG = RelaxGeom<RT>;
-        const WsTiling tilings[2] = {{0, (W + RT - 1) / RT, (H + RT - 1) / RT},
-                                     {RT / 2, (W + RT / 2 + RT - 1) / RT, (H + RT / 2 + RT - 1) / RT}};
-        static_assert(RG::LDS_BYTES <= 64 * 1024, "dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize");
-        // (frame flags and mark buffers: cleared by the one fill above -- the tail kernels may raise flags2 for a fixed point
-        // they had to abandon)
-        {
-            uint8_t *din = dirtyA, *dout = dirtyB;
-            for (int round = 0; round < WS_GRID_ROUNDS; ++round) {
-                const WsTiling &cur = tilings[round & 1], &nxt = tilings[(round + 1) & 1];
-                // (a round's marks go into the next round's list once that round walks a list)
-                const bool lists_next = round + 1 >= WS_LIST_FROM && round + 1 < WS_GRID_ROUNDS;
-                int *lout = lists_next ? round_list[(round + 1) & 1] : nullptr, *cout = lists_next ? round_count + round + 1 : nullptr;
-                if (round < WS_LIST_FROM)
-                    PCSEG_LAUNCH(ws_relax_kernel<RT>, dim3(cur.nx, cur.ny, B), dim3(RG::THREADS), RG::LDS_BYTES, s, inputs, round == 0, val,
-                                 L, din, dout, changed, H, W, cur, nxt, round == 0 ? WS_ROUND0_SWEEPS : WS_ROUND_SWEEPS, lout, cout);
-                else
-                    PCSEG_LAUNCH(ws_relax_list_kernel<RT>, dim3(WS_LIST_GRID), dim3(RG::THREADS), RG::LDS_BYTES, s, inputs,
-                                 val, L, din, dout, changed, H, W, cur, nxt, WS_ROUND_SWEEPS, (const int *)round_list[round & 1],
-                                 (const int *)(round_count + round), lout, cout);
-                PCSEG_CHECK_LAUNCH();
-                ++relax_launches;
-                uint8_t *t = din; din = dout; dout = t;
-            }
-            PCSEG_LAUNCH(ws_relax_tail_kernel<RT>, dim3(B), dim3(RG::THREADS), RG::LDS_BYTES, s, inputs, val, L, din, dout, changed,
-                         changed + 6, flags2, H, W, tilings[0], tilings[1], WS_GRID_ROUNDS, max_rounds);
-            PCSEG_CHECK_LAUNCH();
-        }
-        const dim3 ugrid_full((W + UF_TW - 1) / UF_TW, (H + UF_TH - 1) / UF_TH, B);
-        const dim3 lgrid_full((unsigned)(((size_t)H * W + 255) / 256), B);
-        const int64_t npx = (int64_t)H * W;
-        const int64_t border_px = (int64_t)((H - 1) / UF_TH) * W + (int64_t)((W - 1) / UF_TW) * H;
-        const dim3 bgrid_full((unsigned)((border_px + 255) / 256), B);
-        // label assignment = union-find over "minimum-key neighbour" links.  A component holding two marker ids flags
-        // its frame, stays unlabelled and (first level) marks its tiles active for the next level.
-        const WsTileList tiles{tile_list, tilesX * tilesY, tilesX};
-        auto poison_at = [&](int stage, const int *flist, const uint8_t *act) -> int {
-            if (poison != stage) return PCSEG_OK;
-            PCSEG_LAUNCH(ws_poison_kernel, dim3((B + 63) / 64), dim3(64), 0, s, flist, (const uint8_t *)uf_mask, act, uf_parent, B, H, W,
-                         tilesX, tilesY, stage == PCSEG_WS_POISON_BORDER);
-            PCSEG_CHECK_LAUNCH();
-            return PCSEG_OK;
-        };
-        auto assign_labels = [&](auto *keys, const int *flist, const uint8_t *act, int *out_flags, bool first_level) -> int {
-            using KeyT = std::remove_const_t<std::remove_pointer_t<decltype(keys)>>;
-            const int span = ws_frame_span(flist, B);  // frame dimension of the grids (see ws_for_frames)
-            const dim3 ugrid(ugrid_full.x, ugrid_full.y, span), bgrid(bgrid_full.x, span), lgrid(lgrid_full.x, span);
-            uint8_t *level_bad = first_level ? uf_bad1 : uf_bad2;  // cleared by the tile pass, tile by tile
-            if (flist)  // second level: the listed tiles only
-                PCSEG_LAUNCH((ws_uf_tile_kernel<KeyT, true>), dim3(WS_TILE_GRID), dim3(256), 0, s, tiles, (const KeyT *)keys, (const int *)out, act,
-                             uf_parent, uf_mask, level_bad, H, W, tilesX, tilesY);
-            else
-                PCSEG_LAUNCH((ws_uf_tile_kernel<KeyT, false>), ugrid, dim3(256), 0, s, tiles, (const KeyT *)keys, (const int *)out, act,
-                             uf_parent, uf_mask, level_bad, H, W, tilesX, tilesY);
-            PCSEG_CHECK_LAUNCH();
-            if (const int e = first_level ? poison_at(PCSEG_WS_POISON_BORDER, flist, act) : PCSEG_OK) return e;
-            if (border_px > 0) {
-                PCSEG_LAUNCH(ws_uf_border_kernel, bgrid, dim3(256), 0, s, flist, (const uint8_t *)uf_mask, act, uf_parent, H, W,
-                             tilesX, tilesY, flags2);
-                PCSEG_CHECK_LAUNCH();
-            }
-            if (const int e = poison_at(first_level ? PCSEG_WS_POISON_LABEL : PCSEG_WS_POISON_LEVEL2, flist, act)) return e;
-            if (first_level && act == nullptr && flist == nullptr && (W & 3) == 0 && (((uintptr_t)out | (uintptr_t)uf_parent) & 15) == 0 &&
-                ((uintptr_t)uf_mask & 3) == 0) {
-                PCSEG_LAUNCH(ws_uf_label4_kernel, dim3((unsigned)((npx + 1024 * LABEL4_Q - 1) / (1024 * LABEL4_Q)), B), dim3(256), 0, s,
-                             (const int *)uf_parent, (const uint8_t *)uf_mask, out, uf_bad1, out_flags, npx, flags2);
-                PCSEG_CHECK_LAUNCH();
-            } else if (first_level) {
-                PCSEG_LAUNCH(ws_uf_label_kernel<UF_OPTIMISTIC>, lgrid, dim3(256), 0, s, flist, (const int *)uf_parent, out, act,
-                             uf_bad1, markers, mask, out_flags, (uint8_t *)nullptr, npx, W, tilesX, tilesY, flags2);
-                PCSEG_CHECK_LAUNCH();
-            } else {
-                PCSEG_LAUNCH(ws_uf_label_tiles_kernel<UF_DETECT>, dim3(WS_TILE_GRID), dim3(256), 0, s, tiles, (const int *)uf_parent, out, act,
-                             uf_bad2, markers, mask, out_flags, H, W, tilesX, tilesY, flags2);
-                PCSEG_CHECK_LAUNCH();
-                PCSEG_LAUNCH(ws_uf_label_tiles_kernel<UF_ASSIGN>, dim3(WS_TILE_GRID), dim3(256), 0, s, tiles, (const int *)uf_parent, out, act,
-                             uf_bad2, markers, mask, out_flags, H, W, tilesX, tilesY, flags2);
-                PCSEG_CHECK_LAUNCH();
-            }
-            return PCSEG_OK;
-        };
+        if (const int e = ws_relax_levels(c, ws)) return e;
         // both mark buffers start the second level empty (a fixed point leaves them empty; one that was abandoned may not):
-        // they are carved next to each other -- one fill
-        PCSEG_CHECK_HIP(hipMemsetAsync(dirtyA, 0, (size_t)((char *)dirtyB - (char *)dirtyA) + ntiles_max, s));
-        int rc = assign_labels((const unsigned *)L, (const int *)nullptr, (const uint8_t *)nullptr, flags, true);
-        if (rc) return rc;
+        // they are carved next to each other -- one fill (the half-tile-shifted tiling has one more tile per axis)
+        PCSEG_CHECK_HIP(hipMemsetAsync(ws.dirtyA, 0, (size_t)((char *)ws.dirtyB - (char *)ws.dirtyA) + (size_t)B * (tilesX + 1) * (tilesY + 1), c.s));
+        if (const int e = ws_assign_labels(c, ws, ws.L, nullptr, nullptr, ws.flags, true)) return e;
         if (verify) {
-            PCSEG_LAUNCH(ws_check_kernel<unsigned>, pgrid, dim3(256), 0, s, (const unsigned *)L, (const int *)out, markers, mask,
-                         (const int *)nullptr, flags, H, W);
+            PCSEG_LAUNCH(ws_check_kernel<unsigned>, c.check_grid(), dim3(256), 0, c.s, ws.L, out, markers, mask, nullptr, ws.flags, H, W);
             PCSEG_CHECK_LAUNCH();
         }
-        // which frames need the second level: list and length stay on the device
-        PCSEG_LAUNCH(ws_list_flagged_kernel, dim3(1), dim3(64), 0, s, (const int *)flags, B, frame_list);
-        PCSEG_CHECK_LAUNCH();
-        {
-            unsigned *K2 = heap_idx;
-            unsigned long long *K64 = heap_key;
-            const int span = ws_frame_span(frame_list, B);
-            const dim3 tgrid(tilesX, tilesY, span), lgrid(lgrid_full.x, span), pgrid2(pgrid.x, pgrid.y, span);
-            // the components that hold two marker ids go back to their seeds; their tiles are the second level's work
-            // (uf_bad2 doubles as the per-pixel "in an unresolved component" mark until the second level's tile pass clears
-            // it; the verification build checks keys over whole frames and keeps every lake)
-            uint8_t *in_bad = verify ? nullptr : uf_bad2;
-            PCSEG_LAUNCH(ws_uf_label_kernel<UF_REPAIR>, lgrid, dim3(256), 0, s, (const int *)frame_list, (const int *)uf_parent, out,
-                         (const uint8_t *)nullptr, uf_bad1, markers, mask, flags, active_tiles, npx, W, tilesX, tilesY, flags2, in_bad,
-                         dirtyA);
-            PCSEG_CHECK_LAUNCH();
-            // (the repair pass writes the active set -- still all zero since the call's first fill -- and the first round's
-            // marks itself: two copies and a fill between the kernels gone)
-            if (verify) {
-                // whole flagged frames, so that the explicit per-pixel check of the second level sees valid keys everywhere
-                PCSEG_LAUNCH(ws_activate_frames_kernel, lgrid, dim3(256), 0, s, (const int *)frame_list, (const int *)flags, active_tiles,
-                             dirtyA, markers, mask, out, npx, W, tilesX, tilesY);
-                PCSEG_CHECK_LAUNCH();
-            }
-            // the active tiles as a list: everything below walks it with small fixed grids (see WsTileList)
-            PCSEG_LAUNCH(ws_list_tiles_kernel, dim3(span), dim3(256), 0, s, (const int *)frame_list, (const uint8_t *)active_tiles,
-                         tilesX * tilesY, tile_list);
-            PCSEG_CHECK_LAUNCH();
-            PCSEG_LAUNCH(ws_k2_init_kernel, dim3(WS_TILE_GRID), dim3(256), 0, s, tiles, (const unsigned *)val, (const unsigned *)L, markers, mask,
-                         K2, H, W);
-            PCSEG_CHECK_LAUNCH();
-            // marks of the first round = the active tiles (written by the repair pass); the other buffer is empty
-            uint8_t *din = dirtyA, *dout = dirtyB;
-            for (int round = 0; round < WS_K2_GRID_ROUNDS; ++round) {
-                PCSEG_LAUNCH(ws_k2_relax_kernel, dim3(WS_TILE_GRID), dim3(K2T), 0, s, tiles, (const unsigned *)val,
-                             (const unsigned *)L, K2, (const uint8_t *)active_tiles, din, dout, H, W, tilesX, tilesY,
-                             (const uint8_t *)in_bad);
-                PCSEG_CHECK_LAUNCH();
-                uint8_t *t = din; din = dout; dout = t;
-            }
-            PCSEG_LAUNCH(ws_k2_relax_tail_kernel, dim3(B), dim3(K2T), 0, s, (const int *)frame_list, (const unsigned *)val,
-                         (const unsigned *)L, K2, (const uint8_t *)active_tiles, din, dout, changed + 6, flags2, H, W, tilesX, tilesY,
-                         max_rounds, (const uint8_t *)in_bad);
-            PCSEG_CHECK_LAUNCH();
-            PCSEG_LAUNCH(ws_pack_kernel, dim3(WS_TILE_GRID), dim3(256), 0, s, tiles, (const unsigned *)L, (const unsigned *)K2,
-                         (const uint8_t *)active_tiles, K64, H, W, tilesX, tilesY);
-            PCSEG_CHECK_LAUNCH();
-            rc = assign_labels((const unsigned long long *)K64, (const int *)frame_list, (const uint8_t *)active_tiles, flags2, false);
-            if (rc) return rc;
-            if (verify) {
-                PCSEG_LAUNCH(ws_check_kernel<unsigned long long>, pgrid, dim3(256), 0, s, (const unsigned long long *)K64,
-                             (const int *)out, markers, mask, (const int *)flags, flags2, H, W);
-                PCSEG_CHECK_LAUNCH();
-            }
-        }
+        if (const int e = ws_second_level(c, ws)) return e;
     }
-    if (tie_flags) PCSEG_CHECK_HIP(hipMemcpyAsync(tie_flags, flags2, sizeof(int) * B, hipMemcpyDeviceToDevice, s));
-    if (mode != 2) {
-        const int64_t npx = (int64_t)H * W;
-        PCSEG_LAUNCH(ws_exact_init_kernel, dim3((unsigned)std::min<int64_t>((npx + 1023) / 1024, 64), B), dim3(256), 0, s, markers, mask,
-                     out, (const int *)flags2, npx);
-        PCSEG_CHECK_LAUNCH();
-        int ncu = 256;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        if (B <= ncu)
-            PCSEG_LAUNCH((ws_exact_kernel<EX_LDS_BIG, EX_D_BIG>), dim3(B), dim3(64), 0, s, val, markers, mask, out, flags2, heap_key, heap_idx, H, W);
-        else
-            PCSEG_LAUNCH((ws_exact_kernel<EX_LDS_SMALL, EX_D_SMALL>), dim3(B), dim3(64), 0, s, val, markers, mask, out, flags2, heap_key, heap_idx, H, W);
-        PCSEG_CHECK_LAUNCH();
-    }
+    if (tie_flags) PCSEG_CHECK_HIP(hipMemcpyAsync(tie_flags, ws.flags2, sizeof(int) * B, hipMemcpyDeviceToDevice, c.s));
+    if (const int e = mode != 2 ? ws_exact_pass(c, ws) : PCSEG_OK) return e;
     if (unsigned long long *dev_tiles = ws_dev_tiles()) {
-        PCSEG_LAUNCH(ws_accumulate_kernel, dim3(1), dim3(64), 0, s, (const int *)changed, dev_tiles);
+        PCSEG_LAUNCH(ws_accumulate_kernel, dim3(1), dim3(64), 0, c.s, ws.changed, dev_tiles);
         PCSEG_CHECK_LAUNCH();
     }
-    g_ws_counters[1] += relax_launches;
-    g_ws_counters[2] += 1;
+    if (mode != 1) g_ws_relax_launches += WS_GRID_ROUNDS;
+    g_ws_calls += 1;
     return PCSEG_OK;
 }
 
