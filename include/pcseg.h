@@ -552,6 +552,47 @@ int pcseg_region_hull(const int32_t *labels, const int32_t *counts, const int64_
 int pcseg_hull_properties(const int64_t *stats, const int64_t *hull, const int32_t *counts, double *out, int B, int cap,
                           pcseg_stream_t stream);
 
+/* ---- nearest-label transform, territories and adjacency (csrc/voronoi.hip): how much of the frame a ROI has to itself and
+ * which ROIs are its neighbours.  All values are exact integers.
+ * A SITE is a pixel whose label l lies in 1 .. cap and, with sel (device uint8 (B, cap), may be NULL), has sel[b, l - 1] != 0; a
+ * label outside 1 .. cap is never a site and never an index.
+ * pcseg_nearest_label_i32: labels device int32 (B, H, W), any width and alignment.  For every pixel p
+ *   d2   (device int32 (B, H, W)) = min over the frame's sites q of (pr - qr)^2 + (pc - qc)^2 (0 on a site),
+ *   near (device int32 (B, H, W)) = the SMALLEST label among the sites at that minimum (a site: its own label),
+ *   site (device int32 (B, H, W), may be NULL) = the raster index of the nearest site of label near, the smallest index among equals
+ *   (scipy.ndimage.distance_transform_edt(labels == 0, return_indices=True) with the ties decided).
+ * A frame without site: d2 = -1, near = 0, site = -1 everywhere (scipy's virtual pixel is not reproduced).  Shapes as
+ * pcseg_edt_sq_u8 (check_shape), B <= 65535.
+ * A pixel BELONGS to label near iff d2 >= 0 and d2 <= R2 (R2 < 0: unbounded).
+ * pcseg_territory_labels: out[i] = near[i] where the pixel belongs to it, else 0, over n pixels (skimage.segmentation.expand_labels).
+ * pcseg_territory_reduce: mask device uint8 (B, H, W), may be NULL; out device int64 (B, cap, 4), row l - 1 over the pixels that
+ * belong to l (near outside 1 .. cap is ignored): 0 territory_px, 1 territory_on_px (those with mask != 0), 2 reach2_max (the
+ * largest d2 among them), 3 clipped (1 if one of them lies on the frame's outer row or column).  Every row is written (zeros for
+ * a label that owns nothing).  cap < 2^30.
+ * pcseg_territory_pairs: a LINK is an unordered pair of 4-neighbour pixels that both belong to a label, to different ones; each
+ * is counted once (right and down neighbour).  Per frame an open-addressing table of pair_cap slots keyed by (a, b), a < b,
+ * holds border (links between a and b) and contact (those with d2 = 0 at both ends: the labels touch in the label image).
+ * overflow[b] (device int32 (B)) = 1 where a frame has more pairs than pair_cap: links are dropped then, nothing is written
+ * outside the table and no thread waits.  offsets (device int64 (B + 1)): first row of every frame among the compacted rows;
+ * totals (device int64 (2)) = {rows, frames with overflow}: the one host read between the two calls.
+ * pcseg_territory_pairs_write (same workspace, untouched in between): key (device int64 (rows)) = a << 32 | b, frame (device
+ * int32 (rows)) = b's position in the batch, counts (device int32 (rows, 2)) = border, contact; rows of a frame in table order
+ * (sort by key for (a, b) order).  With degree (device int32 (B, cap, 2 n_types), ZEROED by the caller) and slot_of (device
+ * uint8 (B, cap), a value >= n_types: no type): degree[b, a - 1, slot_of[b]] += 1 for every pair (both directions), and at
+ * n_types + slot for every pair with contact > 0.  Asynchronous, nothing is allocated. */
+size_t pcseg_nearest_label_workspace_bytes(int B, int H, int W);
+int pcseg_nearest_label_i32(const int32_t *labels, const uint8_t *sel, int cap, int32_t *d2, int32_t *near, int32_t *site, int B,
+                            int H, int W, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_territory_labels(const int32_t *near, const int32_t *d2, int64_t R2, int32_t *out, int64_t n, pcseg_stream_t stream);
+int pcseg_territory_reduce(const int32_t *near, const int32_t *d2, const uint8_t *mask, int64_t R2, int cap, int64_t *out, int B,
+                           int H, int W, pcseg_stream_t stream);
+size_t pcseg_territory_pairs_workspace_bytes(int B, int pair_cap);
+int pcseg_territory_pairs(const int32_t *near, const int32_t *d2, int64_t R2, int pair_cap, int32_t *overflow, int64_t *offsets,
+                          int64_t *totals, int B, int H, int W, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_territory_pairs_write(int pair_cap, const int64_t *offsets, const uint8_t *slot_of, int cap, int n_types, int64_t *key,
+                                int32_t *frame, int32_t *counts, int32_t *degree, int B, const void *workspace,
+                                size_t workspace_bytes, pcseg_stream_t stream);
+
 /* ---- X1 (north_star extension; refine_boundaries.py:22 imports skimage.filters and never calls it): the library
  * SURVEY.md 8a names is the oracle -- skimage.filters.threshold_otsu(float32 image, nbins=256), pinned by
  * tests/golden/extensions.npz.  pcseg_otsu_f32: threshold[b] (device float64 (B,), the value is the float32 bin

@@ -1,0 +1,678 @@
+// Nearest-label transform (the exact Euclidean feature transform of a label image) and what follows from it per ROI:
+// territories (discrete Voronoi cells, optionally limited to a reach) and the adjacency graph of the territories
+// (scipy.ndimage.distance_transform_edt(return_indices=True), skimage.segmentation.expand_labels; include/pcseg.h).
+//
+// Integers only, so nothing depends on the order of the atomics.  Launches (asynchronous, no host read):
+//   vor_bits_kernel      site bits of the label image, 32 rows of a column per word (a site: a label in 1 .. cap that `sel` keeps)
+//   vor_carry_kernel     per column and word: distance from the word's first / last row to the nearest site above / below it
+//   vor_row_kernel       a row block's vertical distances staged in LDS as (g, site above, site below); per pixel an expanding
+//                        search over the column offsets k = 0, 1, .. that stops only when k * k > best, so that EQUALLY near
+//                        sites are all seen: (d2, label, raster index) is minimised lexicographically, and a column's upper AND
+//                        lower site are both taken when they are equally far.  The label image is read only for candidates
+//                        with d2 <= best
+//   terr_reduce_kernel   the column-run walk of label_reduce.h over key = (nearest label within reach, on the mask): pixels, pixels
+//                        on the mask and the frame-border flag of a vertical run in closed form, the largest d2 of a run tracked
+//                        beside the walk; LDS slot table, eight-lanes-per-row flush
+//   terr_pairs_kernel    the 4-neighbour links between territories (right and down neighbour), equal links of a column run and of
+//                        neighbouring lanes added up first, then into a per-frame open-addressing table keyed by (a, b) (64-bit
+//                        compare-and-swap, bounded probing, integer atomics); a full table raises the frame's flag
+//   terr_pairs_count / scan / write   the used slots per frame, their offsets and totals, the compacted rows (and the number of
+//                        distinct partners per ROI and type slot)
+#include <type_traits>
+
+#include "label_reduce.h"
+
+// (no floating point in here; the pragma keeps any that is added later rounded operation by operation, as surface.hip)
+#pragma clang fp contract(off)
+
+namespace pcseg {
+
+constexpr int VOR_CH = 32;               // rows per bit word
+constexpr unsigned VOR_NONE = 0xFFFFu;   // carry: no site that way in this column
+// staged vertical distance of a column without site: its square is >= 2^31 > any d2 of a frame (check_shape: H, W <= 32768
+// and H W < 2^30 give d2 < 2^31), and adding k * k (k <= 32767 + 3) still fits 32 bits
+constexpr unsigned VOR_G_NONE = 46341u;
+constexpr unsigned VOR_UP = 1u << 16, VOR_DN = 1u << 17;  // the staged cell: g | VOR_UP (a site g rows up) | VOR_DN (g rows down)
+constexpr unsigned VOR_BEST0 = 0x7FFFFFFFu;
+
+struct SiteTest {
+    const uint8_t *sel;  // the frame's row of the selection, or null
+    int cap;
+    __device__ __forceinline__ bool operator()(int l) const { return l >= 1 && l <= cap && (!sel || sel[l - 1] != 0); }
+};
+
+// one thread per (word, column): site bits of 32 rows (rows past the frame's end re-read its last row and are masked out)
+__global__ void __launch_bounds__(256) vor_bits_kernel(const int *__restrict__ labels, const uint8_t *__restrict__ sel, int cap,
+                                                        unsigned *__restrict__ bits, int H, int W, int nch)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int ch = blockIdx.y, b = blockIdx.z;
+    if (c >= W) return;
+    const int *lab = labels + (int64_t)b * H * W + c;
+    const SiteTest site{sel ? sel + (int64_t)b * cap : nullptr, cap};
+    const int r0 = ch * VOR_CH;
+    int v[VOR_CH];
+#pragma unroll
+    for (int j = 0; j < VOR_CH; ++j) v[j] = lab[rowoff(min(r0 + j, H - 1), W)];
+    unsigned word = 0;
+#pragma unroll
+    for (int j = 0; j < VOR_CH; ++j)
+        if (site(v[j])) word |= 1u << j;
+    const int rows = min(VOR_CH, H - r0);
+    if (rows < 32) word &= (1u << rows) - 1u;
+    bits[((int64_t)b * nch + ch) * W + c] = word;
+}
+
+// per column: up[ch] = distance from the first row of word ch to the nearest site in the words above it, dn[ch] = from its
+// last row to the nearest site in the words below it; VOR_NONE if none.  any_site[b] = 1 if the frame has a site at all
+__global__ void __launch_bounds__(256) vor_carry_kernel(const unsigned *__restrict__ bits, uint16_t *__restrict__ up,
+                                                         uint16_t *__restrict__ dn, int *__restrict__ any_site, int H, int W, int nch)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    const int64_t base = (int64_t)b * nch * W + c;
+    bool has = false;
+    unsigned d = VOR_NONE;
+    for (int ch = 0; c < W && ch < nch; ++ch) {
+        const unsigned w = bits[base + rowoff(ch, W)];
+        up[base + rowoff(ch, W)] = (uint16_t)d;
+        const int rows = min(VOR_CH, H - ch * VOR_CH);
+        if (w) { d = rows - (31 - __clz(w)); has = true; }
+        else d = d == VOR_NONE ? VOR_NONE : d + rows;
+    }
+    if (__syncthreads_or(has) && threadIdx.x == 0) any_site[b] = 1;
+    d = VOR_NONE;
+    for (int ch = nch - 1; c < W && ch >= 0; --ch) {
+        const unsigned w = bits[base + rowoff(ch, W)];
+        dn[base + rowoff(ch, W)] = (uint16_t)d;
+        const int rows = min(VOR_CH, H - ch * VOR_CH);
+        if (w) d = __ffs(w);  // from the last row of the word above to the first site of this one
+        else d = d == VOR_NONE ? VOR_NONE : d + rows;
+    }
+}
+
+// the staged cell of row j (0 .. 31) of a word: distance to the nearest site of the column and on which side(s) it lies
+__device__ __forceinline__ unsigned site_cell(unsigned word, int j, unsigned up, unsigned dn, int rows)
+{
+    const unsigned le_mask = j == 31 ? 0xFFFFFFFFu : ((2u << j) - 1u);
+    const unsigned le = word & le_mask, gt = word & ~le_mask;  // sites in rows <= j (the pixel's own among them), in rows > j
+    const unsigned du = le ? (unsigned)(j - (31 - __clz(le))) : (up == VOR_NONE ? VOR_NONE : up + j);
+    const unsigned dd = gt ? (unsigned)((__ffs(gt) - 1) - j) : (dn == VOR_NONE ? VOR_NONE : dn + (rows - 1 - j));
+    const unsigned g = min(du, dd);
+    if (g == VOR_NONE) return VOR_G_NONE;
+    return g | (du == g ? VOR_UP : 0u) | (dd == g ? VOR_DN : 0u);
+}
+
+template <int RB>
+__global__ void __launch_bounds__(256) vor_row_kernel(const int *__restrict__ labels, const unsigned *__restrict__ bits,
+                                                       const uint16_t *__restrict__ up, const uint16_t *__restrict__ dn,
+                                                       const int *__restrict__ any_site, int *__restrict__ d2_out,
+                                                       int *__restrict__ near_out, int *__restrict__ site_out, int H, int W, int nch)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned cells[];  // [RB][W + 2]: one guard cell either side of a row
+    const int P = W + 2;
+    const int b = blockIdx.y;
+    const int r0 = blockIdx.x * RB;
+    const int ch = r0 / VOR_CH, j0 = r0 % VOR_CH;
+    const int rows_in_word = min(VOR_CH, H - ch * VOR_CH);
+    const int nrows = min(RB, H - r0);
+    const int64_t fbase = (int64_t)b * H * W;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    constexpr int WPR = RB >= 4 ? 1 : 4 / RB, RSTEP = 4 / WPR;  // waves per row; rows the block's four waves cover at a time
+    if (!any_site[b]) {  // a frame without site: d2 = -1, nearest label 0, site -1
+        for (int j = wave / WPR; j < nrows; j += RSTEP)
+            for (int c = lane + 64 * (wave % WPR); c < W; c += 64 * WPR) {
+                const int64_t gi = fbase + rowoff(r0 + j, W) + c;
+                d2_out[gi] = -1;
+                near_out[gi] = 0;
+                if (site_out) site_out[gi] = -1;
+            }
+        return;
+    }
+    const int64_t wbase = ((int64_t)b * nch + ch) * W;
+    for (int c = threadIdx.x; c < W; c += 256) {
+        const unsigned word = bits[wbase + c], u = up[wbase + c], d = dn[wbase + c];
+#pragma unroll
+        for (int j = 0; j < RB; ++j)
+            if (j < nrows) cells[j * P + c + 1] = site_cell(word, j0 + j, u, d, rows_in_word);
+    }
+    if (threadIdx.x < 2 * RB) cells[(threadIdx.x >> 1) * P + ((threadIdx.x & 1) ? W + 1 : 0)] = VOR_G_NONE;
+    __syncthreads();
+    const int *lab = labels + fbase;
+    for (int j = wave / WPR; j < nrows; j += RSTEP)
+        for (int c = lane + 64 * (wave % WPR); c < W; c += 64 * WPR) {
+            const int r = r0 + j;
+            const unsigned *gr = cells + j * P + 1;  // gr[-1] and gr[W] are the guard cells
+            unsigned best = VOR_BEST0;
+            int lbl = 0, q = -1;
+            // column cc holds its nearest site(s) at squared distance d <= best: the label image decides between equals
+            auto take = [&](int cc, unsigned cell, unsigned d) {
+                const int g = (int)(cell & 0xFFFFu);
+#pragma unroll
+                for (int side = 0; side < 2; ++side) {
+                    if (!(cell & (side ? VOR_DN : VOR_UP))) continue;
+                    const int rr = side ? r + g : r - g;
+                    if ((unsigned)rr >= (unsigned)H) continue;
+                    const int idx = (int)rowoff(rr, W) + cc;
+                    const int l = lab[idx];
+                    if (d < best || l < lbl || (l == lbl && idx < q)) {  // (d <= best here)
+                        best = d;
+                        lbl = l;
+                        q = idx;
+                    }
+                }
+            };
+            auto dist = [](unsigned cell, unsigned kk) { const unsigned g = cell & 0xFFFFu; return __umul24(g, g) + kk; };
+            {
+                const unsigned cell = gr[c], d = dist(cell, 0u);
+                if (d <= best) take(c, cell, d);
+            }
+            // offsets k .. k + 3 on both sides per trip (eight LDS reads issued together); indices are clamped onto the guard
+            // cells, which never qualify.  The exit test is STRICT (k * k > best): a column at k * k == best can still hold an
+            // equally near site of a smaller label.  Offsets of a trip beyond that bound cost more than best and fall through
+            const int klim = max(c, W - 1 - c);
+            for (int k = 1; k <= klim && (unsigned)(k * k) <= best; k += 4) {
+                unsigned gl[4], gq[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    gl[t] = gr[max(c - k - t, -1)];
+                    gq[t] = gr[min(c + k + t, W)];
+                }
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const unsigned kk = (unsigned)((k + t) * (k + t));
+                    const unsigned dl = dist(gl[t], kk), dq = dist(gq[t], kk);
+                    if (dl <= best) take(c - k - t, gl[t], dl);
+                    if (dq <= best) take(c + k + t, gq[t], dq);
+                }
+            }
+            const int64_t gi = fbase + rowoff(r, W) + c;
+            d2_out[gi] = (int)best;
+            near_out[gi] = lbl;
+            if (site_out) site_out[gi] = q;
+        }
+}
+
+struct VorWs {
+    unsigned *bits;
+    uint16_t *up, *dn;
+    int *any_site;
+    int nch;
+};
+
+static VorWs vor_carve(Carver &cv, int B, int H, int W)
+{
+    VorWs ws;
+    ws.nch = (H + VOR_CH - 1) / VOR_CH;
+    const size_t words = (size_t)B * ws.nch * W;
+    ws.bits = cv.take<unsigned>(words);
+    ws.up = cv.take<uint16_t>(words);
+    ws.dn = cv.take<uint16_t>(words);
+    ws.any_site = cv.take<int>(B);
+    return ws;
+}
+
+// ---- the label of a pixel within reach
+__global__ void __launch_bounds__(256) terr_labels_kernel(const int *__restrict__ near, const int *__restrict__ d2, int R2,
+                                                           int *__restrict__ out, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const int d = d2[i];
+        out[i] = (d >= 0 && d <= R2) ? near[i] : 0;
+    }
+}
+
+// ---- territory rows
+struct TerrRun {
+    int key;  // label << 1 | on the mask; 0 = none
+    int n, on, clip;
+};
+
+struct TerrRaw {
+    int4 n, d;
+    unsigned m;  // four mask bytes
+};
+__device__ __forceinline__ void landed(const TerrRaw &q) { landed(q.n); landed(q.d); landed(q.m); }
+
+struct TerrSlots {
+    int *tags;
+    int (*cnt)[4];  // px, on_px, reach2_max, clipped
+    unsigned long long *gout;  // the frame's rows
+};
+
+// VEC: W % 4 == 0, near / d2 16-byte and the mask 4-byte aligned
+template <bool VEC>
+struct TerrWalk {
+    using Key = int;
+    using Raw = TerrRaw;
+    using Run = TerrRun;
+    const int *near, *d2;
+    const uint8_t *mask;  // may be null
+    int c, H, W, R2, cap;
+    TerrSlots ls;
+    // the largest d2 of each column's open run, tracked beside the walk (a run's maximum has no closed form)
+    mutable int open_label[4] = {0, 0, 0, 0}, open_max[4] = {0, 0, 0, 0};
+
+    __device__ __forceinline__ Raw load(int r) const
+    {
+        Raw q;
+        q.n = row_labels4<VEC>(near + rowoff(r, W), c, W);
+        q.d = row_labels4<VEC>(d2 + rowoff(r, W), c, W);
+        q.m = 0;
+        if (mask && c < W) {
+            const uint8_t *at = mask + rowoff(r, W) + c;
+            if (VEC) {
+                q.m = *reinterpret_cast<const unsigned *>(at);
+            } else {
+                q.m = at[0];
+                if (c + 1 < W) q.m |= (unsigned)at[1] << 8;
+                if (c + 2 < W) q.m |= (unsigned)at[2] << 16;
+                if (c + 3 < W) q.m |= (unsigned)at[3] << 24;
+            }
+        }
+        return q;
+    }
+    __device__ __forceinline__ void max_commit(int l, int v) const
+    {
+        if (l <= 0) return;
+        const int slot = slot_claim(ls.tags, l);
+        if (slot >= 0) atomicMax(&ls.cnt[slot][2], v);
+        else atomicMax(&ls.gout[(int64_t)(l - 1) * 4 + 2], (unsigned long long)v);
+    }
+    __device__ __forceinline__ void keys(const Raw &q, Key k[4]) const
+    {
+        const int nv[4] = {q.n.x, q.n.y, q.n.z, q.n.w}, dv[4] = {q.d.x, q.d.y, q.d.z, q.d.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            // (columns beyond the frame's width load zeros: never a label)
+            const int l = (nv[j] >= 1 && nv[j] <= cap && dv[j] >= 0 && dv[j] <= R2) ? nv[j] : 0;
+            k[j] = l ? (l << 1) | (int)(((q.m >> (8 * j)) & 255u) != 0) : 0;
+            if (l != open_label[j]) {
+                max_commit(open_label[j], open_max[j]);
+                open_label[j] = l;
+                open_max[j] = 0;
+            }
+            if (l) open_max[j] = max(open_max[j], dv[j]);
+        }
+    }
+    __device__ __forceinline__ void max_flush() const
+    {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) max_commit(open_label[j], open_max[j]);
+    }
+    __device__ __forceinline__ Run run(Key key, int start, int end, int col) const
+    {
+        const int n = end - start;
+        return Run{key, n, (key & 1) ? n : 0, (int)(start == 0 || end == H || col == 0 || col == W - 1)};
+    }
+    static __device__ __forceinline__ Run shfl(const Run &a, int off)
+    {
+        return Run{a.key, __shfl_down(a.n, off), __shfl_down(a.on, off), __shfl_down(a.clip, off)};
+    }
+    static __device__ __forceinline__ void merge(Run &a, const Run &o) { a.n += o.n; a.on += o.on; a.clip |= o.clip; }
+    __device__ __forceinline__ void commit(const Run &a) const
+    {
+        const int l = a.key >> 1;
+        const int slot = slot_claim(ls.tags, l);
+        if (slot >= 0) {
+            atomicAdd(&ls.cnt[slot][0], a.n);
+            if (a.on) atomicAdd(&ls.cnt[slot][1], a.on);
+            if (a.clip) atomicOr(&ls.cnt[slot][3], 1);
+        } else {
+            unsigned long long *t = ls.gout + (int64_t)(l - 1) * 4;
+            atomicAdd(&t[0], (unsigned long long)a.n);
+            if (a.on) atomicAdd(&t[1], (unsigned long long)a.on);
+            if (a.clip) atomicOr(&t[3], 1ull);
+        }
+    }
+};
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) terr_reduce_kernel(const int *__restrict__ near, const int *__restrict__ d2,
+                                                           const uint8_t *__restrict__ mask, int R2, int cap, int H, int W,
+                                                           unsigned long long *__restrict__ out)
+{
+    __shared__ int tags[LABEL_SLOTS];
+    __shared__ int cnt[LABEL_SLOTS][4];
+    const TileIndex ti = xcd_tile_index();  // (a frame's blocks on one XCD: their atomics on the frame's table meet in one L2)
+    const int b = ti.z;
+    unsigned long long *gout = out + (int64_t)b * cap * 4;
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
+        tags[i] = 0;
+        cnt[i][0] = 0; cnt[i][1] = 0; cnt[i][2] = 0; cnt[i][3] = 0;
+    }
+    __syncthreads();
+    const int c = (ti.x * 256 + threadIdx.x) * 4;
+    const int r0 = ti.y * RUN_ROWS;
+    const int64_t fbase = (int64_t)b * H * W;
+    const TerrWalk<VEC> walk{near + fbase, d2 + fbase, mask ? mask + fbase : nullptr, c, H, W, R2, cap, TerrSlots{tags, cnt, gout}};
+    column_run_walk(walk, c, r0, min(H, r0 + RUN_ROWS));
+    walk.max_flush();
+    __syncthreads();
+    slots_flush8(tags, [&](int i, int l, int f) {
+        if (f >= 4) return;
+        const int v = cnt[i][f];
+        if (!v) return;
+        unsigned long long *t = gout + (int64_t)(l - 1) * 4 + f;
+        if (f < 2) atomicAdd(t, (unsigned long long)v);
+        else if (f == 2) atomicMax(t, (unsigned long long)v);
+        else atomicOr(t, 1ull);
+    });
+}
+
+// ---- adjacency: the per-frame pair table
+struct PairTable {
+    unsigned long long *keys;  // [pair_cap] a << 32 | b (a < b), 0 = free
+    unsigned *cnt;             // [pair_cap][2] border, contact
+    int *overflow;             // the frame's flag
+    int pair_cap;
+};
+
+// bounded probing: at most pair_cap slots are looked at; a full table raises the flag and drops the link.  Once the flag is up
+// every later link of the frame is dropped at once (its rows are incomplete anyway): without that each of them would walk the
+// whole full table, links x pair_cap loads
+__device__ __forceinline__ void pair_add(const PairTable &t, unsigned long long key, unsigned border, unsigned contact)
+{
+    if (ld_agent(t.overflow)) return;
+    unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) % (unsigned)t.pair_cap;
+    for (int i = 0; i < t.pair_cap; ++i) {
+        unsigned long long cur = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0) {
+            cur = atomicCAS(&t.keys[s], 0ull, key);
+            if (cur == 0) cur = key;
+        }
+        if (cur == key) {
+            atomicAdd(&t.cnt[2 * (size_t)s], border);
+            if (contact) atomicAdd(&t.cnt[2 * (size_t)s + 1], contact);
+            return;
+        }
+        s = s + 1 == (unsigned)t.pair_cap ? 0u : s + 1;
+    }
+    *t.overflow = 1;
+}
+
+struct PairAcc {
+    unsigned long long key;  // 0 = none
+    unsigned n, ct;
+};
+
+// a lane owns one column and walks down RUN_ROWS rows: the links to the right and to the lower neighbour.  Equal links that
+// follow each other in the column add up in registers (a border that runs down the frame), and at the end of the block
+// neighbouring lanes with the same open pair are summed by the segmented reduction (a border that runs across it)
+__global__ void __launch_bounds__(256) terr_pairs_kernel(const int *__restrict__ near, const int *__restrict__ d2, int R2, int H,
+                                                          int W, unsigned long long *__restrict__ keys, unsigned *__restrict__ cnt,
+                                                          int *__restrict__ overflow, int pair_cap)
+{
+    const TileIndex ti = xcd_tile_index();
+    const int b = ti.z;
+    const PairTable tab{keys + (int64_t)b * pair_cap, cnt + (int64_t)b * pair_cap * 2, overflow + b, pair_cap};
+    const int c = ti.x * 256 + threadIdx.x;
+    const int r0 = ti.y * RUN_ROWS, r1 = min(H, r0 + RUN_ROWS);
+    const int *fn = near + (int64_t)b * H * W, *fd = d2 + (int64_t)b * H * W;
+    const bool in = c < W, right = c + 1 < W;  // (every lane stays for the reductions: a lane past the width walks nothing)
+    PairAcc accR{0, 0, 0}, accD{0, 0, 0};
+    auto own = [R2](int n, int d) { return (n >= 1 && d >= 0 && d <= R2) ? n : 0; };
+    auto feed = [&](PairAcc &a, int la, int da, int lb, int db) {
+        if (la > 0 && lb > 0 && la != lb) {
+            const unsigned long long key = ((unsigned long long)(unsigned)min(la, lb) << 32) | (unsigned)max(la, lb);
+            if (key != a.key) {
+                if (a.key) pair_add(tab, a.key, a.n, a.ct);
+                a = PairAcc{key, 0, 0};
+            }
+            ++a.n;
+            a.ct += (da == 0 && db == 0);
+        }
+    };
+    int n0 = 0, d0 = -1;
+    if (in) {
+        n0 = fn[rowoff(r0, W) + c];
+        d0 = fd[rowoff(r0, W) + c];
+    }
+    for (int r = r0; r < r1; ++r) {
+        int nr = 0, dr = -1, nd = 0, dd = -1;
+        if (right) {
+            nr = fn[rowoff(r, W) + c + 1];
+            dr = fd[rowoff(r, W) + c + 1];
+        }
+        if (in && r + 1 < H) {
+            nd = fn[rowoff(r + 1, W) + c];
+            dd = fd[rowoff(r + 1, W) + c];
+        }
+        const int a = own(n0, d0);
+        feed(accR, a, d0, own(nr, dr), dr);
+        feed(accD, a, d0, own(nd, dd), dd);
+        n0 = nd;
+        d0 = dd;
+    }
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const PairAcc a = pass ? accD : accR;
+        const WaveSeg seg = wave_segment(a.key);
+        uint2 v = make_uint2(a.n, a.ct);
+        segment_reduce(
+            v, seg.remain, [](const uint2 &x, int off) { return make_uint2(__shfl_down(x.x, off), __shfl_down(x.y, off)); },
+            [](uint2 &x, const uint2 &o) { x.x += o.x; x.y += o.y; });
+        if (seg.head && a.key) pair_add(tab, a.key, v.x, v.y);
+    }
+}
+
+// used slots of a frame's table
+__global__ void __launch_bounds__(256) terr_pairs_count_kernel(const unsigned long long *__restrict__ keys, int pair_cap,
+                                                                long long *__restrict__ n_pairs)
+{
+    __shared__ int wsum[4];
+    const int b = blockIdx.x;
+    const unsigned long long *k = keys + (int64_t)b * pair_cap;
+    int n = 0;
+    for (int i = threadIdx.x; i < pair_cap; i += 256) n += k[i] != 0;
+    int tot;
+    block_exclusive_scan<256>(n, &tot, wsum);
+    if (threadIdx.x == 0) n_pairs[b] = tot;
+}
+
+// offsets[0 .. B] of the frames' rows; totals = {rows, frames whose table was full}
+__global__ void __launch_bounds__(64) terr_pairs_scan_kernel(const long long *__restrict__ n_pairs, const int *__restrict__ overflow,
+                                                              int B, long long *__restrict__ offsets, long long *__restrict__ totals)
+{
+    if (threadIdx.x != 0) return;
+    long long acc = 0, over = 0;
+    for (int b = 0; b < B; ++b) {
+        offsets[b] = acc;
+        acc += n_pairs[b];
+        over += overflow[b] != 0;
+    }
+    offsets[B] = acc;
+    totals[0] = acc;
+    totals[1] = over;
+}
+
+// the used slots of frame b, in table order, as rows offsets[b] ..: key, frame position, (border, contact); with slot_of also
+// degree (B, cap, 2 K) += 1 at [a][slot of b] and [b][slot of a], and at K + slot where the pair has contact
+__global__ void __launch_bounds__(256) terr_pairs_write_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ cnt,
+                                                                int pair_cap, const long long *__restrict__ offsets,
+                                                                const uint8_t *__restrict__ slot_of, int cap, int K,
+                                                                long long *__restrict__ key_out, int *__restrict__ frame_out,
+                                                                int *__restrict__ cnt_out, int *__restrict__ degree)
+{
+    __shared__ int wsum[4];
+    const int b = blockIdx.x;
+    const unsigned long long *k = keys + (int64_t)b * pair_cap;
+    const unsigned *v = cnt + (int64_t)b * pair_cap * 2;
+    long long row0 = offsets[b];
+    for (int base = 0; base < pair_cap; base += 256) {
+        const int i = base + (int)threadIdx.x;
+        const unsigned long long key = i < pair_cap ? k[i] : 0ull;
+        int tot;
+        const int pos = block_exclusive_scan<256>((int)(key != 0), &tot, wsum);
+        if (key) {
+            const long long row = row0 + pos;
+            const unsigned border = v[2 * (size_t)i], contact = v[2 * (size_t)i + 1];
+            key_out[row] = (long long)key;
+            frame_out[row] = b;
+            cnt_out[2 * row] = (int)border;
+            cnt_out[2 * row + 1] = (int)contact;
+            const unsigned la = (unsigned)(key >> 32), lb = (unsigned)key;
+            if (degree && la >= 1 && lb >= 1 && la <= (unsigned)cap && lb <= (unsigned)cap) {
+                const int sa = slot_of[(int64_t)b * cap + la - 1], sb = slot_of[(int64_t)b * cap + lb - 1];
+                int *da = degree + ((int64_t)b * cap + la - 1) * 2 * K, *db = degree + ((int64_t)b * cap + lb - 1) * 2 * K;
+                if (sb < K) {
+                    atomicAdd(&da[sb], 1);
+                    if (contact) atomicAdd(&da[K + sb], 1);
+                }
+                if (sa < K) {
+                    atomicAdd(&db[sa], 1);
+                    if (contact) atomicAdd(&db[K + sa], 1);
+                }
+            }
+        }
+        row0 += tot;
+    }
+}
+
+struct PairWs {
+    unsigned long long *keys;
+    unsigned *cnt;
+    long long *n_pairs;
+};
+
+static PairWs pairs_carve(Carver &cv, int B, int pair_cap)
+{
+    PairWs ws;
+    ws.keys = cv.take<unsigned long long>((size_t)B * pair_cap);
+    ws.cnt = cv.take<unsigned>((size_t)B * pair_cap * 2);
+    ws.n_pairs = cv.take<long long>((size_t)B);
+    return ws;
+}
+
+static inline int reach_arg(int64_t R2) { return (R2 < 0 || R2 > 0x7FFFFFFF) ? 0x7FFFFFFF : (int)R2; }
+
+}  // namespace pcseg
+
+using namespace pcseg;
+
+extern "C" {
+
+size_t pcseg_nearest_label_workspace_bytes(int B, int H, int W)
+{
+    if (!check_shape(B, H, W)) return 0;
+    Carver cv(nullptr, 0);
+    vor_carve(cv, B, H, W);
+    return cv.off;
+}
+
+int pcseg_nearest_label_i32(const int32_t *labels, const uint8_t *sel, int cap, int32_t *d2, int32_t *near, int32_t *site, int B,
+                            int H, int W, void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
+{
+    PCSEG_REQUIRE(labels && d2 && near && workspace && check_shape(B, H, W) && cap >= 1 && B <= 65535, "bad arguments");
+    Carver cv(workspace, workspace_bytes);
+    const VorWs ws = vor_carve(cv, B, H, W);
+    if (!cv.ok()) {
+        set_error("nearest_label_i32: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
+        return PCSEG_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    PCSEG_CHECK_HIP(hipMemsetAsync(ws.any_site, 0, sizeof(int) * B, s));
+    PCSEG_LAUNCH(vor_bits_kernel, dim3((W + 255) / 256, ws.nch, B), dim3(256), 0, s, labels, sel, cap, ws.bits, H, W, ws.nch);
+    PCSEG_CHECK_LAUNCH();
+    PCSEG_LAUNCH(vor_carry_kernel, dim3((W + 255) / 256, B), dim3(256), 0, s, (const unsigned *)ws.bits, ws.up, ws.dn, ws.any_site, H,
+                 W, ws.nch);
+    PCSEG_CHECK_LAUNCH();
+    // rows per block: four while a block's stage stays within 64 KB (W <= 4094: two and more blocks per CU; the occupancy
+    // argument of the distance transform's row pass), else one (W = 32768: 128 KB, one block per CU)
+    const size_t per_row = (size_t)(W + 2) * sizeof(unsigned);
+    auto launch_rows = [&](auto rb_tag) -> int {
+        constexpr int RB = decltype(rb_tag)::value;
+        const size_t bytes = RB * per_row;
+        if (bytes > 64 * 1024)
+            PCSEG_CHECK_HIP(hipFuncSetAttribute((const void *)vor_row_kernel<RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        PCSEG_LAUNCH((vor_row_kernel<RB>), dim3((H + RB - 1) / RB, B), dim3(256), bytes, s, labels, (const unsigned *)ws.bits,
+                     (const uint16_t *)ws.up, (const uint16_t *)ws.dn, (const int *)ws.any_site, d2, near, site, H, W, ws.nch);
+        return PCSEG_OK;
+    };
+    int rc;
+    if (4 * per_row <= 64 * 1024) rc = launch_rows(std::integral_constant<int, 4>());
+    else rc = launch_rows(std::integral_constant<int, 1>());
+    if (rc) return rc;
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+int pcseg_territory_labels(const int32_t *near, const int32_t *d2, int64_t R2, int32_t *out, int64_t n, pcseg_stream_t stream)
+{
+    PCSEG_REQUIRE(near && d2 && out && n >= 1 && n < ((int64_t)1 << 39), "bad arguments");
+    PCSEG_LAUNCH(terr_labels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, near, d2, reach_arg(R2), out, n);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+int pcseg_territory_reduce(const int32_t *near, const int32_t *d2, const uint8_t *mask, int64_t R2, int cap, int64_t *out, int B,
+                           int H, int W, pcseg_stream_t stream)
+{
+    PCSEG_REQUIRE(near && d2 && out && check_shape(B, H, W) && cap >= 1 && cap < (1 << 30) && B <= 65535, "bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    PCSEG_CHECK_HIP(hipMemsetAsync(out, 0, sizeof(int64_t) * 4 * (size_t)B * cap, s));
+    const dim3 grid((W + 1023) / 1024, (H + RUN_ROWS - 1) / RUN_ROWS, B);
+    const bool vec = W % 4 == 0 && (((uintptr_t)near | (uintptr_t)d2) & 15) == 0 && ((uintptr_t)mask & 3) == 0;
+    if (vec)
+        PCSEG_LAUNCH(terr_reduce_kernel<true>, grid, dim3(256), 0, s, near, d2, mask, reach_arg(R2), cap, H, W, (unsigned long long *)out);
+    else
+        PCSEG_LAUNCH(terr_reduce_kernel<false>, grid, dim3(256), 0, s, near, d2, mask, reach_arg(R2), cap, H, W, (unsigned long long *)out);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+size_t pcseg_territory_pairs_workspace_bytes(int B, int pair_cap)
+{
+    if (B < 1 || pair_cap < 1) return 0;
+    Carver cv(nullptr, 0);
+    pairs_carve(cv, B, pair_cap);
+    return cv.off;
+}
+
+int pcseg_territory_pairs(const int32_t *near, const int32_t *d2, int64_t R2, int pair_cap, int32_t *overflow, int64_t *offsets,
+                          int64_t *totals, int B, int H, int W, void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
+{
+    PCSEG_REQUIRE(near && d2 && overflow && offsets && totals && workspace && check_shape(B, H, W) && pair_cap >= 1 && B <= 65535,
+                  "bad arguments");
+    Carver cv(workspace, workspace_bytes);
+    const PairWs ws = pairs_carve(cv, B, pair_cap);
+    if (!cv.ok()) {
+        set_error("territory_pairs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
+        return PCSEG_ERR_WORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    PCSEG_CHECK_HIP(hipMemsetAsync(ws.keys, 0, sizeof(unsigned long long) * (size_t)B * pair_cap, s));
+    PCSEG_CHECK_HIP(hipMemsetAsync(ws.cnt, 0, sizeof(unsigned) * 2 * (size_t)B * pair_cap, s));
+    PCSEG_CHECK_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t) * B, s));
+    PCSEG_LAUNCH(terr_pairs_kernel, dim3((W + 255) / 256, (H + RUN_ROWS - 1) / RUN_ROWS, B), dim3(256), 0, s, near, d2, reach_arg(R2), H,
+                 W, ws.keys, ws.cnt, overflow, pair_cap);
+    PCSEG_CHECK_LAUNCH();
+    PCSEG_LAUNCH(terr_pairs_count_kernel, dim3(B), dim3(256), 0, s, (const unsigned long long *)ws.keys, pair_cap, ws.n_pairs);
+    PCSEG_CHECK_LAUNCH();
+    PCSEG_LAUNCH(terr_pairs_scan_kernel, dim3(1), dim3(64), 0, s, (const long long *)ws.n_pairs, (const int *)overflow, B,
+                 (long long *)offsets, (long long *)totals);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+int pcseg_territory_pairs_write(int pair_cap, const int64_t *offsets, const uint8_t *slot_of, int cap, int n_types, int64_t *key,
+                                int32_t *frame, int32_t *counts, int32_t *degree, int B, const void *workspace,
+                                size_t workspace_bytes, pcseg_stream_t stream)
+{
+    PCSEG_REQUIRE(offsets && key && frame && counts && workspace && B >= 1 && B <= 65535 && pair_cap >= 1, "bad arguments");
+    PCSEG_REQUIRE(!degree || (slot_of && cap >= 1 && n_types >= 1 && n_types <= 4), "degree needs slot_of, cap and 1..4 type slots");
+    Carver cv(const_cast<void *>(workspace), workspace_bytes);
+    const PairWs ws = pairs_carve(cv, B, pair_cap);
+    if (!cv.ok()) {
+        set_error("territory_pairs_write: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
+        return PCSEG_ERR_WORKSPACE;
+    }
+    PCSEG_LAUNCH(terr_pairs_write_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const unsigned long long *)ws.keys,
+                 (const unsigned *)ws.cnt, pair_cap, (const long long *)offsets, slot_of, cap, n_types, (long long *)key, frame, counts,
+                 degree);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+}  // extern "C"

@@ -809,7 +809,7 @@ def _rows_below(counts, cap):
 
 def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
                  n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None, convex=False,
-                 shape=False):
+                 shape=False, territory=None, territory_reach=None):
     """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device), then one stage per switch, in
     this order.  ``distance_slots`` (the class value -> type slot table, uint8[256] numpy): ``cell_dist``, one value
     per row of ``cells`` (NaN = no entry).  ``neighbour_slots`` (the same kind of table) with ``n_types`` slots:
@@ -822,10 +822,20 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
     ``refined_nn`` and with ``surface`` ``refined_sf``: the same two dicts over the refined rows of kind >= 1.
     ``shape``: ``shapes`` = :func:`_shape_rows` over the rows of ``cells`` and, with ``refined``, ``refined_shapes`` over
     the refined rows of kind >= 1.  ``convex``: ``convexity`` = :func:`_hull_rows` and ``refined_convexity``, over the same
-    rows."""
+    rows.  ``territory`` (a :class:`ClassTables`) with ``territory_reach`` (um, None: unbounded): ``territories`` /
+    ``adjacency`` = :func:`territory_rows` over the rows of ``cells`` (the labels of kind >= 1 are the sites), the particle
+    mask of ``surface`` as its mask, ``territory_overflow`` and, with ``refined``, ``refined_territories`` /
+    ``refined_adjacency`` / ``refined_territory_overflow`` over the refined rows of kind >= 1 on the watershed labels."""
     out, d = _dense_tables(res, groups, frame_ids, C, ratios, check)
     scale = 512.0 / float(raster)
     cap = res["stats"].shape[1]
+    pmask = None
+    if territory is not None:
+        r2 = reach_um_r2(territory_reach, scale)
+        pmask = particle_mask(res["recreated"], territory.particle_value)
+        out["territories"], out["adjacency"], out["territory_overflow"] = territory_rows(
+            res["labels"], (res["kind"] >= 1) & _rows_below(res["counts"], cap), res["slot_of"], frame_ids, scale,
+            len(territory.slot_names), r2=r2, mask=pmask, check=check)
     if convex:
         out["convexity"] = _hull_rows(res["labels"], res["counts"], res["stats"], (res["kind"] >= 1) & _rows_below(res["counts"], cap),
                                       res["slot_of"], frame_ids, scale)
@@ -838,7 +848,7 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
         out["cell_nn"] = _neighbours(_pack_cells("neighbours_pack_cells", d, neighbour_slots), n_types, scale, pair_edges)
     if surface is not None:
         K = max(len(surface.slot_names), 1)
-        mask, sf = particle_surface(res["recreated"], surface.particle_value)
+        mask, sf = particle_surface(res["recreated"], surface.particle_value, mask=pmask)
         out["cell_sf"] = _surface_rows(_pack_cells("surface_pack_cells", d, surface.slot), sf, mask, scale, K, surface_edges)
         out["cell_sf"].update(surface_px=sf["counts"], filled_area=sf["area"])
         if surface_edges is not None:
@@ -851,7 +861,7 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
             out["refined_nn"] = _neighbours(pts, n_types, scale, pair_edges)
         if surface is not None:
             out["refined_sf"] = _refined_surface(res, pts, sf, mask, scale, K, surface_edges)
-        if convex or shape:
+        if convex or shape or territory is not None:
             live = (out["kind_r"] >= 1) & (res["ws_stats"][:, :, 0] > 0) & _rows_below(res["n_markers"], cap)
         if convex:
             out["refined_convexity"] = _hull_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"], frame_ids,
@@ -859,6 +869,9 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
         if shape:
             out["refined_shapes"] = _shape_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"], frame_ids,
                                                 scale)
+        if territory is not None:
+            out["refined_territories"], out["refined_adjacency"], out["refined_territory_overflow"] = territory_rows(
+                res["ws_labels"], live, out["slot_r"], frame_ids, scale, len(territory.slot_names), r2=r2, mask=pmask, check=check)
     return out
 
 
@@ -1116,15 +1129,225 @@ def surface_shells(surface, mask, edges, scale):
     return shells
 
 
-def particle_surface(recreated, particle_value):
-    """The surface mask of the tables: ``binary_fill_holes(recreated == particle_value)`` (an empty mask without a
-    particle class) and :func:`surface_points` of it (bit words only).  Returns (mask uint8 (B, H, W), surface)."""
+def particle_mask(recreated, particle_value):
+    """The surface mask of the tables: ``binary_fill_holes(recreated == particle_value)``, uint8 (B, H, W) (an empty mask
+    without a particle class)."""
     recreated = _req(recreated, torch.uint8, 3)
     if particle_value is None:
-        mask = torch.zeros_like(recreated)
-    else:
-        mask = fill_holes((recreated == int(particle_value)).view(torch.uint8))
+        return torch.zeros_like(recreated)
+    return fill_holes((recreated == int(particle_value)).view(torch.uint8))
+
+
+def particle_surface(recreated, particle_value, mask=None):
+    """:func:`particle_mask` (or ``mask``, if the caller has it already) and :func:`surface_points` of it (bit words only).
+    Returns (mask uint8 (B, H, W), surface)."""
+    if mask is None:
+        mask = particle_mask(recreated, particle_value)
     return mask, surface_points(mask, 2, want_points=False)
+
+
+def _label_batch(labels, what="labels"):
+    """An int32 (B, H, W) CUDA tensor of any width and alignment (a contiguous view keeps its base address)."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("%s must be an int32 (B, H, W) tensor" % what)
+    return labels if labels.is_contiguous() else labels.contiguous()
+
+
+def nearest_label(labels, sel=None, cap=None, want_site=False):
+    """The exact nearest-label transform (Euclidean feature transform; csrc/voronoi.hip, include/pcseg.h): ``labels`` (B, H,
+    W) int32 CUDA tensor of any width and alignment; a site is a pixel with a label in 1 .. ``cap`` (default: the width
+    of ``sel``, else the largest label) that ``sel`` ((B, cap) uint8 / bool, optional) keeps.  Returns ``(d2, near, site)``,
+    int32 (B, H, W): the squared distance to the nearest site, the SMALLEST label among the sites at that distance and,
+    with ``want_site`` (else None), the raster index of the nearest site of that label (the smallest among equals) --
+    ``scipy.ndimage.distance_transform_edt(labels == 0, return_indices=True)`` with the ties decided.  -1, 0, -1 in a frame
+    without site.  Labels outside 1 .. cap are ignored."""
+    labels = _label_batch(labels)
+    B, H, W = labels.shape
+    if sel is not None:
+        sel = _req(sel, torch.uint8, 2)
+        if cap is None:
+            cap = sel.shape[1]
+        if tuple(sel.shape) != (B, int(cap)):
+            raise ValueError("sel must be (B, cap)")
+    if cap is None:
+        cap = max(int(labels.max().item()), 1)
+    cap = int(cap)
+    dev = labels.device
+    d2 = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    near = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    site = torch.empty((B, H, W), dtype=torch.int32, device=dev) if want_site else None
+    lib = _lib.load()
+    nbytes = lib.pcseg_nearest_label_workspace_bytes(B, H, W)
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.pcseg_nearest_label_i32(_ptr(labels), _ptr(sel), cap, _ptr(d2), _ptr(near), _ptr(site), B, H, W, _ptr(ws), nbytes,
+                                           _stream()), "nearest_label")
+    return d2, near, site
+
+
+def _near_pair(near, d2):
+    near, d2 = _label_batch(near, "near"), _label_batch(d2, "d2")
+    if near.shape != d2.shape:
+        raise ValueError("near and d2 must have one shape")
+    return near, d2
+
+
+def reach_r2(distance):
+    """Host only: the largest integer n with ``np.sqrt(np.float64(n)) <= distance`` (a bisection over that very formula,
+    which is non-decreasing in n); -1 = every n up to 2^53 (unbounded), None = none (``distance`` < 0 or NaN)."""
+    import numpy as np
+    ok = lambda n: bool(np.sqrt(np.float64(n)) <= distance)
+    if not ok(0):
+        return None
+    lo, hi = 0, 1 << 53
+    if ok(hi):
+        return -1
+    while hi - lo > 1:  # ok(lo) and not ok(hi)
+        mid = (lo + hi) // 2
+        if ok(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def reach_um_r2(reach, scale):
+    """Host only: R2 of a reach in um at ``scale`` pixels per um, such that ``d2 <= R2`` iff ``sqrt(d2) / scale < reach``
+    as numpy rounds it (:func:`surface_thresholds`); -1 (unbounded) for ``reach`` None."""
+    if reach is None:
+        return -1
+    if not float(reach) > 0.0:
+        raise ValueError("territory_reach must be a positive distance in um (None: unbounded)")
+    t = int(surface_thresholds([0.0, float(reach)], scale)[1])
+    return -1 if t >= (1 << 62) else t - 1
+
+
+def territory_labels(near, d2, r2=-1):
+    """``near`` where the pixel belongs to it (``0 <= d2 <= r2``; ``r2`` < 0: unbounded), else 0: int32, ``near``'s shape."""
+    near, d2 = _near_pair(near, d2)
+    out = torch.empty_like(near)
+    _lib.check(_lib.load().pcseg_territory_labels(_ptr(near), _ptr(d2), int(r2), _ptr(out), near.numel(), _stream()), "territory_labels")
+    return out
+
+
+def expand_labels(labels, distance=1):
+    """``skimage.segmentation.expand_labels(labels, distance)`` for an (H, W) or (B, H, W) int32 CUDA label image with labels
+    >= 0: every background pixel within ``distance`` (``np.sqrt(d2) <= distance``) of a label takes the nearest one.  Where
+    two labels are equally near -- skimage calls the choice undefined -- the smallest wins."""
+    single = isinstance(labels, torch.Tensor) and labels.dim() == 2
+    lab = _label_batch(labels[None] if single else labels)
+    r2 = reach_r2(distance)
+    if r2 is None:
+        out = torch.zeros_like(lab)
+    else:
+        d2, near, _ = nearest_label(lab)
+        out = territory_labels(near, d2, r2)
+    return out[0] if single else out
+
+
+TERRITORY_COLUMNS = ("territory_px", "territory_on_px", "reach2_max", "clipped")
+
+
+def territory_reduce(near, d2, mask=None, r2=-1, cap=None):
+    """The territory rows of :func:`nearest_label`'s result: int64 (B, cap, 4) in the order of ``TERRITORY_COLUMNS`` -- for
+    label l (row l - 1) over the pixels with ``near == l`` and ``0 <= d2 <= r2`` (``r2`` < 0: unbounded) their count, the
+    count of those on ``mask`` ((B, H, W) uint8 / bool, optional), the largest ``d2`` among them and whether one lies on
+    the frame's outer row or column.  Zeros for a label that owns no pixel; ``near`` outside 1 .. ``cap`` (default: its
+    maximum) is ignored."""
+    near, d2 = _near_pair(near, d2)
+    B, H, W = near.shape
+    if mask is not None:
+        mask = _req(mask, torch.uint8, 3)
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError("mask must have near's shape")
+    if cap is None:
+        cap = max(int(near.max().item()), 1)
+    cap = int(cap)
+    out = torch.empty((B, cap, 4), dtype=torch.int64, device=near.device)
+    _lib.check(_lib.load().pcseg_territory_reduce(_ptr(near), _ptr(d2), _ptr(mask), int(r2), cap, _ptr(out), B, H, W, _stream()),
+               "territory_reduce")
+    return out
+
+
+def territory_pairs(near, d2, r2=-1, pair_cap=None, slot_of=None, n_types=0):
+    """The adjacency graph of the territories of :func:`nearest_label`'s result.  A link is a pair of 4-neighbour pixels
+    that belong (``0 <= d2 <= r2``) to different labels, counted once.  Returns a dict: ``frame`` int64 (n,) position in
+    the batch, ``a`` / ``b`` int64 (n,) the labels (a < b), ``border`` / ``contact`` int64 (n,) the links between them and
+    those with ``d2 == 0`` at both ends (the labels touch in the label image), rows sorted by (frame, a, b); ``overflow``
+    int32 (B,) set where a frame has more than ``pair_cap`` pairs (default 8 x the largest label; its rows are then
+    incomplete) and ``n_overflow``, their number (read back with the row total, the only host read).  With ``slot_of``
+    ((B, cap) uint8, values >= ``n_types``: no type) also ``degree`` int32 (B, cap, 2 n_types): per label the number of
+    distinct partners of every type slot, then of those with contact."""
+    near, d2 = _near_pair(near, d2)
+    B, H, W = near.shape
+    dev = near.device
+    if pair_cap is None:
+        pair_cap = 8 * (slot_of.shape[1] if slot_of is not None else max(int(near.max().item()), 1))
+    pair_cap = int(pair_cap)
+    lib = _lib.load()
+    nbytes = lib.pcseg_territory_pairs_workspace_bytes(B, pair_cap)
+    ws = _ws(nbytes, dev)
+    overflow = torch.empty((B,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.pcseg_territory_pairs(_ptr(near), _ptr(d2), int(r2), pair_cap, _ptr(overflow), _ptr(offsets), _ptr(totals), B, H,
+                                         W, _ptr(ws), nbytes, _stream()), "territory_pairs")
+    n, n_over = (int(v) for v in totals.cpu())
+    key = torch.empty((n + 1,), dtype=torch.int64, device=dev)  # (a spare row: never a null pointer)
+    frame = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    counts = torch.empty((n + 1, 2), dtype=torch.int32, device=dev)
+    degree, cap, K = None, 0, int(n_types)
+    if slot_of is not None:
+        slot_of = _req(slot_of, torch.uint8, 2)
+        cap = slot_of.shape[1]
+        if slot_of.shape[0] != B or not 1 <= K <= 4:
+            raise ValueError("slot_of must be (B, cap), with 1 to 4 type slots")
+        degree = torch.zeros((B, cap, 2 * K), dtype=torch.int32, device=dev)
+    _lib.check(lib.pcseg_territory_pairs_write(pair_cap, _ptr(offsets), _ptr(slot_of), cap, K, _ptr(key), _ptr(frame), _ptr(counts),
+                                               _ptr(degree), B, _ptr(ws), nbytes, _stream()), "territory_pairs_write")
+    # (frame, a, b) order: the rows of a frame are contiguous already, in table order -- two stable sorts, plumbing
+    key, frame, counts = key[:n], frame[:n].to(torch.int64), counts[:n].to(torch.int64)
+    order = torch.sort(key, stable=True)[1]
+    order = order[torch.sort(frame[order], stable=True)[1]]
+    key = key[order]
+    return {"frame": frame[order], "a": key >> 32, "b": key & 0xFFFFFFFF, "border": counts[order, 0], "contact": counts[order, 1],
+            "overflow": overflow, "n_overflow": n_over, "degree": degree}
+
+
+def _slot_column(slot_of, b, l):
+    slot = slot_of[b, l].to(torch.int64)
+    return torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
+
+
+def territory_rows(labels, live, slot_of, frame_ids, scale, n_types, r2=-1, mask=None, check=False, pair_cap=None):
+    """The ``territories`` and ``adjacency`` tables of one label batch whose sites are the labels ``live`` ((B, cap) bool):
+    :func:`nearest_label`, :func:`territory_reduce` and :func:`territory_pairs` on the whole batch, then the rows ``live`` in
+    (frame, label) order as ``[frame, label, slot, territory_px, territory_on_px, reach2_max, clipped, n_adj per type slot,
+    n_contact per type slot, territory_um2, territory_on_um2]`` (areas / ``scale`` ^ 2, ONE correctly rounded division each)
+    and the pairs as ``[frame, label_a, label_b, slot_a, slot_b, border_px, contact_px]`` sorted by (frame, a, b).  Returns
+    (territories, adjacency, overflow int32 (B,)); ``check`` raises where a frame's pair table was full."""
+    B, cap = live.shape
+    K = max(int(n_types), 1)
+    d2, near, _ = nearest_label(labels, live.view(torch.uint8) if live.dtype == torch.bool else live, cap)
+    terr = territory_reduce(near, d2, mask, r2, cap)
+    pairs = territory_pairs(near, d2, r2, pair_cap or 8 * cap, slot_of=slot_of, n_types=K)
+    if check and pairs["n_overflow"]:
+        raise RuntimeError("territory pair table capacity exceeded: raise FramePipeline(cap=...)")
+    b, l = torch.nonzero(live, as_tuple=True)
+    t = terr[b, l].to(torch.float64)
+    # tensor divisor: a correctly rounded division per element (see _hull_rows)
+    per_um2 = torch.full_like(t[:, 0], scale * scale)
+    deg = pairs["degree"][b, l].to(torch.float64)
+    rows = torch.cat([torch.stack([frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), _slot_column(slot_of, b, l)], dim=1), t,
+                      deg[:, :int(n_types)], deg[:, K:K + int(n_types)], torch.stack([t[:, 0] / per_um2, t[:, 1] / per_um2], dim=1)], dim=1)
+    f, a, bb = pairs["frame"], pairs["a"], pairs["b"]
+    inside = (a <= cap) & (bb <= cap)  # (every site label is: near only ever holds site labels)
+    f, a, bb = f[inside], a[inside], bb[inside]
+    adj = torch.stack([frame_ids[f].to(torch.float64), a.to(torch.float64), bb.to(torch.float64), _slot_column(slot_of, f, a - 1),
+                       _slot_column(slot_of, f, bb - 1), pairs["border"][inside].to(torch.float64),
+                       pairs["contact"][inside].to(torch.float64)], dim=1)
+    return rows, adj, pairs["overflow"]
 
 
 def remove_overlapping(dapi, other, threshold):

@@ -390,6 +390,55 @@ def get_cell_convexity(cell_pos, px_to_um=PX_TO_UM_CONV):
     return out
 
 
+def get_cell_territories(z_slice, cell_pos, cell_clusters, cell_types, reach=None, px_to_um=PX_TO_UM_CONV):
+    """How much of the frame every cell has to itself and which cells are its neighbours (csrc/voronoi.hip): the regions
+    of ``cell_pos`` and ``cell_clusters`` (strain -> regions of ONE denoised class map ``z_slice``, as
+    get_cell_positions_and_areas returns them) are the sites of the exact nearest-label transform; a pixel belongs to the
+    nearest of them (the smallest label among equally near ones) if it lies closer than ``reach`` um (None: unbounded).
+    Returns a dict: ``names`` (the strains: type slot k = ``names[k]``), ``territories`` float64 (n, 8 + 2 K) in label order
+    with ``territories_columns`` = label, slot, territory_px, territory_on_px (the part on the reconstructed, hole-filled
+    particle), reach2_max, clipped, n_adj_<strain>.., n_contact_<strain>.., territory_um2, territory_on_um2, and
+    ``adjacency`` float64 (m, 6) sorted by (label_a, label_b) with ``adjacency_columns`` = label_a, label_b, slot_a, slot_b,
+    border_px (4-neighbour links between the two territories), contact_px (those where the regions themselves touch).
+    One device call chain for the frame."""
+    cell_clusters = cell_clusters or {}
+    names = list(cell_pos) + [n for n in cell_clusters if n not in cell_pos]
+    if len(names) > 4:
+        raise ValueError("at most 4 strains")
+    regs = [(t, r) for t, name in enumerate(names) for r in list(cell_pos.get(name, [])) + list(cell_clusters.get(name, []))]
+    z_dev, _ = _to_dev_u8(z_slice)
+    dev = z_dev.device
+    holders = {id(r._im): r._im for _, r in regs}
+    if None in [r._im for _, r in regs] or len(holders) > 1:
+        raise AttributeError("the regions must carry the label image of one frame")
+    K = max(len(names), 1)
+    cols_t = (["label", "slot", "territory_px", "territory_on_px", "reach2_max", "clipped"] + ["n_adj_%s" % n for n in names]
+              + ["n_contact_%s" % n for n in names] + ["territory_um2", "territory_on_um2"])
+    cols_a = ["label_a", "label_b", "slot_a", "slot_b", "border_px", "contact_px"]
+    out = {"names": names, "territories_columns": cols_t, "adjacency_columns": cols_a}
+    if not regs:
+        out.update(territories=np.zeros((0, len(cols_t))), adjacency=np.zeros((0, 6)))
+        return out
+    labels = next(iter(holders.values())).dev[None]
+    cap = max(r.label for _, r in regs)
+    live, slot_of = np.zeros((1, cap), bool), np.full((1, cap), 255, np.uint8)
+    for t, r in regs:
+        live[0, r.label - 1], slot_of[0, r.label - 1] = True, t
+    cell_labels = [label for label, name in cell_types.items() if name in CELL_TYPES]
+    particle_labels = [label for label, name in cell_types.items() if name == "Particle"]
+    particle_label = particle_labels[-1] if particle_labels else None
+    gained = None
+    for cell_label in (cell_labels if particle_label is not None else []):
+        z_dev, gained = ops.fill_particle(z_dev, particle_label, cell_label, particle_label, DILATION_RADIUS, DISTANCE_THRESHOLD,
+                                          gained)
+    rows, adj, _ = ops.territory_rows(labels, torch.from_numpy(live).to(dev), torch.from_numpy(slot_of).to(dev),
+                                      torch.zeros((1,), dtype=torch.int64, device=dev), float(px_to_um), len(names),
+                                      r2=ops.reach_um_r2(reach, float(px_to_um)), mask=ops.particle_mask(z_dev, particle_label),
+                                      check=True)
+    out.update(territories=rows.cpu().numpy()[:, 1:], adjacency=adj.cpu().numpy()[:, 1:])
+    return out
+
+
 def get_cell_surface_distances(z_slice, cell_types, cell_pos=None, cell_clusters=None, px_to_um=PX_TO_UM_CONV, edges=None):
     """Where the cells of one denoised class map sit relative to the particle
     (HCN_nanosims_rois_activity_distance_5iso_YG.m:271-309, the distance of every ROI to the aggregate boundary): the
