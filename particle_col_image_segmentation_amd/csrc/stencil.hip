@@ -416,7 +416,9 @@ int pcseg_argmax_planes_f32(const float *stack, uint8_t *cls, int B, int C, int 
     PCSEG_REQUIRE(stack && cls && C >= 1 && C <= 255 && check_shape(B, H, W), "bad arguments");
     int64_t n = (int64_t)H * W;
     hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0) {
+    // (16-byte loads / 4-byte stores need the alignment too: the unfused route of pcseg_classmap_label_f32 hands the caller's
+    // stack over as it is)
+    if ((n & 3) == 0 && ((uintptr_t)stack & 15) == 0 && ((uintptr_t)cls & 3) == 0) {
         dim3 grid((unsigned)((n / 4 + 255) / 256), B);
         PCSEG_LAUNCH(argmax_kernel<true>, grid, dim3(256), 0, s, stack, cls, C, n);
     } else {

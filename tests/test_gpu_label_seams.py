@@ -1,0 +1,422 @@
+"""Every union-find labelling route at its tile seams, against the CPU oracle; every comparison is integer equality.
+
+The routes share one scheme: an LDS tile pass (64 x 32 pixels; the run-based variant 64 columns x four 32-row bit words),
+a border pass that adds the links across tile edges with global atomics, raster-order compaction.  Both passes skip links
+that a third pixel implies, by rules that change at tile corners, word seams and a tile's first / last column.  Random
+noise meets a given local configuration on a given seam only by chance; here all 65 536 binary 4 x 4 windows are laid
+over the seams, patterns that cross every seam of a frame run through every route, identical frames of one batch must
+come out identical, and the shapes go to the limits check_shape admits.  Inputs: tests/seam_patterns.py.
+
+NaN planes are out of scope.  numpy gives NaN the maximum, and the kernel does so only in plane 0.  No caller produces
+NaN.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import seam_patterns as sp
+from oracle import oracle as orc
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ops():
+    if not torch.cuda.is_available():
+        pytest.fail("no GPU visible: the HIP path has no CPU fallback")
+    from particle_col_image_segmentation_amd import ops as _ops
+    return _ops
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def shifted(t):
+    """A copy of the CUDA tensor ``t`` whose base pointer lies one element (uint8: 1 byte, int32 / float32: 4 bytes) past a
+    16-byte boundary: the kernels' 16-byte and 4-byte load paths do not apply to it."""
+    item = t.element_size()
+    buf = torch.empty(t.numel() + 32, dtype=t.dtype, device=t.device)
+    start = ((item - buf.data_ptr()) % 16) // item
+    out = buf[start:start + t.numel()].view(t.shape)
+    assert out.data_ptr() % 16 == item and out.is_contiguous()
+    out.copy_(t)
+    return out
+
+
+def assert_frames_equal(got, exp, what, names=None, show=None):
+    """torch.equal of two (B, ...) device tensors, naming the first frame that differs (``show``: the (row slice, column
+    slice) of it that the message prints; the comparison is always of whole frames)."""
+    if torch.equal(got, exp):
+        return
+    assert got.shape == exp.shape and got.dtype == exp.dtype, (what, tuple(got.shape), got.dtype, tuple(exp.shape), exp.dtype)
+    bad = torch.nonzero((got != exp).flatten(1).any(1)).flatten()
+    k = int(bad[0])
+    g, e = host(got[k]), host(exp[k])
+    where = ""
+    if show is not None and (g != e).sum() == (g[show] != e[show]).sum():  # (else they also differ outside the part to show)
+        where = " (rows %d.., columns %d..)" % (show[0].start, show[1].start)
+        g, e = g[show], e[show]
+    pytest.fail("%s: %d of %d frames differ, first %s%s\n got:\n%s\n expected:\n%s" % (
+        what, bad.numel(), got.shape[0], names[k] if names else k, where, g, e))
+
+
+# ============================================================================================= exhaustive corner windows
+ALL_WINDOWS = functools.lru_cache(None)(sp.all_binary_windows)
+
+
+@functools.lru_cache(None)
+def binary_window_labels(connectivity):
+    return sp.window_labels(ALL_WINDOWS(), connectivity=connectivity)
+
+
+def pixel_route(ops, route, frames):
+    """(labels, counts) of uint8 (B, H, W) device frames through one of the pixel labelling routes."""
+    if route == "label_bool8":
+        return ops.label_bool8(frames)
+    if route == "label_bool4":
+        return ops.label_bool4(frames)
+    if route in ("label_equal8", "label_equal8_value3"):
+        return ops.label_equal8(frames)
+    if route == "dilated_roots":  # the parent image of the radius-0 "dilation", numbered by compact_labels
+        return ops.compact_labels(ops.dilated_roots(frames, 1 << 1, 0) + 1)
+    raise ValueError(route)
+
+
+def check_windows(ops, route, shape, origin, wins, labs, chunk=8192):
+    """Frames of ``shape`` with window k at ``origin`` through ``route``: labels and counts equal the padded window
+    labellings.  Chunks of at most 20 Mpixels, compared on the device."""
+    counts = labs.reshape(labs.shape[0], -1).max(axis=1).astype(np.int32)
+    for k0 in range(0, wins.shape[0], chunk):
+        w = wins[k0:k0 + chunk]
+        frames = sp.window_frames(shape, origin, w * 3 if route == "label_equal8_value3" else w)
+        got, cnt = pixel_route(ops, route, dev(frames))
+        what = "%s %s windows %d.." % (route, shape, k0)
+        show = (slice(origin[0], origin[0] + w.shape[1]), slice(origin[1], origin[1] + w.shape[2]))
+        assert_frames_equal(got, dev(sp.window_frames(shape, origin, labs[k0:k0 + chunk])), what, show=show)
+        assert_frames_equal(cnt[:, None], dev(counts[k0:k0 + chunk])[:, None], what + " (counts)")
+
+
+PIXEL_WINDOW_ROUTES = ["label_bool8", "label_bool4", "label_equal8", "label_equal8_value3", "dilated_roots"]
+
+
+@pytest.mark.parametrize("route", PIXEL_WINDOW_ROUTES)
+def test_corner_windows_exhaustive(ops, route):
+    """All 65 536 binary 4 x 4 windows at rows 30 .. 33, columns 62 .. 65 of a 34 x 66 frame: 2 x 2 tiles, the window
+    over the tile corner at (32, 64), a pixel count that is a multiple of 4 (the quad relabel pass).  65 536 frames per
+    route, in 8 chunks of 8192 (18.4 Mpixels)."""
+    labs = binary_window_labels(1 if route == "label_bool4" else 2)
+    check_windows(ops, route, (34, 66), (30, 62), ALL_WINDOWS(), labs)
+
+
+@pytest.mark.parametrize("route", PIXEL_WINDOW_ROUTES)
+def test_corner_windows_ragged_frame(ops, route):
+    """A seeded sample of 8192 of the windows on a 35 x 67 frame: an odd pixel count (the scalar relabel pass) and ragged
+    last tiles in both axes."""
+    pick = np.random.default_rng(35067).choice(65536, 8192, replace=False)
+    labs = binary_window_labels(1 if route == "label_bool4" else 2)
+    check_windows(ops, route, (35, 67), (30, 62), ALL_WINDOWS()[pick], labs[pick])
+
+
+@pytest.mark.parametrize("shape", [(34, 66), (35, 67)])
+def test_corner_windows_four_values(ops, shape):
+    """label_equal8 on 40 000 seeded windows over {0, 1, 2, 3}: neighbours that are set but of another value."""
+    wins = sp.random_windows(40000, 4, seed=40000 + shape[0])
+    check_windows(ops, "label_equal8", shape, (30, 62), wins, sp.window_labels(wins, equal=True))
+
+
+# =========================================================================================================== run components
+def runs_checked(ops, frames_np, expected_labels, radius, what, crop=None):
+    """dilated_runs of uint8 0/1 frames at ``radius``: the unpacked bits equal ``expected_labels > 0`` and hold no bit at
+    rows >= H (compared on the device), and the partition of the run components equals ``expected_labels`` (on the host;
+    ``crop`` = (row slice, column slice) that holds every foreground pixel: only that part is compared as a partition)."""
+    B, H, W = frames_np.shape
+    bits, run_parent = ops.dilated_runs(dev(frames_np), 1 << 1, radius)
+    shifts = torch.arange(32, device=bits.device, dtype=torch.int32)[None, None, :, None]
+    un = ((bits[:, :, None, :] >> shifts) & 1).reshape(B, -1, W)
+    exp = dev(expected_labels)
+    assert_frames_equal(un[:, :H].to(torch.uint8), (exp > 0).to(torch.uint8), what + " (bits)")
+    assert not bool(un[:, H:].any()), what + ": a bit of a row >= H is set"
+    roots = sp.run_partition(host(bits), host(run_parent), H)
+    rs, cs = crop if crop is not None else (slice(None), slice(None))
+    if not sp.same_partition(roots[:, rs, cs], expected_labels[:, rs, cs]):
+        for k in range(B):
+            if not sp.same_partition(roots[k, rs, cs], expected_labels[k, rs, cs]):
+                pytest.fail("%s: frame %d, run components\n%s\n expected\n%s" % (what, k, roots[k, rs, cs], expected_labels[k, rs, cs]))
+
+
+@pytest.mark.parametrize("radius", [0, 2])
+@pytest.mark.parametrize("origin", [(30, 62), (126, 62)])
+def test_run_components_windows_exhaustive(ops, origin, radius):
+    """All 65 536 binary windows over (32, 64) -- a word seam inside a run tile crossing a tile-column seam -- and over
+    (128, 64) -- a run-tile corner -- of a 131 x 67 frame, through dilated_runs at radius 0 and 2.  At radius 2 the
+    dilated window is cut by the frame's right (and, at the lower origin, bottom) edge.  65 536 frames per case, in 32
+    chunks of 2048 (18 Mpixels)."""
+    H, W = 131, 67
+    wins = ALL_WINDOWS()
+    r0, c0 = origin[0] - radius, origin[1] - radius
+    room = (min(4 + 2 * radius, H - r0), min(4 + 2 * radius, W - c0))
+    labs = binary_window_labels(2) if radius == 0 else sp.window_labels(wins, radius=radius, room=room)
+    crop = (slice(r0, r0 + room[0]), slice(c0, c0 + room[1]))
+    for k0 in range(0, 65536, 2048):
+        frames = sp.window_frames((H, W), origin, wins[k0:k0 + 2048])
+        runs_checked(ops, frames, sp.window_frames((H, W), (r0, c0), labs[k0:k0 + 2048]), radius,
+                     "dilated_runs r=%d origin %s windows %d.." % (radius, origin, k0), crop)
+
+
+@functools.lru_cache(None)
+def structured(shape):
+    """(names, uint8 (n, H, W) batch) of the structured frames of a shape."""
+    f = sp.structured_frames(shape)
+    return list(f), np.stack(list(f.values()))
+
+
+@pytest.mark.parametrize("radius", [0, 2])
+@pytest.mark.parametrize("shape", [(131, 67), (129, 128), (33, 130)])
+def test_run_components_structured(ops, shape, radius):
+    """The structured frames through dilated_runs: 14 frames per case; 131 x 67: two run-tile rows and a ragged second
+    tile column, 129 x 128: one row into the second run tile, full-width tile columns (the 4-column bit setter), 33 x 130:
+    one row into the second word, three tile columns."""
+    names, batch = structured(shape)
+    m = batch > 0
+    exp = np.stack([orc.label(orc.binary_dilation_disk(f, radius) if radius else f) for f in m])
+    runs_checked(ops, m.astype(np.uint8), exp, radius, "dilated_runs r=%d %s %s" % (radius, shape, names))
+
+
+# ==================================================================================== structured frames, every pixel route
+STRUCT_SHAPES = [(1, 64), (2, 128), (3, 65), (32, 64), (33, 65), (35, 67), (64, 127), (65, 129), (97, 200)]
+STRUCT_ROUTES = ["label_equal8", "label_bool8", "label_bool4", "fill_holes", "local_maxima", "local_maxima_negated"]
+
+
+def route_input(route, batch):
+    """The device input of a structured batch (uint8 class images) for a route."""
+    if route == "label_equal8":
+        return dev(batch)
+    if route == "local_maxima":
+        return dev(batch.astype(np.int32))
+    if route == "local_maxima_negated":  # negated and shifted below zero: plateaus of negative values, the background on top
+        return dev(-batch.astype(np.int32) - 5)
+    return dev((batch > 0).astype(np.uint8))
+
+
+def route_run(ops, route, x):
+    """Tuple of result tensors of a route."""
+    if route.startswith("label_"):
+        return getattr(ops, route)(x)
+    if route == "fill_holes":
+        return (ops.fill_holes(x),)
+    return ops.local_maxima(x)  # is_max, markers, counts
+
+
+@functools.lru_cache(None)
+def route_expected(route, shape, copies=None):
+    """The oracle's results for the structured batch of ``shape`` (``copies``: see stability_batch), as numpy arrays in the
+    order of route_run."""
+    batch = structured(shape)[1] if copies is None else stability_batch(shape, copies)[:: copies]
+    if route.startswith("label_"):
+        conn = 1 if route == "label_bool4" else 2
+        res = [orc.label(f.astype(np.int32) if route == "label_equal8" else f > 0, connectivity=conn, return_num=True) for f in batch]
+        return np.stack([r[0] for r in res]), np.array([r[1] for r in res], np.int32)
+    if route == "fill_holes":
+        return (np.stack([orc.binary_fill_holes(f > 0) for f in batch]).astype(np.uint8),)
+    img = batch.astype(np.int32) if route == "local_maxima" else -batch.astype(np.int32) - 5
+    lm = [orc.local_maxima(f) for f in img]
+    res = [orc.label(m, return_num=True) for m in lm]
+    return np.stack(lm).astype(np.uint8), np.stack([r[0] for r in res]), np.array([r[1] for r in res], np.int32)
+
+
+RESULT_NAMES = {"fill_holes": ("filled",), "local_maxima": ("is_max", "markers", "counts"),
+                "local_maxima_negated": ("is_max", "markers", "counts")}
+
+
+def compare_route(route, got, exp, names, what):
+    for g, e, field in zip(got, exp, RESULT_NAMES.get(route, ("labels", "counts"))):
+        g, e = (g[:, None], e[:, None]) if g.dim() == 1 else (g, e)
+        assert_frames_equal(g, e, "%s %s" % (what, field), names)
+
+
+@pytest.mark.parametrize("route", STRUCT_ROUTES)
+@pytest.mark.parametrize("shape", STRUCT_SHAPES)
+def test_structured_frames(ops, shape, route):
+    """One batch of all 14 structured frames per shape and route, sent from an aligned base pointer and once more from one
+    4 bytes (uint8 inputs: 1 byte) past a 16-byte boundary: both equal the oracle and each other.  The shapes: a single
+    row, two and three rows (less than a 5-row stencil), exactly one tile, one pixel more than a tile in both axes, ragged
+    2 x 2 tiles with an odd pixel count, one column short of two tile columns, one pixel into the third tile row and
+    column, and 4 x 4 tiles."""
+    names, batch = structured(shape)
+    x = route_input(route, batch)
+    exp = [dev(e) for e in route_expected(route, shape)]
+    got = route_run(ops, route, x)
+    compare_route(route, got, exp, names, "%s %s" % (route, shape))
+    got_shifted = route_run(ops, route, shifted(x))
+    compare_route(route, got_shifted, got, names, "%s %s from a shifted base pointer" % (route, shape))
+
+
+# ============================================================================================================ batch stability
+@functools.lru_cache(None)
+def stability_batch(shape, copies):
+    f = sp.structured_frames(shape)
+    return np.concatenate([np.repeat(f["serpentine"][None], copies, 0), np.repeat(f["diag2"][None], copies, 0)])
+
+
+@pytest.mark.parametrize("route", STRUCT_ROUTES)
+def test_identical_frames_of_one_batch_give_identical_results(ops, route):
+    """64 copies of the serpentine and 64 of the period-2 diagonal stripes (97 x 200: 4 x 4 tiles, every seam crossed
+    hundreds of times) in ONE call: the border passes are concurrent atomics on the union-find image, their result must
+    not depend on the order they land in.  Every frame equals frame 0 of its pattern and the oracle.  Twice: scheduling
+    differs from run to run, the result must not."""
+    shape, copies = (97, 200), 64
+    x = route_input(route, stability_batch(shape, copies))
+    exp = [dev(np.repeat(e, copies, 0)) for e in route_expected(route, shape, copies)]
+    names = ["serpentine#%d" % k for k in range(copies)] + ["diag2#%d" % k for k in range(copies)]
+    for _ in range(2):
+        got = route_run(ops, route, x)
+        for g in got:
+            for p in range(2):
+                first = g[p * copies:p * copies + 1].expand_as(g[p * copies:(p + 1) * copies])
+                assert_frames_equal(g[p * copies:(p + 1) * copies].reshape(copies, -1), first.reshape(copies, -1),
+                                    "%s: copies of one frame differ" % route, names[p * copies:])
+        compare_route(route, got, exp, names, route)
+
+
+# =========================================================================================================== dimension limits
+LIMIT_SHAPES = [(32768, 3), (3, 32768)]
+
+
+@functools.lru_cache(None)
+def limit_pairs(shape):
+    """Two B = 2 batches at a limit shape: (full-length line through the middle, isolated pixels at spacing 33 along the
+    long axis) and (full frame, empty frame)."""
+    H, W = shape
+    line, dots = np.zeros(shape, np.uint8), np.zeros(shape, np.uint8)
+    if H > W:
+        line[:, W // 2] = 1
+        dots[::33, W // 2] = 1
+    else:
+        line[H // 2, :] = 1
+        dots[H // 2, ::33] = 1
+    return (("line", "dots"), np.stack([line, dots])), (("full", "empty"), np.stack([np.ones(shape, np.uint8), np.zeros(shape, np.uint8)]))
+
+
+@pytest.mark.parametrize("route", ["label_equal8", "label_bool8", "label_bool4", "fill_holes"])
+@pytest.mark.parametrize("shape", LIMIT_SHAPES)
+def test_dimension_limits_labels(ops, shape, route):
+    """The largest row / column count check_shape admits, three pixels across: 1023 tile-row seams in one column (511
+    tile-column seams in one row), a full-length line = the longest chain of border unions and root walks there is."""
+    for names, batch in limit_pairs(shape):
+        if route.startswith("label_"):
+            conn = 1 if route == "label_bool4" else 2
+            res = [orc.label(f.astype(np.int32) if route == "label_equal8" else f > 0, connectivity=conn, return_num=True) for f in batch]
+            exp = (np.stack([r[0] for r in res]), np.array([r[1] for r in res], np.int32))
+        else:
+            exp = (np.stack([orc.binary_fill_holes(f > 0) for f in batch]).astype(np.uint8),)
+        got = route_run(ops, route, dev(batch))
+        compare_route(route, got, [dev(e) for e in exp], names, "%s %s" % (route, shape))
+
+
+@pytest.mark.parametrize("radius", [0, 2])
+@pytest.mark.parametrize("shape", LIMIT_SHAPES)
+def test_dimension_limits_run_components(ops, shape, radius):
+    """dilated_runs at the limit shapes: 1024 words per column / 512 run-tile columns; at radius 2 the dots stay apart
+    (spacing 33) and the line fills the frame's three rows / columns."""
+    for names, batch in limit_pairs(shape):
+        m = batch > 0
+        exp = np.stack([orc.label(orc.binary_dilation_disk(f, radius) if radius else f) for f in m])
+        runs_checked(ops, batch, exp, radius, "dilated_runs r=%d %s %s" % (radius, shape, names))
+
+
+@pytest.mark.parametrize("shape", LIMIT_SHAPES)
+def test_dimension_limits_edt(ops, shape):
+    """edt_sq at the limit shapes, exact and with cap = 50: a single zero pixel at one end (column distances up to 32 767 in
+    the uint16 carries, a row search over 32 767 offsets), a zero at each end, and the frame without a zero pixel, which
+    the oracle answers like scipy (tests/test_label_seams_cpu.py holds it against scipy at these shapes): (r + 1)^2 + c^2,
+    2^30 and more in the last row of the tall frame, beside the kernel's 0x40000000 for "no zero pixel in reach"."""
+    H, W = shape
+    one = np.ones(shape, np.uint8)
+    one[0, 0] = 0
+    two = one.copy()
+    two[H - 1, W - 1] = 0
+    ones = np.ones(shape, np.uint8)
+    exp = {k: orc.edt_sq(m) for k, m in (("one", one), ("two", two), ("ones", ones))}
+    assert exp["ones"][H - 1, W - 1] == H * H + (W - 1) * (W - 1) and exp["one"][H - 1, W - 1] == (H - 1) ** 2 + (W - 1) ** 2
+    for names in (("one", "two"), ("ones", "one")):  # (the second batch mixes a frame without a zero pixel and one with)
+        batch = dev(np.stack([{"one": one, "two": two, "ones": ones}[k] for k in names]))
+        e = np.stack([exp[k] for k in names])
+        assert_frames_equal(ops.edt_sq(batch), dev(e), "edt_sq %s" % (shape,), names)
+        assert_frames_equal(ops.edt_sq(batch, cap=50), dev(np.minimum(e, 51)), "edt_sq cap=50 %s" % (shape,), names)
+
+
+def test_shape_over_the_limit_is_refused(ops):
+    """One row / column more than check_shape admits: the library's "bad arguments" error, no launch."""
+    from particle_col_image_segmentation_amd._lib import PcsegError
+    for shape in [(1, 32769, 3), (1, 3, 32769)]:
+        x = torch.zeros(shape, dtype=torch.uint8, device="cuda")
+        for call in (ops.label_bool8, ops.label_equal8, ops.label_bool4, ops.fill_holes, ops.edt_sq,
+                     lambda t: ops.dilated_runs(t, 1 << 1, 0), lambda t: ops.dilated_roots(t, 1 << 1, 0)):
+            with pytest.raises(PcsegError, match="bad arguments"):
+                call(x)
+
+
+# ============================================================================================================ fused front end
+FRONT_SHAPES = [(1, 64), (2, 128), (3, 64), (4, 64), (34, 132), (35, 67), (64, 128), (97, 200)]
+FRONT_PLANES = [2, 3, 4, 5, 7]
+FRONT_VARIANTS = ["winner", "quantised_ties", "all_equal", "signed_zeros"]
+
+
+def front_stack(shape, C, variant):
+    """float32 (6, C, H, W): one frame per block-noise offset 0 .. 5 of a class field over 1 .. C."""
+    H, W = shape
+    fields = np.stack([sp.block_noise(shape, C, off, seed=100 * C + off) for off in range(6)])  # (6, H, W), 1 .. C
+    planes = np.arange(1, C + 1, dtype=np.uint8)[None, :, None, None]
+    won = fields[:, None] == planes
+    if variant == "winner":          # the field's class at 0.9, the other planes at 0.1
+        st = np.where(won, 0.9, 0.1)
+    elif variant == "quantised_ties":  # every plane a block field of its own over {3/4, 4/4}: two or more planes tie at the
+        # maximum in most pixels (all planes but one: C / 2^C of them do not), the first of them must win
+        st = np.stack([np.stack([sp.block_noise(shape, 2, off, seed=1000 * C + 10 * k + off) for k in range(C)]) for off in range(6)])
+        st = (st.astype(np.float64) + 2.0) / 4.0
+    elif variant == "all_equal":     # the same values in every plane: class 1 everywhere
+        st = np.repeat(fields[:, None].astype(np.float64) / 4.0, C, axis=1)
+    else:                            # -0.0 against +0.0 (equal: the first plane wins), and 1.0 in the last plane where the field says C
+        st = np.where(won, 0.0, -0.0)
+        st[:, C - 1][fields == C] = 1.0
+    return np.ascontiguousarray(st.astype(np.float32))
+
+
+@pytest.mark.parametrize("shape", FRONT_SHAPES)
+def test_classmap_label_front_end(ops, shape):
+    """classmap_label against argmax_planes -> median5 -> label_equal8 and against numpy's argmax + the oracle's median and
+    labelling, on block-noise stacks of 2, 3, 4, 5 and 7 planes (7: the unfused route) in four variants, each sent from an
+    aligned base pointer (16-byte loads where the width is a multiple of 4 and the tile lies inside the frame) and from
+    one a float past a 16-byte boundary (one pixel per load).  5 plane counts x 4 variants x 6 frames = 120 frames per
+    shape and alignment.  Rows 1, 2, 3: the reflected halo of a frame lower than the stencil, in the 16-byte path."""
+    H, W = shape
+    for C in FRONT_PLANES:
+        for variant in FRONT_VARIANTS:
+            st = front_stack(shape, C, variant)
+            what = "classmap_label %s C=%d %s" % (shape, C, variant)
+            cm = (np.argmax(st, axis=1) + 1).astype(np.uint8)
+            if variant == "all_equal":
+                assert (cm == 1).all()
+            if variant == "quantised_ties":
+                assert ((st == st.max(axis=1, keepdims=True)).sum(axis=1) >= 2).mean() > 0.45, what
+            den = np.stack([orc.median_filter(c) for c in cm])
+            res = [orc.label(d, return_num=True) for d in den]
+            exp = (dev(den), dev(np.stack([r[0] for r in res])), dev(np.array([r[1] for r in res], np.int32))[:, None])
+            x = dev(st)
+            z, lab, cnt = ops.classmap_label(x)
+            cls = ops.argmax_planes(x)
+            assert_frames_equal(cls, dev(cm), what + " (argmax_planes)")
+            z_sep = ops.median5(cls)
+            lab_sep, cnt_sep = ops.label_equal8(z_sep)
+            z_s, lab_s, cnt_s = ops.classmap_label(shifted(x))
+            for name, got in (("fused", (z, lab, cnt)), ("separate kernels", (z_sep, lab_sep, cnt_sep)),
+                              ("fused, shifted base pointer", (z_s, lab_s, cnt_s))):
+                for field, g, e in zip(("denoised", "labels", "counts"), (got[0], got[1], got[2][:, None]), exp):
+                    assert_frames_equal(g, e, "%s: %s %s" % (what, name, field))
