@@ -11,7 +11,7 @@
 // block scan + one exclusive scan of the block totals.
 #include <type_traits>
 
-#include "common.h"
+#include "column_pass.h"  // col_valid: the rows of a 32-row bit word inside the frame
 #include "tile_ops.h"
 
 namespace pcseg {
@@ -656,7 +656,7 @@ __global__ void __launch_bounds__(256) set_bits_kernel(const uint8_t *__restrict
     }
     {
         const int rows = min(32, H - ch * 32);
-        const unsigned valid = rows >= 32 ? 0xFFFFFFFFu : ((1u << rows) - 1u);
+        const unsigned valid = col_valid(rows);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -702,7 +702,7 @@ __global__ void __launch_bounds__(256) dilate_bits_kernel(const unsigned *__rest
         }
     }
     const int rows = min(32, H - ch * 32);
-    if (rows < 32) acc &= (1u << rows) - 1u;
+    acc &= col_valid(rows);
     out[((int64_t)b * nch + ch) * W + c] = acc;
 }
 
@@ -730,7 +730,7 @@ __global__ void __launch_bounds__(256) dilate_bits_disk2_kernel(const unsigned *
     acc |= (cur1 << 1) | (prev1 >> 31) | (cur1 >> 1) | (next1 << 31);
     acc |= (w0 << 2) | (u0 >> 30) | (w0 >> 2) | (d0 << 30);
     const int rows = min(32, H - ch * 32);
-    if (rows < 32) acc &= (1u << rows) - 1u;
+    acc &= col_valid(rows);
     out[((int64_t)b * nch + ch) * W + c] = acc;
 }
 

@@ -2,9 +2,10 @@
 // thresholds of it: disk(r) dilation (A6) and fill_particle_area (A8).
 //
 // Separable, integers only.  The input is read ONCE and reduced to one bit per
-// pixel (32-row column words); vertical distances come from bit scans of those
-// words plus a per-column carry across words, are staged per 8-row block in LDS
-// as uint16, and the horizontal pass is an expanding search that stops as soon
+// pixel; the vertical pass (target bit words, carries across the words of a
+// column, a row's distances, the staging of a row block) is column_pass.h,
+// shared with voronoi.hip -- the one carry kernel is defined here.  A target is
+// a ZERO pixel.  The horizontal pass is an expanding search that stops as soon
 // as k*k >= best (exact: the candidate at offset k is >= k*k).  HBM traffic is
 // the input read plus the int32 (or uint8) result write.
 //
@@ -13,15 +14,11 @@
 // (edt_reach_kernel) serves larger radii.
 #include <type_traits>
 
-#include "common.h"
+#include "column_pass.h"
 
 namespace pcseg {
 
-constexpr int EDT_CH = 32;          // rows per bit word
-constexpr int EDT_RB = 8;           // rows per block of the threshold pass (a divisor of the 32-row word)
-static_assert(EDT_CH % EDT_RB == 0, "a block's rows lie in one bit word");
-constexpr unsigned G_INF = 0xFFFFu;  // "no zero pixel in this column"
-constexpr int EDT_STAGE_TRIPS = 4;   // column words a thread fetches as one batch when it stages a row block
+constexpr int EDT_RB = 8;  // rows per block of the threshold pass (a divisor of the 32-row word)
 
 // ---- foreground predicates (distance is measured TO the nearest non-foreground pixel)
 struct FgNzU8 {
@@ -62,7 +59,7 @@ struct FgNotInSetU8 {
     __device__ __forceinline__ bool operator()(int b, int64_t pix, int64_t n) const { return byte(p[b * n + pix]); }
 };
 
-// one thread per (word, column): fg bits of 32 rows
+// one thread per (word, column): the target bits (NOT foreground, inside the frame) of 32 rows
 // (launch bounds: 94 scalar registers = seven workgroups per CU without the second argument, 78 = eight with it)
 // any_bg (may be null): any_bg[b] = 1 if the frame has a zero pixel at all -- one plain store per wave that saw one
 template <typename Fg>
@@ -72,28 +69,25 @@ __global__ void __launch_bounds__(256, 8) edt_bits_kernel(Fg fg, unsigned *__res
     const int ch = blockIdx.y, b = blockIdx.z;
     if (c >= W) return;
     const int64_t n = (int64_t)H * W;
-    const int r0 = ch * EDT_CH;
+    const int r0 = ch * COL_ROWS;
     unsigned word = 0;
-    if (r0 + EDT_CH <= H) {  // full word: no row test around the loads, all 32 of them in flight together
-        typename Fg::raw_t raw[EDT_CH];
+    if (r0 + COL_ROWS <= H) {  // full word: no row test around the loads, all 32 of them in flight together
+        typename Fg::raw_t raw[COL_ROWS];
 #pragma unroll
-        for (int j = 0; j < EDT_CH; ++j) raw[j] = fg.raw(b, rowoff((r0 + j), W) + c, n);
+        for (int j = 0; j < COL_ROWS; ++j) raw[j] = fg.raw(b, rowoff((r0 + j), W) + c, n);
 #pragma unroll
-        for (int j = 0; j < EDT_CH; ++j)
+        for (int j = 0; j < COL_ROWS; ++j)
             if (fg.from_raw(raw[j], b, rowoff((r0 + j), W) + c, n)) word |= 1u << j;
     } else {
 #pragma unroll 8
-        for (int j = 0; j < EDT_CH; ++j) {
+        for (int j = 0; j < COL_ROWS; ++j) {
             int r = r0 + j;
             if (r < H && fg(b, rowoff(r, W) + c, n)) word |= 1u << j;
         }
     }
+    word = ~word & col_valid(min(COL_ROWS, H - r0));
     bits[((int64_t)b * nch + ch) * W + c] = word;
-    if (any_bg) {
-        const int rows = min(EDT_CH, H - r0);
-        const bool zero = (~word & (rows >= 32 ? 0xFFFFFFFFu : ((1u << rows) - 1u))) != 0;
-        if (__any(zero) && __ffsll((long long)__ballot(true)) - 1 == lane_id()) any_bg[b] = 1;
-    }
+    if (any_bg && __any(word != 0) && __ffsll((long long)__ballot(true)) - 1 == lane_id()) any_bg[b] = 1;
 }
 
 // byte inputs with W % 4 == 0: a lane takes four adjacent columns (one 4-byte load per row, one 16-byte store)
@@ -104,42 +98,38 @@ __global__ void __launch_bounds__(256) edt_bits4_kernel(Fg fg, unsigned *__restr
     const int ch = blockIdx.y, b = blockIdx.z;
     if (c >= W) return;
     const uint8_t *src = fg.p + (int64_t)b * H * W + c;
-    const int r0 = ch * EDT_CH;
+    const int r0 = ch * COL_ROWS;
     unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0;
     // all 32 rows' loads in flight together (a row test around each load made them 32 dependent round trips): rows past the
     // frame's end re-read its last row and are masked out of the words
-    unsigned v[EDT_CH];
+    unsigned v[COL_ROWS];
 #pragma unroll
-    for (int j = 0; j < EDT_CH; ++j) v[j] = *reinterpret_cast<const unsigned *>(src + rowoff(min(r0 + j, H - 1), W));
+    for (int j = 0; j < COL_ROWS; ++j) v[j] = *reinterpret_cast<const unsigned *>(src + rowoff(min(r0 + j, H - 1), W));
 #pragma unroll
-    for (int j = 0; j < EDT_CH; ++j) {
+    for (int j = 0; j < COL_ROWS; ++j) {
         if (fg.byte(v[j] & 255u)) w0 |= 1u << j;
         if (fg.byte((v[j] >> 8) & 255u)) w1 |= 1u << j;
         if (fg.byte((v[j] >> 16) & 255u)) w2 |= 1u << j;
         if (fg.byte(v[j] >> 24)) w3 |= 1u << j;
     }
-    const int rows = min(EDT_CH, H - r0);
-    const unsigned valid = rows >= 32 ? 0xFFFFFFFFu : ((1u << rows) - 1u);
-    w0 &= valid; w1 &= valid; w2 &= valid; w3 &= valid;
+    const unsigned valid = col_valid(min(COL_ROWS, H - r0));
+    w0 = ~w0 & valid; w1 = ~w1 & valid; w2 = ~w2 & valid; w3 = ~w3 & valid;
     *reinterpret_cast<uint4 *>(bits + ((int64_t)b * nch + ch) * W + c) = make_uint4(w0, w1, w2, w3);
-    if (any_bg) {
-        const bool zero = ((~w0 | ~w1 | ~w2 | ~w3) & valid) != 0;
-        if (__any(zero) && __ffsll((long long)__ballot(true)) - 1 == lane_id()) any_bg[b] = 1;
-    }
+    if (any_bg && __any((w0 | w1 | w2 | w3) != 0) && __ffsll((long long)__ballot(true)) - 1 == lane_id()) any_bg[b] = 1;
 }
 
-// per column: distance from the first row of each word to the nearest zero above it (up),
-// and from the last row of each word to the nearest zero below it (dn); G_INF if none.
-// any_bg[b] = 1 if the frame has a zero pixel at all: one plain store per block (a flag that every thread of the bit
+// The carry kernel of column_pass.h.  Per column: up = distance from the first row of each word to the nearest target
+// above it, dn = from the last row of each word to the nearest target below it; COL_NONE if none.
+// any[b] = 1 if the frame has a target at all: one plain store per block (a flag that every thread of the bit
 // pass touches would make all of them queue on one cache line).
-__global__ void __launch_bounds__(256) edt_carry_kernel(const unsigned *__restrict__ bits, uint16_t *__restrict__ up,
-                                                         uint16_t *__restrict__ dn, int *__restrict__ any_bg, int H, int W, int nch)
+__global__ void __launch_bounds__(256) col_carry_kernel(const unsigned *__restrict__ bits, uint16_t *__restrict__ up,
+                                                         uint16_t *__restrict__ dn, int *__restrict__ any, int H, int W, int nch)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
     const int64_t base = (int64_t)b * nch * W + c;
-    bool has_zero = false;
-    unsigned d = G_INF;  // distance from row (r0 - 1) ... tracked as "distance of first row of the word to the zero"
+    bool has = false;
+    unsigned d = COL_NONE;  // distance of the first row of the word to the nearest target above it
     // (the words of a column are loaded eight at a time -- the carry depends on the previous word, the LOADS do not; one
     // load per step of the carry was a memory round trip per word with a quarter of the chip's wave slots in use)
     constexpr int CB = 8;
@@ -152,15 +142,13 @@ __global__ void __launch_bounds__(256) edt_carry_kernel(const unsigned *__restri
             const int ch = ch0 + k;
             if (ch >= nch) break;
             up[base + rowoff(ch, W)] = (uint16_t)d;
-            int rows = min(EDT_CH, H - ch * EDT_CH);
-            unsigned valid = rows == 32 ? 0xFFFFFFFFu : ((1u << rows) - 1u);
-            unsigned zero = ~wv[k] & valid;
-            if (zero) { d = rows - (31 - __clz(zero)); has_zero = true; }  // from first row of next word to the last zero of this word
-            else d = d == G_INF ? G_INF : d + rows;
+            const int rows = min(COL_ROWS, H - ch * COL_ROWS);
+            if (wv[k]) { d = rows - (31 - __clz(wv[k])); has = true; }  // from the first row of the next word to the last target of this one
+            else d = d == COL_NONE ? COL_NONE : d + rows;
         }
     }
-    if (__syncthreads_or(has_zero) && threadIdx.x == 0) any_bg[b] = 1;
-    d = G_INF;
+    if (__syncthreads_or(has) && threadIdx.x == 0) any[b] = 1;
+    d = COL_NONE;
     for (int ch0 = nch - 1; c < W && ch0 >= 0; ch0 -= CB) {
         unsigned wv[CB];
 #pragma unroll
@@ -170,25 +158,17 @@ __global__ void __launch_bounds__(256) edt_carry_kernel(const unsigned *__restri
             const int ch = ch0 - k;
             if (ch < 0) break;
             dn[base + rowoff(ch, W)] = (uint16_t)d;
-            int rows = min(EDT_CH, H - ch * EDT_CH);
-            unsigned valid = rows == 32 ? 0xFFFFFFFFu : ((1u << rows) - 1u);
-            unsigned zero = ~wv[k] & valid;
-            if (zero) d = (__ffs(zero) - 1) + 1;  // from last row of previous word to the first zero of this word
-            else d = d == G_INF ? G_INF : d + rows;
+            if (wv[k]) d = __ffs(wv[k]);  // from the last row of the previous word to the first target of this one
+            else d = d == COL_NONE ? COL_NONE : d + min(COL_ROWS, H - ch * COL_ROWS);
         }
     }
 }
 
-// vertical distance of row j (0..31) of a word
-__device__ __forceinline__ unsigned vdist(unsigned word, unsigned valid, int j, unsigned up, unsigned dn, int rows)
+int col_carry_launch(const ColWs &ws, int B, int H, int W, hipStream_t s)
 {
-    if (!((word >> j) & 1u)) return 0;
-    unsigned zero = ~word & valid;
-    unsigned below_or_at = zero & (j == 31 ? 0xFFFFFFFFu : ((2u << j) - 1u));  // zeros in rows <= j
-    unsigned above = zero & ~(j == 31 ? 0xFFFFFFFFu : ((2u << j) - 1u));        // zeros in rows > j
-    unsigned d1 = below_or_at ? (unsigned)(j - (31 - __clz(below_or_at))) : (up == G_INF ? G_INF : up + j);
-    unsigned d2 = above ? (unsigned)((__ffs(above) - 1) - j) : (dn == G_INF ? G_INF : dn + (rows - 1 - j));
-    return min(min(d1, d2), G_INF);
+    PCSEG_LAUNCH(col_carry_kernel, dim3((W + 255) / 256, B), dim3(256), 0, s, (const unsigned *)ws.bits, ws.up, ws.dn, ws.any, H, W, ws.nch);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
 }
 
 // ---- epilogues of the horizontal pass
@@ -273,34 +253,11 @@ __global__ void __launch_bounds__(256) edt_row_kernel(const unsigned *__restrict
     const int P = W + 2 * EDT_GUARD;
     const int b = blockIdx.y;
     const int r0 = blockIdx.x * RB;
-    const int ch = r0 / EDT_CH, j0 = r0 % EDT_CH;
-    const int rows_in_word = min(EDT_CH, H - ch * EDT_CH);
-    const unsigned valid = rows_in_word == 32 ? 0xFFFFFFFFu : ((1u << rows_in_word) - 1u);
     const int nrows = min(RB, H - r0);
-    const int64_t wbase = ((int64_t)b * nch + ch) * W;
-    // the column words of all trips are fetched as one batch (up to 4 trips = W <= 1024), then turned into distances
-    for (int cbase = 0; cbase < W; cbase += 256 * EDT_STAGE_TRIPS) {
-        unsigned wordv[EDT_STAGE_TRIPS], uv[EDT_STAGE_TRIPS], dv[EDT_STAGE_TRIPS];
-#pragma unroll
-        for (int t = 0; t < EDT_STAGE_TRIPS; ++t) {
-            const int c = min(cbase + (int)threadIdx.x + 256 * t, W - 1);
-            wordv[t] = bits[wbase + c];
-            uv[t] = up[wbase + c];
-            dv[t] = dn[wbase + c];
-        }
-#pragma unroll
-        for (int t = 0; t < EDT_STAGE_TRIPS; ++t) {
-            const int c = cbase + (int)threadIdx.x + 256 * t;
-            if (c < W) {
-#pragma unroll
-                for (int j = 0; j < RB; ++j)
-                    if (j < nrows) {
-                        const unsigned v = vdist(wordv[t], valid, j0 + j, uv[t], dv[t], rows_in_word);
-                        g2[j * P + c + EDT_GUARD] = v == G_INF ? EDT_D2_INF : v * v;
-                    }
-            }
-        }
-    }
+    col_stage_rows<RB>(bits, up, dn, b, r0, H, W, nch, [&](int j, int c, unsigned du, unsigned dd) {
+        const unsigned v = min(du, dd);
+        g2[j * P + c + EDT_GUARD] = v == COL_NONE ? EDT_D2_INF : v * v;
+    });
     if (threadIdx.x < 2 * EDT_GUARD * RB) {
         const int j = threadIdx.x / (2 * EDT_GUARD), q = threadIdx.x % (2 * EDT_GUARD);
         g2[j * P + (q < EDT_GUARD ? q : W + q)] = EDT_D2_INF;
@@ -378,11 +335,7 @@ __global__ void __launch_bounds__(256, 1) edt_reach_kernel(const unsigned *__res
     uint8_t *zb = reinterpret_cast<uint8_t *>(g + EDT_RB * W4);
     const int b = blockIdx.y;
     const int r0 = blockIdx.x * EDT_RB;
-    const int ch = r0 / EDT_CH, j0 = r0 % EDT_CH;
-    const int rows_in_word = min(EDT_CH, H - ch * EDT_CH);
-    const unsigned valid = rows_in_word == 32 ? 0xFFFFFFFFu : ((1u << rows_in_word) - 1u);
     const int nrows = min(EDT_RB, H - r0);
-    const int64_t wbase = ((int64_t)b * nch + ch) * W;
     const int64_t fbase = (int64_t)b * H * W;
     const int R2 = epi.R2();
     const unsigned gmax = (unsigned)sqrtf((float)R2) + 1;  // larger distances can never be within reach
@@ -406,29 +359,11 @@ __global__ void __launch_bounds__(256, 1) edt_reach_kernel(const unsigned *__res
     // rows whose every column is further than that from a zero pixel vertically (most of a frame when the zero set is
     // one compact object, like the particle of fill_particle_area): nothing is within reach, no scan is needed
     bool near = false;
-    for (int cbase = 0; cbase < W; cbase += 256 * EDT_STAGE_TRIPS) {  // batched like the staging of edt_row_kernel
-        unsigned wordv[EDT_STAGE_TRIPS], uv[EDT_STAGE_TRIPS], dv[EDT_STAGE_TRIPS];
-#pragma unroll
-        for (int t = 0; t < EDT_STAGE_TRIPS; ++t) {
-            const int c = min(cbase + (int)threadIdx.x + 256 * t, W - 1);
-            wordv[t] = bits[wbase + c];
-            uv[t] = up[wbase + c];
-            dv[t] = dn[wbase + c];
-        }
-#pragma unroll
-        for (int t = 0; t < EDT_STAGE_TRIPS; ++t) {
-            const int c = cbase + (int)threadIdx.x + 256 * t;
-            if (c < W) {
-#pragma unroll
-                for (int j = 0; j < EDT_RB; ++j)
-                    if (j < nrows) {
-                        const unsigned v = min(vdist(wordv[t], valid, j0 + j, uv[t], dv[t], rows_in_word), 0x7FFFu);
-                        g[j * W4 + c] = (uint16_t)v;  // bit 15 stays free
-                        near = near || v <= gmax;
-                    }
-            }
-        }
-    }
+    col_stage_rows<EDT_RB>(bits, up, dn, b, r0, H, W, nch, [&](int j, int c, unsigned du, unsigned dd) {
+        const unsigned v = min(min(du, dd), 0x7FFFu);
+        g[j * W4 + c] = (uint16_t)v;  // bit 15 stays free
+        near = near || v <= gmax;
+    });
     const bool any_near = __syncthreads_or(near);
     const bool anybg = any_bg[b] != 0;
     const int lane = lane_id(), wave = threadIdx.x >> 6;
@@ -525,7 +460,7 @@ __global__ void __launch_bounds__(RBIT_THREADS) reach_bits_kernel(const unsigned
     unsigned *acc_lds = rb_lds + tab.nslots * RBIT_THREADS;
     const int b = blockIdx.z, ch = blockIdx.y, c0 = blockIdx.x * tab.tc;
     const int t = threadIdx.x, c = c0 - RBIT_HALO + t;
-    // (1) the column's zero bits in the word rows above, here and below (nothing outside the frame is a zero pixel)
+    // (1) the column's target bits in the word rows above, here and below (nothing outside the frame is a zero pixel)
     unsigned w0 = 0, w1 = 0, w2 = 0;
     {
         const int cc = min(max(c, 0), W - 1);
@@ -533,12 +468,10 @@ __global__ void __launch_bounds__(RBIT_THREADS) reach_bits_kernel(const unsigned
         const int64_t base = (int64_t)b * nch * W + cc;
         const unsigned r0w = bits[base + rowoff(max(ch - 1, 0), W)], r1w = bits[base + rowoff(ch, W)],
                        r2w = bits[base + rowoff(min(ch + 1, nch - 1), W)];
-        const int rows_last = H - (nch - 1) * EDT_CH;  // rows of the frame's last word
-        const unsigned v_last = rows_last >= 32 ? 0xFFFFFFFFu : ((1u << rows_last) - 1u);
         if (col_in) {
-            w1 = ~r1w & (ch == nch - 1 ? v_last : 0xFFFFFFFFu);
-            if (ch > 0) w0 = ~r0w;
-            if (ch + 1 < nch) w2 = ~r2w & (ch + 1 == nch - 1 ? v_last : 0xFFFFFFFFu);
+            w1 = r1w;
+            if (ch > 0) w0 = r0w;
+            if (ch + 1 < nch) w2 = r2w;
         }
     }
     {
@@ -579,7 +512,7 @@ __global__ void __launch_bounds__(RBIT_THREADS) reach_bits_kernel(const unsigned
             // the eight rows' bits of the four columns, one byte per column
             const unsigned m = ((a.x >> (8 * g)) & 255u) | (((a.y >> (8 * g)) & 255u) << 8) | (((a.z >> (8 * g)) & 255u) << 16) |
                                (((a.w >> (8 * g)) & 255u) << 24);
-            const int rr0 = ch * EDT_CH + 8 * g;
+            const int rr0 = ch * COL_ROWS + 8 * g;
             unsigned z4[8];
             if (Epi::kInput) {
 #pragma unroll
@@ -598,8 +531,8 @@ __global__ void __launch_bounds__(RBIT_THREADS) reach_bits_kernel(const unsigned
         // business per pixel: scipy's virtual zero pixel): a column per thread, byte by byte
         const unsigned a = acc_lds[RBIT_HALO + t];
         const int cc = c0 + t;
-        for (int j = 0; j < EDT_CH; ++j) {
-            const int r = ch * EDT_CH + j;
+        for (int j = 0; j < COL_ROWS; ++j) {
+            const int r = ch * COL_ROWS + j;
             if (r >= H) break;
             const int64_t i = fbase + rowoff(r, W) + cc;
             epi.out[i] = epi.decide(Epi::kInput ? epi.input()[i] : (uint8_t)0, ((a >> j) & 1u) != 0, anybg, r, cc, cnt);
@@ -620,25 +553,13 @@ __global__ void __launch_bounds__(RBIT_THREADS) reach_bits_kernel(const unsigned
     }
 }
 
-struct EdtWs {
-    unsigned *bits;
-    uint16_t *up, *dn;
-    int *any_bg;
+struct EdtWs : ColWs {
     unsigned long long *block_counts;  // [B][ceil(H / EDT_RB)] partial counts of the threshold epilogues
-    int nch;
 };
 
 static EdtWs edt_carve(Carver &cv, int B, int H, int W)
 {
-    EdtWs ws;
-    ws.nch = (H + EDT_CH - 1) / EDT_CH;
-    size_t words = (size_t)B * ws.nch * W;
-    ws.bits = cv.take<unsigned>(words);
-    ws.up = cv.take<uint16_t>(words);
-    ws.dn = cv.take<uint16_t>(words);
-    ws.any_bg = cv.take<int>(B);
-    ws.block_counts = cv.take<unsigned long long>((size_t)B * ((H + EDT_RB - 1) / EDT_RB));
-    return ws;
+    return EdtWs{col_carve(cv, B, H, W), cv.take<unsigned long long>((size_t)B * ((H + EDT_RB - 1) / EDT_RB))};
 }
 
 template <typename Fg, typename Epi>
@@ -656,7 +577,7 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
         set_error("%s: W = %d too wide for the LDS row stage", who, W);
         return PCSEG_ERR_ARG;
     }
-    PCSEG_CHECK_HIP(hipMemsetAsync(ws.any_bg, 0, sizeof(int) * B, s));
+    PCSEG_CHECK_HIP(hipMemsetAsync(ws.any, 0, sizeof(int) * B, s));
     dim3 g1((W + 255) / 256, ws.nch, B);
     bool wide = false;
     if constexpr (Fg::kBytes) wide = (W & 3) == 0 && ((uintptr_t)fg.p & 3) == 0 && ((uintptr_t)ws.bits & 15) == 0;
@@ -687,7 +608,7 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
             }
         }
     }
-    int *bits_any = bit_path ? ws.any_bg : nullptr;  // (the carry pass sets the flag on the other paths)
+    int *bits_any = bit_path ? ws.any : nullptr;  // (the carry pass sets the flag on the other paths)
     if (wide) {
         if constexpr (Fg::kBytes)
             PCSEG_LAUNCH((edt_bits4_kernel<Fg>), dim3((W / 4 + 255) / 256, ws.nch, B), dim3(256), 0, s, fg, ws.bits, bits_any, H, W, ws.nch);
@@ -704,18 +625,17 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
             tab.tc = std::min(RBIT_TC, (((W + nblk - 1) / nblk) + 3) & ~3);
             const int threads = (tab.tc + 2 * RBIT_HALO + WAVE - 1) / WAVE * WAVE;  // whole waves; the rest of the 512 would idle
             PCSEG_LAUNCH((reach_bits_kernel<Epi>), dim3((W + tab.tc - 1) / tab.tc, ws.nch, B), dim3(threads), bytes, s,
-                         (const unsigned *)ws.bits, (const int *)ws.any_bg, epi, count, tab, H, W, ws.nch);
+                         (const unsigned *)ws.bits, (const int *)ws.any, epi, count, tab, H, W, ws.nch);
             PCSEG_CHECK_LAUNCH();
             return PCSEG_OK;
         }
     }
-    PCSEG_LAUNCH(edt_carry_kernel, dim3((W + 255) / 256, B), dim3(256), 0, s, ws.bits, ws.up, ws.dn, ws.any_bg, H, W, ws.nch);
-    PCSEG_CHECK_LAUNCH();
+    if (const int rc = col_carry_launch(ws, B, H, W, s)) return rc;
     dim3 g2((H + EDT_RB - 1) / EDT_RB, B);
     if constexpr (Epi::kThreshold) {
         if (lds > 64 * 1024)
             PCSEG_CHECK_HIP(hipFuncSetAttribute((const void *)edt_reach_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        PCSEG_LAUNCH((edt_reach_kernel<Epi>), g2, dim3(256), lds, s, ws.bits, ws.up, ws.dn, ws.any_bg, epi,
+        PCSEG_LAUNCH((edt_reach_kernel<Epi>), g2, dim3(256), lds, s, ws.bits, ws.up, ws.dn, ws.any, epi,
                      count ? ws.block_counts : nullptr, H, W, ws.nch);
         if (count) {
             PCSEG_CHECK_LAUNCH();
@@ -728,7 +648,7 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
             const size_t bytes = (size_t)RB * (W + 2 * EDT_GUARD) * sizeof(unsigned);
             if (bytes > 64 * 1024)
                 PCSEG_CHECK_HIP(hipFuncSetAttribute((const void *)edt_row_kernel<Epi, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-            PCSEG_LAUNCH((edt_row_kernel<Epi, RB>), dim3((H + RB - 1) / RB, B), dim3(256), bytes, s, ws.bits, ws.up, ws.dn, ws.any_bg, epi,
+            PCSEG_LAUNCH((edt_row_kernel<Epi, RB>), dim3((H + RB - 1) / RB, B), dim3(256), bytes, s, ws.bits, ws.up, ws.dn, ws.any, epi,
                          count, H, W, ws.nch);
             return PCSEG_OK;
         };

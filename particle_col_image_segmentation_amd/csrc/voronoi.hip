@@ -2,9 +2,11 @@
 // territories (discrete Voronoi cells, optionally limited to a reach) and the adjacency graph of the territories
 // (scipy.ndimage.distance_transform_edt(return_indices=True), skimage.segmentation.expand_labels; include/pcseg.h).
 //
-// Integers only, so nothing depends on the order of the atomics.  Launches (asynchronous, no host read):
+// Integers only, so nothing depends on the order of the atomics.  The vertical pass (bit words whose targets are the SITES,
+// carries, a row's distances, the staging of a row block) is column_pass.h, shared with edt.hip, where its carry kernel lives.
+// Launches (asynchronous, no host read):
 //   vor_bits_kernel      site bits of the label image, 32 rows of a column per word (a site: a label in 1 .. cap that `sel` keeps)
-//   vor_carry_kernel     per column and word: distance from the word's first / last row to the nearest site above / below it
+//   col_carry_kernel     (edt.hip) per column and word: distance from the word's first / last row to the nearest site above / below it
 //   vor_row_kernel       a row block's vertical distances staged in LDS as (g, site above, site below); per pixel an expanding
 //                        search over the column offsets k = 0, 1, .. that stops only when k * k > best, so that EQUALLY near
 //                        sites are all seen: (d2, label, raster index) is minimised lexicographically, and a column's upper AND
@@ -20,6 +22,7 @@
 //                        distinct partners per ROI and type slot)
 #include <type_traits>
 
+#include "column_pass.h"
 #include "label_reduce.h"
 
 // (no floating point in here; the pragma keeps any that is added later rounded operation by operation, as surface.hip)
@@ -27,8 +30,6 @@
 
 namespace pcseg {
 
-constexpr int VOR_CH = 32;               // rows per bit word
-constexpr unsigned VOR_NONE = 0xFFFFu;   // carry: no site that way in this column
 // staged vertical distance of a column without site: its square is >= 2^31 > any d2 of a frame (check_shape: H, W <= 32768
 // and H W < 2^30 give d2 < 2^31), and adding k * k (k <= 32767 + 3) still fits 32 bits
 constexpr unsigned VOR_G_NONE = 46341u;
@@ -50,57 +51,16 @@ __global__ void __launch_bounds__(256) vor_bits_kernel(const int *__restrict__ l
     if (c >= W) return;
     const int *lab = labels + (int64_t)b * H * W + c;
     const SiteTest site{sel ? sel + (int64_t)b * cap : nullptr, cap};
-    const int r0 = ch * VOR_CH;
-    int v[VOR_CH];
+    const int r0 = ch * COL_ROWS;
+    int v[COL_ROWS];
 #pragma unroll
-    for (int j = 0; j < VOR_CH; ++j) v[j] = lab[rowoff(min(r0 + j, H - 1), W)];
+    for (int j = 0; j < COL_ROWS; ++j) v[j] = lab[rowoff(min(r0 + j, H - 1), W)];
     unsigned word = 0;
 #pragma unroll
-    for (int j = 0; j < VOR_CH; ++j)
+    for (int j = 0; j < COL_ROWS; ++j)
         if (site(v[j])) word |= 1u << j;
-    const int rows = min(VOR_CH, H - r0);
-    if (rows < 32) word &= (1u << rows) - 1u;
+    word &= col_valid(min(COL_ROWS, H - r0));
     bits[((int64_t)b * nch + ch) * W + c] = word;
-}
-
-// per column: up[ch] = distance from the first row of word ch to the nearest site in the words above it, dn[ch] = from its
-// last row to the nearest site in the words below it; VOR_NONE if none.  any_site[b] = 1 if the frame has a site at all
-__global__ void __launch_bounds__(256) vor_carry_kernel(const unsigned *__restrict__ bits, uint16_t *__restrict__ up,
-                                                         uint16_t *__restrict__ dn, int *__restrict__ any_site, int H, int W, int nch)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    const int b = blockIdx.y;
-    const int64_t base = (int64_t)b * nch * W + c;
-    bool has = false;
-    unsigned d = VOR_NONE;
-    for (int ch = 0; c < W && ch < nch; ++ch) {
-        const unsigned w = bits[base + rowoff(ch, W)];
-        up[base + rowoff(ch, W)] = (uint16_t)d;
-        const int rows = min(VOR_CH, H - ch * VOR_CH);
-        if (w) { d = rows - (31 - __clz(w)); has = true; }
-        else d = d == VOR_NONE ? VOR_NONE : d + rows;
-    }
-    if (__syncthreads_or(has) && threadIdx.x == 0) any_site[b] = 1;
-    d = VOR_NONE;
-    for (int ch = nch - 1; c < W && ch >= 0; --ch) {
-        const unsigned w = bits[base + rowoff(ch, W)];
-        dn[base + rowoff(ch, W)] = (uint16_t)d;
-        const int rows = min(VOR_CH, H - ch * VOR_CH);
-        if (w) d = __ffs(w);  // from the last row of the word above to the first site of this one
-        else d = d == VOR_NONE ? VOR_NONE : d + rows;
-    }
-}
-
-// the staged cell of row j (0 .. 31) of a word: distance to the nearest site of the column and on which side(s) it lies
-__device__ __forceinline__ unsigned site_cell(unsigned word, int j, unsigned up, unsigned dn, int rows)
-{
-    const unsigned le_mask = j == 31 ? 0xFFFFFFFFu : ((2u << j) - 1u);
-    const unsigned le = word & le_mask, gt = word & ~le_mask;  // sites in rows <= j (the pixel's own among them), in rows > j
-    const unsigned du = le ? (unsigned)(j - (31 - __clz(le))) : (up == VOR_NONE ? VOR_NONE : up + j);
-    const unsigned dd = gt ? (unsigned)((__ffs(gt) - 1) - j) : (dn == VOR_NONE ? VOR_NONE : dn + (rows - 1 - j));
-    const unsigned g = min(du, dd);
-    if (g == VOR_NONE) return VOR_G_NONE;
-    return g | (du == g ? VOR_UP : 0u) | (dd == g ? VOR_DN : 0u);
 }
 
 template <int RB>
@@ -113,8 +73,6 @@ __global__ void __launch_bounds__(256) vor_row_kernel(const int *__restrict__ la
     const int P = W + 2;
     const int b = blockIdx.y;
     const int r0 = blockIdx.x * RB;
-    const int ch = r0 / VOR_CH, j0 = r0 % VOR_CH;
-    const int rows_in_word = min(VOR_CH, H - ch * VOR_CH);
     const int nrows = min(RB, H - r0);
     const int64_t fbase = (int64_t)b * H * W;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -129,13 +87,11 @@ __global__ void __launch_bounds__(256) vor_row_kernel(const int *__restrict__ la
             }
         return;
     }
-    const int64_t wbase = ((int64_t)b * nch + ch) * W;
-    for (int c = threadIdx.x; c < W; c += 256) {
-        const unsigned word = bits[wbase + c], u = up[wbase + c], d = dn[wbase + c];
-#pragma unroll
-        for (int j = 0; j < RB; ++j)
-            if (j < nrows) cells[j * P + c + 1] = site_cell(word, j0 + j, u, d, rows_in_word);
-    }
+    // the staged cell: distance to the nearest site of the column and on which side(s) it lies
+    col_stage_rows<RB>(bits, up, dn, b, r0, H, W, nch, [&](int j, int c, unsigned du, unsigned dd) {
+        const unsigned g = min(du, dd);
+        cells[j * P + c + 1] = g == COL_NONE ? VOR_G_NONE : g | (du == g ? VOR_UP : 0u) | (dd == g ? VOR_DN : 0u);
+    });
     if (threadIdx.x < 2 * RB) cells[(threadIdx.x >> 1) * P + ((threadIdx.x & 1) ? W + 1 : 0)] = VOR_G_NONE;
     __syncthreads();
     const int *lab = labels + fbase;
@@ -191,25 +147,6 @@ __global__ void __launch_bounds__(256) vor_row_kernel(const int *__restrict__ la
             near_out[gi] = lbl;
             if (site_out) site_out[gi] = q;
         }
-}
-
-struct VorWs {
-    unsigned *bits;
-    uint16_t *up, *dn;
-    int *any_site;
-    int nch;
-};
-
-static VorWs vor_carve(Carver &cv, int B, int H, int W)
-{
-    VorWs ws;
-    ws.nch = (H + VOR_CH - 1) / VOR_CH;
-    const size_t words = (size_t)B * ws.nch * W;
-    ws.bits = cv.take<unsigned>(words);
-    ws.up = cv.take<uint16_t>(words);
-    ws.dn = cv.take<uint16_t>(words);
-    ws.any_site = cv.take<int>(B);
-    return ws;
 }
 
 // ---- the label of a pixel within reach
@@ -557,7 +494,7 @@ size_t pcseg_nearest_label_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
     Carver cv(nullptr, 0);
-    vor_carve(cv, B, H, W);
+    col_carve(cv, B, H, W);
     return cv.off;
 }
 
@@ -566,18 +503,16 @@ int pcseg_nearest_label_i32(const int32_t *labels, const uint8_t *sel, int cap, 
 {
     PCSEG_REQUIRE(labels && d2 && near && workspace && check_shape(B, H, W) && cap >= 1 && B <= 65535, "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    const VorWs ws = vor_carve(cv, B, H, W);
+    const ColWs ws = col_carve(cv, B, H, W);
     if (!cv.ok()) {
         set_error("nearest_label_i32: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    PCSEG_CHECK_HIP(hipMemsetAsync(ws.any_site, 0, sizeof(int) * B, s));
+    PCSEG_CHECK_HIP(hipMemsetAsync(ws.any, 0, sizeof(int) * B, s));
     PCSEG_LAUNCH(vor_bits_kernel, dim3((W + 255) / 256, ws.nch, B), dim3(256), 0, s, labels, sel, cap, ws.bits, H, W, ws.nch);
     PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(vor_carry_kernel, dim3((W + 255) / 256, B), dim3(256), 0, s, (const unsigned *)ws.bits, ws.up, ws.dn, ws.any_site, H,
-                 W, ws.nch);
-    PCSEG_CHECK_LAUNCH();
+    if (const int rc = col_carry_launch(ws, B, H, W, s)) return rc;
     // rows per block: four while a block's stage stays within 64 KB (W <= 4094: two and more blocks per CU; the occupancy
     // argument of the distance transform's row pass), else one (W = 32768: 128 KB, one block per CU)
     const size_t per_row = (size_t)(W + 2) * sizeof(unsigned);
@@ -587,7 +522,7 @@ int pcseg_nearest_label_i32(const int32_t *labels, const uint8_t *sel, int cap, 
         if (bytes > 64 * 1024)
             PCSEG_CHECK_HIP(hipFuncSetAttribute((const void *)vor_row_kernel<RB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         PCSEG_LAUNCH((vor_row_kernel<RB>), dim3((H + RB - 1) / RB, B), dim3(256), bytes, s, labels, (const unsigned *)ws.bits,
-                     (const uint16_t *)ws.up, (const uint16_t *)ws.dn, (const int *)ws.any_site, d2, near, site, H, W, ws.nch);
+                     (const uint16_t *)ws.up, (const uint16_t *)ws.dn, (const int *)ws.any, d2, near, site, H, W, ws.nch);
         return PCSEG_OK;
     };
     int rc;
