@@ -39,7 +39,8 @@ enum pcseg_status {
     PCSEG_ERR_ARG = -1,       /* bad shape / null pointer / unsupported size */
     PCSEG_ERR_HIP = -2,       /* a HIP call or launch failed */
     PCSEG_ERR_WORKSPACE = -3, /* workspace too small */
-    PCSEG_ERR_CAPACITY = -4   /* more labels than the caller's table capacity */
+    PCSEG_ERR_CAPACITY = -4,  /* more labels than the caller's table capacity */
+    PCSEG_ERR_CONVERGENCE = -5 /* an iteration passed its bound without reaching its fixed point */
 };
 
 /* layout of one row of the region table (int64 each) -- skimage regionprops
@@ -592,6 +593,43 @@ int pcseg_territory_pairs(const int32_t *near, const int32_t *d2, int64_t R2, in
 int pcseg_territory_pairs_write(int pair_cap, const int64_t *offsets, const uint8_t *slot_of, int cap, int n_types, int64_t *key,
                                 int32_t *frame, int32_t *counts, int32_t *degree, int B, const void *workspace,
                                 size_t workspace_bytes, pcseg_stream_t stream);
+
+/* ---- per-ROI skeletons (csrc/skeleton.hip): exact Guo-Hall thinning, every label on its own -- the union over l of
+ * skimage.morphology.thin(labels == l) of scikit-image 0.18.3 -- and per ROI the length and the ends / junctions of its
+ * skeleton.  Integers only.
+ * pcseg_thin_labels: labels device int32 (B, H, W), any width and alignment; values <= 0 are background, labels may touch and
+ * need not be consecutive.  A neighbour counts only if it is alive and carries the centre's label; outside the frame is
+ * background.  With N = sum 2^i b[i], b[0..7] = E, NE, N, NW, W, SW, S, SE (indices mod 8):
+ *   G1   exactly one i in {0, 2, 4, 6} has !b[i] && (b[i + 1] || b[i + 2])
+ *   G2   min(n1, n2) in {2, 3}, n1 = #{k in {1, 3, 5, 7}: b[k] || b[k - 1]}, n2 = #{k: b[k] || b[k + 1]}
+ *   G3   !((b[1] || b[2] || !b[7]) && b[0])        G3'  !((b[5] || b[6] || !b[3]) && b[4])
+ * the first sub-iteration deletes the alive pixels with G1 && G2 && G3, the second, on its result, those with G1 && G2 && G3';
+ * a full iteration is the pair.  It stops after the first full iteration that deletes nothing or after max_iter full
+ * iterations (max_iter < 0: no limit; 0: none).  peel device uint16 (B, H, W): 0 background, 65535 the pixel survives (the
+ * skeleton), otherwise the 1-based sub-iteration that deleted it (odd: first table; full iteration (s + 1) / 2).  iters
+ * device int32 (B): the full iterations of the frame that deleted a pixel.  The call WAITS for the stream (two counters per
+ * launch decide whether another one follows) and cannot be captured into a graph; H + W full iterations without an end
+ * return PCSEG_ERR_CONVERGENCE ("thinning did not converge").  B <= 65535.
+ * pcseg_region_skeleton: labels and peel as above, counts device int32 (B); table device int64 (B, cap, 6), rows l = 1 ..
+ * min(counts[b], cap) (row l - 1; the others stay untouched, labels above are ignored; zeros for a label without pixel).
+ * Links join skeleton pixels (peel == 65535) of EQUAL label: two 4-adjacent ones form an orthogonal link, two diagonal ones
+ * a diagonal link only if neither of the two pixels 4-adjacent to both is a skeleton pixel of that label (an L-corner is two
+ * links, not three).  The degree of a pixel is its number of links.
+ *   0  skel_px   1  n_orth   2  n_diag   3  n_end (degree 1)   4  n_junction (degree >= 3)
+ *   5  passes: (max s + 1) / 2 over the label's deleted pixels, 0 if none
+ * Asynchronous, nothing is allocated.
+ * pcseg_skeleton_properties: stats device int64 (B, cap, 8) (pcseg_region_col rows of the same labels), out device float64
+ * (B, cap, 2), rows below min(counts[b], cap); NaN for a label without pixel:
+ *   0  length_px = n_orth + n_diag * sqrt(2.0) (one rounded product, one rounded sum, no FMA)
+ *   1  width_px = area / length_px (one division; inf for a one-pixel skeleton) */
+size_t pcseg_thin_labels_workspace_bytes(int B, int H, int W);
+int pcseg_thin_labels(const int32_t *labels, uint16_t *peel, int32_t *iters, int B, int H, int W, int max_iter, void *workspace,
+                      size_t workspace_bytes, pcseg_stream_t stream);
+size_t pcseg_region_skeleton_workspace_bytes(int B, int H, int W, int cap);
+int pcseg_region_skeleton(const int32_t *labels, const uint16_t *peel, const int32_t *counts, int64_t *table, int B, int H, int W,
+                          int cap, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_skeleton_properties(const int64_t *stats, const int64_t *table, const int32_t *counts, double *out, int B, int cap,
+                              pcseg_stream_t stream);
 
 /* ---- X1 (north_star extension; refine_boundaries.py:22 imports skimage.filters and never calls it): the library
  * SURVEY.md 8a names is the oracle -- skimage.filters.threshold_otsu(float32 image, nbins=256), pinned by

@@ -296,6 +296,93 @@ def hull_properties(stats, hull, counts):
     return out
 
 
+SKELETON_COLUMNS = ("skel_px", "n_orth", "n_diag", "n_end", "n_junction", "passes", "length_px", "width_px")
+PEEL_SKELETON = 65535                # the peel value of a pixel that survives
+THIN_TILE, THIN_HALO = (64, 32), 8   # csrc/skeleton.hip: a tile (width, height) and its halo = sub-iterations per launch
+
+
+def _labels_arg(labels):
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("labels must be an int32 (B, H, W) tensor")
+    # (a contiguous view keeps its base address: unaligned images are taken as they are)
+    return labels if labels.is_contiguous() else labels.contiguous()
+
+
+def thin_labels(labels, max_iter=None):
+    """Exact Guo-Hall thinning of a label batch, every label on its own (csrc/skeleton.hip, include/pcseg.h): the union over
+    l of ``skimage.morphology.thin(labels == l, max_iter)`` of scikit-image 0.18.3.  ``labels`` (B, H, W) int32 CUDA tensor
+    of any width and alignment; values <= 0 are background, labels may touch and need not be consecutive.  Returns ``(peel,
+    iters)``: uint16 (B, H, W) -- 0 background, 65535 the pixel survives (the skeleton), otherwise the 1-based sub-iteration
+    that deleted it (full iteration ``(s + 1) // 2``) -- and int32 (B,), the full iterations of a frame that deleted a
+    pixel.  Waits for the device between launches (the host decides whether another one follows): not for graph capture."""
+    labels = _labels_arg(labels)
+    B, H, W = labels.shape
+    dev = labels.device
+    peel = torch.empty((B, H, W), dtype=torch.uint16, device=dev)
+    iters = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.pcseg_thin_labels_workspace_bytes(B, H, W)
+    ws = _ws(nbytes, dev)
+    _lib.check(lib.pcseg_thin_labels(_ptr(labels), _ptr(peel), _ptr(iters), B, H, W, -1 if max_iter is None else int(max_iter),
+                                     _ptr(ws), nbytes, _stream()), "thin_labels")
+    return peel, iters
+
+
+def thin(image, max_iter=None):
+    """``skimage.morphology.thin``: ``image`` a (B, H, W) CUDA tensor, bool / uint8 (a mask: non-zero is foreground) or int32
+    (labels, each thinned on its own) -> the bool skeleton."""
+    if isinstance(image, torch.Tensor) and image.dtype in (torch.bool, torch.uint8):
+        image = (image != 0).to(torch.int32)
+    peel, _ = thin_labels(image, max_iter)
+    # (torch has no comparison kernel for uint16: its bit pattern as int16 -- 65535 is -1)
+    return peel.view(torch.int16) == -1
+
+
+def region_skeleton(labels, peel, counts, cap=None):
+    """The integer skeleton table of a label batch: ``labels`` (B, H, W) int32, ``peel`` of :func:`thin_labels` over the same
+    labels, ``counts`` (B,) int32.  Returns int64 (B, cap, 6) = skel_px, n_orth, n_diag, n_end, n_junction, passes for the
+    labels 1 .. min(counts[b], cap) (rows beyond are not initialised; labels above are ignored; ``cap`` defaults to
+    max(counts)): the skeleton's pixels, its orthogonal and diagonal links between pixels of the same label (a diagonal pair
+    is a link only if neither pixel next to both is on the label's skeleton), the pixels with one link and with three or
+    more, and the full iterations the label took."""
+    labels = _labels_arg(labels)
+    counts = _req(counts, torch.int32, 1)
+    B, H, W = labels.shape
+    if not isinstance(peel, torch.Tensor) or not peel.is_cuda or peel.dtype != torch.uint16 or tuple(peel.shape) != (B, H, W):
+        raise TypeError("peel must be a uint16 CUDA tensor of the labels' shape")
+    peel = peel.contiguous()
+    if counts.shape[0] != B:
+        raise ValueError("counts must have one entry per frame")
+    if cap is None:
+        cap = max(1, int(counts.max().item()))
+    cap = int(cap)
+    table = torch.empty((B, cap, 6), dtype=torch.int64, device=labels.device)
+    lib = _lib.load()
+    nbytes = lib.pcseg_region_skeleton_workspace_bytes(B, H, W, cap)
+    ws = _ws(nbytes, labels.device)
+    _lib.check(lib.pcseg_region_skeleton(_ptr(labels), _ptr(peel), _ptr(counts), _ptr(table), B, H, W, cap, _ptr(ws), nbytes,
+                                         _stream()), "region_skeleton")
+    return table
+
+
+def skeleton_properties(stats, table, counts):
+    """The derived skeleton columns, in pixels: ``stats`` int64 (B, cap, 8) of :func:`region_reduce` and ``table`` of
+    :func:`region_skeleton` over the same labels -> float64 (B, cap, 2) = length_px (n_orth + n_diag * sqrt 2), width_px
+    (area / length_px; inf for a one-pixel skeleton), rows below min(counts[b], cap); NaN for a label without pixel."""
+    stats = _req(stats, torch.int64, 3)
+    table = _req(table, torch.int64, 3)
+    counts = _req(counts, torch.int32, 1)
+    B, cap = stats.shape[0], stats.shape[1]
+    if tuple(stats.shape) != (B, cap, 8) or tuple(table.shape) != (B, cap, 6) or counts.shape[0] != B:
+        raise ValueError("stats must be (B, cap, 8), table (B, cap, 6), counts (B,)")
+    out = torch.empty((B, cap, 2), dtype=torch.float64, device=stats.device)
+    _lib.check(_lib.load().pcseg_skeleton_properties(_ptr(stats), _ptr(table), _ptr(counts), _ptr(out), B, cap, _stream()),
+               "skeleton_properties")
+    return out
+
+
 def threshold_lt(img, threshold):
     """binary_mask = boundary_map < threshold (refine_boundaries.py:44-45)."""
     img = _req(img, torch.float32, 3)
@@ -803,13 +890,36 @@ def _hull_rows(labels, counts, stats, live, slot_of, frame_ids, scale):
                         pr[:, 0] / per_um2], dim=1)
 
 
+def _skeleton_rows(labels, counts, stats, live, slot_of, frame_ids, scale):
+    """The ``skeletons`` table of one label batch: :func:`thin_labels` + :func:`region_skeleton` + :func:`skeleton_properties`
+    on the whole batch, then the rows ``live`` ((B, cap) bool) in (frame, label) order as ``[frame, label, slot, skel_px,
+    n_orth, n_diag, n_end, n_junction, passes, length_um, width_um]`` (the two lengths / ``scale``, each ONE correctly rounded
+    division)."""
+    # only the rows asked for are thinned (every label is thinned on its own, so their skeletons do not change): the class-map
+    # components cover the whole frame, and background and particle would set the iteration count and keep every tile listed
+    B, cap = live.shape
+    keep = torch.zeros((B, cap + 2), dtype=torch.int32, device=labels.device)
+    keep[:, 1:cap + 1] = live * torch.arange(1, cap + 1, dtype=torch.int32, device=labels.device)
+    labels = torch.gather(keep, 1, labels.clamp(0, cap + 1).reshape(B, -1).to(torch.int64)).reshape(labels.shape)
+    peel, _ = thin_labels(labels)
+    table = region_skeleton(labels, peel, counts, cap=cap)
+    props = skeleton_properties(stats, table, counts)
+    b, l = torch.nonzero(live, as_tuple=True)
+    tb, pr = table[b, l].to(torch.float64), props[b, l]
+    slot = slot_of[b, l].to(torch.int64)
+    slot = torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
+    per_um = torch.full_like(pr[:, 0], scale)  # tensor divisor: a correctly rounded division per element (see _hull_rows)
+    return torch.stack([frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), slot] + [tb[:, k] for k in range(6)]
+                       + [pr[:, 0] / per_um, pr[:, 1] / per_um], dim=1)
+
+
 def _rows_below(counts, cap):
     return torch.arange(cap, device=counts.device)[None, :] < counts[:, None]
 
 
 def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
                  n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None, convex=False,
-                 shape=False, territory=None, territory_reach=None):
+                 shape=False, territory=None, territory_reach=None, skeleton=False):
     """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device), then one stage per switch, in
     this order.  ``distance_slots`` (the class value -> type slot table, uint8[256] numpy): ``cell_dist``, one value
     per row of ``cells`` (NaN = no entry).  ``neighbour_slots`` (the same kind of table) with ``n_types`` slots:
@@ -825,7 +935,9 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
     rows.  ``territory`` (a :class:`ClassTables`) with ``territory_reach`` (um, None: unbounded): ``territories`` /
     ``adjacency`` = :func:`territory_rows` over the rows of ``cells`` (the labels of kind >= 1 are the sites), the particle
     mask of ``surface`` as its mask, ``territory_overflow`` and, with ``refined``, ``refined_territories`` /
-    ``refined_adjacency`` / ``refined_territory_overflow`` over the refined rows of kind >= 1 on the watershed labels."""
+    ``refined_adjacency`` / ``refined_territory_overflow`` over the refined rows of kind >= 1 on the watershed labels.
+    ``skeleton``: ``skeletons`` = :func:`_skeleton_rows` over the rows of ``cells`` and, with ``refined``,
+    ``refined_skeletons`` over the refined rows of kind >= 1."""
     out, d = _dense_tables(res, groups, frame_ids, C, ratios, check)
     scale = 512.0 / float(raster)
     cap = res["stats"].shape[1]
@@ -836,6 +948,9 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
         out["territories"], out["adjacency"], out["territory_overflow"] = territory_rows(
             res["labels"], (res["kind"] >= 1) & _rows_below(res["counts"], cap), res["slot_of"], frame_ids, scale,
             len(territory.slot_names), r2=r2, mask=pmask, check=check)
+    if skeleton:
+        out["skeletons"] = _skeleton_rows(res["labels"], res["counts"], res["stats"],
+                                          (res["kind"] >= 1) & _rows_below(res["counts"], cap), res["slot_of"], frame_ids, scale)
     if convex:
         out["convexity"] = _hull_rows(res["labels"], res["counts"], res["stats"], (res["kind"] >= 1) & _rows_below(res["counts"], cap),
                                       res["slot_of"], frame_ids, scale)
@@ -861,8 +976,11 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
             out["refined_nn"] = _neighbours(pts, n_types, scale, pair_edges)
         if surface is not None:
             out["refined_sf"] = _refined_surface(res, pts, sf, mask, scale, K, surface_edges)
-        if convex or shape or territory is not None:
+        if convex or shape or skeleton or territory is not None:
             live = (out["kind_r"] >= 1) & (res["ws_stats"][:, :, 0] > 0) & _rows_below(res["n_markers"], cap)
+        if skeleton:
+            out["refined_skeletons"] = _skeleton_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"],
+                                                      frame_ids, scale)
         if convex:
             out["refined_convexity"] = _hull_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"], frame_ids,
                                                   scale)

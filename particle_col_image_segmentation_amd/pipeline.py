@@ -166,12 +166,12 @@ def _lanes_for(device, lanes):
     return _LANES[key]
 
 
-class TableSwitches(collections.namedtuple("TableSwitches", "neighbours pair_edges refined surface surface_edges territory territory_reach convex shape")):
+class TableSwitches(collections.namedtuple("TableSwitches", "neighbours pair_edges refined surface surface_edges territory territory_reach skeleton convex shape")):
     """The switches of the optional tables, as ``tables`` / ``tables_device`` / ``host_tables`` / ``table_columns`` /
     ``empty_device_tables`` take them (see :meth:`FramePipeline.tables_device`)."""
 
 
-TableSwitches.__new__.__defaults__ = (False, None, False, False, None, False, None, False, False)
+TableSwitches.__new__.__defaults__ = (False, None, False, False, None, False, None, False, False, False)
 
 # THE schema of the optional tables, in the order table_columns names them: name, on(switches), columns(type names,
 # switches), key columns of the gather's sort (distributed._SORT_COLS) and rows(pipeline, frame ids, ops.build_tables
@@ -187,6 +187,8 @@ _sf_rows = lambda p, fid, sf: p._point_rows(fid, sf["points"], sf["inside"], sf[
 _shape_cols = lambda names, o: ["frame", "label", "slot", "n_border", "n_1", "n_sqrt2", "n_mid", "mu_rr", "mu_rc", "mu_cc", "major_um",
                                "minor_um", "eccentricity", "orientation", "equivalent_diameter_um", "extent", "perimeter_um"]
 _hull_cols = lambda names, o: ["frame", "label", "slot", "convex_area", "solidity", "feret_um", "euler_number", "convex_area_um2"]
+_skel_cols = lambda names, o: ["frame", "label", "slot", "skel_px", "n_orth", "n_diag", "n_end", "n_junction", "passes", "length_um",
+                              "width_um"]
 _terr_cols = lambda names, o: (["frame", "label", "slot", "territory_px", "territory_on_px", "reach2_max", "clipped"]
                                + _per_type(names, "n_adj_%s") + _per_type(names, "n_contact_%s") + ["territory_um2", "territory_on_um2"])
 _adj_cols = lambda names, o: ["frame", "label_a", "label_b", "slot_a", "slot_b", "border_px", "contact_px"]
@@ -222,6 +224,8 @@ OPTIONAL_TABLES = (
     _Table("adjacency", lambda o: o.territory, _adj_cols, (0, 1, 2), lambda p, fid, raw: raw["adjacency"]),
     _Table("refined_territories", lambda o: o.refined and o.territory, _terr_cols, (0, 1), lambda p, fid, raw: raw["refined_territories"]),
     _Table("refined_adjacency", lambda o: o.refined and o.territory, _adj_cols, (0, 1, 2), lambda p, fid, raw: raw["refined_adjacency"]),
+    _Table("skeletons", lambda o: o.skeleton, _skel_cols, (0, 1), lambda p, fid, raw: raw["skeletons"]),
+    _Table("refined_skeletons", lambda o: o.refined and o.skeleton, _skel_cols, (0, 1), lambda p, fid, raw: raw["refined_skeletons"]),
     _Table("convexity", lambda o: o.convex, _hull_cols, (0, 1), lambda p, fid, raw: raw["convexity"]),
     _Table("refined_convexity", lambda o: o.refined and o.convex, _hull_cols, (0, 1), lambda p, fid, raw: raw["refined_convexity"]),
     _Table("shapes", lambda o: o.shape, _shape_cols, (0, 1), lambda p, fid, raw: raw["shapes"]),
@@ -543,7 +547,7 @@ class FramePipeline:
 
     # ------------------------------------------------------------------ table output
     def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None, refined=False, surface=False,
-                      surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None):
+                      surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """Column names of every table of :meth:`tables` (known without any data: ranks that own no frame of a
         dataset still agree on the schema, see ``distributed.run_sharded``).  ``neighbours`` / ``pair_edges`` add the
         ``neighbours`` / ``pair_hist`` tables of :meth:`tables_device`, ``refined`` its ``refined`` /
@@ -555,7 +559,7 @@ class FramePipeline:
         tables (and with ``refined`` ``refined_territories`` / ``refined_adjacency``)."""
         return self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
                                                         surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                                                        territory_reach=territory_reach))
+                                                        territory_reach=territory_reach, skeleton=skeleton))
 
     def _columns(self, C, ratios, switches):
         tb = self.tables_
@@ -587,7 +591,7 @@ class FramePipeline:
         return {k: given[k] for k in cls._TABLE_KEYWORDS[method] if k in given}
 
     def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0, neighbours=False,
-                      pair_edges=None, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None):
+                      pair_edges=None, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """The batch as dense row tables, assembled ON THE DEVICE (``csrc/tables.hip``): float64 CUDA tensors ``rois``,
         ``cells``, ``groups`` and ``frames_rec`` (one row per frame: frame id + the int64 record of
         ``pcseg_table_write``, see include/pcseg.h).  One small device-to-host copy (three row totals) sizes the
@@ -650,7 +654,15 @@ class FramePipeline:
         ``[frame, label_a, label_b, slot_a, slot_b, border_px, contact_px]`` sorted by (frame, a, b), a < b: the
         4-neighbour pixel pairs between the two territories, and those between the two ROIs themselves.  With ``refined``
         also ``refined_territories`` / ``refined_adjacency``: the same over the refined rows of kind >= 1 on the watershed
-        labels.  ``check`` also raises where a frame has more than 8 cap pairs."""
+        labels.  ``check`` also raises where a frame has more than 8 cap pairs.
+
+        ``skeleton``: how long and how wide (csrc/skeleton.hip; exact, equal to scikit-image 0.18.3's ``morphology.thin`` of
+        every ROI on its own).  ``skeletons`` = ``[frame, label, slot, skel_px, n_orth, n_diag, n_end, n_junction, passes,
+        length_um, width_um]``, one row per row of ``cells`` in its order: the pixels of the ROI's skeleton, its orthogonal
+        and diagonal links, the pixels with one link and with three or more (two ends and no junction: one rod; a
+        junction: a clump), the full iterations the thinning took, ``(n_orth + n_diag sqrt 2)`` and ``area / length`` at the
+        scale of ``distances``.  With ``refined`` also ``refined_skeletons``: the same over the refined rows of kind >= 1.
+        Runs in the table stage and waits for the device between its launches."""
         res.synchronize()
         B, C, H, W = res["shape"]
         dev = res["stats"].device
@@ -670,7 +682,7 @@ class FramePipeline:
             groups = (res.get("groups") or {}) if self.merged else {}
             o = TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
                               surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                              territory_reach=territory_reach)
+                              territory_reach=territory_reach, skeleton=skeleton)
             want_nn, want_sf = neighbours or pair_edges is not None, surface or surface_edges is not None
             raw = ops.build_tables(res, groups, fid, C, ratios, check=check,  # raises what BatchResult.check() raises
                                    distance_slots=self.tables_.slot if distances else None, raster=raster,
@@ -678,7 +690,8 @@ class FramePipeline:
                                    n_types=len(self.tables_.slot_names), pair_edges=pair_edges,
                                    refined=self.tables_ if refined else None, refined_points=refined and want_nn,
                                    surface=self.tables_ if want_sf else None, surface_edges=surface_edges, shape=shape, convex=convex,
-                                   territory=self.tables_ if territory else None, territory_reach=territory_reach)
+                                   territory=self.tables_ if territory else None, territory_reach=territory_reach,
+                                   skeleton=skeleton)
             dt = {k: raw[k] for k in ("rois", "cells", "groups")}
             dt["frames_rec"] = torch.cat([fid[:, None].to(torch.float64), raw["frames"].to(torch.float64)], dim=1)
             dt["distances"] = self._distance_rows(dt["cells"], raw.get("cell_dist"))
@@ -739,11 +752,11 @@ class FramePipeline:
                           hist.reshape(B, R, -1).to(torch.float64)], dim=2).reshape(B * R, -1)
 
     def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None, refined=False,
-                            surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None):
+                            surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset)."""
         cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
                                                         surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                                                        territory_reach=territory_reach))
+                                                        territory_reach=territory_reach, skeleton=skeleton))
         mk = lambda n: torch.zeros((0, n), dtype=torch.float64, device=device)
         out = {"rois": mk(len(cols["rois"])), "cells": mk(len(cols["cells"])), "groups": mk(len(cols["groups"])),
                "frames_rec": mk(18), "distances": mk(3)}
@@ -753,7 +766,7 @@ class FramePipeline:
         return out
 
     def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0, neighbours=False, pair_edges=None,
-                    refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None):
+                    refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """numpy tables from (downloaded or gathered) :meth:`tables_device` output: ``cells`` / ``rois`` / ``groups`` /
         ``distances`` as they are, ``frames`` after the two ``round(x, 5)`` of get_cell_counts_and_densities
         (tiff_analysis.py:1018-1038; Python's decimal rounding, a handful of numbers per frame).  Every table's width
@@ -761,7 +774,7 @@ class FramePipeline:
         host = _download(dt)
         cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
                                                         surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                                                        territory_reach=territory_reach))
+                                                        territory_reach=territory_reach, skeleton=skeleton))
         tb = self.tables_
         out = {k: host[k] for k in ("cells", "rois", "groups")}
         for k in out:
@@ -796,7 +809,7 @@ class FramePipeline:
         return out
 
     def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, neighbours=False,
-               pair_edges=None, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None):
+               pair_edges=None, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per
         refined ROI), ``frames`` (one row per frame) and ``groups`` (one row per merged group): :meth:`tables_device`
         followed by :meth:`host_tables`.  ``check=False`` skips ``BatchResult.check`` (a caller that has looked at the
@@ -804,9 +817,10 @@ class FramePipeline:
         cluster statistics).  ``neighbours`` / ``pair_edges`` / ``refined``: the ``neighbours`` / ``pair_hist`` and
         refined tables of :meth:`tables_device`; ``surface`` / ``surface_edges``: its surface-distance tables; ``shape``: its
         ``shapes`` / ``refined_shapes`` tables; ``convex``: its ``convexity`` / ``refined_convexity`` tables; ``territory`` /
-        ``territory_reach``: its ``territories`` / ``adjacency`` tables."""
+        ``territory_reach``: its ``territories`` / ``adjacency`` tables; ``skeleton``: its ``skeletons`` / ``refined_skeletons``
+        tables."""
         C = res["shape"][1]
         kw = dict(ratios=ratios, distances=distances, raster=raster, neighbours=neighbours, pair_edges=pair_edges, refined=refined,
                   surface=surface, surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                  territory_reach=territory_reach)
+                  territory_reach=territory_reach, skeleton=skeleton)
         return self.host_tables(self.tables_device(res, frame_ids, check=check, **kw), C, **kw)

@@ -70,7 +70,7 @@ class _LabelImage:
     def __init__(self, dev_labels, stats=None, n=0):
         self.dev = dev_labels
         self._host = None
-        self._stats, self._n, self._shape, self._hull = stats, int(n), None, None
+        self._stats, self._n, self._shape, self._hull, self._skeleton = stats, int(n), None, None, None
 
     @property
     def shape_columns(self):
@@ -95,6 +95,20 @@ class _LabelImage:
             table, _ = ops.region_hull(self.dev[None], counts, self._stats)
             self._hull = ops.hull_properties(self._stats, table, counts)[0, :self._n].cpu().numpy()
         return self._hull
+
+    @property
+    def skeleton_columns(self):
+        """(n, 8) float64 in the order of ``ops.SKELETON_COLUMNS``: ONE device call for the whole frame, at the first
+        :func:`get_cell_skeletons` that meets one of its regions."""
+        if self._skeleton is None:
+            if self._stats is None:
+                raise AttributeError("this region carries no label image to take its shape from")
+            counts = torch.full((1,), self._n, dtype=torch.int32, device=self.dev.device)
+            peel, _ = ops.thin_labels(self.dev[None])
+            table = ops.region_skeleton(self.dev[None], peel, counts, cap=self._stats.shape[1])
+            props = ops.skeleton_properties(self._stats, table, counts)
+            self._skeleton = torch.cat([table.to(torch.float64), props], dim=2)[0, :self._n].cpu().numpy()
+        return self._skeleton
 
     @property
     def host(self):
@@ -387,6 +401,29 @@ def get_cell_convexity(cell_pos, px_to_um=PX_TO_UM_CONV):
         t = np.array(rows, np.float64).reshape(-1, 4)
         out[name] = {"labels": np.array([int(r.label) for r in regs], np.int32), "convex_area": t[:, 0], "solidity": t[:, 1],
                      "feret_um": t[:, 2] / px_to_um, "euler_number": t[:, 3]}
+    return out
+
+
+def get_cell_skeletons(cell_pos, px_to_um=PX_TO_UM_CONV):
+    """How long and how wide, for the regions of ``cell_pos`` (strain -> regions, as get_cell_positions_and_areas returns
+    ``cell_pos`` or ``cell_clusters``): per strain a dict with ``labels`` (the regions' labels in list order) and, in the same
+    order, the skeleton of ``skimage.morphology.thin`` of every region (scikit-image 0.18.3) as ``skel_px``, ``n_orth`` /
+    ``n_diag`` (its orthogonal and diagonal links), ``n_end`` / ``n_junction`` (pixels with one link, with three or more:
+    two ends and no junction is one rod, a junction a clump), ``passes`` (the full iterations the region took),
+    ``length_um`` ((n_orth + n_diag sqrt 2) / px_to_um) and ``width_um`` (area / length in pixels, / px_to_um).  Lazy like
+    :func:`get_cell_convexity`: the regions of a frame share one holder, the first call costs one device call for the
+    frame (csrc/skeleton.hip), later ones none.  The regions themselves gain no attribute."""
+    out = {}
+    cols = ops.SKELETON_COLUMNS
+    for name, regs in cell_pos.items():
+        rows = []
+        for r in regs:
+            if r._im is None:
+                raise AttributeError("this region carries no label image to take its shape from")
+            rows.append(r._im.skeleton_columns[r.label - 1])
+        t = np.array(rows, np.float64).reshape(-1, len(cols))
+        out[name] = {"labels": np.array([int(r.label) for r in regs], np.int32), **{c: t[:, k] for k, c in enumerate(cols[:6])},
+                     "length_um": t[:, 6] / px_to_um, "width_um": t[:, 7] / px_to_um}
     return out
 
 
