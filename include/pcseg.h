@@ -631,6 +631,48 @@ int pcseg_region_skeleton(const int32_t *labels, const uint16_t *peel, const int
 int pcseg_skeleton_properties(const int64_t *stats, const int64_t *table, const int32_t *counts, double *out, int B, int cap,
                               pcseg_stream_t stream);
 
+/* ---- grayscale morphological reconstruction and h-maxima / h-minima (csrc/reconstruct.hip):
+ * skimage.morphology.reconstruction, h_maxima and h_minima of scikit-image 0.18.3 for 2-D frames, exact.
+ * pcseg_reconstruct_{i32,f64}: seed, mask, out device (B, H, W), out distinct from both inputs, NaN-free; conn 8 (the 3 x 3
+ * footprint) or 4; method PCSEG_RECONSTRUCT_DILATION: out = the largest R with seed <= R <= mask in which every value above
+ * the seed is carried along a connected path of pixels whose mask is at least that value, i.e. the fixed point of
+ * R <- max(R, min(mask, max of R over the neighbourhood)) from R = min(seed, mask), nothing outside the frame;
+ * PCSEG_RECONSTRUCT_EROSION: its mirror image (min and max change places).  -0.0 is read as +0.0.  flags device int32 (B),
+ * written by the call: PCSEG_RECONSTRUCT_SEED_BEYOND_MASK where a seed pixel lies above (erosion: below) its mask pixel --
+ * scikit-image raises there, the call clamps the seed to the mask --, PCSEG_RECONSTRUCT_NOT_CONVERGED where the frame's tail
+ * loop reached max_rounds rounds (<= 0: (tiles of a frame + 64) * 64, the watershed's cap; H * W cannot be reached by any
+ * image): out is then NO fixed point and must not be used.  The launch sequence is fixed -- nothing is read back, nothing
+ * allocated -- so the call can be captured into a graph.  B <= 65535.  The first 32 int32 of the workspace are counters of
+ * the last call: [r], 1 <= r < 6, the tiles listed for grid round r (round 0 visits every tile), [16] the tiles those
+ * rounds visited, [17] the tiles the tail kernel visited, [18] the most tail rounds of a frame.
+ * h_maxima(image, h) = (image - reconstruction by dilation of shift(image) under image) >= h, all zero in a frame with
+ * h > max - min (the test is per frame); h_minima its mirror.  sign -1: h_maxima, +1: h_minima; h > 0.
+ * pcseg_hmax_range_*: range device uint64 (B, 2), opaque (order keys of each frame's minimum and maximum).
+ * pcseg_hmax_shift_i32: seed = image -+ h clipped to int32; _f64: (image - h) - (2e-15 |image|) or (image + h) + (2e-15
+ * |image|), one rounding per operation in that order; _edt: from the squared distance d2, dist = sqrt((double)d2) and
+ * seed = the float64 h_maxima shift of dist.
+ * pcseg_hmax_mark_*: out uint8 = residue >= h, residue = image - rec (sign -1) or rec - image (sign +1), zero where h
+ * exceeds the frame's range; range_of_d2 = 1: range holds pcseg_hmax_range_i32 of d2 and the image is its square root
+ * (range = sqrt(max d2) - sqrt(min d2)). */
+#define PCSEG_RECONSTRUCT_DILATION 0
+#define PCSEG_RECONSTRUCT_EROSION 1
+#define PCSEG_RECONSTRUCT_SEED_BEYOND_MASK 1
+#define PCSEG_RECONSTRUCT_NOT_CONVERGED 2
+size_t pcseg_reconstruct_workspace_bytes(int B, int H, int W);
+int pcseg_reconstruct_i32(const int32_t *seed, const int32_t *mask, int32_t *out, int32_t *flags, int B, int H, int W, int conn,
+                          int method, int max_rounds, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_reconstruct_f64(const double *seed, const double *mask, double *out, int32_t *flags, int B, int H, int W, int conn,
+                          int method, int max_rounds, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_hmax_range_i32(const int32_t *img, uint64_t *range, int B, int H, int W, pcseg_stream_t stream);
+int pcseg_hmax_range_f64(const double *img, uint64_t *range, int B, int H, int W, pcseg_stream_t stream);
+int pcseg_hmax_shift_i32(const int32_t *img, int64_t h, int sign, int32_t *seed, int B, int H, int W, pcseg_stream_t stream);
+int pcseg_hmax_shift_f64(const double *img, double h, int sign, double *seed, int B, int H, int W, pcseg_stream_t stream);
+int pcseg_hmax_shift_edt(const int32_t *d2, double h, double *dist, double *seed, int B, int H, int W, pcseg_stream_t stream);
+int pcseg_hmax_mark_i32(const int32_t *img, const int32_t *rec, int64_t h, int sign, const uint64_t *range, uint8_t *out, int B,
+                        int H, int W, pcseg_stream_t stream);
+int pcseg_hmax_mark_f64(const double *img, const double *rec, double h, int sign, const uint64_t *range, int range_of_d2,
+                        uint8_t *out, int B, int H, int W, pcseg_stream_t stream);
+
 /* ---- X1 (north_star extension; refine_boundaries.py:22 imports skimage.filters and never calls it): the library
  * SURVEY.md 8a names is the oracle -- skimage.filters.threshold_otsu(float32 image, nbins=256), pinned by
  * tests/golden/extensions.npz.  pcseg_otsu_f32: threshold[b] (device float64 (B,), the value is the float32 bin

@@ -106,6 +106,16 @@ SIGNATURES = {
     "pcseg_region_skeleton_workspace_bytes": (c_size_t, [_I, _I, _I, _I]),
     "pcseg_region_skeleton": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, c_size_t, _P]),
     "pcseg_skeleton_properties": (c_int, [_P, _P, _P, _P, _I, _I, _P]),
+    "pcseg_reconstruct_workspace_bytes": (c_size_t, [_I, _I, _I]),
+    "pcseg_reconstruct_i32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, c_size_t, _P]),
+    "pcseg_reconstruct_f64": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, c_size_t, _P]),
+    "pcseg_hmax_range_i32": (c_int, [_P, _P, _I, _I, _I, _P]),
+    "pcseg_hmax_range_f64": (c_int, [_P, _P, _I, _I, _I, _P]),
+    "pcseg_hmax_shift_i32": (c_int, [_P, c_int64, _I, _P, _I, _I, _I, _P]),
+    "pcseg_hmax_shift_f64": (c_int, [_P, c_double, _I, _P, _I, _I, _I, _P]),
+    "pcseg_hmax_shift_edt": (c_int, [_P, c_double, _P, _P, _I, _I, _I, _P]),
+    "pcseg_hmax_mark_i32": (c_int, [_P, _P, c_int64, _I, _P, _P, _I, _I, _I, _P]),
+    "pcseg_hmax_mark_f64": (c_int, [_P, _P, c_double, _I, _P, _I, _P, _I, _I, _I, _P]),
     "pcseg_otsu_hist_f32":(c_int, [_P, _P, _P, _I, _I, _I, _P]),
     "pcseg_otsu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "pcseg_morph3x3": (c_int, [_P, _P, _I, _I, _I, _I, _P]),

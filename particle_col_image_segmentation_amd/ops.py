@@ -485,6 +485,152 @@ def local_maxima(img, want_mask=True, want_markers=True):
     return is_max, markers, counts
 
 
+RECONSTRUCT_TILE = (64, 32)          # csrc/reconstruct.hip: a tile (width, height)
+RECONSTRUCT_GRID_ROUNDS = 6          # ... and the rounds it enqueues as grids before the per-frame tail kernel
+RECONSTRUCT_SEED_BEYOND_MASK, RECONSTRUCT_NOT_CONVERGED = 1, 2  # bits of the per-frame flags (include/pcseg.h)
+_RECONSTRUCT_METHODS = {"dilation": 0, "erosion": 1}
+_SEED_MESSAGES = {"dilation": "Intensity of seed image must be less than that of the mask image for reconstruction by dilation.",
+                  "erosion": "Intensity of seed image must be greater than that of the mask image for reconstruction by erosion."}
+
+
+def _gray_pair(seed, mask):
+    """two (B, H, W) CUDA tensors of one dtype, int32 or float64 (float32 is widened, which is exact)"""
+    for t in (seed, mask):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+        if t.dtype not in (torch.int32, torch.float32, torch.float64):
+            raise TypeError("expected an int32, float32 or float64 image, got %s" % t.dtype)
+        if t.dim() != 3:
+            raise ValueError("expected 3 dims, got shape %s" % (tuple(t.shape),))
+    if seed.shape != mask.shape:
+        raise ValueError("seed and mask must have the same shape")
+    if (seed.dtype == torch.int32) != (mask.dtype == torch.int32):
+        raise TypeError("seed and mask must both be int32 or both be floating point")
+    if seed.dtype != torch.int32:
+        seed, mask = seed.to(torch.float64), mask.to(torch.float64)
+    return seed.contiguous(), mask.contiguous()
+
+
+def _reconstruct(seed, mask, method, conn, max_rounds=0):
+    """(out, flags, workspace) of pcseg_reconstruct_*: enqueued, nothing is read back"""
+    if method not in _RECONSTRUCT_METHODS:
+        raise ValueError("Reconstruction method can be one of 'erosion' or 'dilation'. Got '%s'." % (method,))
+    if conn not in (4, 8):
+        raise ValueError("conn must be 4 or 8")
+    B, H, W = seed.shape
+    dev = seed.device
+    out = torch.empty_like(seed)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.pcseg_reconstruct_workspace_bytes(B, H, W)
+    ws = _ws(nbytes, dev)
+    fn = lib.pcseg_reconstruct_i32 if seed.dtype == torch.int32 else lib.pcseg_reconstruct_f64
+    _lib.check(fn(_ptr(seed), _ptr(mask), _ptr(out), _ptr(flags), B, H, W, int(conn), _RECONSTRUCT_METHODS[method], int(max_rounds),
+                  _ptr(ws), nbytes, _stream()), "reconstruct")
+    return out, flags, ws
+
+
+def _check_reconstruct_flags(flags, method=None):
+    f = flags.cpu()
+    if method is not None and bool((f & RECONSTRUCT_SEED_BEYOND_MASK).any()):
+        raise ValueError(_SEED_MESSAGES[method])
+    if bool((f & RECONSTRUCT_NOT_CONVERGED).any()):
+        raise RuntimeError("reconstruction did not converge in frame(s) %s: the round cap was reached"
+                           % [int(b) for b in torch.nonzero(f & RECONSTRUCT_NOT_CONVERGED)[:, 0]])
+
+
+def reconstruct(seed, mask, method="dilation", conn=8, check=True, counters=False):
+    """``skimage.morphology.reconstruction(seed, mask, method)`` of scikit-image 0.18.3 per frame (csrc/reconstruct.hip), exact:
+    ``seed`` and ``mask`` (B, H, W) CUDA tensors, both int32 or both floating point (float32 is widened to float64, which is
+    exact), NaN-free; ``conn`` 8 (the default 3 x 3 footprint) or 4.  Returns ``(out, flags)``: the reconstruction in the
+    (widened) input type and int32 (B,) flags -- bit ``RECONSTRUCT_SEED_BEYOND_MASK`` where a seed pixel lies above (erosion:
+    below) its mask pixel (the seed is clamped to the mask there), bit ``RECONSTRUCT_NOT_CONVERGED`` where the round cap was
+    reached and the frame is no result.  ``check=True`` reads the flags and raises scikit-image's ``ValueError`` for the first,
+    ``RuntimeError`` for the second; ``check=False`` never waits for the device.  ``counters=True`` also returns the call's
+    int32 counters (include/pcseg.h)."""
+    seed, mask = _gray_pair(seed, mask)
+    out, flags, ws = _reconstruct(seed, mask, method, conn)
+    if check:
+        _check_reconstruct_flags(flags, method)
+    return (out, flags, ws[:128].view(torch.int32)) if counters else (out, flags)
+
+
+def _h_extrema(image, h, conn, sign):
+    if not isinstance(image, torch.Tensor) or not image.is_cuda:
+        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    if image.dtype not in (torch.int32, torch.float64) or image.dim() != 3:
+        raise TypeError("expected an int32 or float64 (B, H, W) image, got %s %s" % (image.dtype, tuple(image.shape)))
+    if not h > 0:
+        raise ValueError("h must be positive: h = 0 is ambiguous, use local_maxima() instead?")
+    image = image.contiguous()
+    B, H, W = image.shape
+    dev = image.device
+    lib = _lib.load()
+    rng = torch.empty((B, 2), dtype=torch.int64, device=dev)
+    seed = torch.empty_like(image)
+    mark = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    method = "dilation" if sign < 0 else "erosion"
+    if image.dtype == torch.int32:
+        if float(h) != int(h):
+            raise ValueError("an int32 image needs an integral h (got %r): pass a float64 image instead" % (h,))
+        h = int(h)
+        if h > 0xFFFFFFFF:
+            raise ValueError("The %s constant is not compatible with the image data type." % ("subtracted" if sign < 0 else "added"))
+        _lib.check(lib.pcseg_hmax_range_i32(_ptr(image), _ptr(rng), B, H, W, _stream()), "hmax_range")
+        _lib.check(lib.pcseg_hmax_shift_i32(_ptr(image), h, sign, _ptr(seed), B, H, W, _stream()), "hmax_shift")
+        rec, flags, _ = _reconstruct(seed, image, method, conn)
+        _lib.check(lib.pcseg_hmax_mark_i32(_ptr(image), _ptr(rec), h, sign, _ptr(rng), _ptr(mark), B, H, W, _stream()), "hmax_mark")
+    else:
+        h = float(h)
+        _lib.check(lib.pcseg_hmax_range_f64(_ptr(image), _ptr(rng), B, H, W, _stream()), "hmax_range")
+        _lib.check(lib.pcseg_hmax_shift_f64(_ptr(image), h, sign, _ptr(seed), B, H, W, _stream()), "hmax_shift")
+        rec, flags, _ = _reconstruct(seed, image, method, conn)
+        _lib.check(lib.pcseg_hmax_mark_f64(_ptr(image), _ptr(rec), h, sign, _ptr(rng), 0, _ptr(mark), B, H, W, _stream()), "hmax_mark")
+    _check_reconstruct_flags(flags)
+    return mark
+
+
+def h_maxima(image, h, conn=8):
+    """``skimage.morphology.h_maxima(image, h)`` of scikit-image 0.18.3 per frame: the uint8 mask of the maxima that rise at
+    least ``h`` above their surroundings.  ``image`` (B, H, W) int32 or float64 CUDA tensor, NaN-free; an int32 image needs an
+    integral ``h``.  A frame whose value range is below ``h`` has no h-maxima (the test is per frame).  ``conn`` 8 or 4."""
+    return _h_extrema(image, h, conn, -1)
+
+
+def h_minima(image, h, conn=8):
+    """``skimage.morphology.h_minima(image, h)``: the mirror image of :func:`h_maxima` (reconstruction by erosion of
+    ``image + h``)."""
+    return _h_extrema(image, h, conn, 1)
+
+
+def edt_maxima(d2, h, conn=8, want_mask=True, want_markers=True, counters=False):
+    """The h-maxima of a distance map as watershed markers -- ``h_maxima(sqrt(d2), h)`` and ``measure.label`` of it -- in the
+    place of :func:`local_maxima`: ``d2`` (B, H, W) int32, the squared distance of :func:`edt_sq` / :func:`edt_sq_lt`; ``h`` in
+    pixels of the distance map.  Returns ``(is_max, markers, counts, flags)``: the uint8 mask, its 8-connected components
+    numbered in raster order of their first pixel, their number per frame, and the reconstruction's per-frame flags (non-zero:
+    the frame is no result, see :func:`reconstruct`).  Nothing is read back: the call can be captured into a graph."""
+    d2 = _req(d2, torch.int32, 3)
+    if not h > 0:
+        raise ValueError("h must be positive: h = 0 is ambiguous, use local_maxima() instead?")
+    h = float(h)
+    B, H, W = d2.shape
+    dev = d2.device
+    lib = _lib.load()
+    rng = torch.empty((B, 2), dtype=torch.int64, device=dev)
+    dist = torch.empty((B, H, W), dtype=torch.float64, device=dev)
+    seed = torch.empty_like(dist)
+    is_max = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    _lib.check(lib.pcseg_hmax_range_i32(_ptr(d2), _ptr(rng), B, H, W, _stream()), "hmax_range")
+    _lib.check(lib.pcseg_hmax_shift_edt(_ptr(d2), h, _ptr(dist), _ptr(seed), B, H, W, _stream()), "hmax_shift_edt")
+    rec, flags, ws = _reconstruct(seed, dist, "dilation", conn)
+    _lib.check(lib.pcseg_hmax_mark_f64(_ptr(dist), _ptr(rec), h, -1, _ptr(rng), 1, _ptr(is_max), B, H, W, _stream()), "hmax_mark")
+    markers = counts = None
+    if want_markers:
+        markers, counts = label_bool8(is_max)
+    out = (is_max if want_mask else None, markers, counts, flags)
+    return out + (ws[:128].view(torch.int32),) if counters else out
+
+
 # test-only mode bits of pcseg_watershed4_f32 (include/pcseg.h): poison the union-find parent image before one pass
 WS_POISON_BORDER, WS_POISON_LABEL, WS_POISON_LEVEL2 = 8, 16, 32
 

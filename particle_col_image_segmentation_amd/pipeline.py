@@ -273,13 +273,15 @@ class _GraphSlot:
 
 class FramePipeline:
     def __init__(self, cell_types=None, threshold=0.5, boundary_plane=BOUNDARY_PLANE, cap=None, merged=True,
-                 watershed_mode=0, overlap=True, lanes=None, multi_stream=True, graph=False, max_graphs=None):
+                 watershed_mode=0, overlap=True, lanes=None, multi_stream=True, graph=False, max_graphs=None, marker_h=None):
         """``graph=True``: the chain of a batch (about a hundred launches on five streams) is captured ONCE per input
         buffer as a hipGraph and replayed for every later batch in that buffer -- one host call per batch instead of a
         hundred, no host thread per lane.  Inputs must then live in a small set of reused device buffers (the graph is
         keyed on the buffer's address and shape; ``max_graphs`` bounds the cache), and a result's tensors are the
         graph's static outputs: they stay valid until ``lanes`` further batches have been handed to :meth:`run`.
-        ``lanes``: batches in flight (default 8 host threads in eager mode, 2 replay streams in graph mode)."""
+        ``lanes``: batches in flight (default 8 host threads in eager mode, 2 replay streams in graph mode).
+        ``marker_h`` (pixels of the distance map; None: every local maximum): the watershed's markers are the h-maxima of the
+        distance map (``ops.edt_maxima``) and the result gains ``marker_flags``."""
         if lanes is None:
             lanes = 2 if graph else 8
         self.cell_types = dict(cell_types or CELL_TYPES_5)
@@ -289,6 +291,7 @@ class FramePipeline:
         self.cap = cap
         self.merged = merged
         self.watershed_mode = watershed_mode
+        self.marker_h = None if marker_h is None else float(marker_h)
         self.overlap = overlap
         self.lanes = max(1, int(lanes))
         self.multi_stream = bool(multi_stream)  # False: the class-map chain (incl. merges and fill) on ONE stream
@@ -515,7 +518,10 @@ class FramePipeline:
         # ---- boundary refinement (R1-R4, W1) on the boundary plane, read in place
         bm = stack[:, self.boundary_plane]
         d2, mask = ops.edt_sq_lt(bm, self.threshold)
-        _, markers, n_markers = ops.local_maxima(d2, want_mask=False)
+        if self.marker_h is None:
+            _, markers, n_markers = ops.local_maxima(d2, want_mask=False)
+        else:
+            _, markers, n_markers, res["marker_flags"] = ops.edt_maxima(d2, self.marker_h, want_mask=False)
         ws_labels, tie_flags = ops.watershed(bm, markers, mask, mode=self.watershed_mode)
         res.update(mask=mask, markers=markers, n_markers=n_markers, ws_labels=ws_labels, tie_flags=tie_flags)
         # ---- area / centroid sums of the refined ROIs (plane-free pass); their isotope sums: _sums_stage.  (The fused pass can
@@ -612,7 +618,8 @@ class FramePipeline:
         and cells), ``cell_resolution`` = one row per row of ``cells`` (children, resolved, cells_integrated) and
         ``frames_refined`` = one row per frame (per-type refined counts, resolved / residual clusters,
         count_integrated); with ``neighbours`` / ``pair_edges`` also ``refined_neighbours`` / ``refined_pair_hist``,
-        the same tables over the refined rows of kind >= 1.  ``check`` also raises where a parent label exceeds cap.
+        the same tables over the refined rows of kind >= 1.  ``check`` also raises where a parent label exceeds cap, and
+        ``RuntimeError`` where the h-maxima markers of a frame (``marker_h``) did not converge.
 
         ``surface`` (HCN_nanosims_rois_activity_distance_5iso_YG.m:271-309, the distance of every ROI to the aggregate
         boundary): where the cells sit relative to the particle.  The surface mask is ``binary_fill_holes(recreated ==
@@ -666,6 +673,8 @@ class FramePipeline:
         res.synchronize()
         B, C, H, W = res["shape"]
         dev = res["stats"].device
+        if check and "marker_flags" in res and int((res["marker_flags"] != 0).sum().item()):
+            raise RuntimeError("the h-maxima markers of this batch did not converge (marker_flags): its refined ROIs are no result")
         # a stream of its own, at high priority: the handful of small kernels here must not queue behind the next
         # batch's big ones on a saturated GPU
         if self._table_stream is None or self._table_stream.device != dev:

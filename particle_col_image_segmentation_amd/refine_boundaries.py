@@ -17,26 +17,46 @@ BOUNDARY_CHANNEL = 3  # refine_boundaries.py:34
 THRESHOLD = 0.5  # refine_boundaries.py:44
 
 
-def refine_boundaries_batch(boundary_maps, threshold=THRESHOLD, mode=0):
-    """(B,H,W) float32 CUDA tensor -> dict of device stages (refine_boundaries.py:44-73)."""
+def refine_boundaries_batch(boundary_maps, threshold=THRESHOLD, mode=0, marker_h=None):
+    """(B,H,W) float32 CUDA tensor -> dict of device stages (refine_boundaries.py:44-73).
+
+    ``marker_h`` (pixels of the distance map; None: the script's chain): the markers are the maxima of the distance map that
+    rise at least ``marker_h`` above their surroundings (``skimage.morphology.h_maxima(distance, marker_h)``) instead of
+    every local maximum, ``local_max`` is their mask, and the dict gains ``marker_flags`` int32 (B,): non-zero where the
+    frame's reconstruction did not reach its fixed point and the frame is no result (``ops.reconstruct``)."""
     d2, mask = ops.edt_sq_lt(boundary_maps, threshold)          # :44-45, :60
-    local_max, markers, n_markers = ops.local_maxima(d2)        # :63-64
+    st = {}
+    if marker_h is None:
+        local_max, markers, n_markers = ops.local_maxima(d2)    # :63-64
+    else:
+        local_max, markers, n_markers, st["marker_flags"] = ops.edt_maxima(d2, marker_h)
     labels, tie_flags = ops.watershed(boundary_maps, markers, mask, mode=mode)  # :73
-    return {"binary_mask": mask, "distance_sq": d2, "local_max": local_max, "markers": markers,
-            "n_markers": n_markers, "labels": labels, "tie_flags": tie_flags}
+    st.update({"binary_mask": mask, "distance_sq": d2, "local_max": local_max, "markers": markers,
+               "n_markers": n_markers, "labels": labels, "tie_flags": tie_flags})
+    return st
 
 
-def refine_boundaries(boundary_map, threshold=THRESHOLD, return_stages=False):
+def check_marker_flags(st):
+    """RuntimeError where the h-maxima markers of a frame are no result (``marker_flags`` of refine_boundaries_batch)."""
+    flags = st.get("marker_flags")
+    if flags is not None and int((flags != 0).sum().item()):
+        raise RuntimeError("the h-maxima markers did not converge in frame(s) %s"
+                           % [int(b) for b in torch.nonzero(flags.cpu())[:, 0]])
+
+
+def refine_boundaries(boundary_map, threshold=THRESHOLD, return_stages=False, marker_h=None):
     """2-D boundary probability map -> int32 label image (the script's ``labels``).
 
     ``return_stages=True`` returns the script's globals instead: ``binary_mask``, ``distance`` (float64 =
-    sqrt of the exact integer squared distance), ``local_max``, ``markers``, ``labels``."""
+    sqrt of the exact integer squared distance), ``local_max``, ``markers``, ``labels``.  ``marker_h``: see
+    :func:`refine_boundaries_batch` (``local_max`` is then the h-maxima mask)."""
     was_tensor = isinstance(boundary_map, torch.Tensor)
     t = boundary_map if was_tensor else torch.from_numpy(np.ascontiguousarray(np.asarray(boundary_map, dtype=np.float32)))
     if t.dim() != 2:
         raise ValueError("expected a 2-D boundary map, got shape %s" % (tuple(t.shape),))
     t = t.to(device=_device(), dtype=torch.float32).contiguous()[None]
-    st = refine_boundaries_batch(t, threshold)
+    st = refine_boundaries_batch(t, threshold, marker_h=marker_h)
+    check_marker_flags(st)
     conv = (lambda x: x) if was_tensor else (lambda x: x.cpu().numpy())
     labels = conv(st["labels"][0])
     if not return_stages:
@@ -49,7 +69,7 @@ def refine_boundaries(boundary_map, threshold=THRESHOLD, return_stages=False):
             "labels": labels}
 
 
-def refine_from_h5(file_path=DEFAULT_FILE, channel=BOUNDARY_CHANNEL, threshold=THRESHOLD, return_stages=False):
+def refine_from_h5(file_path=DEFAULT_FILE, channel=BOUNDARY_CHANNEL, threshold=THRESHOLD, return_stages=False, marker_h=None):
     """refine_boundaries.py:28-34 + the chain; ``.npy`` probability stacks are accepted without h5py."""
     if file_path.endswith(".npy"):
         probabilities = np.load(file_path, allow_pickle=False)
@@ -60,7 +80,7 @@ def refine_from_h5(file_path=DEFAULT_FILE, channel=BOUNDARY_CHANNEL, threshold=T
             raise ImportError("reading .h5 probabilities needs h5py; save the stack as .npy instead") from e
         with h5py.File(file_path, "r") as f:
             probabilities = np.array(f["exported_data"])
-    return refine_boundaries(probabilities[channel], threshold, return_stages)
+    return refine_boundaries(probabilities[channel], threshold, return_stages, marker_h=marker_h)
 
 
 if __name__ == "__main__":  # script-compatible entry: same default path, prints the number of segments
