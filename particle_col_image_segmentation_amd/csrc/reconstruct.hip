@@ -9,31 +9,24 @@
 // the values (int32: the sign bit flipped; float64: the usual total-order key, -0.0 read as +0.0) -- nothing is negated, so
 // INT32_MIN and the infinities are values like any other.  Inputs must be free of NaN.
 //
-// The iteration is the watershed's level relaxation (watershed.hip) with one tiling: a tile of REC_TW x REC_TH pixels sits
-// in LDS with a one-pixel halo, its four waves sweep it downwards, upwards, to the right and to the left (Gauss-Seidel: a
-// sweep step reads the line the step before wrote) until a whole iteration of the four changes nothing, the tile is stored and every
-// neighbour tile that touches a rim pixel the visit changed is marked.  A round visits the marked tiles; round 0 visits all
-// of them.  Marks live in two self-clearing buffers (a round reads one and writes the other, a visited tile takes its own
-// mark down), the first marker of a tile appends it to the next round's device list, REC_GRID_ROUNDS grid rounds are
-// enqueued whatever the data, and a tail kernel with one block per frame walks whatever is still marked round by round
-// until a round marks nothing or the round cap is reached (the frame's REC_FLAG_ROUNDS is raised then: the image is no
-// fixed point and must not be used).  No value is read back and nothing is allocated: the launch sequence is fixed.
+// The iteration runs on the marked-tile rounds of tile_rounds.h with one tiling: a tile of REC_TW x REC_TH pixels sits in
+// LDS with a one-pixel halo, its four waves sweep it downwards, upwards, to the right and to the left (Gauss-Seidel: a sweep
+// step reads the line the step before wrote) until a whole iteration of the four changes nothing, the tile is stored and
+// every neighbour tile that touches a rim pixel the visit changed is marked.  Round 0 visits every tile, REC_GRID_ROUNDS
+// rounds are grids, the tail kernel does the rest; at the round cap the frame's REC_FLAG_ROUNDS is raised: the image is no
+// fixed point and must not be used.  No value is read back and nothing is allocated: the launch sequence is fixed.
 //
-// WHY RACING HALO READS ARE HARMLESS.  Inside a round, tiles run concurrently and a tile may load a neighbour's rim while
-// that neighbour stores it.  (Dilation; erosion with the order reversed.)
-//   * values only rise: R(0) <= every later R <= the fixed point F (induction: min(mask, max over neighbours of something
-//     <= F) <= F), so whatever a tile reads from a neighbour's rim -- the clamped seed in round 0, an older or a newer stored
-//     value later -- is a lower bound of F, and so is everything the tile derives from it;
-//   * stores are naturally aligned 4- or 8-byte words: a racing load returns the old or the new value, never a mixture;
-//   * a tile that changed a rim pixel marks, AFTER its store, every neighbour that can read that pixel, in the buffer the
-//     NEXT round reads: the reader is visited again and then sees the stored value (kernel boundary; in the tail kernel the
-//     block's own barrier).  A tile is visited by one block per round, so its own pixels have one writer.
-// When a round marks nothing every tile is at its local fixed point for the halo values that are stored now: the image is
-// the fixed point of the whole frame, and being between R(0) and F it is F.
+// WHAT THE ROUNDS NEED: MONOTONE VALUES.  (Dilation; erosion with the order reversed.)  Values only rise: R(0) <= every
+// later R <= the fixed point F (induction: min(mask, max over neighbours of something <= F) <= F), so whatever a tile reads
+// from a neighbour's rim while that neighbour stores it -- the clamped seed in round 0, an older or a newer stored value
+// later, never a mixture: stores are naturally aligned 4- or 8-byte words -- is a lower bound of F, and so is everything the
+// tile derives from it.  A tile marks after its store (rec_tile).  So when a round marks nothing the image is a fixed point
+// of the whole frame, and being between R(0) and F it is F.
 #include <algorithm>
 #include <climits>
 
 #include "common.h"
+#include "tile_rounds.h"
 
 // the elementwise kernels must round as numpy does: one rounding per written operation, no fused multiply-add
 #pragma clang fp contract(off)
@@ -45,7 +38,6 @@ constexpr int REC_SW = REC_TW + 2, REC_SH = REC_TH + 2;   // with halo
 constexpr int REC_THREADS = 256;                          // one wave per sweep direction
 constexpr int REC_GRID_ROUNDS = 6;                        // rounds enqueued as grids (round 0: every tile; then device lists)
 constexpr int REC_LIST_GRID = 512;                        // blocks of a list-walking round
-constexpr int REC_TAIL_LIST = 1024;                       // marked tiles the tail kernel lists per round (more: it walks every tile)
 // iterations of one tile visit: an iteration that changes something settles at least one more pixel of the tile for good
 constexpr int REC_MAX_SWEEPS = REC_TW * REC_TH + 2;
 constexpr int REC_FLAG_SEED = PCSEG_RECONSTRUCT_SEED_BEYOND_MASK, REC_FLAG_ROUNDS = PCSEG_RECONSTRUCT_NOT_CONVERGED;
@@ -100,16 +92,6 @@ struct RecArgs {
     int H, W, conn, tilesX, tilesY;
 };
 
-// as ws_take_mark (watershed.hip).  Block-uniform: false = no mark, the block leaves the tile; every thread has read the
-// mark before thread 0 clears it.
-__device__ __forceinline__ bool rec_take_mark(uint8_t *mark)
-{
-    if (!*mark) return false;
-    __syncthreads();
-    if (threadIdx.x == 0) *mark = 0;
-    return true;
-}
-
 // the lanes of one wave have written LDS and are about to read each other's values (what a cooperative group of the
 // wave's size does to synchronise)
 __device__ __forceinline__ void rec_wave_sync()
@@ -119,19 +101,11 @@ __device__ __forceinline__ void rec_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// mark tile (tx, ty) of frame b for the next round; with a list, the first marker of a tile appends it (test-and-set on the
-// mark's byte inside its 32-bit word: the mark buffers are 256-byte aligned)
+// mark tile (tx, ty) of frame b, if the frame has it, for the next round
 __device__ __forceinline__ void rec_mark(uint8_t *dout, int *list_out, int *count_out, int b, int tx, int ty, int tilesX, int tilesY)
 {
     if (tx < 0 || tx >= tilesX || ty < 0 || ty >= tilesY) return;
-    const int64_t m = ((int64_t)b * tilesY + ty) * tilesX + tx;
-    if (list_out) {
-        const unsigned bit = 1u << (8 * (int)(m & 3));
-        const unsigned old = atomicOr(reinterpret_cast<unsigned *>(dout + (m & ~(int64_t)3)), bit);
-        if (!(old & bit)) list_out[atomicAdd(count_out, 1)] = (int)m;
-    } else {
-        dout[m] = 1;
-    }
+    mark_tile(dout, list_out, count_out, ((int64_t)b * tilesY + ty) * tilesX + tx);
 }
 
 // One visit of tile (tx, ty) of frame b (block-uniform control flow: every return is taken by all threads of the block).
@@ -146,7 +120,7 @@ __device__ __forceinline__ void rec_tile(typename RecKey<T>::K *sR, typename Rec
     using O = RecOrder<K, ERODE>;
     constexpr int TW = REC_TW, TH = REC_TH, SW = REC_SW, SH = REC_SH, NT = REC_THREADS;
     const int tid = threadIdx.x;
-    if (!FIRST && !rec_take_mark(din + ((int64_t)b * a.tilesY + ty) * a.tilesX + tx)) return;
+    if (!FIRST && !take_mark(din + ((int64_t)b * a.tilesY + ty) * a.tilesX + tx)) return;
     if (!FIRST && tid == 0) atomicAdd(a.counters + counter, 1);
     const int H = a.H, W = a.W;
     const int r0 = ty * TH, c0 = tx * TW;
@@ -263,60 +237,37 @@ __global__ void __launch_bounds__(REC_THREADS) rec_first_kernel(RecArgs<T> a, ui
     rec_tile<T, ERODE>(sR, sM, a, true, nullptr, dout, list_out, count_out, 0, blockIdx.z, blockIdx.x, blockIdx.y);
 }
 
-// rounds 1 .. REC_GRID_ROUNDS - 1: a fixed grid walks the list of tiles the round before marked (entry = frame * tiles per
-// frame + tile; entries blockIdx.x, blockIdx.x + gridDim.x, .. below the count as it is when the kernel starts)
+// rounds 1 .. REC_GRID_ROUNDS - 1: a fixed grid walks the list of tiles the round before marked.  (walk_list and the list's
+// decode rather than for_tiles around them: through the second closure the kernel takes 102 scalar registers instead of
+// 100, and the int32 kernels then hold 7 waves per SIMD where their LDS allows 8 -- profiles/tile_rounds/resource_usage.md.)
 template <typename T, bool ERODE>
 __global__ void __launch_bounds__(REC_THREADS) rec_list_kernel(RecArgs<T> a, uint8_t *din, uint8_t *dout, const int *list, const int *count,
                                                                int *list_out, int *count_out)
 {
     PCSEG_REC_LDS(T)
-    const int n = *count, ntpf = a.tilesX * a.tilesY;
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const int e = list[i], b = e / ntpf, t = e % ntpf;
-        rec_tile<T, ERODE>(sR, sM, a, false, din, dout, list_out, count_out, REC_CNT_GRID_TILES, b, t % a.tilesX, t / a.tilesX);
+    const TileList tiles{list, count, a.tilesX * a.tilesY, a.tilesX};
+    walk_list(list, count, blockIdx.x, gridDim.x, [&](const int e) {
+        const TileAt t = tiles.at(e);
+        rec_tile<T, ERODE>(sR, sM, a, false, din, dout, list_out, count_out, REC_CNT_GRID_TILES, t.b, t.tx, t.ty);
         __syncthreads();  // the next listed tile reuses the LDS tile
-    }
+    });
 }
 
-// the rest of the fixed point, one block per frame (ws_tail_rounds of watershed.hip): rounds of one frame only depend on that
-// frame's tiles, so the block's own barrier is the only synchronisation.  It gives up after max_rounds rounds.
+// the rest of the fixed point, one block per frame; at the round cap (max_rounds) the frame is flagged
 template <typename T, bool ERODE>
 __global__ void __launch_bounds__(REC_THREADS) rec_tail_kernel(RecArgs<T> a, uint8_t *din, uint8_t *dout, int max_rounds)
 {
     PCSEG_REC_LDS(T)
-    __shared__ int tail_list[REC_TAIL_LIST];
-    __shared__ int tail_count;
-    const int b = blockIdx.x, ntiles = a.tilesX * a.tilesY;
-    for (int round = 0;; ++round) {
-        const uint8_t *marks = din + (int64_t)b * ntiles;
-        __syncthreads();
-        if (threadIdx.x == 0) tail_count = 0;
-        __syncthreads();
-        for (int t = threadIdx.x; t < ntiles; t += REC_THREADS)
-            if (marks[t] != 0) {
-                const int k = atomicAdd(&tail_count, 1);
-                if (k < REC_TAIL_LIST) tail_list[k] = t;
-            }
-        __syncthreads();
-        const int marked = tail_count;
-        if (marked == 0) {
-            if (threadIdx.x == 0 && round > 0) atomicMax(a.counters + REC_CNT_TAIL_ROUNDS, round);
-            return;
-        }
-        if (round >= max_rounds) {
-            if (threadIdx.x == 0) atomicOr(a.flags + b, REC_FLAG_ROUNDS);
-            return;
-        }
-        const int walk = marked <= REC_TAIL_LIST ? marked : ntiles;  // (a list that overflowed: every tile, each checks its mark)
-        for (int k = 0; k < walk; ++k) {
-            const int t = marked <= REC_TAIL_LIST ? tail_list[k] : k;
-            rec_tile<T, ERODE>(sR, sM, a, false, din, dout, nullptr, nullptr, REC_CNT_TAIL_TILES, b, t % a.tilesX, t / a.tilesX);
-            __syncthreads();  // the tile's stores (pixels, marks) before the next tile loads its halo / the next round scans
-        }
-        uint8_t *tmp = din;
-        din = dout;
-        dout = tmp;
-    }
+    const int b = blockIdx.x;
+    const Tiling tiling{0, a.tilesX, a.tilesY};
+    const int rounds = tail_rounds<REC_THREADS>(
+        b, din, dout, 0, max_rounds, tiling, tiling, [](const int) { return true; },
+        [&](const Tiling &, const Tiling &, const int tx, const int ty, uint8_t *in, uint8_t *out) {
+            rec_tile<T, ERODE>(sR, sM, a, false, in, out, nullptr, nullptr, REC_CNT_TAIL_TILES, b, tx, ty);
+        });
+    if (threadIdx.x != 0) return;
+    if (rounds < 0) atomicOr(a.flags + b, REC_FLAG_ROUNDS);
+    else if (rounds > 0) atomicMax(a.counters + REC_CNT_TAIL_ROUNDS, rounds);
 }
 
 struct RecWorkspace {

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "tile_rounds.h"
 
 namespace pcseg {
 
@@ -59,19 +60,9 @@ __global__ void __launch_bounds__(256) ws_init_kernel(const float *__restrict__ 
     out[i] = mk;
 }
 
-// ---- work lists and tile marks: what the drivers below share.  Work that is a few tiles of a few frames is LISTED on the
-// device and walked by a small fixed grid: a launch over every tile retires thousands of workgroups that read one byte and
-// leave, each of which first has to find a CU with its LDS and wave slots free among the kernels of the other batches in
-// flight (2 048 blocks of 1 024 threads and 58 KB for one K2 round; same box, fewer such grid rounds made the STEP faster
-// although the serial time went up: 4.53-4.57 ms against 4.62-4.75, profiles/r04/ab_logs/r4f_*).  ONE walk serves every
-// list: entries first, first + stride, .. below the count as it is when the kernel starts.
-template <typename Body>
-__device__ __forceinline__ void ws_walk_list(const int *list, const int *count, int first, int stride, Body &&body)
-{
-    const int n = *count;
-    for (int i = first; i < n; i += stride) body(list[i]);
-}
-
+// ---- work lists and tile marks: both fixed points (levels, second-level keys) run on the marked-tile rounds of
+// tile_rounds.h -- the list walk, the tile lists, the marks and the tail loop are there.
+//
 // Frames: the second level's kernels run on the flagged frames only (frame_list[-1] = their number).  A launch over the
 // list spans WS_LIST_SPAN entries in the frame dimension of its grid and every block walks the list with that stride: a
 // launch that finds the list empty (the usual case on tie-free data) retires few blocks, a batch in which every frame is
@@ -81,28 +72,13 @@ template <typename Body>
 __device__ __forceinline__ void ws_for_frames(const int *frame_list, int grid_index, int grid_size, Body &&body)
 {
     if (!frame_list) body(grid_index);
-    else ws_walk_list(frame_list, frame_list - 1, grid_index, grid_size, body);
+    else walk_list(frame_list, frame_list - 1, grid_index, grid_size, body);
 }
 static inline int ws_frame_span(const int *frame_list, int B) { return frame_list ? (B < WS_LIST_SPAN ? B : WS_LIST_SPAN) : B; }
 
-// Tiles: entry = frame * tiles per frame + tile.  The second level lists its active tiles once (benchmark batch: 31 tiles in
-// 7 frames; the count sits in front of the list), the relaxation per round the tiles the round before marked, in that round's
-// tiling (ws_relax_list_kernel).  Blocks walk with the grid's stride; a body that uses LDS ends with a barrier: the next tile reuses it.
-struct WsTileList {
-    const int *list;
-    const int *count;  // number of entries
-    int ntpf, tilesX;  // tiles per frame, tiles per tile row
-};
+// Tiles (TileList): the second level lists its active tiles once (benchmark batch: 31 tiles in 7 frames; the count sits in
+// front of the list), the relaxation per round the tiles the round before marked, in that round's tiling (ws_relax_list_kernel).
 constexpr int WS_TILE_GRID = 512;  // blocks of a list-walking launch (two per CU: a quantised batch lists every tile)
-
-template <typename Body>
-__device__ __forceinline__ void ws_for_tiles(const WsTileList &tl, Body &&body)
-{
-    ws_walk_list(tl.list, tl.count, blockIdx.x, gridDim.x, [&](const int e) {
-        const int b = e / tl.ntpf, t = e % tl.ntpf;
-        body(b, t % tl.tilesX, t / tl.tilesX);
-    });
-}
 
 // the in-frame pixels of 64 x 64 tile (tx, ty) for a block of 256 threads: lane = column, wave w takes rows w, w + 4, ..
 template <typename Body>
@@ -113,18 +89,6 @@ __device__ __forceinline__ void ws_for_tile_pixels(int tx, int ty, int H, int W,
         const int r = ty * WS_T + rr;
         if (r < H && c < W) body(r, c);
     }
-}
-
-// Both fixed points (levels, second-level keys) keep one mark per tile, "a neighbour changed my halo", in two buffers: a
-// round reads one and writes the other.  A visited tile takes its mark down itself: the buffer is all zero again when it
-// becomes the output of the round after next, and no memset has to sit between two rounds.  Block-uniform: false = no
-// mark, the block leaves the tile; every thread has read the mark before thread 0 clears it.
-__device__ __forceinline__ bool ws_take_mark(uint8_t *mark)
-{
-    if (!*mark) return false;
-    __syncthreads();
-    if (threadIdx.x == 0) *mark = 0;
-    return true;
 }
 
 // (1) minimax relaxation, tile-local fixed point in LDS.  L and the pixel value share one 64-bit LDS word (x = L,
@@ -284,22 +248,18 @@ struct WsInputs {
 // cell plus outside neighbour both lie in the ONE tile of the other tiling that is centred on the nearest tile
 // corner.  So each tile marks, per corner quadrant, that corner's tile if one of the quadrant's two outer half
 // edges changed.  (grid = this round's tiling, dirty_in in its layout; dirty_out in the other tiling's layout.)
-struct WsTiling {
-    int off;     // 0 or T / 2
-    int nx, ny;  // tiles per frame in x and y
-};
 
 // One tile of one round (block-uniform control flow: every return is taken by all threads of the block).
 __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, const bool FIRST, unsigned *__restrict__ val,
                                               unsigned *__restrict__ L, uint8_t *__restrict__ dirty_in,
                                               uint8_t *__restrict__ dirty_out, int *__restrict__ any_changed, int H, int W,
-                                              const WsTiling &cur, const WsTiling &nxt, int max_iter, int tx, int ty, int b,
+                                              const Tiling &cur, const Tiling &nxt, int max_iter, int tx, int ty, int b,
                                               int *__restrict__ list_out = nullptr, int *__restrict__ count_out = nullptr)
 {
     using G = RelaxGeom;
     constexpr int T = WS_T, S = G::S, P = G::P, NT = G::THREADS, QW = T / 4;  // QW: 16-byte quads per tile row
     const int tid = threadIdx.x;
-    if (!FIRST && !ws_take_mark(dirty_in + ((int64_t)b * cur.ny + ty) * cur.nx + tx)) return;
+    if (!FIRST && !take_mark(dirty_in + ((int64_t)b * cur.ny + ty) * cur.nx + tx)) return;
     // 64 x 64 units actually processed (measurement: bench.py roofline), spread over 16 cache lines: one counter would
     // make every block of the launch queue on the same line
     if (tid == 0) atomicAdd(any_changed + WS_CNT0 + WS_CNT_STRIDE * ((tx + 5 * ty + 3 * b) & 15), 1);
@@ -457,18 +417,9 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
         if (rim_thread && edge_changed && ej == 0) {
             // the tile of the other tiling that holds this corner quadrant (rows r0 + qy * T / 2 .., cols c0 + qx * T / 2 ..)
             const int oy = (r0 + qy * G::HE + nxt.off) / T, ox = (c0 + qx * G::HE + nxt.off) / T;
-            if (oy >= 0 && oy < nxt.ny && ox >= 0 && ox < nxt.nx) {
-                const int64_t m = ((int64_t)b * nxt.ny + oy) * nxt.nx + ox;
-                if (list_out) {
-                    // the next round walks a LIST of marked tiles (ws_relax_list_kernel): the first marker of a tile appends it
-                    // (test-and-set on the mark's byte inside its 32-bit word: the mark arrays are 256-byte aligned)
-                    const unsigned bit = 1u << (8 * (int)(m & 3));
-                    const unsigned old = atomicOr(reinterpret_cast<unsigned *>(dirty_out + (m & ~(int64_t)3)), bit);
-                    if (!(old & bit)) list_out[atomicAdd(count_out, 1)] = (int)m;
-                } else {
-                    dirty_out[m] = 1;
-                }
-            }
+            // (with a list the next round walks the marked tiles: ws_relax_list_kernel)
+            if (oy >= 0 && oy < nxt.ny && ox >= 0 && ox < nxt.nx)
+                mark_tile(dirty_out, list_out, count_out, ((int64_t)b * nxt.ny + oy) * nxt.nx + ox);
         }
     }
     __syncthreads();
@@ -493,7 +444,7 @@ __device__ __forceinline__ void ws_relax_tile(uint2 *sLV, const WsInputs &in, co
 __global__ void __launch_bounds__(RelaxGeom::THREADS) ws_relax_kernel(WsInputs in, const bool FIRST, unsigned *__restrict__ val,
                                                                          unsigned *__restrict__ L, uint8_t *__restrict__ dirty_in,
                                                                          uint8_t *__restrict__ dirty_out, int *__restrict__ any_changed,
-                                                                         int H, int W, WsTiling cur, WsTiling nxt, int max_iter,
+                                                                         int H, int W, Tiling cur, Tiling nxt, int max_iter,
                                                                          int *__restrict__ list_out, int *__restrict__ count_out)
 {
     extern __shared__ __attribute__((aligned(16))) uint2 relax_lds[];  // RelaxGeom::N cells
@@ -503,88 +454,43 @@ __global__ void __launch_bounds__(RelaxGeom::THREADS) ws_relax_kernel(WsInputs i
 }
 
 // Late rounds visit a few per cent of the tiles, and a workgroup that only reads its mark still has to be given 36 KB of LDS
-// and four wave slots first (see ws_walk_list: the empty grids of the second level cost the STEP 3 %).  From round WS_LIST_FROM
+// and four wave slots first (see walk_list, tile_rounds.h: the empty grids of the second level cost the STEP 3 %).  From round WS_LIST_FROM
 // on a round is a fixed small grid walking the list of tiles the round before marked (appended by the first marker of a tile).
 constexpr int WS_LIST_FROM = 4, WS_LIST_GRID = 1024;  // first list-walking round; blocks of a list-walking launch
 
 __global__ void __launch_bounds__(RelaxGeom::THREADS) ws_relax_list_kernel(WsInputs in, unsigned *__restrict__ val, unsigned *__restrict__ L,
                                                                            uint8_t *__restrict__ dirty_in, uint8_t *__restrict__ dirty_out,
-                                                                           int *__restrict__ any_changed, int H, int W, WsTiling cur,
-                                                                           WsTiling nxt, int max_iter, WsTileList tiles,
+                                                                           int *__restrict__ any_changed, int H, int W, Tiling cur,
+                                                                           Tiling nxt, int max_iter, TileList tiles,
                                                                            int *__restrict__ list_out, int *__restrict__ count_out)
 {
     extern __shared__ __attribute__((aligned(16))) uint2 relax_lds[];
-    ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
+    for_tiles(tiles, [&](const int b, const int tx, const int ty) {
         ws_relax_tile(relax_lds + RelaxGeom::PAD, in, false, val, L, dirty_in, dirty_out, any_changed, H, W, cur, nxt, max_iter, tx, ty, b,
                       list_out, count_out);
         __syncthreads();  // the next listed tile reuses the LDS tile
     });
 }
 
-// The fixed points are driven WITHOUT the host: a fixed number of grid rounds is enqueued (a round that finds no mark
-// costs a few microseconds), and whatever is still marked after them -- a few tiles of a few frames, if anything -- is
-// finished by a tail kernel: one block per frame walks the frame's marked tiles round by round until a round marks
-// nothing.  Rounds of one frame only depend on that frame's tiles, so the block's own barrier is the only synchronisation
-// (stores and loads of one workgroup go through the same L1).  This is that block's loop for frame b; the two tail kernels
-// supply the tilings of even and odd rounds, counts(t) -- does marked tile t count (one that does not is never visited) --
-// and visit(cur, nxt, tx, ty, din, dout): one tile of tiling cur, takes its mark in din down, marks tiles of nxt in dout.
-// It gives up after max_rounds rounds (cannot happen for a monotone fixed point; never spin for ever): the frame's keys are
-// then no fixed point, and whatever the union-find makes of them must not be reported as exact -- the frame's tie flag is
+// Both tail kernels are tail_rounds (tile_rounds.h) for their frame.  When it gives up at the round cap the frame's keys are
+// no fixed point, and whatever the union-find makes of them must not be reported as exact -- the frame's tie flag is
 // raised, so the exact flood (mode 0) recomputes it and mode 2 reports it.
-constexpr int WS_TAIL_LIST = 1024;  // marked tiles a tail kernel lists per round (more: it walks every tile)
-
-template <int THREADS, typename Counts, typename Visit>
-__device__ __forceinline__ void ws_tail_rounds(const int b, uint8_t *din, uint8_t *dout, const int first_round, const int max_rounds,
-                                               int *__restrict__ not_converged, int *__restrict__ exact_flags, const WsTiling &t_even,
-                                               const WsTiling &t_odd, Counts &&counts, Visit &&visit)
-{
-    __shared__ int tail_list[WS_TAIL_LIST];
-    __shared__ int tail_count;
-    for (int round = first_round;; ++round) {
-        const WsTiling cur = (round & 1) ? t_odd : t_even, nxt = (round & 1) ? t_even : t_odd;
-        const int ntiles = cur.nx * cur.ny;
-        const uint8_t *marks = din + (int64_t)b * ntiles;
-        // the round's work list: the marked tiles, gathered in parallel (walking ALL tiles and letting each look at its own
-        // mark costs a dependent global load per tile -- 256 round trips per round for a handful of marked tiles)
-        __syncthreads();  // (a block that walks a frame list: the frame before has read tail_count)
-        if (threadIdx.x == 0) tail_count = 0;
-        __syncthreads();
-        for (int t = threadIdx.x; t < ntiles; t += THREADS)
-            if (marks[t] != 0 && counts(t)) {
-                const int k = atomicAdd(&tail_count, 1);
-                if (k < WS_TAIL_LIST) tail_list[k] = t;
-            }
-        __syncthreads();
-        const int marked = tail_count;
-        if (marked == 0) return;
-        if (round - first_round >= max_rounds) {
-            if (threadIdx.x == 0) { *not_converged = 1; exact_flags[b] = 1; }
-            return;
-        }
-        const int walk = marked <= WS_TAIL_LIST ? marked : ntiles;  // (a list that overflowed: every tile, each checks its mark)
-        for (int k = 0; k < walk; ++k) {
-            const int t = marked <= WS_TAIL_LIST ? tail_list[k] : k;
-            visit(cur, nxt, t % cur.nx, t / cur.nx, din, dout);
-            __syncthreads();  // the tile's stores (keys, marks) before the next tile loads its halo / the next round scans
-        }
-        uint8_t *tmp = din; din = dout; dout = tmp;
-    }
-}
-
+//
 // the rest of the levels' fixed point after the grid rounds (which end with round first_round - 1), one block per frame
 __global__ void __launch_bounds__(RelaxGeom::THREADS) ws_relax_tail_kernel(WsInputs in, unsigned *__restrict__ val, unsigned *__restrict__ L,
                                                                            uint8_t *__restrict__ dirtyA, uint8_t *__restrict__ dirtyB,
                                                                            int *__restrict__ any_changed, int *__restrict__ not_converged,
-                                                                           int *__restrict__ exact_flags, int H, int W, WsTiling t0,
-                                                                           WsTiling t1, int first_round, int max_rounds)
+                                                                           int *__restrict__ exact_flags, int H, int W, Tiling t0,
+                                                                           Tiling t1, int first_round, int max_rounds)
 {
     extern __shared__ __attribute__((aligned(16))) uint2 relax_lds[];
     const int b = blockIdx.x;
-    ws_tail_rounds<RelaxGeom::THREADS>(
-        b, dirtyA, dirtyB, first_round, max_rounds, not_converged, exact_flags, t0, t1, [](const int) { return true; },
-        [&](const WsTiling &cur, const WsTiling &nxt, const int tx, const int ty, uint8_t *din, uint8_t *dout) {
+    const int rounds = tail_rounds<RelaxGeom::THREADS>(
+        b, dirtyA, dirtyB, first_round, max_rounds, t0, t1, [](const int) { return true; },
+        [&](const Tiling &cur, const Tiling &nxt, const int tx, const int ty, uint8_t *din, uint8_t *dout) {
             ws_relax_tile(relax_lds + RelaxGeom::PAD, in, false, val, L, din, dout, any_changed, H, W, cur, nxt, 100000, tx, ty, b);
         });
+    if (rounds < 0 && threadIdx.x == 0) { *not_converged = 1; exact_flags[b] = 1; }
 }
 
 // stage-2 work is restricted to the 64x64 tiles that hold a pixel of an unresolved component (active == nullptr: all)
@@ -841,7 +747,7 @@ __device__ __forceinline__ void ws_uf_tile_frame(KeyT *sK, int *par, uint8_t *sM
 // LIST = false: every frame (first level), one frame per grid slice, straight-line code (32 VGPRs, 8 waves / SIMD; the
 // looping variant needs 80); LIST = true: the listed frames, see ws_for_frames
 template <typename KeyT, bool LIST>
-__global__ void __launch_bounds__(256) ws_uf_tile_kernel(WsTileList tiles, const KeyT *__restrict__ K, const int *__restrict__ F,
+__global__ void __launch_bounds__(256) ws_uf_tile_kernel(TileList tiles, const KeyT *__restrict__ K, const int *__restrict__ F,
                                                           const uint8_t *__restrict__ active, int *__restrict__ parent,
                                                           uint8_t *__restrict__ minmask, uint8_t *__restrict__ bad, int H, int W,
                                                           int tilesX, int tilesY)
@@ -854,7 +760,7 @@ __global__ void __launch_bounds__(256) ws_uf_tile_kernel(WsTileList tiles, const
         ws_uf_tile_frame<KeyT>(sK, par, sM, t.z, t.x, t.y, K, F, active, parent, minmask, bad, H, W, tilesX, tilesY);
     } else {
         // the listed 64 x 64 tiles, two union-find tiles (64 x 32) each
-        ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
+        for_tiles(tiles, [&](const int b, const int tx, const int ty) {
             for (int half = 0; half < WS_T / UF_TH; ++half) {
                 if ((ty * (WS_T / UF_TH) + half) * UF_TH < H)
                     ws_uf_tile_frame<KeyT>(sK, par, sM, b, tx, ty * (WS_T / UF_TH) + half, K, F, active, parent, minmask, bad, H, W, tilesX,
@@ -995,13 +901,13 @@ __global__ void __launch_bounds__(256) ws_uf_label_kernel(const int *__restrict_
 
 // the same pass over the listed 64 x 64 tiles only (second level: UF_DETECT, UF_ASSIGN)
 template <int MODE>
-__global__ void __launch_bounds__(256) ws_uf_label_tiles_kernel(WsTileList tiles, const int *__restrict__ parent, int *__restrict__ F,
+__global__ void __launch_bounds__(256) ws_uf_label_tiles_kernel(TileList tiles, const int *__restrict__ parent, int *__restrict__ F,
                                                                  const uint8_t *__restrict__ active, uint8_t *__restrict__ bad,
                                                                  const int *__restrict__ markers, const uint8_t *__restrict__ mask,
                                                                  int *__restrict__ tie_flags, int H, int W, int tilesX, int tilesY,
                                                                  int *__restrict__ exact_flags)
 {
-    ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
+    for_tiles(tiles, [&](const int b, const int tx, const int ty) {
         ws_for_tile_pixels(tx, ty, H, W, [&](const int r, const int c) {
             ws_uf_label_pixel<MODE>(b, (int64_t)r * W + c, parent, F, active, bad, markers, mask, tie_flags, nullptr, (int64_t)H * W, W,
                                     tilesX, tilesY, exact_flags, nullptr, nullptr);
@@ -1268,11 +1174,11 @@ __global__ void __launch_bounds__(256) ws_check_kernel(const KeyT *__restrict__ 
 // K2(lake pixel) = min K2 over the neighbours of the same level (the earliest entry floods the whole lake).
 constexpr unsigned WS_SECONDARY = 0xFFFFFFFEu;
 
-__global__ void __launch_bounds__(256) ws_k2_init_kernel(WsTileList tiles, const unsigned *__restrict__ val, const unsigned *__restrict__ L,
+__global__ void __launch_bounds__(256) ws_k2_init_kernel(TileList tiles, const unsigned *__restrict__ val, const unsigned *__restrict__ L,
                                                           const int *__restrict__ markers, const uint8_t *__restrict__ mask,
                                                           unsigned *__restrict__ K2, int H, int W)
 {
-    ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
+    for_tiles(tiles, [&](const int b, const int tx, const int ty) {
     ws_for_tile_pixels(tx, ty, H, W, [&](const int r, const int c) {
         const int64_t i = (int64_t)b * H * W + (int64_t)r * W + c;
         const unsigned l = L[i];
@@ -1353,7 +1259,7 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
     unsigned *sL = lds.sL, *sK = lds.sK;
     uint8_t *sLake = lds.sLake;
     if (!active[((int64_t)b * tilesY + ty) * tilesX + tx]) return;  // K2 is only defined inside the active tiles
-    if (!ws_take_mark(dirty_in + ((int64_t)b * tilesY + ty) * tilesX + tx)) return;
+    if (!take_mark(dirty_in + ((int64_t)b * tilesY + ty) * tilesX + tx)) return;
     const int r0 = ty * WS_T, c0 = tx * WS_T;
     const int64_t fbase = (int64_t)b * H * W;
     {
@@ -1452,19 +1358,19 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
     ws_store_tile(sK, K2 + fbase, r0, c0, H, W);
 }
 
-__global__ void __launch_bounds__(K2T) ws_k2_relax_kernel(WsTileList tiles, const unsigned *__restrict__ val, const unsigned *__restrict__ L,
+__global__ void __launch_bounds__(K2T) ws_k2_relax_kernel(TileList tiles, const unsigned *__restrict__ val, const unsigned *__restrict__ L,
                                                            unsigned *__restrict__ K2, const uint8_t *__restrict__ active,
                                                            uint8_t *__restrict__ dirty_in, uint8_t *__restrict__ dirty_out,
                                                            int H, int W, int tilesX, int tilesY, const uint8_t *__restrict__ in_bad)
 {
     __shared__ WsK2Lds lds;
-    ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
+    for_tiles(tiles, [&](const int b, const int tx, const int ty) {
         ws_k2_relax_tile(lds, val, L, K2, active, dirty_in, dirty_out, H, W, tilesX, tilesY, tx, ty, b, in_bad);
         __syncthreads();  // the next listed tile reuses the tile arrays
     });
 }
 
-// the rest of the second-level fixed point after its grid rounds, one block per flagged frame (ws_tail_rounds)
+// the rest of the second-level fixed point after its grid rounds, one block per flagged frame (tail_rounds)
 __global__ void __launch_bounds__(K2T) ws_k2_relax_tail_kernel(const int *__restrict__ frame_list, const unsigned *__restrict__ val,
                                                                 const unsigned *__restrict__ L, unsigned *__restrict__ K2,
                                                                 const uint8_t *__restrict__ active, uint8_t *__restrict__ dirtyA,
@@ -1473,15 +1379,16 @@ __global__ void __launch_bounds__(K2T) ws_k2_relax_tail_kernel(const int *__rest
                                                                 int max_rounds, const uint8_t *__restrict__ in_bad)
 {
     __shared__ WsK2Lds lds;
-    const WsTiling tiling{0, tilesX, tilesY};
+    const Tiling tiling{0, tilesX, tilesY};
     ws_for_frames(frame_list, blockIdx.x, gridDim.x, [&](const int b) {
         // (a mark on a tile outside the active set is never taken down -- such tiles are not visited -- and is no work)
         const uint8_t *act = active + (int64_t)b * tilesX * tilesY;
-        ws_tail_rounds<K2T>(
-            b, dirtyA, dirtyB, 0, max_rounds, not_converged, exact_flags, tiling, tiling, [&](const int t) { return act[t] != 0; },
-            [&](const WsTiling &, const WsTiling &, const int tx, const int ty, uint8_t *din, uint8_t *dout) {
+        const int rounds = tail_rounds<K2T>(
+            b, dirtyA, dirtyB, 0, max_rounds, tiling, tiling, [&](const int t) { return act[t] != 0; },
+            [&](const Tiling &, const Tiling &, const int tx, const int ty, uint8_t *din, uint8_t *dout) {
                 ws_k2_relax_tile(lds, val, L, K2, active, din, dout, H, W, tilesX, tilesY, tx, ty, b, in_bad);
             });
+        if (rounds < 0 && threadIdx.x == 0) { *not_converged = 1; exact_flags[b] = 1; }
     });
 }
 
@@ -1489,11 +1396,11 @@ __global__ void __launch_bounds__(K2T) ws_k2_relax_tail_kernel(const int *__rest
 // tiles, where it must never look like a minimum-key neighbour (it is not in the component, so its L is larger than the
 // minimum anyway): the one-pixel ring around a listed tile gets (L, worst K2) wherever it does not belong to another active
 // tile (which packs its own pixels).  Nothing further out is ever read at this level.
-__global__ void __launch_bounds__(256) ws_pack_kernel(WsTileList tiles, const unsigned *__restrict__ L, const unsigned *__restrict__ K2,
+__global__ void __launch_bounds__(256) ws_pack_kernel(TileList tiles, const unsigned *__restrict__ L, const unsigned *__restrict__ K2,
                                                        const uint8_t *__restrict__ active, unsigned long long *__restrict__ K64, int H, int W,
                                                        int tilesX, int tilesY)
 {
-    ws_for_tiles(tiles, [&](const int b, const int tx, const int ty) {
+    for_tiles(tiles, [&](const int b, const int tx, const int ty) {
         const int64_t fbase = (int64_t)b * H * W;
         ws_for_tile_pixels(tx, ty, H, W, [&](const int r, const int c) {
             const int64_t g = fbase + (int64_t)r * W + c;
@@ -1927,7 +1834,7 @@ struct WsCall {
     unsigned pixel_blocks() const { return (unsigned)((npx() + 255) / 256); }
     dim3 check_grid() const { return dim3((W + 63) / 64, (H + 3) / 4, B); }
     // the second level's active tiles (listed by ws_list_tiles_kernel)
-    WsTileList active_list(const WsWorkspace &ws) const { return WsTileList{ws.tiles(), ws.tiles() - 1, tilesX * tilesY, tilesX}; }
+    TileList active_list(const WsWorkspace &ws) const { return TileList{ws.tiles(), ws.tiles() - 1, tilesX * tilesY, tilesX}; }
 };
 
 // (1) minimax levels: WS_GRID_ROUNDS grid rounds over the two alternating tilings (the benchmark batch needs 10; a round
@@ -1937,10 +1844,10 @@ static int ws_relax_levels(const WsCall &c, const WsWorkspace &ws)
 {
     using RG = RelaxGeom;
     static_assert(RG::LDS_BYTES <= 64 * 1024, "dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize");
-    const WsTiling tilings[2] = {{0, c.tilesX, c.tilesY}, {WS_T / 2, (c.W + WS_T / 2 + WS_T - 1) / WS_T, (c.H + WS_T / 2 + WS_T - 1) / WS_T}};
+    const Tiling tilings[2] = {{0, c.tilesX, c.tilesY}, {WS_T / 2, (c.W + WS_T / 2 + WS_T - 1) / WS_T, (c.H + WS_T / 2 + WS_T - 1) / WS_T}};
     uint8_t *din = ws.dirtyA, *dout = ws.dirtyB;
     for (int round = 0; round < WS_GRID_ROUNDS; ++round) {
-        const WsTiling &cur = tilings[round & 1], &nxt = tilings[(round + 1) & 1];
+        const Tiling &cur = tilings[round & 1], &nxt = tilings[(round + 1) & 1];
         // (a round's marks go into the next round's list once that round walks a list)
         const bool lists_next = round + 1 >= WS_LIST_FROM && round + 1 < WS_GRID_ROUNDS;
         int *lout = lists_next ? ws.round_list[(round + 1) & 1] : nullptr, *cout = lists_next ? ws.round_count + round + 1 : nullptr;
@@ -1949,7 +1856,7 @@ static int ws_relax_levels(const WsCall &c, const WsWorkspace &ws)
                          ws.changed, c.H, c.W, cur, nxt, round == 0 ? WS_ROUND0_SWEEPS : WS_ROUND_SWEEPS, lout, cout);
         else
             PCSEG_LAUNCH(ws_relax_list_kernel, dim3(WS_LIST_GRID), dim3(RG::THREADS), RG::LDS_BYTES, c.s, c.in, ws.val, ws.L, din, dout, ws.changed,
-                         c.H, c.W, cur, nxt, WS_ROUND_SWEEPS, (WsTileList{ws.round_list[round & 1], ws.round_count + round, cur.nx * cur.ny, cur.nx}),
+                         c.H, c.W, cur, nxt, WS_ROUND_SWEEPS, (TileList{ws.round_list[round & 1], ws.round_count + round, cur.nx * cur.ny, cur.nx}),
                          lout, cout);
         PCSEG_CHECK_LAUNCH();
         uint8_t *t = din; din = dout; dout = t;
@@ -1978,7 +1885,7 @@ static int ws_assign_labels(const WsCall &c, const WsWorkspace &ws, const KeyT *
 {
     const int H = c.H, W = c.W, span = ws_frame_span(flist, c.B);  // span: frame dimension of the grids (see ws_for_frames)
     const int64_t border_px = (int64_t)((H - 1) / UF_TH) * W + (int64_t)((W - 1) / UF_TW) * H;
-    const WsTileList tiles = c.active_list(ws);
+    const TileList tiles = c.active_list(ws);
     uint8_t *level_bad = first_level ? ws.uf_bad1 : ws.uf_bad2;  // cleared by the tile pass, tile by tile
     if (flist)  // second level: the listed tiles only
         PCSEG_LAUNCH((ws_uf_tile_kernel<KeyT, true>), dim3(WS_TILE_GRID), dim3(256), 0, c.s, tiles, keys, c.in.out, act, ws.uf_parent, ws.uf_mask,
@@ -2024,7 +1931,7 @@ static int ws_second_level(const WsCall &c, const WsWorkspace &ws)
     unsigned *K2 = ws.heap_idx;
     unsigned long long *K64 = ws.heap_key;
     const int *frame_list = ws.frames();
-    const WsTileList tiles = c.active_list(ws);
+    const TileList tiles = c.active_list(ws);
     // which frames need the second level: list and length stay on the device
     PCSEG_LAUNCH(ws_list_flagged_kernel, dim3(1), dim3(64), 0, c.s, ws.flags, c.B, ws.frames());
     PCSEG_CHECK_LAUNCH();

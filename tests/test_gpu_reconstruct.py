@@ -120,14 +120,20 @@ def test_edt_maxima_equal_skimage_h_maxima_of_the_distance():
     assert none is None and counts is None and is_max is not None
 
 
-def test_frames_of_one_batch_end_at_different_times():
-    """frame 0 a serpentine (hundreds of tail rounds), frame 1 constant (none), frame 2 random: each equals its own result"""
-    _need_gpu()
+def _uneven_batch():
+    """(seed, mask), 3 x 70 x 130 int32: frame 0 a serpentine seeded at its first pixel, frame 1 constant, frame 2 random"""
     H, W = 70, 130
     rng = np.random.default_rng(11)
     mask = np.stack([serpentine(H, W), np.full((H, W), 4, np.int32), rng.integers(-3, 6, (H, W)).astype(np.int32)])
     seed = np.stack([np.zeros((H, W), np.int32), np.full((H, W), 1, np.int32), mask[2] - rng.integers(0, 5, (H, W)).astype(np.int32)])
     seed[0, 0, 0] = 3
+    return seed, mask
+
+
+def test_frames_of_one_batch_end_at_different_times():
+    """frame 0 a serpentine (hundreds of tail rounds), frame 1 constant (none), frame 2 random: each equals its own result"""
+    _need_gpu()
+    seed, mask = _uneven_batch()
     for dtype in (np.int32, np.float64):
         for conn in (8, 4):
             s, m = seed.astype(dtype), mask.astype(dtype)
@@ -138,6 +144,72 @@ def test_frames_of_one_batch_end_at_different_times():
                 np.testing.assert_array_equal(got[b], alone, err_msg="frame %d" % b)
                 np.testing.assert_array_equal(got[b], reconstruct_np(s[b], m[b], conn=conn), err_msg="frame %d" % b)
     assert (got[0] == 3).sum() == (mask[0] == 5).sum() == 4585
+
+
+GRID_ROUNDS = 6  # csrc/reconstruct.hip: REC_GRID_ROUNDS
+
+
+def _serpentine_round_bound(H, W):
+    """(C, L) for the serpentine: its corridor is a simple path, so the seed's level enters the tiles in the order the path
+    does, C seam crossings in all.  A crossing into a tile takes a visit of that tile that loads after the tile before stored,
+    and a round visits a tile once: the crossings of one round enter different tiles, at most L = the longest run of
+    consecutive crossings into distinct tiles.  (With 8 neighbours the level cuts the corners at the row ends; those lie in
+    the tile of the pixels next to them.)  After k rounds at most k L crossings are made, whatever the order of the visits."""
+    path = []
+    for k, r in enumerate(range(0, H, 2)):
+        cols = range(W) if k % 2 == 0 else range(W - 1, -1, -1)
+        path += [(r, c) for c in cols]
+        if r + 1 < H:
+            path.append((r + 1, path[-1][1]))
+    assert len(path) == (serpentine(H, W) == 5).sum() and all(serpentine(H, W)[p] == 5 for p in path)
+    tiles = [(r // TH, c // TW) for r, c in path]
+    entered = [t for s, t in zip(tiles, tiles[1:]) if s != t]
+    longest = max(n for i in range(len(entered)) for n in range(1, len(entered) - i + 1) if len(set(entered[i:i + n])) == n)
+    return len(entered), longest
+
+
+def _rounds_with_a_change(seed, mask, conn):
+    """rounds of the tiling that change a pixel when every tile reads the halo the round before left (the slowest order: values
+    only rise, so a visit that reads anything newer is no further from the fixed point).  The round after the last of them
+    finds nothing to do and marks nothing, so the frame has no mark left after that many + 1 rounds at the most."""
+    H, W = mask.shape
+    R = np.minimum(seed, mask)
+    for rounds in range(1000):
+        new = R.copy()
+        for r0 in range(0, H, TH):
+            for c0 in range(0, W, TW):
+                ra, rb, ca, cb = max(r0 - 1, 0), min(r0 + TH + 1, H), max(c0 - 1, 0), min(c0 + TW + 1, W)
+                m = R[ra:rb, ca:cb].copy()      # the halo cannot rise: its mask is its value
+                m[r0 - ra:r0 - ra + TH, c0 - ca:c0 - ca + TW] = mask[r0:r0 + TH, c0:c0 + TW]
+                local = reconstruct_np(R[ra:rb, ca:cb], m, conn=conn)
+                new[r0:r0 + TH, c0:c0 + TW] = local[r0 - ra:r0 - ra + TH, c0 - ca:c0 - ca + TW]
+        if (new == R).all():
+            np.testing.assert_array_equal(R, reconstruct_np(seed, mask, conn=conn))
+            return rounds
+        R = new
+    raise AssertionError("no fixed point")
+
+
+def test_the_round_cap_flags_the_frame_that_reaches_it_and_no_other():
+    """max_rounds = 2: the tail gives up on a frame that still has a mark after GRID_ROUNDS + 2 rounds.  The serpentine of frame 0
+    does (its level has C = 72 seams to cross and crosses at most L = 6 a round); frames 1 and 2 are done within the grid rounds
+    (no round, 3 rounds change a pixel of them) and are results.  The call is bounded: the cap is what ends it."""
+    _need_gpu()
+    from particle_col_image_segmentation_amd import ops
+    seed, mask = _uneven_batch()
+    crossings, per_round = _serpentine_round_bound(*mask[0].shape)
+    print("serpentine: %d seam crossings, at most %d a round" % (crossings, per_round))
+    assert (GRID_ROUNDS + 2) * per_round < crossings
+    for b in (1, 2):
+        n = _rounds_with_a_change(seed[b], mask[b], 8)
+        print("frame %d: %d rounds change a pixel" % (b, n))
+        assert n + 1 < GRID_ROUNDS
+    out, flags, _ = ops._reconstruct(_dev(seed), _dev(mask), "dilation", 8, max_rounds=2)
+    assert flags.cpu().tolist() == [ops.RECONSTRUCT_NOT_CONVERGED, 0, 0]
+    for b in (1, 2):
+        np.testing.assert_array_equal(out[b].cpu().numpy(), reconstruct_np(seed[b], mask[b], conn=8), err_msg="frame %d" % b)
+    with pytest.raises(RuntimeError, match=r"did not converge in frame\(s\) \[0\]"):
+        ops._check_reconstruct_flags(flags)
 
 
 DIRECTIONS = ((0, 1), (0, -1), (1, 0), (-1, 0), (1, 1), (1, -1), (-1, 1), (-1, -1))
