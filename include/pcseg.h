@@ -129,8 +129,8 @@ int pcseg_region_init(const int32_t *counts, int cap, int C, int B, int H, int W
 /* Plane sums of TWO label images over the same planes in ONE pass (.m:122-135 for the class-map components and for the
  * refined ROIs; the planes are the largest thing a reduction reads): sums_a (B, cap_a, C) += per-label sums of labels_a
  * restricted to the pixels whose class-map value is in sum_class_bits (0 = every pixel), sums_b (B, cap_b, C) += per-label
- * sums of labels_b.  stats_b != NULL: image B's integer columns (pcseg_region_col) are accumulated in the same walk into
- * stats_b (B, cap_b, 8) / overflow_b.  Every table must have been initialised (pcseg_region_init, or
+ * sums of labels_b.  stats_b != NULL: image B's integer columns (pcseg_region_col) are accumulated into stats_b
+ * (B, cap_b, 8) / overflow_b by the plane-free pass, launched ahead of the sums.  Every table must have been initialised (pcseg_region_init, or
  * pcseg_region_reduce_sel for image A); without stats_b labels above the capacity are skipped silently.  W % 4 == 0,
  * 16-byte aligned images. */
 int pcseg_region_sums2(const int32_t *labels_a, const uint8_t *cls, uint64_t sum_class_bits, int cap_a, double *sums_a,

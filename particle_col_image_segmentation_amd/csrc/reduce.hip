@@ -1,19 +1,24 @@
-// Per-label reductions: regionprops fields (A3), per-ROI isotope sums (M1),
-// region classification / cluster cell counts (A3/A4 tail) and the proximity
-// merge grouping (A6 tail).
+// Per-label reductions: regionprops fields (A3), per-ROI isotope sums (M1), region classification / cluster cell counts
+// (A3/A4 tail) and the proximity merge grouping (A6 tail).
 //
-// Main kernels: a lane owns 4 adjacent columns and walks down 32 rows, accumulating each vertical run of equal labels in
-// registers (int4 / float4 loads, no cross-lane traffic) and committing it when the label changes.  All table columns are
-// integers, so the result does not depend on the order of the atomics; a 256-slot direct-mapped LDS table absorbs the hot
-// labels (background, particle) and is flushed once per block.  The walk of the plane-free pass, the slot table and the
-// segmented wave reduction are label_reduce.h's.  Frames with planes whose width or base address rules out 16-byte loads
-// take the row fallback: one wave per 64-pixel row segment, label runs from a ballot, closed-form run sums.
+// A region table is made by two walks (and, for one aligned image with planes, by the fused kernel that repeats both: see
+// region_reduce_col_kernel).  The INTEGER columns (area, centroid sums, bounding box, first pixel) come from the
+// plane-free pass, region_stats_col_kernel: the column-run walk of label_reduce.h over the label image alone, 4 bytes per
+// pixel, any width and alignment.  All of them are integers, so the result does not depend on the order of the atomics; a
+// 256-slot direct-mapped LDS table absorbs the hot labels (background, particle) and is flushed once per block.  The PLANE
+// SUMS come from a pass that only sums, region_sums2_col_kernel: a lane owns 4 adjacent columns and walks down 32 rows with
+// each vertical run's float64 sums in registers (int4 / float4 loads, no cross-lane traffic), for two label images over the
+// same planes.  One image whose width or base addresses rule out 16-byte loads takes region_sums_row_kernel instead: one wave
+// per 64-pixel row segment, label runs from a ballot.  The slot table, the segmented wave reduction and the walk of the
+// plane-free pass are label_reduce.h's.
+#include <type_traits>
+
 #include "label_reduce.h"
 
 namespace pcseg {
 
 constexpr int RED_MAXC = 8;
-constexpr int RED_ROWS = 16;  // rows per block
+constexpr int RED_ROWS = 16;  // rows per block of the row kernel
 
 __device__ __forceinline__ void atomic_min_i64(long long *p, long long v) { atomicMin(p, v); }
 __device__ __forceinline__ void atomic_max_i64(long long *p, long long v) { atomicMax(p, v); }
@@ -32,135 +37,25 @@ __global__ void __launch_bounds__(256) region_init_kernel(long long *__restrict_
     if (sums && f < C) sums[((int64_t)b * cap + l) * C + f] = 0.0;
 }
 
-// the fallback for frames WITH planes whose width or base address rules out 16-byte loads (plane-free frames of any width
-// and alignment go through region_stats_col_kernel)
-__global__ void __launch_bounds__(256) region_reduce_kernel(const int *__restrict__ labels, const float *__restrict__ planes,
-                                                             const uint8_t *__restrict__ cls, unsigned long long sel, int C, int H,
-                                                             int W, int cap, long long *__restrict__ stats,
-                                                             double *__restrict__ sums, int *__restrict__ overflow)
-{
-    __shared__ int tags[LABEL_SLOTS];
-    __shared__ long long lstat[LABEL_SLOTS][8];
-    __shared__ double lsum[LABEL_SLOTS][RED_MAXC];
-    const int b = blockIdx.y;
-    const int64_t n = (int64_t)H * W;
-    const int *lab = labels + (int64_t)b * n;
-    const float *pl = planes + (int64_t)b * C * n;
-    long long *gst = stats + (int64_t)b * cap * 8;
-    double *gsum = sums + (int64_t)b * cap * C;
-    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
-        tags[i] = 0;
-        lstat[i][0] = 0; lstat[i][1] = 0; lstat[i][2] = 0; lstat[i][3] = H; lstat[i][4] = W; lstat[i][5] = 0; lstat[i][6] = 0;
-        lstat[i][7] = 0x7FFFFFFFFFFFFFFFLL;
-        for (int k = 0; k < RED_MAXC; ++k) lsum[i][k] = 0.0;
-    }
-    __syncthreads();
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    const int row0 = blockIdx.x * RED_ROWS;
-    const int segs = (W + 63) / 64;
-    // wave w handles (row, segment) pairs round-robin
-    for (int item = wid; item < RED_ROWS * segs; item += 4) {
-        const int r = row0 + item / segs;
-        if (r >= H) break;
-        const int c = (item % segs) * 64 + lane;
-        const bool inb = c < W;
-        const int l = inb ? lab[rowoff(r, W) + c] : 0;
-        // sel != 0: plane sums only where the class map holds one of the selected values
-        bool want = inb && l > 0;
-        if (want && sel) {
-            const unsigned cv = cls[(int64_t)b * n + rowoff(r, W) + c];
-            want = cv < 64 && ((sel >> cv) & 1ull);
-        }
-        struct Acc {
-            double v[RED_MAXC];
-        } acc;
-#pragma unroll
-        for (int k = 0; k < RED_MAXC; ++k) acc.v[k] = (k < C && want) ? (double)pl[(int64_t)k * n + rowoff(r, W) + c] : 0.0;
-        // label runs of the row segment; per run the float64 sums of the channel values (suffix sums inside the run)
-        const WaveSeg seg = wave_segment(l);
-        const int len = seg.remain + 1;
-        segment_reduce(
-            acc, seg.remain,
-            [](const Acc &a, int off) {
-                Acc o;
-#pragma unroll
-                for (int k = 0; k < RED_MAXC; ++k) o.v[k] = __shfl_down(a.v[k], off);
-                return o;
-            },
-            [C](Acc &a, const Acc &o) {
-#pragma unroll
-                for (int k = 0; k < RED_MAXC; ++k)
-                    if (k < C) a.v[k] += o.v[k];
-            });
-        if (seg.head && l > 0) {
-            if (l > cap) {
-                if (overflow) overflow[b] = 1;
-            } else {
-                const long long L = len, c0 = c, c1 = c + len - 1;
-                const long long s_area = L, s_r = (long long)r * L, s_c = (c0 + c1) * L / 2;
-                const long long first = (long long)r * W + c0;
-                // the same adds on the slot's row in LDS or on the label's row in global memory (there zero sums are skipped)
-                auto add = [&](long long *t, double *ts, bool skip_zero) {
-                    atomicAdd((unsigned long long *)&t[0], (unsigned long long)s_area);
-                    atomicAdd((unsigned long long *)&t[1], (unsigned long long)s_r);
-                    atomicAdd((unsigned long long *)&t[2], (unsigned long long)s_c);
-                    atomic_min_i64(&t[3], (long long)r);
-                    atomic_min_i64(&t[4], c0);
-                    atomic_max_i64(&t[5], (long long)r + 1);
-                    atomic_max_i64(&t[6], c1 + 1);
-                    atomic_min_i64(&t[7], first);
-#pragma unroll
-                    for (int k = 0; k < RED_MAXC; ++k)
-                        if (k < C && !(skip_zero && acc.v[k] == 0.0)) atomicAdd(&ts[k], acc.v[k]);
-                };
-                const int slot = slot_claim(tags, l);
-                if (slot >= 0) add(lstat[slot], lsum[slot], false);
-                else add(gst + (int64_t)(l - 1) * 8, gsum + (int64_t)(l - 1) * C, true);
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
-        const int l = tags[i];
-        if (l == 0) continue;
-        long long *t = gst + (int64_t)(l - 1) * 8;
-        atomicAdd((unsigned long long *)&t[0], (unsigned long long)lstat[i][0]);
-        atomicAdd((unsigned long long *)&t[1], (unsigned long long)lstat[i][1]);
-        atomicAdd((unsigned long long *)&t[2], (unsigned long long)lstat[i][2]);
-        atomic_min_i64(&t[3], lstat[i][3]);
-        atomic_min_i64(&t[4], lstat[i][4]);
-        atomic_max_i64(&t[5], lstat[i][5]);
-        atomic_max_i64(&t[6], lstat[i][6]);
-        atomic_min_i64(&t[7], lstat[i][7]);
-        for (int k = 0; k < C; ++k) atomicAdd(&gsum[(int64_t)(l - 1) * C + k], lsum[i][k]);
-    }
-}
-
-// shared commit step of the column-run reduce kernels: LDS slot if the label owns (or can claim) it, else global atomics.
-// A block covers COL_ROWS rows x 1024 columns (32768 pixels at most) of a frame no larger than 32768 x 32768, so every
-// block-local partial -- area, row and column sums, the first raster index -- fits 32 bits: the LDS table and the lane
-// accumulators are 32-bit (full-rate ds atomics, half the LDS traffic of 64-bit ones), widened at the flush.
+// ---- the plane-free pass (area, centroid sums, bounding box, first pixel): 4 bytes per pixel, frames of any width and
+// alignment.  The column-run walk of label_reduce.h: a vertical run is just (label, first row, end row) -- its area, row sum
+// and column sum follow.  What bounds the pass is not the walk (64 us with the commits taken out: 4.2 TB/s) but the LDS
+// atomics of the commits, eight per run and column (72 us), and the block's flush to the frame's table (55 us): hence the
+// walk's parking and its segmented reduction over the lanes.
+//
+// The commit step: LDS slot if the label owns (or can claim) it, else global atomics.  A block covers RUN_ROWS rows x 1024
+// columns (32768 pixels at most) of a frame no larger than 32768 x 32768, so every block-local partial -- area, row and
+// column sums, the first raster index -- fits 32 bits: the LDS table and the lane accumulators are 32-bit (full-rate ds
+// atomics, half the LDS traffic of 64-bit ones), widened at the flush.
 struct RegionSlots {
     int *tags;
     int (*lstat)[8];
-    double (*lsum)[RED_MAXC];
+    double (*lsum)[RED_MAXC];  // (the fused kernel's; the plane-free pass has none)
 };
 
 __device__ __forceinline__ void region_slots_clear(int *t, int H, int W)
 {
     t[0] = 0; t[1] = 0; t[2] = 0; t[3] = H; t[4] = W; t[5] = 0; t[6] = 0; t[7] = 0x7FFFFFFF;
-}
-
-__device__ __forceinline__ void region_slots_flush(const int *s, long long *t)
-{
-    atomicAdd((unsigned long long *)&t[0], (unsigned long long)(unsigned)s[0]);
-    atomicAdd((unsigned long long *)&t[1], (unsigned long long)(unsigned)s[1]);
-    atomicAdd((unsigned long long *)&t[2], (unsigned long long)(unsigned)s[2]);
-    atomic_min_i64(&t[3], (long long)s[3]);
-    atomic_min_i64(&t[4], (long long)s[4]);
-    atomic_max_i64(&t[5], (long long)s[5]);
-    atomic_max_i64(&t[6], (long long)s[6]);
-    atomic_min_i64(&t[7], (long long)s[7]);
 }
 
 // column f of a slot's row into the label's row t: the three adds, the three mins, the two maxes
@@ -171,6 +66,7 @@ __device__ __forceinline__ void region_slots_flush_word(int v, long long *t, int
     else atomic_min_i64(&t[f], (long long)v);
 }
 
+// (NC > 0: the run's plane sums go with its integer columns -- region_reduce_col_kernel)
 template <int NC>
 __device__ __forceinline__ void region_commit(const RegionSlots &ls, long long *gst, double *gsum, int *overflow, int b, int cap,
                                               int C, int l, int s_area, int s_r, int s_c, int rmin, int rmax1, int c0, int c1,
@@ -210,191 +106,6 @@ __device__ __forceinline__ void region_commit(const RegionSlots &ls, long long *
     }
 }
 
-// Column-run variant (W % 4 == 0): a lane owns 4 adjacent columns and walks DOWN COL_ROWS rows; it accumulates the
-// vertical run of equal labels in registers (area, row sum, plane sums in float64) and commits when the label
-// changes.  No cross-lane traffic at all; loads are int4 / float4 and coalesced along the row.
-constexpr int COL_ROWS = 32;
-
-// (NC == 0 is kept for completeness; the pipeline's plane-free pass is region_stats_col_kernel below)
-template <int NC>
-__global__ void __launch_bounds__(256, NC > 0 ? 2 : 4) region_reduce_col_kernel(const int *__restrict__ labels, const float *__restrict__ planes,
-                                                                 const uint8_t *__restrict__ cls, unsigned long long sel, int C,
-                                                                 int H, int W, int cap, long long *__restrict__ stats,
-                                                                 double *__restrict__ sums, int *__restrict__ overflow)
-{
-    __shared__ int tags[LABEL_SLOTS];
-    __shared__ int lstat[LABEL_SLOTS][8];
-    __shared__ double lsum[NC > 0 ? LABEL_SLOTS : 1][RED_MAXC];
-    const TileIndex ti = xcd_tile_index();  // (a frame's blocks on one XCD: their atomics on the frame's tables meet in one L2)
-    const int b = ti.z;
-    const int64_t n = (int64_t)H * W;
-    const int *lab = labels + (int64_t)b * n;
-    const float *pl = NC > 0 ? planes + (int64_t)b * C * n : nullptr;
-    long long *gst = stats + (int64_t)b * cap * 8;
-    double *gsum = NC > 0 ? sums + (int64_t)b * cap * C : nullptr;
-    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
-        tags[i] = 0;
-        region_slots_clear(lstat[i], H, W);
-        if (NC > 0)
-            for (int k = 0; k < RED_MAXC; ++k) lsum[i][k] = 0.0;
-    }
-    __syncthreads();
-    const RegionSlots ls{tags, lstat, lsum};
-    const int c = (ti.x * 256 + threadIdx.x) * 4;
-    const int r0 = ti.y * COL_ROWS, r1 = min(H, r0 + COL_ROWS);
-    if (c < W) {
-        int cur[4] = {0, 0, 0, 0}, start[4] = {0, 0, 0, 0};
-        int area[4] = {0, 0, 0, 0}, srow[4] = {0, 0, 0, 0};
-        double acc[4][NC > 0 ? NC : 1];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int k = 0; k < (NC > 0 ? NC : 1); ++k) acc[j][k] = 0.0;
-        // the next row's six 16-byte loads are issued before this row is processed (the run logic below is a chain of
-        // branches the compiler does not move loads across)
-        int4 l4n = make_int4(0, 0, 0, 0);
-        float4 vn[NC > 0 ? NC : 1];
-        // sel != 0: plane sums only where the class map holds one of the selected values -- the planes of a 4-pixel
-        // group without such a pixel are not even read (for class-map components only cell regions need sums, and they
-        // are a small part of a frame)
-        unsigned wantn = 0xF;
-        int64_t at = rowoff(r0, W) + c;  // (fetch() walks the rows in order)
-        auto fetch = [&](int r) {
-            l4n = make_int4(0, 0, 0, 0);
-            if (r < r1) {
-                l4n = *reinterpret_cast<const int4 *>(lab + at);
-                if (NC > 0) {
-                    if (sel) {
-                        const unsigned cw = *reinterpret_cast<const unsigned *>(cls + (int64_t)b * n + at);
-                        wantn = 0;
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const unsigned cv = (cw >> (8 * j)) & 255u;
-                            if (cv < 64 && ((sel >> cv) & 1ull)) wantn |= 1u << j;
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < NC; ++k)
-                        vn[k] = (k < C && wantn) ? *reinterpret_cast<const float4 *>(pl + (int64_t)k * n + at)
-                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                at += W;
-            }
-        };
-        // one row of the walk (r == r1: the flush after the last row, with an all-zero label quad)
-        auto step = [&](const int r, const int4 l4, const unsigned want, const float4 *v) {
-            const int ll[4] = {l4.x, l4.y, l4.z, l4.w};
-            if (r == r1) {
-                // end of the block: the four columns of a lane usually sit in the same region; folding them first
-                // quarters the number of same-slot LDS atomics the whole block fires at once
-                int scol[4], rmin[4], rmax1[4], cmin[4], cmax[4], first[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    scol[j] = __mul24(c + j, area[j]);
-                    rmin[j] = start[j];
-                    rmax1[j] = start[j] + area[j];
-                    cmin[j] = cmax[j] = c + j;
-                    first[j] = __mul24(start[j], W) + c + j;
-                }
-#pragma unroll
-                for (int j = 1; j < 4; ++j)
-#pragma unroll
-                    for (int i = 0; i < j; ++i)
-                        if (cur[j] > 0 && cur[j] == cur[i]) {
-                            area[i] += area[j]; srow[i] += srow[j]; scol[i] += scol[j];
-                            rmin[i] = min(rmin[i], rmin[j]); rmax1[i] = max(rmax1[i], rmax1[j]);
-                            cmin[i] = min(cmin[i], cmin[j]); cmax[i] = max(cmax[i], cmax[j]); first[i] = min(first[i], first[j]);
-#pragma unroll
-                            for (int k = 0; k < (NC > 0 ? NC : 1); ++k) acc[i][k] += acc[j][k];
-                            cur[j] = 0;
-                        }
-                // ... and when a whole WAVE sits in one region (background, the particle: most waves of a class map) the 64
-                // lanes are reduced with shuffles and one lane commits: otherwise they all fire their eight atomics at the
-                // same LDS slot, which serialises them
-                const int l0 = __builtin_amdgcn_readfirstlane(cur[0]);
-                // (only a fully active wave: a shuffle from a lane beyond the frame's width would read nothing defined)
-                if (__ballot(true) == ~0ull && __all(cur[0] == l0 && l0 > 0 && cur[1] == 0 && cur[2] == 0 && cur[3] == 0)) {
-                    int v_area = area[0], v_srow = srow[0], v_scol = scol[0], v_rmin = rmin[0], v_rmax = rmax1[0], v_cmin = cmin[0],
-                        v_cmax = cmax[0], v_first = first[0];
-                    for (int off = 32; off; off >>= 1) {
-                        v_area += __shfl_xor(v_area, off);
-                        v_srow += __shfl_xor(v_srow, off);
-                        v_scol += __shfl_xor(v_scol, off);
-                        v_rmin = min(v_rmin, __shfl_xor(v_rmin, off));
-                        v_rmax = max(v_rmax, __shfl_xor(v_rmax, off));
-                        v_cmin = min(v_cmin, __shfl_xor(v_cmin, off));
-                        v_cmax = max(v_cmax, __shfl_xor(v_cmax, off));
-                        v_first = min(v_first, __shfl_xor(v_first, off));
-#pragma unroll
-                        for (int k = 0; k < (NC > 0 ? NC : 1); ++k) acc[0][k] += __shfl_xor(acc[0][k], off);
-                    }
-                    if (lane_id() == 0)
-                        region_commit<NC>(ls, gst, gsum, overflow, b, cap, C, l0, v_area, v_srow, v_scol, v_rmin, v_rmax, v_cmin, v_cmax,
-                                          v_first, acc[0]);
-                    return;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (cur[j] > 0)
-                        region_commit<NC>(ls, gst, gsum, overflow, b, cap, C, cur[j], area[j], srow[j], scol[j], rmin[j], rmax1[j],
-                                          cmin[j], cmax[j], first[j], acc[j]);
-                return;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (ll[j] != cur[j]) {
-                    if (cur[j] > 0)
-                        region_commit<NC>(ls, gst, gsum, overflow, b, cap, C, cur[j], area[j], srow[j], __mul24(c + j, area[j]),
-                                          start[j], start[j] + area[j], c + j, c + j, __mul24(start[j], W) + c + j, acc[j]);
-                    cur[j] = ll[j];
-                    start[j] = r;
-                    area[j] = 0;
-                    srow[j] = 0;
-#pragma unroll
-                    for (int k = 0; k < (NC > 0 ? NC : 1); ++k) acc[j][k] = 0.0;
-                }
-                if (ll[j] > 0) {
-                    area[j] += 1;
-                    srow[j] += r;
-                    if (NC > 0 && ((want >> j) & 1u)) {
-#pragma unroll
-                        for (int k = 0; k < NC; ++k) {
-                            const float4 f = v[k];
-                            acc[j][k] += (double)(j == 0 ? f.x : (j == 1 ? f.y : (j == 2 ? f.z : f.w)));
-                        }
-                    }
-                }
-            }
-                };
-        fetch(r0);
-        for (int r = r0; r <= r1; ++r) {
-            const int4 l4 = l4n;
-            const unsigned want = wantn;
-            float4 v[NC > 0 ? NC : 1];
-#pragma unroll
-            for (int k = 0; k < (NC > 0 ? NC : 1); ++k) v[k] = vn[k];
-            landed(l4);
-            if (NC > 0) {
-#pragma unroll
-                for (int k = 0; k < NC; ++k) landed(v[k]);
-            }
-            fetch(r + 1);
-            step(r, l4, want, v);
-        }
-    }
-    __syncthreads();
-    // flush: one lane per column of the integer row, one per plane sum
-    slots_flush8(tags, [&](int i, int l, int f) {
-        region_slots_flush_word(lstat[i][f], gst + (int64_t)(l - 1) * 8, f);
-        if (NC > 0 && f < C) atomicAdd(&gsum[(int64_t)(l - 1) * C + f], lsum[i][f]);
-    });
-}
-
-// ---- the plane-free pass (area, centroid sums, bounding box, first pixel): 4 bytes per pixel, frames of any width and
-// alignment.  The column-run walk of label_reduce.h: a vertical run is just (label, first row, end row) -- its area, row sum
-// and column sum follow.  What bounds the pass is not the walk (64 us with the commits taken out: 4.2 TB/s) but the LDS
-// atomics of the commits, eight per run and column (72 us), and the block's flush to the frame's table (55 us): hence the
-// walk's parking and its segmented reduction over the lanes.
 struct RunSum {
     int key;  // the label; 0 = none
     int area, srow, scol, rmin, rmax1, cmin, cmax, first;
@@ -455,12 +166,11 @@ __global__ void __launch_bounds__(256, 4) region_stats_col_kernel(const int *__r
     slots_flush8(tags, [&](int i, int l, int f) { region_slots_flush_word(lstat[i][f], gst + (int64_t)(l - 1) * 8, f); });
 }
 
-// ---- plane sums of TWO label images in one pass over the planes (M1 for the class-map components and for the refined
-// ROIs: both tables report isotope sums, both label images are final by the end of a batch's chains, and the planes are
-// by far the largest thing either reduction reads).  Same column-run scheme as region_reduce_col_kernel -- a lane owns 4
-// adjacent columns, walks down COL_ROWS rows and keeps each vertical run's float64 sums in registers -- but only the
-// sums: the integer columns (area, centroid sums, bounding box, first pixel) come from the plane-free kernel, which
-// reads 4 bytes per pixel.  Image A is restricted to the classes in `sel` (bit v = class value v; 0 = every pixel).
+// ---- the plane sums (M1), of TWO label images in one pass over the planes (the class-map components and the refined
+// ROIs: both tables report isotope sums, both label images are final by the end of a batch's chains, and the planes are by
+// far the largest thing either reduction reads).  Only the sums: the integer columns are the plane-free pass's.  A run
+// commits its float64 sums to the block's LDS slot table or, for a label that does not own its slot, straight to the
+// frame's table; a run whose sums are all zero (a region outside the class selection, zero-valued planes) commits nothing.
 struct SumSlots {
     int *tags;
     double (*lsum)[RED_MAXC];
@@ -486,50 +196,56 @@ __device__ __forceinline__ void sums_commit(const SumSlots &ls, double *gsum, in
     }
 }
 
-// STATS_B: image B's integer columns (area, centroid sums, bounding box, first pixel) are accumulated in the same walk
-// (its runs are tracked anyway): the refined ROIs' table then needs no pass of its own.
-// (five planes without image B's integer columns fit 168 registers: three blocks per CU instead of two, 409 us a launch
-// against 497)
+// flush of a block's sums table: one lane per plane (a row's neighbouring sums are merged per 64-byte line by the hardware)
+__device__ __forceinline__ void sums_flush(const int *tags, const double (*lsum)[RED_MAXC], double *gsum, int C)
+{
+    static_assert(RED_MAXC == 8, "eight lanes per slot");
+    slots_flush8(tags, [&](int i, int l, int k) {
+        if (k < C && lsum[i][k] != 0.0) atomicAdd(&gsum[(int64_t)(l - 1) * C + k], lsum[i][k]);
+    });
+}
+
+// The column kernel (W % 4 == 0, 16-byte aligned images): a lane owns 4 adjacent columns and walks DOWN COL_ROWS rows; it
+// keeps each vertical run's float64 sums in registers and commits when the label changes.  No cross-lane traffic at all;
+// loads are int4 / float4 and coalesced along the row.  Image A is restricted to the classes in `sel` (bit v = class value
+// v; 0 = every pixel).
+// NC: the planes a lane carries, 5 or 8 (five planes fit 168 registers: three blocks per CU instead of two, 409 us a launch
+// against 497).
 // EXACT: C == NC, the plane loads carry no test of C (each test is a scalar branch, and the compiler drains the load queue
 // at some of them).
-template <int NC, bool STATS_B, bool EXACT>
-__global__ void __launch_bounds__(256, (NC <= 5 && !STATS_B) ? 3 : 2) region_sums2_col_kernel(const int *__restrict__ labels_a, const uint8_t *__restrict__ cls,
+constexpr int COL_ROWS = 32;
+
+template <int NC, bool EXACT>
+__global__ void __launch_bounds__(256, NC <= 5 ? 3 : 2) region_sums2_col_kernel(const int *__restrict__ labels_a, const uint8_t *__restrict__ cls,
                                                                   unsigned long long sel, const int *__restrict__ labels_b,
                                                                   const float *__restrict__ planes, int C, int H, int W, int cap_a,
-                                                                  int cap_b, double *__restrict__ sums_a, double *__restrict__ sums_b,
-                                                                  long long *__restrict__ stats_b, int *__restrict__ overflow_b)
+                                                                  int cap_b, double *__restrict__ sums_a, double *__restrict__ sums_b)
 {
     __shared__ int tags_a[LABEL_SLOTS], tags_b[LABEL_SLOTS];
     __shared__ double lsum_a[LABEL_SLOTS][RED_MAXC], lsum_b[LABEL_SLOTS][RED_MAXC];
-    __shared__ int lstat_b[STATS_B ? LABEL_SLOTS : 1][8];
     const TileIndex ti = xcd_tile_index();  // (a frame's blocks on one XCD: their atomics on the frame's tables meet in one L2)
     const int b = ti.z;
     const int64_t n = (int64_t)H * W;
     const int *la = labels_a + (int64_t)b * n, *lb = labels_b + (int64_t)b * n;
     const float *pl = planes + (int64_t)b * C * n;
     double *ga = sums_a + (int64_t)b * cap_a * C, *gb = sums_b + (int64_t)b * cap_b * C;
-    long long *gst_b = STATS_B ? stats_b + (int64_t)b * cap_b * 8 : nullptr;
     for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
         tags_a[i] = 0;
         tags_b[i] = 0;
         for (int k = 0; k < RED_MAXC; ++k) { lsum_a[i][k] = 0.0; lsum_b[i][k] = 0.0; }
-        if (STATS_B) region_slots_clear(lstat_b[i], H, W);
     }
     __syncthreads();
     const SumSlots sa{tags_a, lsum_a}, sb{tags_b, lsum_b};
-    const RegionSlots sbb{tags_b, lstat_b, lsum_b};
     const int c = (ti.x * 256 + threadIdx.x) * 4;
     const int r0 = ti.y * COL_ROWS, r1 = min(H, r0 + COL_ROWS);
     if (c < W) {
         int cur_a[4] = {0, 0, 0, 0}, cur_b[4] = {0, 0, 0, 0};
-        int start_b[4] = {0, 0, 0, 0}, area_b[4] = {0, 0, 0, 0};
-        int srow_b[4] = {0, 0, 0, 0};
         double acc_a[4][NC], acc_b[4][NC];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int k = 0; k < NC; ++k) { acc_a[j][k] = 0.0; acc_b[j][k] = 0.0; }
-        // the next row's eight 16-byte loads are issued before this row is processed
+        // the next row's 16-byte loads (two label quads, NC plane quads) are issued before this row is processed
         int4 a4n = make_int4(0, 0, 0, 0), b4n = make_int4(0, 0, 0, 0);
         float4 vn[NC];
         // (the class bytes are decoded when the row is processed, not when it is fetched: a decode here would wait for the
@@ -591,27 +307,13 @@ __global__ void __launch_bounds__(256, (NC <= 5 && !STATS_B) ? 3 : 2) region_sum
                     for (int k = 0; k < NC; ++k) acc_a[j][k] = 0.0;
                 }
                 if (bb[j] != cur_b[j]) {
-                    if (STATS_B) {
-                        if (cur_b[j] > 0)
-                            region_commit<NC>(sbb, gst_b, gb, overflow_b, b, cap_b, C, cur_b[j], area_b[j], srow_b[j],
-                                              __mul24(c + j, area_b[j]), start_b[j], start_b[j] + area_b[j], c + j, c + j,
-                                              __mul24(start_b[j], W) + c + j, acc_b[j]);
-                        start_b[j] = r;
-                        area_b[j] = 0;
-                        srow_b[j] = 0;
-                    } else {
-                        sums_commit<NC>(sb, gb, cap_b, C, cur_b[j], acc_b[j]);
-                    }
+                    sums_commit<NC>(sb, gb, cap_b, C, cur_b[j], acc_b[j]);
                     cur_b[j] = bb[j];
 #pragma unroll
                     for (int k = 0; k < NC; ++k) acc_b[j][k] = 0.0;
                 }
                 if (r < r1) {
                     const bool in_a = aa[j] > 0 && ((want >> j) & 1u), in_b = bb[j] > 0;
-                    if (STATS_B && in_b) {
-                        area_b[j] += 1;
-                        srow_b[j] += r;
-                    }
 #pragma unroll
                     for (int k = 0; k < NC; ++k) {
                         const float4 f = v[k];
@@ -624,15 +326,243 @@ __global__ void __launch_bounds__(256, (NC <= 5 && !STATS_B) ? 3 : 2) region_sum
         }
     }
     __syncthreads();
-    // flush: one lane per plane (a row's neighbouring sums are merged per 64-byte line by the hardware)
-    static_assert(RED_MAXC == 8, "eight lanes per slot");
-    slots_flush8(tags_a, [&](int i, int l, int k) {
-        if (k < C && lsum_a[i][k] != 0.0) atomicAdd(&ga[(int64_t)(l - 1) * C + k], lsum_a[i][k]);
+    sums_flush(tags_a, lsum_a, ga, C);
+    sums_flush(tags_b, lsum_b, gb, C);
+}
+
+// The fused kernel of ONE image (W % 4 == 0, 16-byte aligned): integer columns AND plane sums in one walk of the sums
+// kernel's kind -- a lane owns 4 adjacent columns, walks down COL_ROWS rows and commits a run when the label changes.  It
+// repeats what the two walks above do and is kept for one reason: pcseg_region_reduce on ONE frame (roi_activity goes frame
+// by frame) is 98 us as the plane-free pass plus a sums pass and 93 us fused (1024 x 1024, seven planes; a batch of 16
+// frames is 5 % faster split, profiles/plane_sums/speed.md): a single frame's plane-free pass is 32 blocks on 256 CUs.
+template <int NC>
+__global__ void __launch_bounds__(256, 2) region_reduce_col_kernel(const int *__restrict__ labels, const float *__restrict__ planes,
+                                                                 const uint8_t *__restrict__ cls, unsigned long long sel, int C,
+                                                                 int H, int W, int cap, long long *__restrict__ stats,
+                                                                 double *__restrict__ sums, int *__restrict__ overflow)
+{
+    __shared__ int tags[LABEL_SLOTS];
+    __shared__ int lstat[LABEL_SLOTS][8];
+    __shared__ double lsum[LABEL_SLOTS][RED_MAXC];
+    const TileIndex ti = xcd_tile_index();  // (a frame's blocks on one XCD: their atomics on the frame's tables meet in one L2)
+    const int b = ti.z;
+    const int64_t n = (int64_t)H * W;
+    const int *lab = labels + (int64_t)b * n;
+    const float *pl = planes + (int64_t)b * C * n;
+    long long *gst = stats + (int64_t)b * cap * 8;
+    double *gsum = sums + (int64_t)b * cap * C;
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
+        tags[i] = 0;
+        region_slots_clear(lstat[i], H, W);
+        for (int k = 0; k < RED_MAXC; ++k) lsum[i][k] = 0.0;
+    }
+    __syncthreads();
+    const RegionSlots ls{tags, lstat, lsum};
+    const int c = (ti.x * 256 + threadIdx.x) * 4;
+    const int r0 = ti.y * COL_ROWS, r1 = min(H, r0 + COL_ROWS);
+    if (c < W) {
+        int cur[4] = {0, 0, 0, 0}, start[4] = {0, 0, 0, 0};
+        int area[4] = {0, 0, 0, 0}, srow[4] = {0, 0, 0, 0};
+        double acc[4][NC];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int k = 0; k < NC; ++k) acc[j][k] = 0.0;
+        // the next row's six 16-byte loads are issued before this row is processed (the run logic below is a chain of
+        // branches the compiler does not move loads across)
+        int4 l4n = make_int4(0, 0, 0, 0);
+        float4 vn[NC];
+        // sel != 0: plane sums only where the class map holds one of the selected values -- the planes of a 4-pixel
+        // group without such a pixel are not even read (for class-map components only cell regions need sums, and they
+        // are a small part of a frame)
+        unsigned wantn = 0xF;
+        int64_t at = rowoff(r0, W) + c;  // (fetch() walks the rows in order)
+        auto fetch = [&](int r) {
+            l4n = make_int4(0, 0, 0, 0);
+            if (r < r1) {
+                l4n = *reinterpret_cast<const int4 *>(lab + at);
+                if (sel) {
+                    const unsigned cw = *reinterpret_cast<const unsigned *>(cls + (int64_t)b * n + at);
+                    wantn = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const unsigned cv = (cw >> (8 * j)) & 255u;
+                        if (cv < 64 && ((sel >> cv) & 1ull)) wantn |= 1u << j;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < NC; ++k)
+                    vn[k] = (k < C && wantn) ? *reinterpret_cast<const float4 *>(pl + (int64_t)k * n + at)
+                                             : make_float4(0.f, 0.f, 0.f, 0.f);
+                at += W;
+            }
+        };
+        // one row of the walk (r == r1: the flush after the last row, with an all-zero label quad)
+        auto step = [&](const int r, const int4 l4, const unsigned want, const float4 *v) {
+            const int ll[4] = {l4.x, l4.y, l4.z, l4.w};
+            if (r == r1) {
+                // end of the block: the four columns of a lane usually sit in the same region; folding them first
+                // quarters the number of same-slot LDS atomics the whole block fires at once
+                int scol[4], rmin[4], rmax1[4], cmin[4], cmax[4], first[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    scol[j] = __mul24(c + j, area[j]);
+                    rmin[j] = start[j];
+                    rmax1[j] = start[j] + area[j];
+                    cmin[j] = cmax[j] = c + j;
+                    first[j] = __mul24(start[j], W) + c + j;
+                }
+#pragma unroll
+                for (int j = 1; j < 4; ++j)
+#pragma unroll
+                    for (int i = 0; i < j; ++i)
+                        if (cur[j] > 0 && cur[j] == cur[i]) {
+                            area[i] += area[j]; srow[i] += srow[j]; scol[i] += scol[j];
+                            rmin[i] = min(rmin[i], rmin[j]); rmax1[i] = max(rmax1[i], rmax1[j]);
+                            cmin[i] = min(cmin[i], cmin[j]); cmax[i] = max(cmax[i], cmax[j]); first[i] = min(first[i], first[j]);
+#pragma unroll
+                            for (int k = 0; k < NC; ++k) acc[i][k] += acc[j][k];
+                            cur[j] = 0;
+                        }
+                // ... and when a whole WAVE sits in one region (background, the particle: most waves of a class map) the 64
+                // lanes are reduced with shuffles and one lane commits: otherwise they all fire their eight atomics at the
+                // same LDS slot, which serialises them
+                const int l0 = __builtin_amdgcn_readfirstlane(cur[0]);
+                // (only a fully active wave: a shuffle from a lane beyond the frame's width would read nothing defined)
+                if (__ballot(true) == ~0ull && __all(cur[0] == l0 && l0 > 0 && cur[1] == 0 && cur[2] == 0 && cur[3] == 0)) {
+                    int v_area = area[0], v_srow = srow[0], v_scol = scol[0], v_rmin = rmin[0], v_rmax = rmax1[0], v_cmin = cmin[0],
+                        v_cmax = cmax[0], v_first = first[0];
+                    for (int off = 32; off; off >>= 1) {
+                        v_area += __shfl_xor(v_area, off);
+                        v_srow += __shfl_xor(v_srow, off);
+                        v_scol += __shfl_xor(v_scol, off);
+                        v_rmin = min(v_rmin, __shfl_xor(v_rmin, off));
+                        v_rmax = max(v_rmax, __shfl_xor(v_rmax, off));
+                        v_cmin = min(v_cmin, __shfl_xor(v_cmin, off));
+                        v_cmax = max(v_cmax, __shfl_xor(v_cmax, off));
+                        v_first = min(v_first, __shfl_xor(v_first, off));
+#pragma unroll
+                        for (int k = 0; k < NC; ++k) acc[0][k] += __shfl_xor(acc[0][k], off);
+                    }
+                    if (lane_id() == 0)
+                        region_commit<NC>(ls, gst, gsum, overflow, b, cap, C, l0, v_area, v_srow, v_scol, v_rmin, v_rmax, v_cmin, v_cmax,
+                                          v_first, acc[0]);
+                    return;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (cur[j] > 0)
+                        region_commit<NC>(ls, gst, gsum, overflow, b, cap, C, cur[j], area[j], srow[j], scol[j], rmin[j], rmax1[j],
+                                          cmin[j], cmax[j], first[j], acc[j]);
+                return;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (ll[j] != cur[j]) {
+                    if (cur[j] > 0)
+                        region_commit<NC>(ls, gst, gsum, overflow, b, cap, C, cur[j], area[j], srow[j], __mul24(c + j, area[j]),
+                                          start[j], start[j] + area[j], c + j, c + j, __mul24(start[j], W) + c + j, acc[j]);
+                    cur[j] = ll[j];
+                    start[j] = r;
+                    area[j] = 0;
+                    srow[j] = 0;
+#pragma unroll
+                    for (int k = 0; k < NC; ++k) acc[j][k] = 0.0;
+                }
+                if (ll[j] > 0) {
+                    area[j] += 1;
+                    srow[j] += r;
+                    if ((want >> j) & 1u) {
+#pragma unroll
+                        for (int k = 0; k < NC; ++k) {
+                            const float4 f = v[k];
+                            acc[j][k] += (double)(j == 0 ? f.x : (j == 1 ? f.y : (j == 2 ? f.z : f.w)));
+                        }
+                    }
+                }
+            }
+        };
+        fetch(r0);
+        for (int r = r0; r <= r1; ++r) {
+            const int4 l4 = l4n;
+            const unsigned want = wantn;
+            float4 v[NC];
+#pragma unroll
+            for (int k = 0; k < NC; ++k) v[k] = vn[k];
+            landed(l4);
+#pragma unroll
+            for (int k = 0; k < NC; ++k) landed(v[k]);
+            fetch(r + 1);
+            step(r, l4, want, v);
+        }
+    }
+    __syncthreads();
+    // flush: one lane per column of the integer row, one per plane sum
+    slots_flush8(tags, [&](int i, int l, int f) {
+        region_slots_flush_word(lstat[i][f], gst + (int64_t)(l - 1) * 8, f);
+        if (f < C) atomicAdd(&gsum[(int64_t)(l - 1) * C + f], lsum[i][f]);
     });
-    slots_flush8(tags_b, [&](int i, int l, int k) {
-        if (k < C && lsum_b[i][k] != 0.0) atomicAdd(&gb[(int64_t)(l - 1) * C + k], lsum_b[i][k]);
-        if (STATS_B && k == 0) region_slots_flush(lstat_b[i], gst_b + (int64_t)(l - 1) * 8);
-    });
+}
+
+// The row kernel, for frames whose width or base addresses rule out 16-byte loads: a wave takes 64-pixel row segments; the
+// label runs of a segment come from a ballot, a run's float64 sums from a segmented reduction over its lanes, and the
+// first lane of a run commits them.
+__global__ void __launch_bounds__(256) region_sums_row_kernel(const int *__restrict__ labels, const float *__restrict__ planes,
+                                                               const uint8_t *__restrict__ cls, unsigned long long sel, int C, int H,
+                                                               int W, int cap, double *__restrict__ sums)
+{
+    __shared__ int tags[LABEL_SLOTS];
+    __shared__ double lsum[LABEL_SLOTS][RED_MAXC];
+    const int b = blockIdx.y;
+    const int64_t n = (int64_t)H * W;
+    const int *lab = labels + (int64_t)b * n;
+    const float *pl = planes + (int64_t)b * C * n;
+    double *gsum = sums + (int64_t)b * cap * C;
+    for (int i = threadIdx.x; i < LABEL_SLOTS; i += 256) {
+        tags[i] = 0;
+        for (int k = 0; k < RED_MAXC; ++k) lsum[i][k] = 0.0;
+    }
+    __syncthreads();
+    const SumSlots ls{tags, lsum};
+    const int lane = lane_id(), wid = threadIdx.x >> 6;
+    const int row0 = blockIdx.x * RED_ROWS;
+    const int segs = (W + 63) / 64;
+    // wave w handles (row, segment) pairs round-robin
+    for (int item = wid; item < RED_ROWS * segs; item += 4) {
+        const int r = row0 + item / segs;
+        if (r >= H) break;
+        const int c = (item % segs) * 64 + lane;
+        const bool inb = c < W;
+        const int l = inb ? lab[rowoff(r, W) + c] : 0;
+        // sel != 0: plane sums only where the class map holds one of the selected values
+        bool want = inb && l > 0;
+        if (want && sel) {
+            const unsigned cv = cls[(int64_t)b * n + rowoff(r, W) + c];
+            want = cv < 64 && ((sel >> cv) & 1ull);
+        }
+        struct Acc {
+            double v[RED_MAXC];
+        } acc;
+#pragma unroll
+        for (int k = 0; k < RED_MAXC; ++k) acc.v[k] = (k < C && want) ? (double)pl[(int64_t)k * n + rowoff(r, W) + c] : 0.0;
+        const WaveSeg seg = wave_segment(l);
+        segment_reduce(
+            acc, seg.remain,
+            [](const Acc &a, int off) {
+                Acc o;
+#pragma unroll
+                for (int k = 0; k < RED_MAXC; ++k) o.v[k] = __shfl_down(a.v[k], off);
+                return o;
+            },
+            [C](Acc &a, const Acc &o) {
+#pragma unroll
+                for (int k = 0; k < RED_MAXC; ++k)
+                    if (k < C) a.v[k] += o.v[k];
+            });
+        if (seg.head) sums_commit<RED_MAXC>(ls, gsum, cap, C, l, acc.v);
+    }
+    __syncthreads();
+    sums_flush(tags, lsum, gsum, C);
 }
 
 __global__ void __launch_bounds__(256) region_class_kernel(const long long *__restrict__ stats, const uint8_t *__restrict__ cls,
@@ -1021,6 +951,31 @@ static int merge_groups_launch(const char *who, Source src, const int64_t *stats
     return PCSEG_OK;
 }
 
+// the plane-free pass over one label image; `vec`: W % 4 == 0 and a 16-byte aligned base
+static void stats_launch(bool vec, const int *labels, int B, int H, int W, int cap, long long *stats, int *overflow, hipStream_t s)
+{
+    const dim3 grid((W + 1023) / 1024, (H + RUN_ROWS - 1) / RUN_ROWS, B);
+    if (vec) PCSEG_LAUNCH(region_stats_col_kernel<true>, grid, dim3(256), 0, s, labels, H, W, cap, stats, overflow);
+    else PCSEG_LAUNCH(region_stats_col_kernel<false>, grid, dim3(256), 0, s, labels, H, W, cap, stats, overflow);
+}
+
+// the column sums kernel for C planes: NC = 5 up to five planes, else 8; EXACT where C == NC
+static void sums_launch(const int *labels_a, const uint8_t *cls, unsigned long long sel, const int *labels_b, const float *planes, int C,
+                        int B, int H, int W, int cap_a, int cap_b, double *sums_a, double *sums_b, hipStream_t s)
+{
+    const dim3 grid((W / 4 + 255) / 256, (H + COL_ROWS - 1) / COL_ROWS, B);
+    auto launch = [&](auto nc, auto exact) {
+        PCSEG_LAUNCH((region_sums2_col_kernel<decltype(nc)::value, decltype(exact)::value>), grid, dim3(256), 0, s, labels_a, cls,
+                     sel, labels_b, planes, C, H, W, cap_a, cap_b, sums_a, sums_b);
+    };
+    using Five = std::integral_constant<int, 5>;
+    using Eight = std::integral_constant<int, 8>;
+    if (C == 5) launch(Five{}, std::true_type{});
+    else if (C < 5) launch(Five{}, std::false_type{});
+    else if (C == 8) launch(Eight{}, std::true_type{});
+    else launch(Eight{}, std::false_type{});
+}
+
 }  // namespace pcseg
 
 using namespace pcseg;
@@ -1052,25 +1007,26 @@ int pcseg_region_reduce_sel(const int32_t *labels, const int32_t *counts, const 
     dim3 gi((cap * 8 + 255) / 256, B);  // eight lanes per row
     PCSEG_LAUNCH(region_init_kernel, gi, dim3(256), 0, s, (long long *)stats, sums, counts, cap, C, H, W);
     PCSEG_CHECK_LAUNCH();
-    dim3 grid((H + RED_ROWS - 1) / RED_ROWS, B);
-    const bool vec = (W % 4) == 0 && ((uintptr_t)labels % 16) == 0 && (!planes || ((uintptr_t)planes % 16) == 0) &&
-                     (!sel || ((uintptr_t)cls % 4) == 0);
-    const dim3 cgrid((W / 4 + 255) / 256, (H + COL_ROWS - 1) / COL_ROWS, B);
-    const dim3 sgrid((W + 1023) / 1024, (H + RUN_ROWS - 1) / RUN_ROWS, B);  // the plane-free pass: any width
-    if (vec && planes && C <= 5)
-        PCSEG_LAUNCH(region_reduce_col_kernel<5>, cgrid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats, sums,
-                     overflow);
-    else if (vec && planes)
-        PCSEG_LAUNCH(region_reduce_col_kernel<8>, cgrid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats, sums,
-                     overflow);
-    else if (planes)
-        PCSEG_LAUNCH(region_reduce_kernel, grid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats, sums,
-                     overflow);
-    else if (vec)
-        PCSEG_LAUNCH(region_stats_col_kernel<true>, sgrid, dim3(256), 0, s, labels, H, W, cap, (long long *)stats, overflow);
-    else
-        PCSEG_LAUNCH(region_stats_col_kernel<false>, sgrid, dim3(256), 0, s, labels, H, W, cap, (long long *)stats, overflow);
-    PCSEG_CHECK_LAUNCH();
+    const bool vec = (W % 4) == 0 && ((uintptr_t)labels % 16) == 0;  // 16-byte label loads
+    if (planes && vec && ((uintptr_t)planes % 16) == 0 && (!sel || ((uintptr_t)cls % 4) == 0)) {
+        const dim3 cgrid((W / 4 + 255) / 256, (H + COL_ROWS - 1) / COL_ROWS, B);
+        if (C <= 5)
+            PCSEG_LAUNCH(region_reduce_col_kernel<5>, cgrid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats,
+                         sums, overflow);
+        else
+            PCSEG_LAUNCH(region_reduce_col_kernel<8>, cgrid, dim3(256), 0, s, labels, planes, cls, sel, C, H, W, cap, (long long *)stats,
+                         sums, overflow);
+        PCSEG_CHECK_LAUNCH();
+    } else {
+        // the integer columns from the labels alone; planes that rule out 16-byte loads are summed by rows
+        stats_launch(vec, labels, B, H, W, cap, (long long *)stats, overflow, s);
+        PCSEG_CHECK_LAUNCH();
+        if (planes) {
+            PCSEG_LAUNCH(region_sums_row_kernel, dim3((H + RED_ROWS - 1) / RED_ROWS, B), dim3(256), 0, s, labels, planes, cls, sel, C, H,
+                         W, cap, sums);
+            PCSEG_CHECK_LAUNCH();
+        }
+    }
     if (cls) {
         PCSEG_LAUNCH(region_class_kernel, gi, dim3(256), 0, s, (const long long *)stats, cls, counts, cls_out, cap,
                            (int64_t)H * W);
@@ -1109,20 +1065,11 @@ int pcseg_region_sums2(const int32_t *labels_a, const uint8_t *cls, uint64_t sum
                       (!sum_class_bits || ((uintptr_t)cls % 4) == 0),
                   "W must be a multiple of 4 and the images 16-byte aligned (use pcseg_region_reduce_sel per image otherwise)");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 cgrid((W / 4 + 255) / 256, (H + COL_ROWS - 1) / COL_ROWS, B);
-    const unsigned long long sel = sum_class_bits;
-#define PCSEG_SUMS2(NCV, ST)                                                                                                        \
-    if (C == NCV)                                                                                                                   \
-        PCSEG_LAUNCH((region_sums2_col_kernel<NCV, ST, true>), cgrid, dim3(256), 0, s, labels_a, cls, sel, labels_b, planes, C, H, W, \
-                     cap_a, cap_b, sums_a, sums_b, (long long *)stats_b, overflow_b);                                              \
-    else                                                                                                                            \
-        PCSEG_LAUNCH((region_sums2_col_kernel<NCV, ST, false>), cgrid, dim3(256), 0, s, labels_a, cls, sel, labels_b, planes, C, H, W, cap_a, cap_b, \
-                 sums_a, sums_b, (long long *)stats_b, overflow_b)
-    if (C <= 5 && stats_b) { PCSEG_SUMS2(5, true); }
-    else if (C <= 5) { PCSEG_SUMS2(5, false); }
-    else if (stats_b) { PCSEG_SUMS2(8, true); }
-    else { PCSEG_SUMS2(8, false); }
-#undef PCSEG_SUMS2
+    if (stats_b) {  // (the plane-free pass, not a fold into the sums walk: that form measured slower)
+        stats_launch(true, labels_b, B, H, W, cap_b, (long long *)stats_b, overflow_b, s);
+        PCSEG_CHECK_LAUNCH();
+    }
+    sums_launch(labels_a, cls, sum_class_bits, labels_b, planes, C, B, H, W, cap_a, cap_b, sums_a, sums_b, s);
     PCSEG_CHECK_LAUNCH();
     return PCSEG_OK;
 }

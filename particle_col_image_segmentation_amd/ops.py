@@ -132,7 +132,7 @@ def region_sums2(labels_a, cls, sum_classes, sums_a, labels_b, sums_b, planes, s
     """Per-label plane sums of two label images in ONE pass over the planes (csrc/reduce.hip region_sums2_col_kernel):
     ``sums_a`` / ``sums_b`` (float64 (B, cap, C), zeroed by ``region_reduce(..., zero_sums=C)`` or ``region_init``) are
     added to in place; image A only under the class values in ``sum_classes`` (bit v = value v, 0 = everywhere).
-    ``stats_b`` / ``overflow_b`` (from ``region_init``): image B's integer columns are accumulated in the same walk."""
+    ``stats_b`` / ``overflow_b`` (from ``region_init``): image B's integer columns are accumulated too, by the plane-free pass."""
     labels_a = _req(labels_a, torch.int32, 3)
     labels_b = _req(labels_b, torch.int32, 3)
     planes = _req(planes, torch.float32, 4)

@@ -524,9 +524,10 @@ class FramePipeline:
             _, markers, n_markers, res["marker_flags"] = ops.edt_maxima(d2, self.marker_h, want_mask=False)
         ws_labels, tie_flags = ops.watershed(bm, markers, mask, mode=self.watershed_mode)
         res.update(mask=mask, markers=markers, n_markers=n_markers, ws_labels=ws_labels, tie_flags=tie_flags)
-        # ---- area / centroid sums of the refined ROIs (plane-free pass); their isotope sums: _sums_stage.  (The fused pass can
-        # take the integer columns along -- region_sums2(stats_b=...) -- but the refined ROIs are small, every lane ends a
-        # run or two per 32-row block, and eight 64-bit LDS atomics per run end cost more there (614 us against 407 + 191).)
+        # ---- area / centroid sums of the refined ROIs (plane-free pass); their isotope sums: _sums_stage.  (The sums pass
+        # does not take the integer columns along: that form was built and removed -- the refined ROIs are small, every lane
+        # ends a run or two per 32-row block, and eight 64-bit LDS atomics per run end cost more there (614 us against
+        # 407 + 191).)
         ws_stats, _, ws_sums, ws_overflow = ops.region_reduce(ws_labels, n_markers, cap=cap, zero_sums=C)
         res.update(ws_stats=ws_stats, ws_sums=ws_sums, ws_overflow=ws_overflow)
 
@@ -544,8 +545,8 @@ class FramePipeline:
         if W % 4 == 0 and aligned:
             ops.region_sums2(res["labels"], res["denoised"], cell_bits, res["cc_sums"], res["ws_labels"], res["ws_sums"], stack)
             return
-        # ragged widths: the per-image kernels (their plane pass adds nothing to the already counted integer columns'
-        # cost worth a special path)
+        # ragged widths: region_reduce per image (the row sums kernel; the integer columns it returns are those _class_stage
+        # and _refine_chain already have)
         cap = res["stats"].shape[1]
         _, _, res["cc_sums"], _ = ops.region_reduce(res["labels"], res["counts"], cls=res["denoised"], planes=stack, cap=cap,
                                                     sum_classes=cell_bits)

@@ -55,9 +55,17 @@ def np_region_rows(lab, n):
     return out[1:]
 
 
-def np_plane_sums(lab, planes, n):
-    """float64 (n, C): per label the sum of every float32 plane, accumulated in float64"""
+def class_bits_mask(cls, bits):
+    """the pixels whose class byte v is selected: v < 64 and bit v of ``bits`` set"""
+    return (cls < 64) & (((np.uint64(bits) >> np.minimum(cls, 63).astype(np.uint64)) & np.uint64(1)) == 1)
+
+
+def np_plane_sums(lab, planes, n, cls=None, bits=0):
+    """float64 (n, C): per label the sum of every float32 plane, accumulated in float64; with ``bits`` != 0 only over the
+    pixels whose class byte in ``cls`` is selected (a label without such a pixel keeps 0)"""
     keep = (lab > 0) & (lab <= n)
+    if bits:
+        keep &= class_bits_mask(cls, bits)
     out = np.zeros((n + 1, planes.shape[0]), np.float64)
     for k, p in enumerate(planes):
         np.add.at(out[:, k], lab[keep], p[keep].astype(np.float64))
@@ -74,6 +82,28 @@ def test_banded_images_are_what_the_docstring_says():
         if H >= 32:
             assert (np.diff(lab[0][:32, 0]) != 0).sum() >= 15  # runs a column ends inside the first block
         assert set(lab[:, 2:4].ravel().tolist()) <= {0, 257} and len(live)
+
+
+def test_class_selected_plane_sums_against_a_plain_loop():
+    lab = banded(2, 33, 70)[0]
+    n = int(lab.max())
+    rng = np.random.default_rng(5)
+    cls = rng.integers(0, 6, lab.shape).astype(np.uint8)
+    cls[0, :4] = (63, 64, 200, 255)  # bit 63 is a class, bytes of 64 and above never are
+    planes = (rng.random((3, 33, 70)) * 100).astype(np.float32)
+    bits = (1 << 1) | (1 << 4) | (1 << 63)
+    want = np.zeros((n, 3), np.float64)
+    for r in range(33):
+        for c in range(70):
+            l, v = int(lab[r, c]), int(cls[r, c])
+            if l > 0 and v < 64 and (bits >> v) & 1:
+                for k in range(3):
+                    want[l - 1, k] += float(planes[k, r, c])
+    np.testing.assert_array_equal(np_plane_sums(lab, planes, n, cls, bits), want)
+    assert class_bits_mask(cls[0, :4], bits).tolist() == [True, False, False, False]
+    # no selection: every pixel, the class map is not looked at
+    np.testing.assert_array_equal(np_plane_sums(lab, planes, n, cls, 0), np_plane_sums(lab, planes, n))
+    assert (np_plane_sums(lab, planes, n, cls, 1 << 7) == 0).all()  # a class no pixel has
 
 
 def test_expectations_and_restatements_agree_with_the_oracle_region_table():
