@@ -594,6 +594,45 @@ int pcseg_territory_pairs_write(int pair_cap, const int64_t *offsets, const uint
                                 int32_t *frame, int32_t *counts, int32_t *degree, int B, const void *workspace,
                                 size_t workspace_bytes, pcseg_stream_t stream);
 
+/* ---- agreement of two label images (csrc/agreement.hip): the contingency table of a truth image T and a test image S, and
+ * per-label / per-frame agreement figures from it.  All values but the IoUs are exact integers.
+ * T, S device int32 (B, H, W), any width and alignment.  A value outside 0 .. cap_t (S: 0 .. cap_s) is read as 0; negative
+ * values silently (as pcseg_thin_labels), a value above its cap raises bit 2 (value 2) of the frame's overflow word.
+ * n(t, s) = pixels with T = t and S = s; A_t = sum over s >= 0 of n(t, s), B_s = sum over t >= 0 of n(t, s).
+ * pcseg_label_contingency: per frame an open-addressing table of pair_cap slots keyed by t << 32 | s that holds every pair with
+ * n > 0 except (0, 0) -- pairs with the background included, so the marginals are row sums and n(0, 0) = H W - sum.  overflow
+ * (device int32 (B)): bit 1 (value 1) where the frame has more pairs than pair_cap -- pairs are dropped then, nothing is written
+ * outside the table and no thread waits --, bit 2 as above.  offsets (device int64 (B + 1)): first row of every frame among
+ * the compacted rows; totals (device int64 (2)) = {rows, frames with overflow bit 1}: the one host read between the two calls.
+ * One read of each image; cap_t, cap_s, pair_cap >= 1, shapes as pcseg_edt_sq_u8 (check_shape), B <= 65535.
+ * pcseg_contingency_write (same workspace, untouched in between): key (device int64 (rows)) = t << 32 | s, frame (device int32
+ * (rows)) = the frame's position in the batch, n (device int64 (rows)); rows of a frame in table order (not deterministic; sort
+ * by key for (t, s) order).
+ * pcseg_agreement_match: key, n device int64 (rows) SORTED by (frame, key), offsets as above, rows = offsets[B]; rows with a label
+ * above its cap are ignored.  thresholds: HOST float64 (n_thr), n_thr <= 8, 0.5 <= tau <= 1.  Written (every element):
+ *   area_t device int64 (B, cap_t) = A_t, area_s device int64 (B, cap_s) = B_s
+ *   for a pair t >= 1, s >= 1 with n > 0: U = A_t + B_s - n, iou = (double)n / (double)U (one division)
+ *   best_t device int32 (B, cap_t, 3): 0 the best partner of t -- the s >= 1 with the largest n / U, compared exactly (n U' against
+ *   n' U in unsigned 64 bits), the smallest s among equals, 0 if none --, 1 its n, 2 the number of s >= 1 with n(t, s) > 0;
+ *   iou_t device float64 (B, cap_t): the partner's iou, NaN without one;  best_s (B, cap_s, 3), iou_s (B, cap_s): the mirror image
+ *   match_t device uint8 (B, cap_t), match_s (B, cap_s): bit k set where the label's best partner has 2 n > U and iou >= tau_k
+ *   (2 n > U means n > A_t / 2 and n > B_s / 2: at most one such partner per label, on both sides, and it is the best one -- no
+ *   assignment problem, no dependence on order)
+ *   frame_ints device int64 (B, 6 + n_thr): 0 n_truth (t >= 1 with A_t > 0), 1 n_rois (s >= 1 with B_s > 0), 2 N1 = sum over
+ *   t >= 1 of A_t, 3 S_pp = sum over t >= 1, s >= 0 of n^2, 4 S_a = sum over t >= 1 of A_t^2, 5 S_b = sum over s >= 0 of (sum over
+ *   t >= 1 of n(t, s))^2, 6 + k TP_k = truth labels matched at tau_k.
+ * Rows of labels without pixel stay zero / NaN.  Asynchronous, nothing is allocated. */
+size_t pcseg_contingency_workspace_bytes(int B, int pair_cap);
+int pcseg_label_contingency(const int32_t *labels_t, const int32_t *labels_s, int cap_t, int cap_s, int pair_cap, int32_t *overflow,
+                            int64_t *offsets, int64_t *totals, int B, int H, int W, void *workspace, size_t workspace_bytes,
+                            pcseg_stream_t stream);
+int pcseg_contingency_write(int pair_cap, const int64_t *offsets, int64_t *key, int32_t *frame, int64_t *n, int B,
+                            const void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_agreement_match(const int64_t *key, const int64_t *n, const int64_t *offsets, int64_t rows, int cap_t, int cap_s,
+                          const double *thresholds, int n_thr, int64_t *area_t, int64_t *area_s, int32_t *best_t, double *iou_t,
+                          int32_t *best_s, double *iou_s, uint8_t *match_t, uint8_t *match_s, int64_t *frame_ints, int B,
+                          pcseg_stream_t stream);
+
 /* ---- per-ROI skeletons (csrc/skeleton.hip): exact Guo-Hall thinning, every label on its own -- the union over l of
  * skimage.morphology.thin(labels == l) of scikit-image 0.18.3 -- and per ROI the length and the ends / junctions of its
  * skeleton.  Integers only.

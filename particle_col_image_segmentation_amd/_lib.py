@@ -101,6 +101,10 @@ SIGNATURES = {
     "pcseg_territory_pairs_workspace_bytes": (c_size_t, [_I, _I]),
     "pcseg_territory_pairs": (c_int, [_P, _P, c_int64, _I, _P, _P, _P, _I, _I, _I, _P, c_size_t, _P]),
     "pcseg_territory_pairs_write": (c_int, [_I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, c_size_t, _P]),
+    "pcseg_contingency_workspace_bytes": (c_size_t, [_I, _I]),
+    "pcseg_label_contingency": (c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, c_size_t, _P]),
+    "pcseg_contingency_write": (c_int, [_I, _P, _P, _P, _P, _I, _P, c_size_t, _P]),
+    "pcseg_agreement_match": (c_int, [_P, _P, _P, c_int64, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "pcseg_thin_labels_workspace_bytes": (c_size_t, [_I, _I, _I]),
     "pcseg_thin_labels": (c_int, [_P, _P, _P, _I, _I, _I, _I, _P, c_size_t, _P]),
     "pcseg_region_skeleton_workspace_bytes": (c_size_t, [_I, _I, _I, _I]),

@@ -17,13 +17,14 @@
 //                        beside the walk; LDS slot table, eight-lanes-per-row flush
 //   terr_pairs_kernel    the 4-neighbour links between territories (right and down neighbour), equal links of a column run and of
 //                        neighbouring lanes added up first, then into a per-frame open-addressing table keyed by (a, b) (64-bit
-//                        compare-and-swap, bounded probing, integer atomics); a full table raises the frame's flag
-//   terr_pairs_count / scan / write   the used slots per frame, their offsets and totals, the compacted rows (and the number of
-//                        distinct partners per ROI and type slot)
+//                        compare-and-swap, bounded probing, integer atomics); a full table raises the frame's flag.  The table,
+//                        its probing rule and the count / scan kernels behind offsets and totals are pair_table.h's
+//   terr_pairs_write_kernel   the compacted rows (and the number of distinct partners per ROI and type slot)
 #include <type_traits>
 
 #include "column_pass.h"
 #include "label_reduce.h"
+#include "pair_table.h"
 
 // (no floating point in here; the pragma keeps any that is added later rounded operation by operation, as surface.hip)
 #pragma clang fp contract(off)
@@ -298,36 +299,8 @@ __global__ void __launch_bounds__(256) terr_reduce_kernel(const int *__restrict_
     });
 }
 
-// ---- adjacency: the per-frame pair table
-struct PairTable {
-    unsigned long long *keys;  // [pair_cap] a << 32 | b (a < b), 0 = free
-    unsigned *cnt;             // [pair_cap][2] border, contact
-    int *overflow;             // the frame's flag
-    int pair_cap;
-};
-
-// bounded probing: at most pair_cap slots are looked at; a full table raises the flag and drops the link.  Once the flag is up
-// every later link of the frame is dropped at once (its rows are incomplete anyway): without that each of them would walk the
-// whole full table, links x pair_cap loads
-__device__ __forceinline__ void pair_add(const PairTable &t, unsigned long long key, unsigned border, unsigned contact)
-{
-    if (ld_agent(t.overflow)) return;
-    unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) % (unsigned)t.pair_cap;
-    for (int i = 0; i < t.pair_cap; ++i) {
-        unsigned long long cur = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0) {
-            cur = atomicCAS(&t.keys[s], 0ull, key);
-            if (cur == 0) cur = key;
-        }
-        if (cur == key) {
-            atomicAdd(&t.cnt[2 * (size_t)s], border);
-            if (contact) atomicAdd(&t.cnt[2 * (size_t)s + 1], contact);
-            return;
-        }
-        s = s + 1 == (unsigned)t.pair_cap ? 0u : s + 1;
-    }
-    *t.overflow = 1;
-}
+// ---- adjacency: the per-frame pair table (pair_table.h) with two counters per pair: border, contact
+constexpr int TERR_NV = 2;
 
 struct PairAcc {
     unsigned long long key;  // 0 = none
@@ -343,7 +316,7 @@ __global__ void __launch_bounds__(256) terr_pairs_kernel(const int *__restrict__
 {
     const TileIndex ti = xcd_tile_index();
     const int b = ti.z;
-    const PairTable tab{keys + (int64_t)b * pair_cap, cnt + (int64_t)b * pair_cap * 2, overflow + b, pair_cap};
+    const PairTable<TERR_NV> tab = pair_table_of<TERR_NV>(keys, cnt, overflow, pair_cap, b);
     const int c = ti.x * 256 + threadIdx.x;
     const int r0 = ti.y * RUN_ROWS, r1 = min(H, r0 + RUN_ROWS);
     const int *fn = near + (int64_t)b * H * W, *fd = d2 + (int64_t)b * H * W;
@@ -354,7 +327,7 @@ __global__ void __launch_bounds__(256) terr_pairs_kernel(const int *__restrict__
         if (la > 0 && lb > 0 && la != lb) {
             const unsigned long long key = ((unsigned long long)(unsigned)min(la, lb) << 32) | (unsigned)max(la, lb);
             if (key != a.key) {
-                if (a.key) pair_add(tab, a.key, a.n, a.ct);
+                if (a.key) pair_add(tab, a.key, {a.n, a.ct});
                 a = PairAcc{key, 0, 0};
             }
             ++a.n;
@@ -390,38 +363,8 @@ __global__ void __launch_bounds__(256) terr_pairs_kernel(const int *__restrict__
         segment_reduce(
             v, seg.remain, [](const uint2 &x, int off) { return make_uint2(__shfl_down(x.x, off), __shfl_down(x.y, off)); },
             [](uint2 &x, const uint2 &o) { x.x += o.x; x.y += o.y; });
-        if (seg.head && a.key) pair_add(tab, a.key, v.x, v.y);
+        if (seg.head && a.key) pair_add(tab, a.key, {v.x, v.y});
     }
-}
-
-// used slots of a frame's table
-__global__ void __launch_bounds__(256) terr_pairs_count_kernel(const unsigned long long *__restrict__ keys, int pair_cap,
-                                                                long long *__restrict__ n_pairs)
-{
-    __shared__ int wsum[4];
-    const int b = blockIdx.x;
-    const unsigned long long *k = keys + (int64_t)b * pair_cap;
-    int n = 0;
-    for (int i = threadIdx.x; i < pair_cap; i += 256) n += k[i] != 0;
-    int tot;
-    block_exclusive_scan<256>(n, &tot, wsum);
-    if (threadIdx.x == 0) n_pairs[b] = tot;
-}
-
-// offsets[0 .. B] of the frames' rows; totals = {rows, frames whose table was full}
-__global__ void __launch_bounds__(64) terr_pairs_scan_kernel(const long long *__restrict__ n_pairs, const int *__restrict__ overflow,
-                                                              int B, long long *__restrict__ offsets, long long *__restrict__ totals)
-{
-    if (threadIdx.x != 0) return;
-    long long acc = 0, over = 0;
-    for (int b = 0; b < B; ++b) {
-        offsets[b] = acc;
-        acc += n_pairs[b];
-        over += overflow[b] != 0;
-    }
-    offsets[B] = acc;
-    totals[0] = acc;
-    totals[1] = over;
 }
 
 // the used slots of frame b, in table order, as rows offsets[b] ..: key, frame position, (border, contact); with slot_of also
@@ -465,21 +408,6 @@ __global__ void __launch_bounds__(256) terr_pairs_write_kernel(const unsigned lo
         }
         row0 += tot;
     }
-}
-
-struct PairWs {
-    unsigned long long *keys;
-    unsigned *cnt;
-    long long *n_pairs;
-};
-
-static PairWs pairs_carve(Carver &cv, int B, int pair_cap)
-{
-    PairWs ws;
-    ws.keys = cv.take<unsigned long long>((size_t)B * pair_cap);
-    ws.cnt = cv.take<unsigned>((size_t)B * pair_cap * 2);
-    ws.n_pairs = cv.take<long long>((size_t)B);
-    return ws;
 }
 
 static inline int reach_arg(int64_t R2) { return (R2 < 0 || R2 > 0x7FFFFFFF) ? 0x7FFFFFFF : (int)R2; }
@@ -561,7 +489,7 @@ size_t pcseg_territory_pairs_workspace_bytes(int B, int pair_cap)
 {
     if (B < 1 || pair_cap < 1) return 0;
     Carver cv(nullptr, 0);
-    pairs_carve(cv, B, pair_cap);
+    pairs_carve<TERR_NV>(cv, B, pair_cap);
     return cv.off;
 }
 
@@ -571,24 +499,17 @@ int pcseg_territory_pairs(const int32_t *near, const int32_t *d2, int64_t R2, in
     PCSEG_REQUIRE(near && d2 && overflow && offsets && totals && workspace && check_shape(B, H, W) && pair_cap >= 1 && B <= 65535,
                   "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    const PairWs ws = pairs_carve(cv, B, pair_cap);
+    const PairWs<TERR_NV> ws = pairs_carve<TERR_NV>(cv, B, pair_cap);
     if (!cv.ok()) {
         set_error("territory_pairs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    PCSEG_CHECK_HIP(hipMemsetAsync(ws.keys, 0, sizeof(unsigned long long) * (size_t)B * pair_cap, s));
-    PCSEG_CHECK_HIP(hipMemsetAsync(ws.cnt, 0, sizeof(unsigned) * 2 * (size_t)B * pair_cap, s));
-    PCSEG_CHECK_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t) * B, s));
+    if (const int rc = pairs_begin(ws, overflow, B, pair_cap, s)) return rc;
     PCSEG_LAUNCH(terr_pairs_kernel, dim3((W + 255) / 256, (H + RUN_ROWS - 1) / RUN_ROWS, B), dim3(256), 0, s, near, d2, reach_arg(R2), H,
                  W, ws.keys, ws.cnt, overflow, pair_cap);
     PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(terr_pairs_count_kernel, dim3(B), dim3(256), 0, s, (const unsigned long long *)ws.keys, pair_cap, ws.n_pairs);
-    PCSEG_CHECK_LAUNCH();
-    PCSEG_LAUNCH(terr_pairs_scan_kernel, dim3(1), dim3(64), 0, s, (const long long *)ws.n_pairs, (const int *)overflow, B,
-                 (long long *)offsets, (long long *)totals);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    return pairs_finish(ws, overflow, offsets, totals, B, pair_cap, s);
 }
 
 int pcseg_territory_pairs_write(int pair_cap, const int64_t *offsets, const uint8_t *slot_of, int cap, int n_types, int64_t *key,
@@ -598,7 +519,7 @@ int pcseg_territory_pairs_write(int pair_cap, const int64_t *offsets, const uint
     PCSEG_REQUIRE(offsets && key && frame && counts && workspace && B >= 1 && B <= 65535 && pair_cap >= 1, "bad arguments");
     PCSEG_REQUIRE(!degree || (slot_of && cap >= 1 && n_types >= 1 && n_types <= 4), "degree needs slot_of, cap and 1..4 type slots");
     Carver cv(const_cast<void *>(workspace), workspace_bytes);
-    const PairWs ws = pairs_carve(cv, B, pair_cap);
+    const PairWs<TERR_NV> ws = pairs_carve<TERR_NV>(cv, B, pair_cap);
     if (!cv.ok()) {
         set_error("territory_pairs_write: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
         return PCSEG_ERR_WORKSPACE;

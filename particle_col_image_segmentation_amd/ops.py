@@ -1185,6 +1185,207 @@ def label_parent(labels_a, labels_r, counts_r, cls_a=None, cap=None, stats_r=Non
     return out + (n_spilled,) if return_spilled else out
 
 
+def _contingency_rows(labels_t, labels_s, cap_t, cap_s, pair_cap):
+    """The two calls of the contingency table and the (frame, t, s) sort of its rows."""
+    lt, ls = _label_batch(labels_t, "labels_t"), _label_batch(labels_s, "labels_s")
+    if lt.shape != ls.shape:
+        raise ValueError("labels_t and labels_s must have one shape")
+    B, H, W = lt.shape
+    dev = lt.device
+    if cap_t is None or cap_s is None:
+        top = torch.stack([lt.max(), ls.max()]).cpu()  # (one read for both defaults)
+        cap_t = int(top[0]) if cap_t is None else cap_t
+        cap_s = int(top[1]) if cap_s is None else cap_s
+    cap_t, cap_s = max(int(cap_t), 1), max(int(cap_s), 1)
+    if pair_cap is None:
+        pair_cap = 1 << (4 * (cap_t + cap_s) + 64 - 1).bit_length()
+    pair_cap = int(pair_cap)
+    lib = _lib.load()
+    nbytes = lib.pcseg_contingency_workspace_bytes(B, pair_cap)
+    ws = _ws(nbytes, dev)
+    overflow = torch.empty((B,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((B + 1,), dtype=torch.int64, device=dev)
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.pcseg_label_contingency(_ptr(lt), _ptr(ls), cap_t, cap_s, pair_cap, _ptr(overflow), _ptr(offsets), _ptr(totals),
+                                           B, H, W, _ptr(ws), nbytes, _stream()), "label_contingency")
+    rows, n_over = (int(v) for v in totals.cpu())
+    key = torch.empty((rows + 1,), dtype=torch.int64, device=dev)  # (a spare row: never a null pointer)
+    frame = torch.empty((rows + 1,), dtype=torch.int32, device=dev)
+    n = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.pcseg_contingency_write(pair_cap, _ptr(offsets), _ptr(key), _ptr(frame), _ptr(n), B, _ptr(ws), nbytes, _stream()),
+               "contingency_write")
+    # (frame, t, s) order: the rows of a frame are contiguous already, in table order -- two stable sorts, plumbing; the
+    # frames' offsets hold for the sorted rows too
+    key, frame, n = key[:rows], frame[:rows].to(torch.int64), n[:rows]
+    order = torch.sort(key, stable=True)[1]
+    order = order[torch.sort(frame[order], stable=True)[1]]
+    return {"key": key[order].contiguous(), "frame": frame[order], "n": n[order].contiguous(), "offsets": offsets, "rows": rows,
+            "overflow": overflow, "n_overflow": n_over, "cap_t": cap_t, "cap_s": cap_s, "pair_cap": pair_cap, "shape": (B, H, W)}
+
+
+def _agreement_match(rows, thresholds):
+    """pcseg_agreement_match on :func:`_contingency_rows`' result."""
+    B = rows["shape"][0]
+    cap_t, cap_s = rows["cap_t"], rows["cap_s"]
+    dev = rows["offsets"].device
+    thr = [float(v) for v in thresholds]
+    if len(thr) > 8 or any(not 0.5 <= v <= 1.0 for v in thr):
+        raise ValueError("at most 8 IoU thresholds, each in [0.5, 1]")
+    thr_arg = (ctypes.c_double * max(len(thr), 1))(*thr)
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    out = {"area_t": new((B, cap_t), torch.int64), "area_s": new((B, cap_s), torch.int64),
+           "best_t": new((B, cap_t, 3), torch.int32), "iou_t": new((B, cap_t), torch.float64),
+           "best_s": new((B, cap_s, 3), torch.int32), "iou_s": new((B, cap_s), torch.float64),
+           "match_t": new((B, cap_t), torch.uint8), "match_s": new((B, cap_s), torch.uint8),
+           "frame_ints": new((B, 6 + len(thr)), torch.int64)}
+    _lib.check(_lib.load().pcseg_agreement_match(
+        _ptr(rows["key"]), _ptr(rows["n"]), _ptr(rows["offsets"]), rows["rows"], cap_t, cap_s, ctypes.cast(thr_arg, ctypes.c_void_p),
+        len(thr), _ptr(out["area_t"]), _ptr(out["area_s"]), _ptr(out["best_t"]), _ptr(out["iou_t"]), _ptr(out["best_s"]),
+        _ptr(out["iou_s"]), _ptr(out["match_t"]), _ptr(out["match_s"]), _ptr(out["frame_ints"]), B, _stream()), "agreement_match")
+    return out
+
+
+def label_contingency(labels_t, labels_s, cap_t=None, cap_s=None, pair_cap=None):
+    """The contingency table of two label images (csrc/agreement.hip, include/pcseg.h): ``labels_t`` (truth) / ``labels_s``
+    (test) int32 (B, H, W) CUDA tensors of any width and alignment; a value outside 0 .. ``cap_t`` / ``cap_s`` (default: the
+    largest label, read back once) is read as background.  Returns a dict: ``frame``, ``t``, ``s``, ``n`` int64 (rows,) --
+    every pair with n > 0 pixels except (0, 0), pairs with the background included, sorted by (frame, t, s) --, ``area_t``
+    int64 (B, cap_t) and ``area_s`` int64 (B, cap_s) the pixels per label, ``overflow`` int32 (B,): bit 1 (value 1) where
+    the frame has more pairs than ``pair_cap`` (default: a power of two >= 4 (cap_t + cap_s) + 64; its rows are then
+    incomplete), bit 2 (value 2) where a label above its cap was seen, and ``n_overflow``, the number of frames with bit 1
+    (read back with the row total, the one host read between the two calls)."""
+    rows = _contingency_rows(labels_t, labels_s, cap_t, cap_s, pair_cap)
+    m = _agreement_match(rows, ())
+    key = rows["key"]
+    return {"frame": rows["frame"], "t": key >> 32, "s": key & 0xFFFFFFFF, "n": rows["n"], "area_t": m["area_t"], "area_s": m["area_s"],
+            "overflow": rows["overflow"], "n_overflow": rows["n_overflow"], "pair_cap": rows["pair_cap"]}
+
+
+AGREEMENT_SCORES = ("tp", "fp", "fn", "precision", "recall", "f1", "ap", "mean_matched_iou")
+
+
+def agreement_scores(frame_ints, iou_t, match_t, frame, t, s, n, area_t, area_s, n_px, n_thr):
+    """Host only: the per-frame scores from the integers of the match step, float64, IEEE results for a zero denominator.
+    Arrays are numpy: ``frame_ints`` (B, 6 + n_thr), ``iou_t`` / ``match_t`` (B, cap_t), the sorted pair rows, the areas and
+    ``n_px`` = H W.  Returns a dict of arrays: the ``AGREEMENT_SCORES`` (B, n_thr); ``are``, ``are_precision``,
+    ``are_recall`` (``skimage.metrics.adapted_rand_error(T, S)``: truth 0 ignored) and ``vi_split``, ``vi_merge``
+    (``skimage.metrics.variation_of_information(T, S)``: label 0 and n(0, 0) included), (B,).  Sums of floats are
+    ``math.fsum``: exactly rounded, so no order enters."""
+    import math
+    import numpy as np
+    B = frame_ints.shape[0]
+    out = {k: np.zeros((B, n_thr), np.float64) for k in AGREEMENT_SCORES}
+    for k in ("are", "are_precision", "are_recall", "vi_split", "vi_merge"):
+        out[k] = np.zeros((B,), np.float64)
+    first = np.searchsorted(frame, np.arange(B + 1))
+    f64 = np.float64
+    with np.errstate(all="ignore"):
+        for b in range(B):
+            fi = [int(v) for v in frame_ints[b]]
+            n_truth, n_rois, N1, S_pp, S_a, S_b = fi[:6]
+            for k in range(n_thr):
+                tp = fi[6 + k]
+                matched = (match_t[b] >> k) & 1 != 0
+                out["tp"][b, k], out["fp"][b, k], out["fn"][b, k] = tp, n_rois - tp, n_truth - tp
+                out["precision"][b, k] = f64(tp) / f64(n_rois)
+                out["recall"][b, k] = f64(tp) / f64(n_truth)
+                out["f1"][b, k] = f64(2 * tp) / f64(n_truth + n_rois)
+                out["ap"][b, k] = f64(tp) / f64(n_truth + n_rois - tp)
+                out["mean_matched_iou"][b, k] = f64(math.fsum(iou_t[b][matched].tolist())) / f64(tp)
+            p2 = S_pp - N1
+            prec = f64(p2) / f64(S_a - N1)
+            rec = f64(p2) / f64(S_b - N1)
+            f = 2. * prec * rec / (prec + rec)
+            out["are"][b], out["are_precision"][b], out["are_recall"][b] = 1. - f, prec, rec
+            # variation of information over every pair, (0, 0) included
+            lo, hi = first[b], first[b + 1]
+            tt, ss, nn = t[lo:hi].tolist(), s[lo:hi].tolist(), n[lo:hi].tolist()
+            n00 = n_px - sum(nn)
+            a0 = n00 + sum(v for u, v in zip(tt, nn) if u == 0)
+            b0 = n00 + sum(v for u, v in zip(ss, nn) if u == 0)
+            at, bs = [a0] + area_t[b].tolist(), [b0] + area_s[b].tolist()
+            if n00 > 0:
+                tt, ss, nn = tt + [0], ss + [0], nn + [n00]
+            split = [(v / n_px) * math.log2(v / at[u]) for u, v in zip(tt, nn)]
+            merge = [(v / n_px) * math.log2(v / bs[u]) for u, v in zip(ss, nn)]
+            out["vi_split"][b], out["vi_merge"][b] = -math.fsum(split), -math.fsum(merge)
+    return out
+
+
+def label_agreement(labels_t, labels_s, thresholds=(0.5, 0.75, 0.9), cap_t=None, cap_s=None, pair_cap=None):
+    """How well the test labels ``labels_s`` agree with the truth labels ``labels_t`` (arguments as
+    :func:`label_contingency`).  Returns a dict: the pair rows ``frame``, ``t``, ``s``, ``n``; the arrays of
+    pcseg_agreement_match (include/pcseg.h) as CUDA tensors -- ``area_t``, ``area_s``, ``best_t`` / ``best_s`` int32 (B, cap,
+    3) = best partner (the largest IoU, compared exactly; the smallest label among equals), its overlap, the number of
+    partners, ``iou_t`` / ``iou_s`` float64 (NaN without partner), ``match_t`` / ``match_s`` uint8: bit k set where the label
+    is matched at ``thresholds[k]`` (``2 n > U`` and ``iou >= tau``: at most one partner per label qualifies, so no
+    assignment is needed), ``frame_ints`` int64 (B, 6 + n_thr) --; ``thresholds``; ``overflow`` / ``n_overflow``; and
+    ``scores``, :func:`agreement_scores` of every frame (numpy, computed on the host from the integers)."""
+    thresholds = tuple(float(v) for v in thresholds)
+    rows = _contingency_rows(labels_t, labels_s, cap_t, cap_s, pair_cap)
+    out = _agreement_match(rows, thresholds)
+    key = rows["key"]
+    out.update({"frame": rows["frame"], "t": key >> 32, "s": key & 0xFFFFFFFF, "n": rows["n"], "thresholds": thresholds,
+                "overflow": rows["overflow"], "n_overflow": rows["n_overflow"], "pair_cap": rows["pair_cap"]})
+    B, H, W = rows["shape"]
+    host = {k: out[k].cpu().numpy() for k in ("frame_ints", "iou_t", "match_t", "frame", "t", "s", "n", "area_t", "area_s")}
+    out["scores"] = agreement_scores(n_px=H * W, n_thr=len(thresholds), **host)
+    return out
+
+
+def agreement_columns(thresholds):
+    """Column names of :func:`agreement_tables` for these IoU thresholds."""
+    tags = ["%g" % v for v in thresholds]
+    per_label = lambda partner: ["frame", "label", "area", partner, "overlap_px", "iou", "n_partners"] + ["matched_" + g for g in tags]
+    return {"agreement_pairs": ["frame", "truth", "label", "px", "truth_area", "area", "iou"],
+            "agreement_rois": per_label("best_truth"), "agreement_truth": per_label("best_label"),
+            "frames_agreement": ["frame", "n_truth", "n_rois"] + ["%s_%s" % (k, g) for g in tags for k in AGREEMENT_SCORES]
+                                + ["are", "are_precision", "are_recall", "vi_split", "vi_merge"]}
+
+
+def agreement_tables(ag, frame_ids=None):
+    """Host only: :func:`label_agreement`'s result as float64 numpy tables with ``<name>_columns`` lists --
+    ``agreement_pairs`` (one row per pair of a truth label and a test label that share pixels), ``agreement_rois`` /
+    ``agreement_truth`` (one row per test / truth label with pixels, in label order) and ``frames_agreement`` (one row per
+    frame).  ``frame_ids``: the frames' ids (default: their position in the batch)."""
+    import numpy as np
+    thr = ag["thresholds"]
+    host = {k: ag[k].cpu().numpy() for k in ("frame", "t", "s", "n", "area_t", "area_s", "best_t", "best_s", "iou_t", "iou_s", "match_t",
+                                           "match_s", "frame_ints")}
+    B = host["area_t"].shape[0]
+    fid = np.arange(B, dtype=np.float64) if frame_ids is None else np.asarray(frame_ids, np.float64)
+    if fid.shape != (B,):
+        raise ValueError("frame_ids must name every frame of the batch")
+    cols = agreement_columns(thr)
+    out = {}
+    fg = (host["t"] >= 1) & (host["s"] >= 1)
+    f, t, s, n = (host[k][fg] for k in ("frame", "t", "s", "n"))
+    at, bs = host["area_t"][f, t - 1], host["area_s"][f, s - 1]
+    out["agreement_pairs"] = np.stack([fid[f], t, s, n, at, bs, n.astype(np.float64) / (at + bs - n).astype(np.float64)],
+                                      axis=1).astype(np.float64).reshape(-1, 7)
+    for name, side in (("agreement_rois", "s"), ("agreement_truth", "t")):
+        area, best, iou, match = host["area_" + side], host["best_" + side], host["iou_" + side], host["match_" + side]
+        b, l = np.nonzero(area > 0)
+        columns = [fid[b], l + 1, area[b, l], best[b, l, 0], best[b, l, 1], iou[b, l], best[b, l, 2]]
+        columns += [(match[b, l] >> k) & 1 for k in range(len(thr))]
+        out[name] = np.stack(columns, axis=1).astype(np.float64).reshape(-1, len(cols[name]))
+    sc = ag["scores"]
+    columns = [fid, host["frame_ints"][:, 0], host["frame_ints"][:, 1]]
+    columns += [sc[k][:, i] for i in range(len(thr)) for k in AGREEMENT_SCORES]
+    columns += [sc[k] for k in ("are", "are_precision", "are_recall", "vi_split", "vi_merge")]
+    out["frames_agreement"] = np.stack(columns, axis=1).astype(np.float64).reshape(B, len(cols["frames_agreement"]))
+    for k, v in cols.items():
+        out[k + "_columns"] = v
+    return out
+
+
+def check_agreement_overflow(ag):
+    """RuntimeError where a frame's pair table was full (overflow bit 1): its rows are incomplete."""
+    if ag["n_overflow"]:
+        full = [int(b) for b in torch.nonzero((ag["overflow"] & 1).cpu())[:, 0]]
+        raise RuntimeError("the contingency table of frame(s) %s is full: pair_cap = %d is too small" % (full, ag["pair_cap"]))
+
+
 def refined_inputs(res, lp, rc, frame_ids, n_slots):
     """struct pcseg_refined_inputs of one batch: ``res`` (the pipeline's result), ``lp`` (:func:`label_parent` on it),
     ``rc`` (:func:`classify_regions` on the refined ROIs).  Returns (struct, tensors the pointers refer to)."""

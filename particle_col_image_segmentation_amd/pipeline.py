@@ -818,6 +818,28 @@ class FramePipeline:
             out[k + "_columns"] = v
         return out
 
+    def agreement(self, res, truth, of="refined", thresholds=(0.5, 0.75, 0.9), frame_ids=None, truth_cap=None, pair_cap=None):
+        """Score one batch's segmentation against a truth label image: ``truth`` int32 (B, H, W) CUDA tensor (0: background),
+        ``of`` = "refined" (``res["ws_labels"]``, labels 1 .. ``res["n_markers"]``) or "components" (``res["labels"]``,
+        labels 1 .. ``res["counts"]``).  Returns numpy tables with ``<name>_columns`` lists (``ops.agreement_tables``):
+        ``agreement_pairs`` -- frame, truth, label, px, truth_area, area, iou for every pair of a truth label and a ROI that
+        share pixels --, ``agreement_rois`` (one row per ROI with pixels: its best truth label, the overlap, the IoU, the
+        number of partners and ``matched_<tau>`` per IoU threshold), ``agreement_truth`` (the mirror image) and
+        ``frames_agreement`` (per frame n_truth, n_rois; tp, fp, fn, precision, recall, f1, ap and mean_matched_iou per
+        threshold; adapted Rand error with its precision and recall; the two halves of the variation of information).  A
+        label is matched at tau when its best partner covers more than half of their union and ``iou >= tau``
+        (``ops.label_agreement``).  ``truth_cap``: the largest truth label (default: read back).  RuntimeError where a frame
+        has more pairs than ``pair_cap`` (default: 4 x the label caps).  ``res`` is only read."""
+        if of not in ("refined", "components"):
+            raise ValueError('of must be "refined" or "components"')
+        labels, counts = (res["ws_labels"], res["n_markers"]) if of == "refined" else (res["labels"], res["counts"])
+        if not isinstance(truth, torch.Tensor) or truth.dtype != torch.int32 or tuple(truth.shape) != tuple(labels.shape):
+            raise TypeError("truth must be an int32 CUDA tensor of the batch's (B, H, W)")
+        cap_s = max(int(counts.max().item()), 1)
+        ag = ops.label_agreement(truth, labels, thresholds, cap_t=truth_cap, cap_s=cap_s, pair_cap=pair_cap)
+        ops.check_agreement_overflow(ag)
+        return ops.agreement_tables(ag, frame_ids)
+
     def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, neighbours=False,
                pair_edges=None, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per

@@ -69,6 +69,27 @@ def refine_boundaries(boundary_map, threshold=THRESHOLD, return_stages=False, ma
             "labels": labels}
 
 
+def score_refinement(boundary_maps, truth, thresholds=(THRESHOLD,), marker_hs=(None,), iou_thresholds=(0.5, 0.75, 0.9)):
+    """The sweep over the chain's knobs: :func:`refine_boundaries_batch` once per (threshold, marker_h) on ``boundary_maps``
+    ((B, H, W) float32 CUDA tensor), each result scored against ``truth`` (int32 (B, H, W) CUDA label image, 0: background)
+    on the device (``ops.label_agreement``).  Returns a list of dicts, one per setting in the order of
+    ``itertools.product(thresholds, marker_hs)``: ``threshold``, ``marker_h``, ``frames_agreement`` (float64 numpy, one row
+    per frame) and ``frames_agreement_columns`` as ``FramePipeline.agreement`` returns them."""
+    out = []
+    truth_cap = max(int(truth.max().item()), 1)
+    for threshold in thresholds:
+        for marker_h in marker_hs:
+            st = refine_boundaries_batch(boundary_maps, threshold, marker_h=marker_h)
+            check_marker_flags(st)
+            ag = ops.label_agreement(truth, st["labels"], iou_thresholds, cap_t=truth_cap,
+                                     cap_s=max(int(st["n_markers"].max().item()), 1))
+            ops.check_agreement_overflow(ag)
+            tables = ops.agreement_tables(ag)
+            out.append({"threshold": threshold, "marker_h": marker_h, "frames_agreement": tables["frames_agreement"],
+                        "frames_agreement_columns": tables["frames_agreement_columns"]})
+    return out
+
+
 def refine_from_h5(file_path=DEFAULT_FILE, channel=BOUNDARY_CHANNEL, threshold=THRESHOLD, return_stages=False, marker_h=None):
     """refine_boundaries.py:28-34 + the chain; ``.npy`` probability stacks are accepted without h5py."""
     if file_path.endswith(".npy"):

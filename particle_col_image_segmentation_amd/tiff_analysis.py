@@ -428,6 +428,39 @@ def get_cell_skeletons(cell_pos, px_to_um=PX_TO_UM_CONV):
     return out
 
 
+def get_segmentation_agreement(truth_labels, labels, thresholds=(0.5, 0.75, 0.9)):
+    """How well the label image ``labels`` agrees with the truth label image ``truth_labels`` (both (H, W), integers, 0:
+    background; numpy arrays or tensors): ``ops.label_agreement`` for ONE frame -- the same dict without the frame
+    dimension, its arrays numpy if both images came as numpy.  ``t``, ``s``, ``n``: the pairs of labels that share pixels;
+    ``best_s`` / ``iou_s`` / ``match_s``: per label of ``labels`` its best truth label (row l - 1), the IoU and the
+    thresholds it is matched at; ``scores``: precision, recall, f1, ap per threshold, the adapted Rand error and the
+    variation of information of the frame (csrc/agreement.hip)."""
+    was_tensor = isinstance(truth_labels, torch.Tensor) or isinstance(labels, torch.Tensor)
+    dev = _device()
+
+    def frame(a):
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.int32)))
+        if t.dim() != 2:
+            raise ValueError("expected a 2-D label image, got shape %s" % (tuple(t.shape),))
+        return t.to(device=dev, dtype=torch.int32).contiguous()[None]
+    ag = ops.label_agreement(frame(truth_labels), frame(labels), thresholds)
+    ops.check_agreement_overflow(ag)
+    conv = (lambda x: x) if was_tensor else (lambda x: x.cpu().numpy())
+    out = {}
+    for k, v in ag.items():
+        if k == "scores":
+            out[k] = {name: col[0] for name, col in v.items()}
+        elif k in ("t", "s", "n"):
+            out[k] = conv(v)
+        elif k == "frame":
+            continue
+        elif isinstance(v, torch.Tensor):
+            out[k] = conv(v[0])
+        else:
+            out[k] = v
+    return out
+
+
 def get_cell_territories(z_slice, cell_pos, cell_clusters, cell_types, reach=None, px_to_um=PX_TO_UM_CONV):
     """How much of the frame every cell has to itself and which cells are its neighbours (csrc/voronoi.hip): the regions
     of ``cell_pos`` and ``cell_clusters`` (strain -> regions of ONE denoised class map ``z_slice``, as
