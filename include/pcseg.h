@@ -391,6 +391,38 @@ int pcseg_neighbours_pack_cells(const double *cells, int ncol, const uint8_t *cl
                                 size_t table_workspace_bytes, double *xy, int32_t *slot, int32_t *id, int64_t *frame_offsets,
                                 pcseg_stream_t stream);
 
+/* ---- random-labelling envelopes of those pair histograms (csrc/mixing.hip): the points stay, the slots are shuffled.
+ * xy / slot / frame_offsets / K / scale / edges as for pcseg_point_neighbours (edges required, n_edges = m + 1);
+ * frame_keys device int64 (B): the id of every frame (its low 24 bits enter the generator).  The typed points of a frame
+ * are those with 0 <= slot < K, in the caller's order, i = 0 .. n_t - 1; every other point takes part in nothing.
+ * Labelling p = 0 is the observed one; for p = 1 .. n_perm, with rem[s] = the frame's typed points of slot s, tot = n_t,
+ * for i = 0 .. n_t - 1 (all uint64, mod 2^64):
+ *     c = ((key & 0xFFFFFF) << 40) ^ (p << 24) ^ i;  z = c * 0x9E3779B97F4A7C15 + seed;
+ *     z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31;
+ *     r = (z * tot) >> 64 (the high half of the 128-bit product);  label_p(i) = the smallest s with r < rem[0] + .. +
+ *     rem[s];  rem[s] -= 1;  tot -= 1
+ * (sequential sampling without replacement: every arrangement with the observed per-slot counts equally likely up to the
+ * 2^-40 bias of the multiply-high; a frame's result depends on its key, not on its place in the batch).
+ *   counts   device int64 (B, n_perm + 1, Q, m), Q = K (K + 1) / 2 rows in (slot_a <= slot_b) order, or NULL (then the
+ *            workspace holds them: pcseg_mixing_workspace_bytes(.., with_counts = 1)): N_p = the unordered pairs of typed
+ *            points whose labels under p are {a, b} and whose distance lies in bin k (pcseg_point_neighbours' bin rule
+ *            to the bit; pairs at d >= edges[m] are not counted)
+ *   envelope device int64 (12, B, Q, m): obs = N_0, then over p = 1 .. n_perm lo = min, hi = max, sum, n_le = #{p: N_p <=
+ *            obs}, n_ge = #{p: N_p >= obs}; then the same six of the cumulative counts C_p[k] = N_p[0] + .. + N_p[k].
+ *            With n_perm = 0 everything but obs and the cumulative obs is 0.
+ * Exact integers, the same bits for the same arguments.  Every count is a 64-bit integer: a frame has fewer than 2^24
+ * points, so fewer than 2^47 pairs, and the sums over at most 65535 permutations stay below 2^63 -- nothing can wrap, and
+ * a batch of n_points >= 2^24 is rejected with PCSEG_ERR_ARG like every other bad argument: K outside 1..4, edges that
+ * pcseg_point_neighbours would reject, n_perm outside 0..65535, a null pointer (counts excepted); a short workspace gives
+ * PCSEG_ERR_WORKSPACE.  pcseg_mixing_workspace_bytes returns 0 for sizes it rejects.  pcseg_mixing_tile: the points of
+ * one LDS tile of the pair walk (larger frames are walked tile against tile). */
+size_t pcseg_mixing_workspace_bytes(int64_t n_points, int B, int K, int n_edges, int n_perm, int with_counts);
+int pcseg_pair_label_mixing(const double *xy, const int32_t *slot, const int64_t *frame_offsets, const int64_t *frame_keys,
+                            int64_t n_points, int B, int K, double scale, const double *edges, int n_edges, int n_perm,
+                            uint64_t seed, int64_t *counts, int64_t *envelope, void *workspace, size_t workspace_bytes,
+                            pcseg_stream_t stream);
+int pcseg_mixing_tile(void);
+
 /* ---- goal 2 of refine_boundaries.py:1-12 (refined ROIs related to the class-map components they split), batched.
  * pcseg_label_parent: labels_a (class-map components) and labels_r (refined ROIs), device int32 (B, H, W), any width
  * and alignment; counts_r device int32 (B).  ov(r, a) = #pixels with labels_r = r and labels_a = a, a >= 1 (pixels on

@@ -74,6 +74,9 @@ SIGNATURES = {
     "pcseg_neighbours_workspace_bytes": (c_size_t, [c_int64, _I, _I, _I]),
     "pcseg_point_neighbours": (c_int, [_P, _P, _P, _P, c_int64, _I, _I, c_double, _P, _I, _P, _P, _P, _P, c_size_t, _P]),
     "pcseg_neighbours_pack_cells": (c_int, [_P, _I, _P, _I, _P, c_size_t, _P, _P, _P, _P, _P]),
+    "pcseg_mixing_workspace_bytes": (c_size_t, [c_int64, _I, _I, _I, _I, _I]),
+    "pcseg_pair_label_mixing": (c_int, [_P, _P, _P, _P, c_int64, _I, _I, c_double, _P, _I, _I, c_uint64, _P, _P, _P, c_size_t, _P]),
+    "pcseg_mixing_tile": (c_int, []),
     "pcseg_label_parent_workspace_bytes": (c_size_t, [_I, _I, _I, _I]),
     "pcseg_label_parent": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, c_size_t, _P]),
     "pcseg_refined_workspace_bytes": (c_size_t, [_I, _I]),

@@ -1064,14 +1064,15 @@ def _rows_below(counts, cap):
 
 
 def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
-                 n_types=0, pair_edges=None, refined=None, refined_points=False, surface=None, surface_edges=None, convex=False,
+                 n_types=0, pair_edges=None, mixing=0, mixing_seed=0, refined=None, refined_points=False, surface=None, surface_edges=None, convex=False,
                  shape=False, territory=None, territory_reach=None, skeleton=False):
     """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device), then one stage per switch, in
     this order.  ``distance_slots`` (the class value -> type slot table, uint8[256] numpy): ``cell_dist``, one value
     per row of ``cells`` (NaN = no entry).  ``neighbour_slots`` (the same kind of table) with ``n_types`` slots:
     ``cell_nn`` = dict of ``dist`` / ``nn_id`` / ``hist`` of :func:`point_neighbours` (``hist`` None without
     ``pair_edges``) and the ``points`` (:class:`Points`) it ran over, the rows of ``cells``, at the scale of
-    ``cell_dist``.  ``surface`` (a :class:`ClassTables`; .m:271-309): ``cell_sf`` = the dict of :func:`_surface_rows`
+    ``cell_dist``; ``mixing`` (P > 0, with ``pair_edges``): ``cell_mix`` = :func:`pair_label_mixing` over the same points
+    (``mixing_seed``, keys = ``frame_ids``) and with ``refined_points`` ``refined_mix``.  ``surface`` (a :class:`ClassTables`; .m:271-309): ``cell_sf`` = the dict of :func:`_surface_rows`
     over the rows of ``cells`` against the surface of ``binary_fill_holes(res["recreated"] == Particle)``, plus
     ``surface_px`` / ``filled_area`` (B,) and with ``surface_edges`` ``hist`` and ``shells`` (:func:`surface_shells`).
     ``refined`` (a :class:`ClassTables`): the outputs of :func:`refined_tables`, with ``refined_points``
@@ -1107,6 +1108,10 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
         out["cell_dist"] = _cell_distances(d, distance_slots, raster)
     if neighbour_slots is not None:
         out["cell_nn"] = _neighbours(_pack_cells("neighbours_pack_cells", d, neighbour_slots), n_types, scale, pair_edges)
+        if mixing:
+            out["mixing_args"] = (pair_edges, mixing)
+            out["cell_mix"] = pair_label_mixing(out["cell_nn"]["points"], None, None, n_types, scale, pair_edges, mixing, mixing_seed,
+                                                frame_keys=frame_ids)
     if surface is not None:
         K = max(len(surface.slot_names), 1)
         mask, sf = particle_surface(res["recreated"], surface.particle_value, mask=pmask)
@@ -1120,6 +1125,9 @@ def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=
         pts = out.pop("points", None)
         if refined_points:
             out["refined_nn"] = _neighbours(pts, n_types, scale, pair_edges)
+            if mixing:
+                out["refined_mix"] = pair_label_mixing(pts, None, None, n_types, scale, pair_edges, mixing, mixing_seed,
+                                                       frame_keys=frame_ids)
         if surface is not None:
             out["refined_sf"] = _refined_surface(res, pts, sf, mask, scale, K, surface_edges)
         if convex or shape or skeleton or territory is not None:
@@ -1482,6 +1490,68 @@ def point_neighbours(xy, slot, ids, frame_offsets, K, scale, edges=None):
     _lib.check(lib.pcseg_point_neighbours(_ptr(xy), _ptr(slot), _ptr(ids), _ptr(frame_offsets), n, B, K, float(scale),
                                           e_ptr, n_edges, _ptr(dist), _ptr(nn_id), _ptr(hist), _ptr(ws), nbytes, _stream()), "point_neighbours")
     return dist[:n], nn_id[:n], hist
+
+
+MIXING_FIELDS = ("obs", "lo", "hi", "sum", "n_le", "n_ge", "cum_obs", "cum_lo", "cum_hi", "cum_sum", "cum_n_le", "cum_n_ge")
+
+
+def mixing_tile():
+    """The points of one LDS tile of :func:`pair_label_mixing`'s pair walk (larger frames: tile against tile)."""
+    return int(_lib.load().pcseg_mixing_tile())
+
+
+def pair_label_mixing(xy, slot, frame_offsets, K, scale, edges, permutations, seed=0, frame_keys=None, counts=False):
+    """Random-labelling envelopes of the pair-distance histograms of :func:`point_neighbours` (csrc/mixing.hip): the points
+    stay where they are, the slots of a frame's typed points (``0 <= slot < K``) are shuffled ``permutations`` (P <= 65535)
+    times by the counter-based rule of include/pcseg.h (``seed``, and per frame ``frame_keys``, (B,) int64, default 0 ..
+    B - 1: a frame's result depends on its key, not on its place in the batch).  ``xy`` / ``slot`` / ``frame_offsets`` as
+    for :func:`point_neighbours`, or ``xy`` a :class:`Points` and the other two None; ``edges`` m + 1 increasing values
+    from 0.  Returns a dict of (B, Q, m) int64 CUDA tensors, Q = K (K + 1) / 2 slot pairs in (a <= b) order: ``obs`` (the
+    histogram itself, without its n_pairs and overflow columns) and over the P shuffled histograms ``lo`` (minimum), ``hi``
+    (maximum), ``sum``, ``n_le`` = #{p: N_p <= obs}, ``n_ge`` = #{p: N_p >= obs}; ``cum_*``: the same six of the counts
+    summed over the bins 0 .. k (the K-function form).  With P = 0 only ``obs`` / ``cum_obs`` are meaningful (the rest 0).
+    The one-sided Monte Carlo p-values are ``(1 + n_ge) / (1 + P)`` for attraction (more pairs than chance) and
+    ``(1 + n_le) / (1 + P)`` for segregation.  ``counts=True``: also ``counts``, (B, P + 1, Q, m) int64, every labelling's
+    histogram (p = 0 the observed one).  Exact integers, bit for bit reproducible."""
+    if isinstance(xy, Points):
+        if slot is not None or frame_offsets is not None:
+            raise ValueError("with a Points as xy, slot and frame_offsets must be None")
+        xy, slot, frame_offsets = xy.coords, xy.slot, xy.frame_offsets
+    xy = _req(xy, torch.float64, 2)
+    slot = _req(slot, torch.int32, 1)
+    frame_offsets = _req(frame_offsets, torch.int64, 1)
+    n, B, K, P = xy.shape[0], frame_offsets.shape[0] - 1, int(K), int(permutations)
+    if xy.shape[1] != 2 or slot.shape[0] != n:
+        raise ValueError("xy must be (n, 2) with n slots")
+    e, e_ptr, n_edges = _edges_arg(edges)
+    if e is None:
+        raise ValueError("pair_label_mixing needs edges")
+    dev = xy.device
+    Q, m = K * (K + 1) // 2, max(n_edges - 1, 0)
+    if frame_keys is None:
+        frame_keys = torch.arange(max(B, 0), dtype=torch.int64, device=dev)
+    frame_keys = _req(frame_keys, torch.int64, 1)
+    if frame_keys.shape[0] != B:
+        raise ValueError("frame_keys must have one entry per frame")
+    if B < 1:
+        out = {k: torch.zeros((0, Q, m), dtype=torch.int64, device=dev) for k in MIXING_FIELDS}
+        if counts:
+            out["counts"] = torch.zeros((0, max(P, 0) + 1, Q, m), dtype=torch.int64, device=dev)
+        return out
+    lib = _lib.load()
+    nbytes = lib.pcseg_mixing_workspace_bytes(n, B, K, n_edges, P, 0 if counts else 1)
+    ws = _ws(nbytes, dev)
+    env = torch.empty((len(MIXING_FIELDS), B, Q, m), dtype=torch.int64, device=dev)
+    cnt = torch.empty((B, P + 1, Q, m), dtype=torch.int64, device=dev) if counts and nbytes else None
+    spare = torch.empty((2,), dtype=torch.float64, device=dev)  # (an empty point set: never a null pointer)
+    _lib.check(lib.pcseg_pair_label_mixing(_ptr(xy) if n else _ptr(spare), _ptr(slot) if n else _ptr(spare), _ptr(frame_offsets),
+                                           _ptr(frame_keys), n, B, K, float(scale), e_ptr, n_edges, P,
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(cnt), _ptr(env), _ptr(ws), nbytes, _stream()),
+               "pair_label_mixing")
+    out = dict(zip(MIXING_FIELDS, env))
+    if counts:
+        out["counts"] = cnt
+    return out
 
 
 def _edges_arg(edges):

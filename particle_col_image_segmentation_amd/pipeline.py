@@ -166,12 +166,12 @@ def _lanes_for(device, lanes):
     return _LANES[key]
 
 
-class TableSwitches(collections.namedtuple("TableSwitches", "neighbours pair_edges refined surface surface_edges territory territory_reach skeleton convex shape")):
+class TableSwitches(collections.namedtuple("TableSwitches", "neighbours pair_edges mixing mixing_seed refined surface surface_edges territory territory_reach skeleton convex shape")):
     """The switches of the optional tables, as ``tables`` / ``tables_device`` / ``host_tables`` / ``table_columns`` /
     ``empty_device_tables`` take them (see :meth:`FramePipeline.tables_device`)."""
 
 
-TableSwitches.__new__.__defaults__ = (False, None, False, False, None, False, None, False, False, False)
+TableSwitches.__new__.__defaults__ = (False, None, None, 0, False, False, None, False, None, False, False, False)
 
 # THE schema of the optional tables, in the order table_columns names them: name, on(switches), columns(type names,
 # switches), key columns of the gather's sort (distributed._SORT_COLS) and rows(pipeline, frame ids, ops.build_tables
@@ -192,11 +192,14 @@ _skel_cols = lambda names, o: ["frame", "label", "slot", "skel_px", "n_orth", "n
 _terr_cols = lambda names, o: (["frame", "label", "slot", "territory_px", "territory_on_px", "reach2_max", "clipped"]
                                + _per_type(names, "n_adj_%s") + _per_type(names, "n_contact_%s") + ["territory_um2", "territory_on_um2"])
 _adj_cols = lambda names, o: ["frame", "label_a", "label_b", "slot_a", "slot_b", "border_px", "contact_px"]
+_mix_cols = lambda names, o: list(ta.MIXING_COLUMNS)
 _pairs, _shells = (lambda o: o.pair_edges is not None), (lambda o: o.surface_edges is not None)
+_mixes = lambda o: bool(o.mixing) and _pairs(o)
 OPTIONAL_TABLES = (
     _Table("neighbours", lambda o: o.neighbours, _nn_cols, (0, 1),
            lambda p, fid, raw: p._neighbour_rows(raw["cells"], raw["cell_nn"]["dist"], raw["cell_nn"]["nn_id"])),
     _Table("pair_hist", _pairs, _pair_cols, (0, 1, 2), lambda p, fid, raw: p._pair_rows(fid, raw["cell_nn"]["hist"])),
+    _Table("mixing", _mixes, _mix_cols, (0, 1, 2, 3), lambda p, fid, raw: p._mixing_rows(fid, raw["cell_mix"], raw["mixing_args"])),
     _Table("refined", lambda o: o.refined, lambda names, o: ["frame", "label", "parent", "parent_px", "n_overlap", "class", "kind",
                                                              "cells", "area", "centroid_row", "centroid_col"], (0, 1),
            lambda p, fid, raw: raw["refined"]),
@@ -210,6 +213,8 @@ OPTIONAL_TABLES = (
            lambda p, fid, raw: p._point_rows(fid, raw["refined_nn"]["points"], raw["refined_nn"]["dist"], raw["refined_nn"]["nn_id"])),
     _Table("refined_pair_hist", lambda o: o.refined and _pairs(o), _pair_cols, (0, 1, 2),
            lambda p, fid, raw: p._pair_rows(fid, raw["refined_nn"]["hist"])),
+    _Table("refined_mixing", lambda o: o.refined and _mixes(o), _mix_cols, (0, 1, 2, 3),
+           lambda p, fid, raw: p._mixing_rows(fid, raw["refined_mix"], raw["mixing_args"])),
     _Table("surface", lambda o: o.surface, _sf_cols, (0, 1), lambda p, fid, raw: _sf_rows(p, fid, raw["cell_sf"])),
     _Table("frames_surface", lambda o: o.surface, lambda names, o: ["frame", "surface_px", "filled_area"], (0,),
            lambda p, fid, raw: torch.stack([fid, raw["cell_sf"]["surface_px"], raw["cell_sf"]["filled_area"]], dim=1).to(torch.float64)),
@@ -553,22 +558,31 @@ class FramePipeline:
         _, _, res["ws_sums"], _ = ops.region_reduce(res["ws_labels"], res["n_markers"], planes=stack, cap=cap)
 
     # ------------------------------------------------------------------ table output
-    def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None, refined=False, surface=False,
+    def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None, mixing=None, mixing_seed=0, refined=False, surface=False,
                       surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """Column names of every table of :meth:`tables` (known without any data: ranks that own no frame of a
         dataset still agree on the schema, see ``distributed.run_sharded``).  ``neighbours`` / ``pair_edges`` add the
         ``neighbours`` / ``pair_hist`` tables of :meth:`tables_device`, ``refined`` its ``refined`` /
         ``cell_resolution`` / ``frames_refined`` tables (and with the other two ``refined_neighbours`` /
-        ``refined_pair_hist``), ``surface`` its ``surface`` / ``frames_surface`` tables, ``surface_edges`` its
+        ``refined_pair_hist``), ``mixing`` (with ``pair_edges``) its ``mixing`` table (and with ``refined``
+        ``refined_mixing``), ``surface`` its ``surface`` / ``frames_surface`` tables, ``surface_edges`` its
         ``surface_hist`` / ``surface_shells`` tables (and with ``refined`` ``refined_surface`` /
         ``refined_surface_hist``), ``shape`` its ``shapes`` table (and with ``refined`` ``refined_shapes``), ``convex`` its ``convexity`` table (and
         with ``refined`` ``refined_convexity``), ``territory`` (with ``territory_reach``) its ``territories`` / ``adjacency``
         tables (and with ``refined`` ``refined_territories`` / ``refined_adjacency``)."""
-        return self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
+        return self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined, surface=surface,
                                                         surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
                                                         territory_reach=territory_reach, skeleton=skeleton))
 
+    @staticmethod
+    def _check_switches(o):
+        if o.mixing and o.pair_edges is None:
+            raise ValueError("mixing needs pair_edges: the envelopes are those of the pair_hist bins")
+        if o.mixing and not 0 < int(o.mixing) <= 65535:
+            raise ValueError("mixing: 1 .. 65535 permutations (0 or None: off)")
+
     def _columns(self, C, ratios, switches):
+        self._check_switches(switches)
         tb = self.tables_
         rn = [r[0] for r in ratios]
         cols = {
@@ -598,7 +612,7 @@ class FramePipeline:
         return {k: given[k] for k in cls._TABLE_KEYWORDS[method] if k in given}
 
     def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0, neighbours=False,
-                      pair_edges=None, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
+                      pair_edges=None, mixing=None, mixing_seed=0, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """The batch as dense row tables, assembled ON THE DEVICE (``csrc/tables.hip``): float64 CUDA tensors ``rois``,
         ``cells``, ``groups`` and ``frames_rec`` (one row per frame: frame id + the int64 record of
         ``pcseg_table_write``, see include/pcseg.h).  One small device-to-host copy (three row totals) sizes the
@@ -613,6 +627,17 @@ class FramePipeline:
         (m + 1 increasing values from 0, in um): also ``pair_hist`` = ``[frame, slot_a, slot_b, n_pairs, bin_0..
         bin_m-1, over]``, K (K + 1) / 2 rows per frame (slot_a <= slot_b, all-zero rows included): the pairs of rows of
         the two types whose distance d lies in ``[edges[k], edges[k + 1])``, and those at ``d >= edges[m]``.
+
+        ``mixing`` (P permutations, an int; 0 / None: off; needs ``pair_edges``, else ``ValueError``; csrc/mixing.hip): are
+        two strains closer together or further apart than chance?  The random-labelling test of ``pair_hist``: the rows
+        stay where they are, the slots of a frame's typed rows are shuffled P times (``mixing_seed`` and the frame's id
+        set the shuffles, see ``ops.pair_label_mixing``: a frame's rows do not depend on its batch or shard).  ``mixing`` =
+        ``[frame, slot_a, slot_b, bin, r_lo_um, r_hi_um, n_perm, obs, mean, lo, hi, n_le, n_ge, cum_obs, cum_mean, cum_lo,
+        cum_hi, cum_n_le, cum_n_ge]``, one row per (frame, slot pair, bin), B Q m rows: the observed count of the bin, mean
+        (``sum / P``), minimum and maximum of the shuffled counts, how many shuffles gave ``<= obs`` and ``>= obs``, and the
+        same of the counts summed over the bins 0 .. k (the K-function form).  The one-sided Monte Carlo p-values are
+        ``(1 + n_ge) / (1 + n_perm)`` for attraction and ``(1 + n_le) / (1 + n_perm)`` for segregation; they are not in the
+        table.  With ``refined`` also ``refined_mixing``, over the refined rows of kind >= 1.
 
         ``refined`` (refine_boundaries.py:1-12, goal 2): the refined ROIs classified by their parent class-map
         component (``ops.refined_tables``).  ``refined`` = one row per row of ``rois`` (its parent, overlap, class, kind
@@ -690,14 +715,16 @@ class FramePipeline:
             else:
                 fid = torch.tensor(ids, dtype=torch.int64).to(dev)
             groups = (res.get("groups") or {}) if self.merged else {}
-            o = TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
+            o = TableSwitches(neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined, surface=surface,
                               surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
                               territory_reach=territory_reach, skeleton=skeleton)
+            self._check_switches(o)
             want_nn, want_sf = neighbours or pair_edges is not None, surface or surface_edges is not None
             raw = ops.build_tables(res, groups, fid, C, ratios, check=check,  # raises what BatchResult.check() raises
                                    distance_slots=self.tables_.slot if distances else None, raster=raster,
                                    neighbour_slots=self.tables_.slot if want_nn else None,
                                    n_types=len(self.tables_.slot_names), pair_edges=pair_edges,
+                                   mixing=int(mixing or 0), mixing_seed=mixing_seed,
                                    refined=self.tables_ if refined else None, refined_points=refined and want_nn,
                                    surface=self.tables_ if want_sf else None, surface_edges=surface_edges, shape=shape, convex=convex,
                                    territory=self.tables_ if territory else None, territory_reach=territory_reach,
@@ -745,6 +772,22 @@ class FramePipeline:
         return torch.cat([fid.to(torch.float64)[:, None, None].expand(B, P, 1), ab[None].expand(B, P, 2),
                           hist.to(torch.float64)], dim=2).reshape(B * P, -1)
 
+    def _mixing_rows(self, fid, mix, args):
+        """``[frame, slot_a, slot_b, bin, r_lo_um, r_hi_um, n_perm, obs, mean, lo, hi, n_le, n_ge, cum_..]``: one row per
+        (frame, slot pair, bin) of ``ops.pair_label_mixing``'s tensors; ``args`` = (edges, P)."""
+        edges, P = args
+        B, Q, m = mix["obs"].shape
+        K = len(self.tables_.slot_names)
+        dev = mix["obs"].device
+        ab = torch.tensor([(a, b) for a in range(K) for b in range(a, K)], dtype=torch.float64, device=dev)
+        e = torch.as_tensor(np.asarray(edges, np.float64).reshape(-1)).to(dev)
+        bins = torch.stack([torch.arange(m, dtype=torch.float64, device=dev), e[:-1], e[1:]], dim=1)
+        f64 = lambda k: mix[k].to(torch.float64)[:, :, :, None]
+        per = torch.full((B, Q, m, 1), float(P), dtype=torch.float64, device=dev)  # tensor divisor: a correctly rounded division
+        half = lambda c: [f64(c + "obs"), f64(c + "sum") / per, f64(c + "lo"), f64(c + "hi"), f64(c + "n_le"), f64(c + "n_ge")]
+        return torch.cat([fid.to(torch.float64)[:, None, None, None].expand(B, Q, m, 1), ab[None, :, None, :].expand(B, Q, m, 2),
+                          bins[None, None].expand(B, Q, m, 3), per] + half("") + half("cum_"), dim=3).reshape(B * Q * m, -1)
+
     def _point_rows(self, fid, points, *columns):
         """``[frame, label, slot, columns..]`` for every point of a packed point set (``ops.Points``)."""
         foff, ids = points.frame_offsets, points.ids
@@ -761,10 +804,10 @@ class FramePipeline:
         return torch.cat([fid.to(torch.float64)[:, None, None].expand(B, R, 1), key[None].expand(B, R, key.shape[1]),
                           hist.reshape(B, R, -1).to(torch.float64)], dim=2).reshape(B * R, -1)
 
-    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None, refined=False,
+    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None, mixing=None, mixing_seed=0, refined=False,
                             surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset)."""
-        cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
+        cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined, surface=surface,
                                                         surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
                                                         territory_reach=territory_reach, skeleton=skeleton))
         mk = lambda n: torch.zeros((0, n), dtype=torch.float64, device=device)
@@ -776,13 +819,13 @@ class FramePipeline:
         return out
 
     def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0, neighbours=False, pair_edges=None,
-                    refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
+                    mixing=None, mixing_seed=0, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """numpy tables from (downloaded or gathered) :meth:`tables_device` output: ``cells`` / ``rois`` / ``groups`` /
         ``distances`` as they are, ``frames`` after the two ``round(x, 5)`` of get_cell_counts_and_densities
         (tiff_analysis.py:1018-1038; Python's decimal rounding, a handful of numbers per frame).  Every table's width
         must be the one :meth:`table_columns` names for ``C`` planes and these ``ratios``."""
         host = _download(dt)
-        cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, refined=refined, surface=surface,
+        cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined, surface=surface,
                                                         surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
                                                         territory_reach=territory_reach, skeleton=skeleton))
         tb = self.tables_
@@ -841,18 +884,18 @@ class FramePipeline:
         return ops.agreement_tables(ag, frame_ids)
 
     def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, neighbours=False,
-               pair_edges=None, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
+               pair_edges=None, mixing=None, mixing_seed=0, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per
         refined ROI), ``frames`` (one row per frame) and ``groups`` (one row per merged group): :meth:`tables_device`
         followed by :meth:`host_tables`.  ``check=False`` skips ``BatchResult.check`` (a caller that has looked at the
         flags itself, e.g. to keep the ROI rows of a batch in which the reference would have raised on one frame's
         cluster statistics).  ``neighbours`` / ``pair_edges`` / ``refined``: the ``neighbours`` / ``pair_hist`` and
-        refined tables of :meth:`tables_device`; ``surface`` / ``surface_edges``: its surface-distance tables; ``shape``: its
+        refined tables of :meth:`tables_device`; ``mixing`` / ``mixing_seed``: its ``mixing`` / ``refined_mixing`` tables; ``surface`` / ``surface_edges``: its surface-distance tables; ``shape``: its
         ``shapes`` / ``refined_shapes`` tables; ``convex``: its ``convexity`` / ``refined_convexity`` tables; ``territory`` /
         ``territory_reach``: its ``territories`` / ``adjacency`` tables; ``skeleton``: its ``skeletons`` / ``refined_skeletons``
         tables."""
         C = res["shape"][1]
-        kw = dict(ratios=ratios, distances=distances, raster=raster, neighbours=neighbours, pair_edges=pair_edges, refined=refined,
+        kw = dict(ratios=ratios, distances=distances, raster=raster, neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined,
                   surface=surface, surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
                   territory_reach=territory_reach, skeleton=skeleton)
         return self.host_tables(self.tables_device(res, frame_ids, check=check, **kw), C, **kw)

@@ -384,6 +384,45 @@ def get_cell_neighbour_distances(cell_pos, px_to_um=PX_TO_UM_CONV, edges=None):
                  for p, (a, b) in enumerate(pairs) if b < len(names)}
 
 
+MIXING_COLUMNS = ["frame", "slot_a", "slot_b", "bin", "r_lo_um", "r_hi_um", "n_perm", "obs", "mean", "lo", "hi", "n_le", "n_ge",
+                  "cum_obs", "cum_mean", "cum_lo", "cum_hi", "cum_n_le", "cum_n_ge"]
+
+
+def get_cell_mixing(cell_pos, edges, permutations=199, seed=0, px_to_um=PX_TO_UM_CONV):
+    """Do the strains of one frame sit closer together or further apart than chance?  The random-labelling test of the
+    pair-distance histogram (csrc/mixing.hip) on the regions of ``cell_pos`` (strain -> regions, as
+    get_cell_positions_and_areas returns it; strain t of the dict is slot t): the regions stay where they are, their strain
+    labels are shuffled ``permutations`` times (``seed``; frame key 0), and every bin ``[edges[k], edges[k + 1])`` (um,
+    increasing from 0) of every strain pair is compared with the shuffled counts.  One device call.  Returns ``(columns,
+    rows)``: the ``mixing`` table of ``FramePipeline.tables`` for this frame as numpy, one row per (slot_a <= slot_b, bin):
+    ``obs`` the observed pairs, ``mean`` / ``lo`` / ``hi`` of the shuffled ones, ``n_le`` / ``n_ge`` how many shuffles
+    gave at most / at least ``obs``, and ``cum_*`` the same for the counts summed over the bins 0 .. k.  The one-sided
+    Monte Carlo p-values are ``(1 + n_ge) / (1 + n_perm)`` for attraction and ``(1 + n_le) / (1 + n_perm)`` for
+    segregation.  The regions are taken in label order at the tables' positions (centroid_col + 1, centroid_row + 1), so
+    the shuffles are those of the pipeline's table for a frame with id 0."""
+    names = list(cell_pos)
+    if len(names) > 4:
+        raise ValueError("at most 4 strains")
+    regs = sorted(((int(r.label), t, r) for t, name in enumerate(names) for r in cell_pos[name]), key=lambda v: v[:2])
+    dev = _device()
+    xy = torch.tensor([[float(r.centroid[1]) + 1.0, float(r.centroid[0]) + 1.0] for _, _, r in regs],
+                      dtype=torch.float64).reshape(-1, 2).to(dev)
+    slot = torch.tensor([t for _, t, _ in regs], dtype=torch.int32).to(dev)
+    foff = torch.tensor([0, len(regs)], dtype=torch.int64).to(dev)
+    K, P = max(len(names), 1), int(permutations)
+    mix = ops.pair_label_mixing(xy, slot, foff, K, px_to_um, edges, P, seed=seed)
+    host = {k: v[0].cpu().numpy().astype(np.float64) for k, v in mix.items()}
+    e = np.asarray(edges, np.float64).reshape(-1)
+    Q, m = host["obs"].shape
+    ab = np.array([(a, b) for a in range(K) for b in range(a, K)], np.float64)
+    per = np.full((Q, m), float(P))
+    with np.errstate(invalid="ignore"):
+        half = lambda c: [host[c + "obs"], host[c + "sum"] / per, host[c + "lo"], host[c + "hi"], host[c + "n_le"], host[c + "n_ge"]]
+        cols = [np.zeros((Q, m)), np.repeat(ab[:, :1], m, 1), np.repeat(ab[:, 1:], m, 1), np.tile(np.arange(m, dtype=np.float64), (Q, 1)),
+                np.tile(e[:-1], (Q, 1)), np.tile(e[1:], (Q, 1)), per] + half("") + half("cum_")
+    return list(MIXING_COLUMNS), np.stack(cols, axis=2).reshape(Q * m, -1)
+
+
 def get_cell_convexity(cell_pos, px_to_um=PX_TO_UM_CONV):
     """One cell or a clump, for the regions of ``cell_pos`` (strain -> regions, as get_cell_positions_and_areas returns
     ``cell_pos`` or ``cell_clusters``): per strain a dict with ``labels`` (the regions' labels in list order) and, in the
