@@ -665,6 +665,58 @@ int pcseg_agreement_match(const int64_t *key, const int64_t *n, const int64_t *o
                           int32_t *best_s, double *iou_s, uint8_t *match_t, uint8_t *match_s, int64_t *frame_ints, int B,
                           pcseg_stream_t stream);
 
+/* ---- borders between touching regions and the merge of over-segmented regions by border strength (csrc/borders.hip): what
+ * skimage.graph.rag_boundary + cut_threshold do after a watershed, and the classical merge of basins over a low pass.
+ * Inputs.  L device int32 (B, H, W), any width and alignment.  V device float32, frame b at V + b * value_stride (elements,
+ *   >= H * W; rows contiguous): a (B, H, W) image or one plane of a (B, C, H, W) stack.
+ * Labels.  A label outside 0 .. cap is read as 0; a label above cap raises bit 2 (value 2) of the frame's overflow word, as in
+ *   pcseg_label_contingency.
+ * Links.  A LINK is an unordered pair of pixels p, q that are 4-neighbours (conn = 4) or 8-neighbours (conn = 8) with labels
+ *   a = L[p] >= 1, b = L[q] >= 1, a != b.  Every link is counted exactly once.  A link's value is max(V[p], V[q]): the ridge
+ *   between the two regions, whichever side of the cut it fell on.
+ * Values.  V is read as a probability: a NaN is read as 0, a value outside [0, 1] is clamped; either raises bit 4 (value 4).
+ * Per pair (a < b) with at least one link:
+ *   links   the number of links
+ *   saddle  the smallest link value, the exact float32 (non-negative floats order like their bit patterns)
+ *   sum     the sum over the links of rint(value * 2^32), an unsigned 64-bit integer.  A float32 in [2^-9, 1] is a multiple of
+ *           2^-32: for such values (the k/100 maps included) sum is the exact sum; below 2^-9 a value is off by at most 2^-33.
+ *           sum does not depend on any order of addition: results are reproducible bit for bit from run to run.
+ *   mean    = sum / (links * 2^32), left to the caller (in float64: the correctly rounded quotient when sum < 2^53)
+ * Merge rule.  below is a float64 in [0, 1].  by = PCSEG_BORDER_BY_MEAN: the pair is JOINED iff sum < rint(below * 2^32) * links, in
+ *   unsigned 64-bit integers, strictly.  by = PCSEG_BORDER_BY_SADDLE: JOINED iff saddle < (float)below.  The GROUPS are the connected
+ *   components of the joined pairs over the labels 1 .. count, count = counts[b] held to 0 .. cap (counts NULL: cap).  One
+ *   pass: weights are not updated after a union (cut_threshold, not merge_hierarchical); links and sum are additive, so a
+ *   second call on the merged image is the exact second round.
+ * Numbering.  Groups are numbered 1 .. m in the order of their smallest member.  map device int32 (B, cap + 1), old label to new
+ *   label: map[b, 0] = 0, map[b, l] = 0 for l > count; n_merged[b] = m; the merged image is map[b, L].  A region that touches
+ *   nothing keeps a group of its own, relative order is preserved, and with no joined pair the map is the identity on 1 .. count.
+ * pcseg_label_borders: per frame an open-addressing table of pair_cap slots (24 bytes each) keyed by a << 32 | b.  overflow (device
+ *   int32 (B)): bit 1 (value 1) where the frame has more pairs than pair_cap -- pairs are dropped then, nothing is written outside
+ *   the table and no thread waits --, bits 2 and 4 as above.  offsets (device int64 (B + 1)), totals (device int64 (2)) = {rows,
+ *   frames with bit 1}: the one host read between the two calls, as for pcseg_territory_pairs.  L and V are read once each.
+ *   cap, pair_cap >= 1, cap < 2^30, shapes as pcseg_edt_sq_u8 (check_shape), B <= 65535.
+ * pcseg_label_borders_write (same workspace, untouched in between): key (device int64 (rows)) = a << 32 | b, frame (device int32
+ *   (rows)), links (device int32 (rows)), sum (device int64 (rows)), saddle (device float32 (rows)); rows of a frame in table order.
+ * pcseg_border_merge (same workspace, straight after pcseg_label_borders: nothing is read back): flags is that call's overflow
+ *   array.  A frame with bit 1 keeps map as the identity on 1 .. count and n_merged = count: its merge is no result.  Bit 8 (value
+ *   8) is raised where a walk of the grouping met a parent entry outside its fence (a workspace overwritten while the call ran):
+ *   never a fault or an endless loop, and no result either.  Parents live in LDS where cap + 1 <= lds_labels, else in the workspace.
+ * pcseg_relabel_map: out[b, p] = map[b, L[b, p]], 0 where L is outside 0 .. cap; out device int32 (B, H, W), may not alias L.
+ * pcseg_border_block: HOST int32 (3) = rows and columns of a block of the fill kernel, lds_labels.
+ * Asynchronous, nothing is allocated; fill -> merge -> relabel can be captured in a graph. */
+#define PCSEG_BORDER_BY_MEAN 0
+#define PCSEG_BORDER_BY_SADDLE 1
+int pcseg_border_block(int32_t *rows_cols_lds);
+size_t pcseg_label_borders_workspace_bytes(int B, int pair_cap, int cap);
+int pcseg_label_borders(const int32_t *labels, const float *values, int64_t value_stride, int cap, int conn, int pair_cap,
+                        int32_t *overflow, int64_t *offsets, int64_t *totals, int B, int H, int W, void *workspace,
+                        size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_label_borders_write(int pair_cap, int cap, const int64_t *offsets, int64_t *key, int32_t *frame, int32_t *links, int64_t *sum,
+                              float *saddle, int B, const void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_border_merge(int pair_cap, int cap, const int32_t *counts, double below, int by, int32_t *flags, int32_t *map,
+                       int32_t *n_merged, int B, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);
+int pcseg_relabel_map(const int32_t *labels, const int32_t *map, int cap, int32_t *out, int B, int H, int W, pcseg_stream_t stream);
+
 /* ---- per-ROI skeletons (csrc/skeleton.hip): exact Guo-Hall thinning, every label on its own -- the union over l of
  * skimage.morphology.thin(labels == l) of scikit-image 0.18.3 -- and per ROI the length and the ends / junctions of its
  * skeleton.  Integers only.

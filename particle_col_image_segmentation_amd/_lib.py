@@ -108,6 +108,12 @@ SIGNATURES = {
     "pcseg_label_contingency": (c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, c_size_t, _P]),
     "pcseg_contingency_write": (c_int, [_I, _P, _P, _P, _P, _I, _P, c_size_t, _P]),
     "pcseg_agreement_match": (c_int, [_P, _P, _P, c_int64, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "pcseg_border_block": (c_int, [_P]),
+    "pcseg_label_borders_workspace_bytes": (c_size_t, [_I, _I, _I]),
+    "pcseg_label_borders": (c_int, [_P, _P, c_int64, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, c_size_t, _P]),
+    "pcseg_label_borders_write": (c_int, [_I, _I, _P, _P, _P, _P, _P, _P, _I, _P, c_size_t, _P]),
+    "pcseg_border_merge": (c_int, [_I, _I, _P, c_double, _I, _P, _P, _P, _I, _P, c_size_t, _P]),
+    "pcseg_relabel_map": (c_int, [_P, _P, _I, _P, _I, _I, _I, _P]),
     "pcseg_thin_labels_workspace_bytes": (c_size_t, [_I, _I, _I]),
     "pcseg_thin_labels": (c_int, [_P, _P, _P, _I, _I, _I, _I, _P, c_size_t, _P]),
     "pcseg_region_skeleton_workspace_bytes": (c_size_t, [_I, _I, _I, _I]),

@@ -5,7 +5,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["stencil.hip", "ccl.hip", "reduce.hip", "edt.hip", "watershed.hip", "tables.hip", "frontend.hip", "neighbours.hip", "refined.hip", "surface.hip", "shape.hip", "hull.hip", "voronoi.hip", "skeleton.hip", "reconstruct.hip", "agreement.hip", "mixing.hip"]
+SOURCES = ["stencil.hip", "ccl.hip", "reduce.hip", "edt.hip", "watershed.hip", "tables.hip", "frontend.hip", "neighbours.hip", "refined.hip", "surface.hip", "shape.hip", "hull.hip", "voronoi.hip", "skeleton.hip", "reconstruct.hip", "agreement.hip", "mixing.hip", "borders.hip"]
 LIB = os.path.join(HERE, "libpcseg.so")
 
 

@@ -1,7 +1,7 @@
-// The per-frame pair table of voronoi.hip (territory adjacency) and agreement.hip (label contingency): open addressing over
-// 64-bit keys with NV 32-bit counters per slot, the probing and overflow rule, and the count / scan kernels behind the
-// `offsets` and `totals` of the two-call protocol (first call: fill, count, scan; one host read of totals; second call:
-// compact the used slots into rows).  One definition of each.
+// The per-frame pair table of voronoi.hip (territory adjacency), agreement.hip (label contingency) and borders.hip (border
+// strength; its slot: pair_add_border): open addressing over 64-bit keys with NV 32-bit counters per slot, the probing and
+// overflow rule, and the count / scan kernels behind the `offsets` and `totals` of the two-call protocol (first call: fill,
+// count, scan; one host read of totals; second call: compact the used slots into rows).  One definition of each.
 #pragma once
 #include "common.h"
 
@@ -44,6 +44,36 @@ __device__ __forceinline__ void pair_add(const PairTable<NV> &t, unsigned long l
 #pragma unroll
             for (int k = 1; k < NV; ++k)
                 if (v[k]) atomicAdd(&t.cnt[NV * (size_t)s + k], v[k]);
+            return;
+        }
+        s = s + 1 == (unsigned)t.pair_cap ? 0u : s + 1;
+    }
+    atomicOr(t.overflow, PAIR_TABLE_FULL);
+}
+
+// ---- the border slot (borders.hip): a pair's links, its saddle and the 64-bit sum of its link values in the four counters of a
+// PairTable<4> slot -- [0] links, [1] ~(bits of the smallest link value) under an atomic max: a zero-filled slot reads as
+// "no value yet" (bits 0xFFFFFFFF, above every float in [0, 1]), [2..3] the sum as ONE aligned 64-bit word (the counters start
+// on a 256-byte boundary and a slot is 16 bytes).  pair_add's probing and overflow rule, with these three updates at the slot.
+constexpr int BORDER_NV = 4;
+enum { BORDER_LINKS = 0, BORDER_SADDLE = 1, BORDER_SUM = 2 };
+
+__device__ __forceinline__ void pair_add_border(const PairTable<BORDER_NV> &t, unsigned long long key, unsigned links,
+                                                unsigned long long sum, unsigned saddle_bits)
+{
+    if (ld_agent(t.overflow) & PAIR_TABLE_FULL) return;
+    unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) % (unsigned)t.pair_cap;
+    for (int i = 0; i < t.pair_cap; ++i) {
+        unsigned long long cur = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == 0) {
+            cur = atomicCAS(&t.keys[s], 0ull, key);
+            if (cur == 0) cur = key;
+        }
+        if (cur == key) {
+            unsigned *c = t.cnt + BORDER_NV * (size_t)s;
+            atomicAdd(c + BORDER_LINKS, links);
+            atomicMax(c + BORDER_SADDLE, ~saddle_bits);
+            atomicAdd(reinterpret_cast<unsigned long long *>(c + BORDER_SUM), sum);
             return;
         }
         s = s + 1 == (unsigned)t.pair_cap ? 0u : s + 1;

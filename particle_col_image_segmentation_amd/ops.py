@@ -1394,6 +1394,136 @@ def check_agreement_overflow(ag):
         raise RuntimeError("the contingency table of frame(s) %s is full: pair_cap = %d is too small" % (full, ag["pair_cap"]))
 
 
+BORDER_TABLE_FULL, BORDER_ABOVE_CAP, BORDER_VALUE, BORDER_CORRUPT = 1, 2, 4, 8  # bits of the per-frame border flags (include/pcseg.h)
+_BORDER_BY = {"mean": 0, "saddle": 1}
+
+
+@functools.lru_cache(maxsize=None)
+def border_block():
+    """``(R, C, lds_labels)`` of csrc/borders.hip: rows and columns of a block of the fill kernel, and the ``cap + 1`` up to
+    which the merge keeps its parents in LDS."""
+    out = (ctypes.c_int32 * 3)()
+    _lib.check(_lib.load().pcseg_border_block(ctypes.cast(out, ctypes.c_void_p)), "border_block")
+    return tuple(int(v) for v in out)
+
+
+def _border_fill(labels, strength, conn, cap, pair_cap):
+    """pcseg_label_borders: the filled tables.  Returns the state the second calls need."""
+    labels = _label_batch(labels)
+    strength, fstride = _plane_view(strength)
+    if tuple(strength.shape) != tuple(labels.shape):
+        raise ValueError("labels and strength must have one shape")
+    if conn not in (4, 8):
+        raise ValueError("conn must be 4 or 8")
+    B, H, W = labels.shape
+    dev = labels.device
+    if cap is None:
+        cap = int(labels.max().item())
+    cap = max(int(cap), 1)
+    pair_cap = 4 * cap if pair_cap is None else int(pair_cap)
+    lib = _lib.load()
+    nbytes = lib.pcseg_label_borders_workspace_bytes(B, pair_cap, cap)
+    st = {"labels": labels, "B": B, "H": H, "W": W, "cap": cap, "pair_cap": pair_cap, "nbytes": nbytes, "ws": _ws(nbytes, dev),
+          "overflow": torch.empty((B,), dtype=torch.int32, device=dev), "offsets": torch.empty((B + 1,), dtype=torch.int64, device=dev),
+          "totals": torch.empty((2,), dtype=torch.int64, device=dev)}
+    _lib.check(lib.pcseg_label_borders(_ptr(labels), _ptr(strength), fstride, cap, conn, pair_cap, _ptr(st["overflow"]),
+                                       _ptr(st["offsets"]), _ptr(st["totals"]), B, H, W, _ptr(st["ws"]), nbytes, _stream()),
+               "label_borders")
+    return st
+
+
+def label_borders(labels, strength, conn=8, cap=None, pair_cap=None):
+    """The borders between touching regions of a label image, weighed by a probability image (csrc/borders.hip; the
+    definitions: include/pcseg.h): ``labels`` int32 (B, H, W) CUDA tensor of any width and alignment, ``strength`` float32 of
+    the same shape (a plane view of a (B, C, H, W) stack is read in place).  A link is a pair of 4- (``conn`` = 4) or
+    8-neighbour pixels with different labels in 1 .. ``cap`` (default: the largest label, read back once), counted once; its
+    value is the larger of the two pixels' strengths, NaN read as 0 and values clamped to [0, 1].  Returns a dict, rows sorted
+    by (frame, a, b): ``frame``, ``a``, ``b`` (a < b), ``links`` int64; ``sum`` int64, the sum over the links of
+    ``rint(value * 2**32)`` (exact, independent of any order: identical from run to run); ``saddle`` float32, the smallest
+    link value; ``mean`` float64 = ``sum / (links * 2**32)``, one IEEE division: the correctly rounded quotient when ``sum <
+    2**53``; ``overflow`` int32 (B,): bit 1 (value 1) where the frame has more pairs than ``pair_cap`` (its rows are then
+    incomplete), 2 where a label above ``cap`` was seen, 4 where a strength was NaN or outside [0, 1]; ``n_overflow``, the
+    frames with bit 1 (read back with the row total, the one host read between the two calls).  ``pair_cap`` defaults to
+    ``4 * cap`` -- a region adjacency graph is planar for ``conn`` = 4 and nearly so for 8: about 3 pairs per label -- and a
+    slot takes 24 bytes: 96 ``cap`` bytes of table per frame."""
+    st = _border_fill(labels, strength, conn, cap, pair_cap)
+    dev = st["labels"].device
+    n, n_over = (int(v) for v in st["totals"].cpu())
+    key = torch.empty((n + 1,), dtype=torch.int64, device=dev)  # (a spare row: never a null pointer)
+    frame = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    links = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    total = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    saddle = torch.empty((n + 1,), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().pcseg_label_borders_write(st["pair_cap"], st["cap"], _ptr(st["offsets"]), _ptr(key), _ptr(frame), _ptr(links),
+                                                     _ptr(total), _ptr(saddle), st["B"], _ptr(st["ws"]), st["nbytes"], _stream()),
+               "label_borders_write")
+    # (frame, a, b) order: the rows of a frame are contiguous already, in table order -- two stable sorts, plumbing
+    key, frame = key[:n], frame[:n].to(torch.int64)
+    order = torch.sort(key, stable=True)[1]
+    order = order[torch.sort(frame[order], stable=True)[1]]
+    key, links, total = key[order], links[:n][order].to(torch.int64), total[:n][order]
+    mean = total.to(torch.float64) / (links.to(torch.float64) * 4294967296.0)
+    return {"frame": frame[order], "a": key >> 32, "b": key & 0xFFFFFFFF, "links": links, "sum": total, "saddle": saddle[:n][order],
+            "mean": mean, "overflow": st["overflow"], "n_overflow": n_over, "pair_cap": st["pair_cap"]}
+
+
+def relabel_map(labels, label_map):
+    """``label_map[b, labels[b]]`` (0 where a label lies outside 0 .. ``label_map.shape[1] - 1``): int32 (B, H, W)."""
+    labels = _label_batch(labels)
+    label_map = _req(label_map, torch.int32, 2)
+    B, H, W = labels.shape
+    if label_map.shape[0] != B or label_map.shape[1] < 2:
+        raise ValueError("label_map must be (B, cap + 1)")
+    out = torch.empty_like(labels)
+    _lib.check(_lib.load().pcseg_relabel_map(_ptr(labels), _ptr(label_map), label_map.shape[1] - 1, _ptr(out), B, H, W, _stream()),
+               "relabel_map")
+    return out
+
+
+def merge_by_border(labels, strength, below, by="mean", conn=8, counts=None, cap=None, pair_cap=None):
+    """Dissolve the weak borders of a label image (csrc/borders.hip, include/pcseg.h): the pairs of :func:`label_borders`
+    with ``mean < below`` (``by`` = "mean": ``sum < rint(below * 2**32) * links`` in integers, strictly) or ``saddle <
+    float32(below)`` (``by`` = "saddle") are joined, the groups are the connected components of the joined pairs over the
+    labels 1 .. ``counts[b]`` (int32 (B,); default ``cap``) and are numbered 1 .. m in the order of their smallest member.
+    One pass, as ``skimage.graph.cut_threshold``: weights are not updated after a union; a second call on the result is the
+    exact second round.  Returns ``(merged, n_merged, map, flags)``: the merged image int32 (B, H, W) = ``map[b, labels]``,
+    the groups per frame int32 (B,), ``map`` int32 (B, cap + 1) and ``flags`` int32 (B,) -- :func:`label_borders`'
+    ``overflow`` bits, and 8 where the grouping met a corrupt parent entry.  A frame with bit 1 keeps the identity map: see
+    :func:`check_border_flags`.  Fill, merge and relabel are enqueued one after the other: with ``cap`` given nothing is read
+    back (the default reads the largest label once), and the call can be captured in a graph.  ``pair_cap``: as for
+    :func:`label_borders`."""
+    if by not in _BORDER_BY:
+        raise ValueError('by must be "mean" or "saddle"')
+    below = float(below)
+    if not 0.0 <= below <= 1.0:
+        raise ValueError("below must lie in [0, 1]")
+    st = _border_fill(labels, strength, conn, cap, pair_cap)
+    B, cap, dev = st["B"], st["cap"], st["labels"].device
+    if counts is not None:
+        counts = _req(counts, torch.int32, 1)
+        if counts.shape[0] != B:
+            raise ValueError("counts must be (B,)")
+    label_map = torch.empty((B, cap + 1), dtype=torch.int32, device=dev)
+    n_merged = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().pcseg_border_merge(st["pair_cap"], cap, _ptr(counts), below, _BORDER_BY[by], _ptr(st["overflow"]),
+                                              _ptr(label_map), _ptr(n_merged), B, _ptr(st["ws"]), st["nbytes"], _stream()),
+               "border_merge")
+    return relabel_map(st["labels"], label_map), n_merged, label_map, st["overflow"]
+
+
+def check_border_flags(flags):
+    """RuntimeError where a frame's merge is no result (``flags`` of :func:`merge_by_border`): its pair table was full (1), a
+    label above the cap was dropped (2) or the grouping met a corrupt parent entry (8).  A clamped strength (4) is a defined
+    reading and does not raise."""
+    if flags is None:
+        return
+    bad = flags & (BORDER_TABLE_FULL | BORDER_ABOVE_CAP | BORDER_CORRUPT)
+    if int((bad != 0).sum().item()):
+        bad = bad.cpu()
+        raise RuntimeError("the border merge of frame(s) %s is no result (flags %s: 1 = pair table full, raise pair_cap; 2 = a label "
+                           "above cap; 8 = corrupt parent)" % ([int(b) for b in torch.nonzero(bad)[:, 0]], [int(v) for v in bad[bad != 0]]))
+
+
 def refined_inputs(res, lp, rc, frame_ids, n_slots):
     """struct pcseg_refined_inputs of one batch: ``res`` (the pipeline's result), ``lp`` (:func:`label_parent` on it),
     ``rc`` (:func:`classify_regions` on the refined ROIs).  Returns (struct, tensors the pointers refer to)."""

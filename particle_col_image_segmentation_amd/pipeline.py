@@ -38,6 +38,7 @@ class BatchResult(dict):
     _pending = None
     _slot = None   # graph mode: the capture slot whose static tensors this result aliases ...
     _gen = 0       # ... and the slot's replay count when this result was handed out
+    _stack = None  # the input of the run (FramePipeline.borders reads its boundary plane); not an entry: run()'s keys stay
 
     def _check_alive(self):
         if self._slot is not None and self._slot.gen != self._gen:
@@ -140,6 +141,8 @@ class BatchResult(dict):
         if int(self["nan_flag"].sum().item()):
             # tiff_analysis.py:776-781: clusters of a type without any single cell -> int(NaN)
             raise ValueError("cannot convert float NaN to integer")
+        if dict.__contains__(self, "border_flags"):
+            ops.check_border_flags(self["border_flags"])
         return self
 
 
@@ -278,7 +281,8 @@ class _GraphSlot:
 
 class FramePipeline:
     def __init__(self, cell_types=None, threshold=0.5, boundary_plane=BOUNDARY_PLANE, cap=None, merged=True,
-                 watershed_mode=0, overlap=True, lanes=None, multi_stream=True, graph=False, max_graphs=None, marker_h=None):
+                 watershed_mode=0, overlap=True, lanes=None, multi_stream=True, graph=False, max_graphs=None, marker_h=None,
+                 merge_below=None, merge_by="mean"):
         """``graph=True``: the chain of a batch (about a hundred launches on five streams) is captured ONCE per input
         buffer as a hipGraph and replayed for every later batch in that buffer -- one host call per batch instead of a
         hundred, no host thread per lane.  Inputs must then live in a small set of reused device buffers (the graph is
@@ -286,7 +290,14 @@ class FramePipeline:
         graph's static outputs: they stay valid until ``lanes`` further batches have been handed to :meth:`run`.
         ``lanes``: batches in flight (default 8 host threads in eager mode, 2 replay streams in graph mode).
         ``marker_h`` (pixels of the distance map; None: every local maximum): the watershed's markers are the h-maxima of the
-        distance map (``ops.edt_maxima``) and the result gains ``marker_flags``."""
+        distance map (``ops.edt_maxima``) and the result gains ``marker_flags``.
+        ``merge_below`` (a boundary probability in [0, 1]; None: no merge, nothing more is launched) / ``merge_by`` ("mean" or
+        "saddle"): after the flood, touching refined ROIs whose border in the boundary plane is weaker than ``merge_below``
+        are joined (``ops.merge_by_border``, 8-neighbour links; eagerly and in the captured graph alike, nothing is read
+        back).  ``ws_labels`` and ``n_markers`` of the result are then the MERGED image and its counts, so the sums stage,
+        the refined tables, the shapes and :meth:`agreement` see the merged ROIs; the result gains ``ws_labels_unmerged``,
+        ``n_unmerged``, ``merge_map`` and ``border_flags``.  ``markers`` stays the flood's marker image, numbered as
+        ``ws_labels_unmerged``."""
         if lanes is None:
             lanes = 2 if graph else 8
         self.cell_types = dict(cell_types or CELL_TYPES_5)
@@ -297,6 +308,10 @@ class FramePipeline:
         self.merged = merged
         self.watershed_mode = watershed_mode
         self.marker_h = None if marker_h is None else float(marker_h)
+        self.merge_below = None if merge_below is None else float(merge_below)
+        if merge_by not in ("mean", "saddle") or (self.merge_below is not None and not 0.0 <= self.merge_below <= 1.0):
+            raise ValueError('merge_by must be "mean" or "saddle" and merge_below a probability in [0, 1]')
+        self.merge_by = merge_by
         self.overlap = overlap
         self.lanes = max(1, int(lanes))
         self.multi_stream = bool(multi_stream)  # False: the class-map chain (incl. merges and fill) on ONE stream
@@ -318,6 +333,7 @@ class FramePipeline:
             return self._run_graph(stack)
         stack = stack.contiguous()
         res = BatchResult()
+        res._stack = stack
         res["shape"] = tuple(stack.shape)
         if not self.overlap:
             self._class_stage(stack, res)
@@ -376,6 +392,7 @@ class FramePipeline:
             done.record(slot.stream)
         slot.gen += 1
         res = BatchResult(slot.entries)
+        res._stack = stack
         res._pending, res._slot, res._gen = [done], slot, slot.gen
         return res
 
@@ -528,6 +545,11 @@ class FramePipeline:
         else:
             _, markers, n_markers, res["marker_flags"] = ops.edt_maxima(d2, self.marker_h, want_mask=False)
         ws_labels, tie_flags = ops.watershed(bm, markers, mask, mode=self.watershed_mode)
+        if self.merge_below is not None:
+            # ---- over-segmentation: dissolve the borders the classifier did not see (fill -> merge -> relabel, no host read)
+            res.update(ws_labels_unmerged=ws_labels, n_unmerged=n_markers)
+            ws_labels, n_markers, res["merge_map"], res["border_flags"] = ops.merge_by_border(
+                ws_labels, bm, self.merge_below, by=self.merge_by, counts=n_markers, cap=cap)
         res.update(mask=mask, markers=markers, n_markers=n_markers, ws_labels=ws_labels, tie_flags=tie_flags)
         # ---- area / centroid sums of the refined ROIs (plane-free pass); their isotope sums: _sums_stage.  (The sums pass
         # does not take the integer columns along: that form was built and removed -- the refined ROIs are small, every lane
@@ -701,6 +723,8 @@ class FramePipeline:
         dev = res["stats"].device
         if check and "marker_flags" in res and int((res["marker_flags"] != 0).sum().item()):
             raise RuntimeError("the h-maxima markers of this batch did not converge (marker_flags): its refined ROIs are no result")
+        if check:
+            ops.check_border_flags(res.get("border_flags"))
         # a stream of its own, at high priority: the handful of small kernels here must not queue behind the next
         # batch's big ones on a saturated GPU
         if self._table_stream is None or self._table_stream.device != dev:
@@ -882,6 +906,33 @@ class FramePipeline:
         ag = ops.label_agreement(truth, labels, thresholds, cap_t=truth_cap, cap_s=cap_s, pair_cap=pair_cap)
         ops.check_agreement_overflow(ag)
         return ops.agreement_tables(ag, frame_ids)
+
+    def borders(self, res, frame_ids=None, conn=8, raster=19.0, pair_cap=None):
+        """The borders between the refined ROIs of one batch, weighed by the boundary plane (``ops.label_borders`` on
+        ``res["ws_labels"]`` and the boundary plane of the input ``res`` was run on (the result keeps a reference to it) -- with ``merge_below`` these are the borders that survived
+        the merge).  Returns ``{"borders": float64 numpy rows, "borders_columns": [...]}``, one row per pair of touching ROIs
+        sorted by (frame, roi_a, roi_b): the frame's id (``frame_ids``; default: its position), ``roi_a`` < ``roi_b``,
+        ``links`` (4- or 8-neighbour pixel pairs across the border, ``conn``), ``mean`` and ``saddle`` (the mean and the
+        smallest boundary probability along it) and ``length_um`` = ``links`` at ``512 / raster`` pixels per um (the
+        scale of ``distances``).
+        RuntimeError where a frame has more pairs than ``pair_cap`` (default: 4 x the largest ROI count).  ``res`` is only
+        read."""
+        stack = getattr(res, "_stack", None)
+        if stack is None:
+            raise TypeError("borders needs a result of run(): it reads the boundary plane of the run's input")
+        labels = res["ws_labels"]
+        B = labels.shape[0]
+        fid = np.arange(B, dtype=np.float64) if frame_ids is None else np.asarray(frame_ids, np.float64)
+        if fid.shape != (B,):
+            raise ValueError("frame_ids must name every frame of the batch")
+        bd = ops.label_borders(labels, stack[:, self.boundary_plane], conn=conn, cap=max(int(res["n_markers"].max().item()), 1), pair_cap=pair_cap)
+        if bd["n_overflow"]:
+            raise RuntimeError("the border table of frame(s) %s is full: pair_cap = %d is too small"
+                               % ([int(b) for b in torch.nonzero((bd["overflow"] & 1).cpu())[:, 0]], bd["pair_cap"]))
+        host = {k: bd[k].cpu().numpy() for k in ("frame", "a", "b", "links", "mean", "saddle")}
+        rows = np.stack([fid[host["frame"]], host["a"], host["b"], host["links"], host["mean"], host["saddle"].astype(np.float64),
+                         host["links"] / (512.0 / float(raster))], axis=1).astype(np.float64).reshape(-1, 7)
+        return {"borders": rows, "borders_columns": ["frame", "roi_a", "roi_b", "links", "mean", "saddle", "length_um"]}
 
     def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, neighbours=False,
                pair_edges=None, mixing=None, mixing_seed=0, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):

@@ -17,13 +17,20 @@ BOUNDARY_CHANNEL = 3  # refine_boundaries.py:34
 THRESHOLD = 0.5  # refine_boundaries.py:44
 
 
-def refine_boundaries_batch(boundary_maps, threshold=THRESHOLD, mode=0, marker_h=None):
+def refine_boundaries_batch(boundary_maps, threshold=THRESHOLD, mode=0, marker_h=None, merge_below=None, merge_by="mean", merge_conn=8):
     """(B,H,W) float32 CUDA tensor -> dict of device stages (refine_boundaries.py:44-73).
 
     ``marker_h`` (pixels of the distance map; None: the script's chain): the markers are the maxima of the distance map that
     rise at least ``marker_h`` above their surroundings (``skimage.morphology.h_maxima(distance, marker_h)``) instead of
     every local maximum, ``local_max`` is their mask, and the dict gains ``marker_flags`` int32 (B,): non-zero where the
-    frame's reconstruction did not reach its fixed point and the frame is no result (``ops.reconstruct``)."""
+    frame's reconstruction did not reach its fixed point and the frame is no result (``ops.reconstruct``).
+
+    ``merge_below`` (a boundary probability in [0, 1]; None: the chain as it was, nothing more is launched): after the flood,
+    touching regions whose border is weaker than ``merge_below`` in ``boundary_maps`` itself are joined
+    (``ops.merge_by_border`` with ``by=merge_by``, ``conn=merge_conn``: one pass over the region adjacency graph, the remedy
+    for one cell cut in pieces by two maxima of its distance map).  ``labels`` is then the merged image and the dict gains
+    ``labels_unmerged``, ``n_merged`` int32 (B,), ``merge_map`` int32 (B, cap + 1) and ``border_flags`` int32 (B,)
+    (:func:`check_border_flags`); ``markers`` / ``n_markers`` stay the flood's."""
     d2, mask = ops.edt_sq_lt(boundary_maps, threshold)          # :44-45, :60
     st = {}
     if marker_h is None:
@@ -31,6 +38,11 @@ def refine_boundaries_batch(boundary_maps, threshold=THRESHOLD, mode=0, marker_h
     else:
         local_max, markers, n_markers, st["marker_flags"] = ops.edt_maxima(d2, marker_h)
     labels, tie_flags = ops.watershed(boundary_maps, markers, mask, mode=mode)  # :73
+    if merge_below is not None:
+        st["labels_unmerged"] = labels
+        cap = max(int(n_markers.max().item()), 1)
+        labels, st["n_merged"], st["merge_map"], st["border_flags"] = ops.merge_by_border(
+            labels, boundary_maps, merge_below, by=merge_by, conn=merge_conn, counts=n_markers, cap=cap)
     st.update({"binary_mask": mask, "distance_sq": d2, "local_max": local_max, "markers": markers,
                "n_markers": n_markers, "labels": labels, "tie_flags": tie_flags})
     return st
@@ -44,19 +56,27 @@ def check_marker_flags(st):
                            % [int(b) for b in torch.nonzero(flags.cpu())[:, 0]])
 
 
-def refine_boundaries(boundary_map, threshold=THRESHOLD, return_stages=False, marker_h=None):
+def check_border_flags(st):
+    """RuntimeError where the border merge of a frame is no result (``border_flags`` of refine_boundaries_batch)."""
+    ops.check_border_flags(st.get("border_flags"))
+
+
+def refine_boundaries(boundary_map, threshold=THRESHOLD, return_stages=False, marker_h=None, merge_below=None, merge_by="mean",
+                      merge_conn=8):
     """2-D boundary probability map -> int32 label image (the script's ``labels``).
 
     ``return_stages=True`` returns the script's globals instead: ``binary_mask``, ``distance`` (float64 =
     sqrt of the exact integer squared distance), ``local_max``, ``markers``, ``labels``.  ``marker_h``: see
-    :func:`refine_boundaries_batch` (``local_max`` is then the h-maxima mask)."""
+    :func:`refine_boundaries_batch` (``local_max`` is then the h-maxima mask).  ``merge_below`` / ``merge_by`` /
+    ``merge_conn``: its merge by border strength (``labels`` is then the merged image)."""
     was_tensor = isinstance(boundary_map, torch.Tensor)
     t = boundary_map if was_tensor else torch.from_numpy(np.ascontiguousarray(np.asarray(boundary_map, dtype=np.float32)))
     if t.dim() != 2:
         raise ValueError("expected a 2-D boundary map, got shape %s" % (tuple(t.shape),))
     t = t.to(device=_device(), dtype=torch.float32).contiguous()[None]
-    st = refine_boundaries_batch(t, threshold, marker_h=marker_h)
+    st = refine_boundaries_batch(t, threshold, marker_h=marker_h, merge_below=merge_below, merge_by=merge_by, merge_conn=merge_conn)
     check_marker_flags(st)
+    check_border_flags(st)
     conv = (lambda x: x) if was_tensor else (lambda x: x.cpu().numpy())
     labels = conv(st["labels"][0])
     if not return_stages:
@@ -69,28 +89,34 @@ def refine_boundaries(boundary_map, threshold=THRESHOLD, return_stages=False, ma
             "labels": labels}
 
 
-def score_refinement(boundary_maps, truth, thresholds=(THRESHOLD,), marker_hs=(None,), iou_thresholds=(0.5, 0.75, 0.9)):
-    """The sweep over the chain's knobs: :func:`refine_boundaries_batch` once per (threshold, marker_h) on ``boundary_maps``
-    ((B, H, W) float32 CUDA tensor), each result scored against ``truth`` (int32 (B, H, W) CUDA label image, 0: background)
-    on the device (``ops.label_agreement``).  Returns a list of dicts, one per setting in the order of
-    ``itertools.product(thresholds, marker_hs)``: ``threshold``, ``marker_h``, ``frames_agreement`` (float64 numpy, one row
-    per frame) and ``frames_agreement_columns`` as ``FramePipeline.agreement`` returns them."""
+def score_refinement(boundary_maps, truth, thresholds=(THRESHOLD,), marker_hs=(None,), iou_thresholds=(0.5, 0.75, 0.9),
+                     merge_belows=(None,)):
+    """The sweep over the chain's knobs: :func:`refine_boundaries_batch` once per (threshold, marker_h, merge_below) on
+    ``boundary_maps`` ((B, H, W) float32 CUDA tensor), each result scored against ``truth`` (int32 (B, H, W) CUDA label
+    image, 0: background) on the device (``ops.label_agreement``).  Returns a list of dicts, one per setting in the order of
+    ``itertools.product(thresholds, marker_hs, merge_belows)``: ``threshold``, ``marker_h``, ``merge_below``,
+    ``frames_agreement`` (float64 numpy, one row per frame) and ``frames_agreement_columns`` as ``FramePipeline.agreement``
+    returns them."""
     out = []
     truth_cap = max(int(truth.max().item()), 1)
     for threshold in thresholds:
         for marker_h in marker_hs:
-            st = refine_boundaries_batch(boundary_maps, threshold, marker_h=marker_h)
-            check_marker_flags(st)
-            ag = ops.label_agreement(truth, st["labels"], iou_thresholds, cap_t=truth_cap,
-                                     cap_s=max(int(st["n_markers"].max().item()), 1))
-            ops.check_agreement_overflow(ag)
-            tables = ops.agreement_tables(ag)
-            out.append({"threshold": threshold, "marker_h": marker_h, "frames_agreement": tables["frames_agreement"],
-                        "frames_agreement_columns": tables["frames_agreement_columns"]})
+            for merge_below in merge_belows:
+                st = refine_boundaries_batch(boundary_maps, threshold, marker_h=marker_h, merge_below=merge_below)
+                check_marker_flags(st)
+                check_border_flags(st)
+                ag = ops.label_agreement(truth, st["labels"], iou_thresholds, cap_t=truth_cap,
+                                         cap_s=max(int(st["n_markers"].max().item()), 1))
+                ops.check_agreement_overflow(ag)
+                tables = ops.agreement_tables(ag)
+                out.append({"threshold": threshold, "marker_h": marker_h, "merge_below": merge_below,
+                            "frames_agreement": tables["frames_agreement"],
+                            "frames_agreement_columns": tables["frames_agreement_columns"]})
     return out
 
 
-def refine_from_h5(file_path=DEFAULT_FILE, channel=BOUNDARY_CHANNEL, threshold=THRESHOLD, return_stages=False, marker_h=None):
+def refine_from_h5(file_path=DEFAULT_FILE, channel=BOUNDARY_CHANNEL, threshold=THRESHOLD, return_stages=False, marker_h=None,
+                   merge_below=None, merge_by="mean", merge_conn=8):
     """refine_boundaries.py:28-34 + the chain; ``.npy`` probability stacks are accepted without h5py."""
     if file_path.endswith(".npy"):
         probabilities = np.load(file_path, allow_pickle=False)
@@ -101,7 +127,8 @@ def refine_from_h5(file_path=DEFAULT_FILE, channel=BOUNDARY_CHANNEL, threshold=T
             raise ImportError("reading .h5 probabilities needs h5py; save the stack as .npy instead") from e
         with h5py.File(file_path, "r") as f:
             probabilities = np.array(f["exported_data"])
-    return refine_boundaries(probabilities[channel], threshold, return_stages, marker_h=marker_h)
+    return refine_boundaries(probabilities[channel], threshold, return_stages, marker_h=marker_h, merge_below=merge_below,
+                             merge_by=merge_by, merge_conn=merge_conn)
 
 
 if __name__ == "__main__":  # script-compatible entry: same default path, prints the number of segments

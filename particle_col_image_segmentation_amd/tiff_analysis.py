@@ -265,7 +265,7 @@ def get_cell_positions_and_areas(z_slice, cell_types, merged=False):
     return cell_pos, cell_clusters, particle_area, merged_clusters
 
 
-def get_refined_cell_positions_and_areas(z_slice, boundary_map, cell_types, threshold=0.5, marker_h=None):
+def get_refined_cell_positions_and_areas(z_slice, boundary_map, cell_types, threshold=0.5, marker_h=None, merge_below=None):
     """Goal 2 of refine_boundaries.py:1-12 for one frame: the watershed-refined ROIs of ``boundary_map`` (the chain of
     refine_boundaries.refine_boundaries) classified by the class-map component of ``z_slice`` they share the most
     pixels with (``ops.label_parent``), with the reference's own per-region loop (tiff_analysis.py:754-781) run on
@@ -274,8 +274,9 @@ def get_refined_cell_positions_and_areas(z_slice, boundary_map, cell_types, thre
     strain ``{"resolved": [class-map labels of clusters split into >= 2 refined cells / clusters], "residual":
     [(label, cells) of the other clusters], "count_integrated": cells + sum of the integrated cluster counts}``
     (-1 where a term is -1).  Raises ValueError as the reference loop does where a strain has refined clusters but no
-    refined cell.  ``marker_h``: the h-maxima markers of ``refine_boundaries_batch`` (None: every local maximum)."""
-    from .refine_boundaries import check_marker_flags, refine_boundaries_batch
+    refined cell.  ``marker_h``: the h-maxima markers of ``refine_boundaries_batch`` (None: every local maximum);
+    ``merge_below``: its merge of refined ROIs across borders weaker than this boundary probability (None: no merge)."""
+    from .refine_boundaries import check_border_flags, check_marker_flags, refine_boundaries_batch
     z_dev, _ = _to_dev_u8(z_slice)
     bm = boundary_map if isinstance(boundary_map, torch.Tensor) else torch.from_numpy(
         np.ascontiguousarray(np.asarray(boundary_map, dtype=np.float32)))
@@ -288,9 +289,10 @@ def get_refined_cell_positions_and_areas(z_slice, boundary_map, cell_types, thre
         cell_types[int(value)]  # KeyError for an unmapped class value, as at :756
     tables = ops.ClassTables(cell_types, CELL_TYPES, MIN_CELL_AREA, MIN_CLUSTER_AREA)
     verdict = ops.classify_regions(stats, cls_out, counts, tables)
-    st = refine_boundaries_batch(bm, threshold, marker_h=marker_h)
+    st = refine_boundaries_batch(bm, threshold, marker_h=marker_h, merge_below=merge_below)
     check_marker_flags(st)
-    ws_labels, n_markers = st["labels"], st["n_markers"]
+    check_border_flags(st)
+    ws_labels, n_markers = st["labels"], st.get("n_merged", st["n_markers"])
     n, m = len(regions), int(n_markers[0].item())
     cap = max(n, m, 1)
     cls_a = torch.zeros((1, cap), dtype=torch.uint8, device=z_dev.device)
