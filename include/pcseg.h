@@ -229,7 +229,9 @@ int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers
  *   PCSEG_WS_POISON_BORDER  first level, before the cross-tile border pass (roots named from a union-find tile seam)
  *   PCSEG_WS_POISON_LABEL   first level, before the label pass
  *   PCSEG_WS_POISON_LEVEL2  second level (listed frames, active tiles), before its label passes
- * frame_stride: as for pcseg_edt_sq_lt_f32 (0 = H*W). */
+ * frame_stride: as for pcseg_edt_sq_lt_f32 (0 = H*W).
+ * img: any float32 but NaN -- -0.0 and +0.0 are one level, infinities and subnormals are ordinary levels; a NaN
+ * inside the mask is outside the contract (the reference's comparisons are unordered there, the labels undefined). */
 enum pcseg_ws_poison { PCSEG_WS_POISON_BORDER = 8, PCSEG_WS_POISON_LABEL = 16, PCSEG_WS_POISON_LEVEL2 = 32 };
 size_t pcseg_watershed_workspace_bytes(int B, int H, int W);
 /* measurement aid: out[0] = 64x64 tiles the minimax relaxation actually processed (marked tiles over all rounds;
