@@ -34,6 +34,15 @@ def _req(t, dtype, ndim):
     return t.contiguous()
 
 
+def _label_batch(labels, what="labels"):
+    """An int32 (B, H, W) CUDA tensor of any width and alignment (a contiguous view keeps its base address)."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise TypeError("%s must be an int32 (B, H, W) tensor" % what)
+    return labels if labels.is_contiguous() else labels.contiguous()
+
+
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
@@ -204,12 +213,7 @@ def region_shape(labels, counts, cap=None):
     of any width and alignment, ``counts`` (B,) int32.  Returns ``(shape, overflow)``: int64 (B, cap, 8) = sum r^2, sum
     r c, sum c^2, n_1, n_sqrt2, n_mid, n_border, 0 for the labels 1 .. min(counts[b], cap) (rows beyond are not
     initialised) and int32 (B,) set where a label exceeds ``cap`` (default: max(counts))."""
-    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
-        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("labels must be an int32 (B, H, W) tensor")
-    if not labels.is_contiguous():  # (a contiguous view keeps its base address: unaligned images are taken as they are)
-        labels = labels.contiguous()
+    labels = _label_batch(labels)
     counts = _req(counts, torch.int32, 1)
     B, H, W = labels.shape
     if counts.shape[0] != B:
@@ -253,12 +257,7 @@ def region_hull(labels, counts, stats, cap=None):
     same labels (a ROI is looked for inside the bounding box its row names).  Returns ``(hull, overflow)``: int64 (B, cap,
     4) = convex_area, feret_sq4, euler number, 0 for the labels 1 .. min(counts[b], cap) (rows beyond are not initialised)
     and int32 (B,) set where ``counts[b]`` exceeds ``cap`` (default: the height of ``stats``)."""
-    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
-        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("labels must be an int32 (B, H, W) tensor")
-    if not labels.is_contiguous():  # (a contiguous view keeps its base address: unaligned images are taken as they are)
-        labels = labels.contiguous()
+    labels = _label_batch(labels)
     counts = _req(counts, torch.int32, 1)
     stats = _req(stats, torch.int64, 3)
     B, H, W = labels.shape
@@ -301,15 +300,6 @@ PEEL_SKELETON = 65535                # the peel value of a pixel that survives
 THIN_TILE, THIN_HALO = (64, 32), 8   # csrc/skeleton.hip: a tile (width, height) and its halo = sub-iterations per launch
 
 
-def _labels_arg(labels):
-    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
-        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("labels must be an int32 (B, H, W) tensor")
-    # (a contiguous view keeps its base address: unaligned images are taken as they are)
-    return labels if labels.is_contiguous() else labels.contiguous()
-
-
 def thin_labels(labels, max_iter=None):
     """Exact Guo-Hall thinning of a label batch, every label on its own (csrc/skeleton.hip, include/pcseg.h): the union over
     l of ``skimage.morphology.thin(labels == l, max_iter)`` of scikit-image 0.18.3.  ``labels`` (B, H, W) int32 CUDA tensor
@@ -317,7 +307,7 @@ def thin_labels(labels, max_iter=None):
     iters)``: uint16 (B, H, W) -- 0 background, 65535 the pixel survives (the skeleton), otherwise the 1-based sub-iteration
     that deleted it (full iteration ``(s + 1) // 2``) -- and int32 (B,), the full iterations of a frame that deleted a
     pixel.  Waits for the device between launches (the host decides whether another one follows): not for graph capture."""
-    labels = _labels_arg(labels)
+    labels = _label_batch(labels)
     B, H, W = labels.shape
     dev = labels.device
     peel = torch.empty((B, H, W), dtype=torch.uint16, device=dev)
@@ -347,7 +337,7 @@ def region_skeleton(labels, peel, counts, cap=None):
     max(counts)): the skeleton's pixels, its orthogonal and diagonal links between pixels of the same label (a diagonal pair
     is a link only if neither pixel next to both is on the label's skeleton), the pixels with one link and with three or
     more, and the full iterations the label took."""
-    labels = _labels_arg(labels)
+    labels = _label_batch(labels)
     counts = _req(counts, torch.int32, 1)
     B, H, W = labels.shape
     if not isinstance(peel, torch.Tensor) or not peel.is_cuda or peel.dtype != torch.uint16 or tuple(peel.shape) != (B, H, W):
@@ -1002,148 +992,172 @@ def _refined_surface(res, points, surface, mask, scale, K, edges):
     return _surface_rows(points._replace(coords=rc[:n]), surface, mask, scale, K, edges)
 
 
-def _shape_rows(labels, counts, stats, live, slot_of, frame_ids, scale):
-    """The ``shapes`` table of one label batch: :func:`region_shape` + :func:`shape_properties` on the whole batch, then
-    the rows ``live`` ((B, cap) bool) in (frame, label) order as ``[frame, label, slot, n_border, n_1, n_sqrt2, n_mid, mu_rr,
-    mu_rc, mu_cc, major_um, minor_um, eccentricity, orientation, equivalent_diameter_um, extent, perimeter_um]``
-    (lengths / ``scale``; the second central moments stay in pixels)."""
-    cap = stats.shape[1]
-    shape, _ = region_shape(labels, counts, cap=cap)
-    props = shape_properties(stats, shape, counts)
-    b, l = torch.nonzero(live, as_tuple=True)
-    sh, pr = shape[b, l].to(torch.float64), props[b, l]
-    slot = slot_of[b, l].to(torch.int64)
-    slot = torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
-    um = lambda k: pr[:, k] / scale
-    return torch.stack([frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), slot, sh[:, 6], sh[:, 3], sh[:, 4], sh[:, 5],
-                        pr[:, 2], -pr[:, 1], pr[:, 0], um(5), um(6), pr[:, 7], pr[:, 8], um(9), pr[:, 10], um(11)], dim=1)
-
-
-def _hull_rows(labels, counts, stats, live, slot_of, frame_ids, scale):
-    """The ``convexity`` table of one label batch: :func:`region_hull` + :func:`hull_properties` on the whole batch, then
-    the rows ``live`` ((B, cap) bool) in (frame, label) order as ``[frame, label, slot, convex_area, solidity, feret_um,
-    euler_number, convex_area_um2]`` (the length / ``scale``, the area / ``scale`` ^ 2, each ONE correctly rounded division)."""
-    hull, _ = region_hull(labels, counts, stats, cap=stats.shape[1])
-    props = hull_properties(stats, hull, counts)
-    b, l = torch.nonzero(live, as_tuple=True)
-    pr = props[b, l]
-    slot = slot_of[b, l].to(torch.int64)
-    slot = torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
-    # tensor divisors: a correctly rounded division per element (a Python scalar divisor is turned into a multiplication by
-    # its reciprocal on the device, one ulp off for some values -- the columns are promised equal to numpy's quotient)
-    per_um, per_um2 = torch.full_like(pr[:, 0], scale), torch.full_like(pr[:, 0], scale * scale)
-    return torch.stack([frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), slot, pr[:, 0], pr[:, 1], pr[:, 2] / per_um, pr[:, 3],
-                        pr[:, 0] / per_um2], dim=1)
-
-
-def _skeleton_rows(labels, counts, stats, live, slot_of, frame_ids, scale):
-    """The ``skeletons`` table of one label batch: :func:`thin_labels` + :func:`region_skeleton` + :func:`skeleton_properties`
-    on the whole batch, then the rows ``live`` ((B, cap) bool) in (frame, label) order as ``[frame, label, slot, skel_px,
-    n_orth, n_diag, n_end, n_junction, passes, length_um, width_um]`` (the two lengths / ``scale``, each ONE correctly rounded
-    division)."""
-    # only the rows asked for are thinned (every label is thinned on its own, so their skeletons do not change): the class-map
-    # components cover the whole frame, and background and particle would set the iteration count and keep every tile listed
-    B, cap = live.shape
-    keep = torch.zeros((B, cap + 2), dtype=torch.int32, device=labels.device)
-    keep[:, 1:cap + 1] = live * torch.arange(1, cap + 1, dtype=torch.int32, device=labels.device)
-    labels = torch.gather(keep, 1, labels.clamp(0, cap + 1).reshape(B, -1).to(torch.int64)).reshape(labels.shape)
-    peel, _ = thin_labels(labels)
-    table = region_skeleton(labels, peel, counts, cap=cap)
-    props = skeleton_properties(stats, table, counts)
-    b, l = torch.nonzero(live, as_tuple=True)
-    tb, pr = table[b, l].to(torch.float64), props[b, l]
-    slot = slot_of[b, l].to(torch.int64)
-    slot = torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
-    per_um = torch.full_like(pr[:, 0], scale)  # tensor divisor: a correctly rounded division per element (see _hull_rows)
-    return torch.stack([frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), slot] + [tb[:, k] for k in range(6)]
-                       + [pr[:, 0] / per_um, pr[:, 1] / per_um], dim=1)
+# The ROIs of one label batch that a per-ROI table has a row for: the label image, its per-frame label counts, its region
+# table ((B, cap, 8) of region_reduce), the rows wanted ((B, cap) bool) and their type slots ((B, cap) uint8).
+RoiRows = collections.namedtuple("RoiRows", "labels counts stats live slot_of")
 
 
 def _rows_below(counts, cap):
     return torch.arange(cap, device=counts.device)[None, :] < counts[:, None]
 
 
-def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, neighbour_slots=None,
-                 n_types=0, pair_edges=None, mixing=0, mixing_seed=0, refined=None, refined_points=False, surface=None, surface_edges=None, convex=False,
-                 shape=False, territory=None, territory_reach=None, skeleton=False):
-    """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device), then one stage per switch, in
-    this order.  ``distance_slots`` (the class value -> type slot table, uint8[256] numpy): ``cell_dist``, one value
-    per row of ``cells`` (NaN = no entry).  ``neighbour_slots`` (the same kind of table) with ``n_types`` slots:
-    ``cell_nn`` = dict of ``dist`` / ``nn_id`` / ``hist`` of :func:`point_neighbours` (``hist`` None without
-    ``pair_edges``) and the ``points`` (:class:`Points`) it ran over, the rows of ``cells``, at the scale of
-    ``cell_dist``; ``mixing`` (P > 0, with ``pair_edges``): ``cell_mix`` = :func:`pair_label_mixing` over the same points
-    (``mixing_seed``, keys = ``frame_ids``) and with ``refined_points`` ``refined_mix``.  ``surface`` (a :class:`ClassTables`; .m:271-309): ``cell_sf`` = the dict of :func:`_surface_rows`
-    over the rows of ``cells`` against the surface of ``binary_fill_holes(res["recreated"] == Particle)``, plus
-    ``surface_px`` / ``filled_area`` (B,) and with ``surface_edges`` ``hist`` and ``shells`` (:func:`surface_shells`).
-    ``refined`` (a :class:`ClassTables`): the outputs of :func:`refined_tables`, with ``refined_points``
-    ``refined_nn`` and with ``surface`` ``refined_sf``: the same two dicts over the refined rows of kind >= 1.
-    ``shape``: ``shapes`` = :func:`_shape_rows` over the rows of ``cells`` and, with ``refined``, ``refined_shapes`` over
-    the refined rows of kind >= 1.  ``convex``: ``convexity`` = :func:`_hull_rows` and ``refined_convexity``, over the same
-    rows.  ``territory`` (a :class:`ClassTables`) with ``territory_reach`` (um, None: unbounded): ``territories`` /
-    ``adjacency`` = :func:`territory_rows` over the rows of ``cells`` (the labels of kind >= 1 are the sites), the particle
-    mask of ``surface`` as its mask, ``territory_overflow`` and, with ``refined``, ``refined_territories`` /
-    ``refined_adjacency`` / ``refined_territory_overflow`` over the refined rows of kind >= 1 on the watershed labels.
-    ``skeleton``: ``skeletons`` = :func:`_skeleton_rows` over the rows of ``cells`` and, with ``refined``,
-    ``refined_skeletons`` over the refined rows of kind >= 1."""
+def class_rows(res):
+    """:class:`RoiRows` of the class-map components of a batch: the rows of ``cells`` (kind >= 1)."""
+    live = (res["kind"] >= 1) & _rows_below(res["counts"], res["stats"].shape[1])
+    return RoiRows(res["labels"], res["counts"], res["stats"], live, res["slot_of"])
+
+
+def refined_rows(res, kind_r, slot_r):
+    """:class:`RoiRows` of the refined ROIs of a batch, classified by :func:`refined_tables` (its ``kind_r`` / ``slot_r``):
+    the refined rows of kind >= 1 that own a pixel."""
+    live = (kind_r >= 1) & (res["ws_stats"][:, :, 0] > 0) & _rows_below(res["n_markers"], res["stats"].shape[1])
+    return RoiRows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, slot_r)
+
+
+def _slot_column(slot_of, b, l):
+    slot = slot_of[b, l].to(torch.int64)
+    return torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
+
+
+def _row_head(live, slot_of, frame_ids):
+    """The rows ``live`` in (frame, label) order: their indices ``b, l`` and the columns ``[frame, label, slot]``."""
+    b, l = torch.nonzero(live, as_tuple=True)
+    return b, l, [frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), _slot_column(slot_of, b, l)]
+
+
+def _over(x, divisor):
+    """``x / divisor`` with a TENSOR divisor: a correctly rounded division per element (a Python scalar divisor is turned
+    into a multiplication by its reciprocal on the device, one ulp off for some values -- the columns are promised equal to
+    numpy's quotient)."""
+    return x / torch.full_like(x, divisor)
+
+
+def _shape_rows(rows, frame_ids, scale):
+    """The ``shapes`` table of one label batch (:class:`RoiRows`): :func:`region_shape` + :func:`shape_properties` on the
+    whole batch, then the rows ``live`` in (frame, label) order as ``[frame, label, slot, n_border, n_1, n_sqrt2, n_mid, mu_rr,
+    mu_rc, mu_cc, major_um, minor_um, eccentricity, orientation, equivalent_diameter_um, extent, perimeter_um]``
+    (lengths / ``scale``; the second central moments stay in pixels)."""
+    shape, _ = region_shape(rows.labels, rows.counts, cap=rows.stats.shape[1])
+    props = shape_properties(rows.stats, shape, rows.counts)
+    b, l, head = _row_head(rows.live, rows.slot_of, frame_ids)
+    sh, pr = shape[b, l].to(torch.float64), props[b, l]
+    um = lambda k: pr[:, k] / scale
+    return torch.stack(head + [sh[:, 6], sh[:, 3], sh[:, 4], sh[:, 5], pr[:, 2], -pr[:, 1], pr[:, 0], um(5), um(6), pr[:, 7],
+                               pr[:, 8], um(9), pr[:, 10], um(11)], dim=1)
+
+
+def _hull_rows(rows, frame_ids, scale):
+    """The ``convexity`` table of one label batch (:class:`RoiRows`): :func:`region_hull` + :func:`hull_properties` on the
+    whole batch, then the rows ``live`` in (frame, label) order as ``[frame, label, slot, convex_area, solidity, feret_um,
+    euler_number, convex_area_um2]`` (the length / ``scale``, the area / ``scale`` ^ 2, each ONE correctly rounded division)."""
+    hull, _ = region_hull(rows.labels, rows.counts, rows.stats, cap=rows.stats.shape[1])
+    props = hull_properties(rows.stats, hull, rows.counts)
+    b, l, head = _row_head(rows.live, rows.slot_of, frame_ids)
+    pr = props[b, l]
+    return torch.stack(head + [pr[:, 0], pr[:, 1], _over(pr[:, 2], scale), pr[:, 3], _over(pr[:, 0], scale * scale)], dim=1)
+
+
+def _skeleton_rows(rows, frame_ids, scale):
+    """The ``skeletons`` table of one label batch (:class:`RoiRows`): :func:`thin_labels` + :func:`region_skeleton` +
+    :func:`skeleton_properties` on the whole batch, then the rows ``live`` in (frame, label) order as ``[frame, label, slot,
+    skel_px, n_orth, n_diag, n_end, n_junction, passes, length_um, width_um]`` (the two lengths / ``scale``, each ONE correctly
+    rounded division)."""
+    # only the rows asked for are thinned (every label is thinned on its own, so their skeletons do not change): the class-map
+    # components cover the whole frame, and background and particle would set the iteration count and keep every tile listed
+    live, labels = rows.live, rows.labels
+    B, cap = live.shape
+    keep = torch.zeros((B, cap + 2), dtype=torch.int32, device=labels.device)
+    keep[:, 1:cap + 1] = live * torch.arange(1, cap + 1, dtype=torch.int32, device=labels.device)
+    labels = torch.gather(keep, 1, labels.clamp(0, cap + 1).reshape(B, -1).to(torch.int64)).reshape(labels.shape)
+    peel, _ = thin_labels(labels)
+    table = region_skeleton(labels, peel, rows.counts, cap=cap)
+    props = skeleton_properties(rows.stats, table, rows.counts)
+    b, l, head = _row_head(live, rows.slot_of, frame_ids)
+    return torch.cat([torch.stack(head, dim=1), table[b, l].to(torch.float64), _over(props[b, l], scale)], dim=1)
+
+
+TableSwitches = collections.namedtuple(
+    "TableSwitches", "neighbours pair_edges mixing mixing_seed refined surface surface_edges territory territory_reach skeleton convex shape",
+    defaults=(False, None, None, 0, False, False, None, False, None, False, False, False))
+TableSwitches.__doc__ = """The switches of the optional tables, as ``FramePipeline.tables`` / ``tables_device`` /
+``host_tables`` / ``table_columns`` / ``empty_device_tables`` take them as keywords and :func:`build_tables` as one object.
+What each one adds is described once, in the docstring of ``FramePipeline.tables_device``; the tables and their columns
+stand in ``pipeline.OPTIONAL_TABLES``."""
+
+# the per-ROI tables that one RoiRows -> rows function makes: (table name, switch, rows function), in stage order
+_ROI_TABLES = (("skeletons", "skeleton", _skeleton_rows), ("convexity", "convex", _hull_rows), ("shapes", "shape", _shape_rows))
+
+
+def build_tables(res, groups, frame_ids, C, ratios, check=False, distance_slots=None, raster=19.0, tables=None,
+                 switches=TableSwitches()):
+    """csrc/tables.hip: dense row tables of one batch (see FramePipeline.tables_device), then one stage per switch of
+    ``switches`` (a :class:`TableSwitches`), in this order; ``tables`` is the pipeline's :class:`ClassTables` (None only
+    where no switch is on).  ``territory`` with ``territory_reach`` (um, None: unbounded): ``territories`` / ``adjacency`` =
+    :func:`territory_rows` over the rows of ``cells`` (:func:`class_rows`: the labels of kind >= 1 are the sites), the
+    particle mask of ``surface`` as its mask, and ``territory_overflow``.  ``skeleton`` / ``convex`` / ``shape``: ``skeletons`` /
+    ``convexity`` / ``shapes`` = :func:`_skeleton_rows` / :func:`_hull_rows` / :func:`_shape_rows` over the same rows.
+    ``distance_slots`` (the class value -> type slot table, uint8[256] numpy): ``cell_dist``, one value per row of ``cells``
+    (NaN = no entry).  ``neighbours`` or ``pair_edges``: ``cell_nn`` = dict of ``dist`` / ``nn_id`` / ``hist`` of
+    :func:`point_neighbours` (``hist`` None without ``pair_edges``) and the ``points`` (:class:`Points`) it ran over, the rows
+    of ``cells``, at the scale of ``cell_dist``; ``mixing`` (P > 0, with ``pair_edges``): ``cell_mix`` =
+    :func:`pair_label_mixing` over the same points (``mixing_seed``, keys = ``frame_ids``).  ``surface`` or ``surface_edges``
+    (.m:271-309): ``cell_sf`` = the dict of :func:`_surface_rows` over the rows of ``cells`` against the surface of
+    ``binary_fill_holes(res["recreated"] == Particle)``, plus ``surface_px`` / ``filled_area`` (B,) and with ``surface_edges``
+    ``hist`` and ``shells`` (:func:`surface_shells`).  ``refined``: the outputs of :func:`refined_tables`, then ``refined_nn`` /
+    ``refined_mix``, ``refined_sf`` and, with the ``refined_`` prefix, the per-ROI tables above: the same stages over the
+    refined rows of kind >= 1 (:func:`refined_rows`, on the watershed labels)."""
+    o = switches
     out, d = _dense_tables(res, groups, frame_ids, C, ratios, check)
     scale = 512.0 / float(raster)
-    cap = res["stats"].shape[1]
+    n_types = len(tables.slot_names) if tables is not None else 0
     pmask = None
-    if territory is not None:
-        r2 = reach_um_r2(territory_reach, scale)
-        pmask = particle_mask(res["recreated"], territory.particle_value)
-        out["territories"], out["adjacency"], out["territory_overflow"] = territory_rows(
-            res["labels"], (res["kind"] >= 1) & _rows_below(res["counts"], cap), res["slot_of"], frame_ids, scale,
-            len(territory.slot_names), r2=r2, mask=pmask, check=check)
-    if skeleton:
-        out["skeletons"] = _skeleton_rows(res["labels"], res["counts"], res["stats"],
-                                          (res["kind"] >= 1) & _rows_below(res["counts"], cap), res["slot_of"], frame_ids, scale)
-    if convex:
-        out["convexity"] = _hull_rows(res["labels"], res["counts"], res["stats"], (res["kind"] >= 1) & _rows_below(res["counts"], cap),
-                                      res["slot_of"], frame_ids, scale)
-    if shape:
-        out["shapes"] = _shape_rows(res["labels"], res["counts"], res["stats"], (res["kind"] >= 1) & _rows_below(res["counts"], cap),
-                                    res["slot_of"], frame_ids, scale)
+    if o.territory:
+        r2 = reach_um_r2(o.territory_reach, scale)
+        pmask = particle_mask(res["recreated"], tables.particle_value)
+
+    def roi_tables(prefix, rows):
+        """the per-ROI stages over one set of rows: territory, then skeleton, convex and shape"""
+        if o.territory:
+            out[prefix + "territories"], out[prefix + "adjacency"], out[prefix + "territory_overflow"] = territory_rows(
+                rows.labels, rows.live, rows.slot_of, frame_ids, scale, n_types, r2=r2, mask=pmask, check=check)
+        for name, switch, rows_of in _ROI_TABLES:
+            if getattr(o, switch):
+                out[prefix + name] = rows_of(rows, frame_ids, scale)
+
+    per_roi = o.territory or any(getattr(o, switch) for _, switch, _ in _ROI_TABLES)
+    if per_roi:
+        roi_tables("", class_rows(res))
     if distance_slots is not None:
         out["cell_dist"] = _cell_distances(d, distance_slots, raster)
-    if neighbour_slots is not None:
-        out["cell_nn"] = _neighbours(_pack_cells("neighbours_pack_cells", d, neighbour_slots), n_types, scale, pair_edges)
+    want_nn = o.neighbours or o.pair_edges is not None
+    mixing = int(o.mixing or 0)
+    if want_nn:
+        out["cell_nn"] = _neighbours(_pack_cells("neighbours_pack_cells", d, tables.slot), n_types, scale, o.pair_edges)
         if mixing:
-            out["mixing_args"] = (pair_edges, mixing)
-            out["cell_mix"] = pair_label_mixing(out["cell_nn"]["points"], None, None, n_types, scale, pair_edges, mixing, mixing_seed,
-                                                frame_keys=frame_ids)
-    if surface is not None:
-        K = max(len(surface.slot_names), 1)
-        mask, sf = particle_surface(res["recreated"], surface.particle_value, mask=pmask)
-        out["cell_sf"] = _surface_rows(_pack_cells("surface_pack_cells", d, surface.slot), sf, mask, scale, K, surface_edges)
+            out["mixing_args"] = (o.pair_edges, mixing)
+            out["cell_mix"] = pair_label_mixing(out["cell_nn"]["points"], None, None, n_types, scale, o.pair_edges, mixing,
+                                                o.mixing_seed, frame_keys=frame_ids)
+    want_sf = o.surface or o.surface_edges is not None
+    if want_sf:
+        K = max(n_types, 1)
+        mask, sf = particle_surface(res["recreated"], tables.particle_value, mask=pmask)
+        out["cell_sf"] = _surface_rows(_pack_cells("surface_pack_cells", d, tables.slot), sf, mask, scale, K, o.surface_edges)
         out["cell_sf"].update(surface_px=sf["counts"], filled_area=sf["area"])
-        if surface_edges is not None:
-            out["cell_sf"]["shells"] = surface_shells(sf, mask, surface_edges, scale)
-    if refined is not None:
-        want_points = refined_points or surface is not None
-        out.update(refined_tables(res, frame_ids, refined, d.ws, (d.n_roi, d.n_cell), check=check, points=want_points))
+        if o.surface_edges is not None:
+            out["cell_sf"]["shells"] = surface_shells(sf, mask, o.surface_edges, scale)
+    if o.refined:
+        refined_points = o.refined and want_nn
+        out.update(refined_tables(res, frame_ids, tables, d.ws, (d.n_roi, d.n_cell), check=check, points=refined_points or want_sf))
         pts = out.pop("points", None)
         if refined_points:
-            out["refined_nn"] = _neighbours(pts, n_types, scale, pair_edges)
+            out["refined_nn"] = _neighbours(pts, n_types, scale, o.pair_edges)
             if mixing:
-                out["refined_mix"] = pair_label_mixing(pts, None, None, n_types, scale, pair_edges, mixing, mixing_seed,
+                out["refined_mix"] = pair_label_mixing(pts, None, None, n_types, scale, o.pair_edges, mixing, o.mixing_seed,
                                                        frame_keys=frame_ids)
-        if surface is not None:
-            out["refined_sf"] = _refined_surface(res, pts, sf, mask, scale, K, surface_edges)
-        if convex or shape or skeleton or territory is not None:
-            live = (out["kind_r"] >= 1) & (res["ws_stats"][:, :, 0] > 0) & _rows_below(res["n_markers"], cap)
-        if skeleton:
-            out["refined_skeletons"] = _skeleton_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"],
-                                                      frame_ids, scale)
-        if convex:
-            out["refined_convexity"] = _hull_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"], frame_ids,
-                                                  scale)
-        if shape:
-            out["refined_shapes"] = _shape_rows(res["ws_labels"], res["n_markers"], res["ws_stats"], live, out["slot_r"], frame_ids,
-                                                scale)
-        if territory is not None:
-            out["refined_territories"], out["refined_adjacency"], out["refined_territory_overflow"] = territory_rows(
-                res["ws_labels"], live, out["slot_r"], frame_ids, scale, len(territory.slot_names), r2=r2, mask=pmask, check=check)
+        if want_sf:
+            out["refined_sf"] = _refined_surface(res, pts, sf, mask, scale, K, o.surface_edges)
+        if per_roi:
+            roi_tables("refined_", refined_rows(res, out["kind_r"], out["slot_r"]))
     return out
 
 
@@ -1811,15 +1825,6 @@ def particle_surface(recreated, particle_value, mask=None):
     return mask, surface_points(mask, 2, want_points=False)
 
 
-def _label_batch(labels, what="labels"):
-    """An int32 (B, H, W) CUDA tensor of any width and alignment (a contiguous view keeps its base address)."""
-    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
-        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise TypeError("%s must be an int32 (B, H, W) tensor" % what)
-    return labels if labels.is_contiguous() else labels.contiguous()
-
-
 def nearest_label(labels, sel=None, cap=None, want_site=False):
     """The exact nearest-label transform (Euclidean feature transform; csrc/voronoi.hip, include/pcseg.h): ``labels`` (B, H,
     W) int32 CUDA tensor of any width and alignment; a site is a pixel with a label in 1 .. ``cap`` (default: the width
@@ -1980,11 +1985,6 @@ def territory_pairs(near, d2, r2=-1, pair_cap=None, slot_of=None, n_types=0):
             "overflow": overflow, "n_overflow": n_over, "degree": degree}
 
 
-def _slot_column(slot_of, b, l):
-    slot = slot_of[b, l].to(torch.int64)
-    return torch.where(slot < 4, slot, torch.full_like(slot, -1)).to(torch.float64)
-
-
 def territory_rows(labels, live, slot_of, frame_ids, scale, n_types, r2=-1, mask=None, check=False, pair_cap=None):
     """The ``territories`` and ``adjacency`` tables of one label batch whose sites are the labels ``live`` ((B, cap) bool):
     :func:`nearest_label`, :func:`territory_reduce` and :func:`territory_pairs` on the whole batch, then the rows ``live`` in
@@ -1999,13 +1999,11 @@ def territory_rows(labels, live, slot_of, frame_ids, scale, n_types, r2=-1, mask
     pairs = territory_pairs(near, d2, r2, pair_cap or 8 * cap, slot_of=slot_of, n_types=K)
     if check and pairs["n_overflow"]:
         raise RuntimeError("territory pair table capacity exceeded: raise FramePipeline(cap=...)")
-    b, l = torch.nonzero(live, as_tuple=True)
+    b, l, head = _row_head(live, slot_of, frame_ids)
     t = terr[b, l].to(torch.float64)
-    # tensor divisor: a correctly rounded division per element (see _hull_rows)
-    per_um2 = torch.full_like(t[:, 0], scale * scale)
     deg = pairs["degree"][b, l].to(torch.float64)
-    rows = torch.cat([torch.stack([frame_ids[b].to(torch.float64), (l + 1).to(torch.float64), _slot_column(slot_of, b, l)], dim=1), t,
-                      deg[:, :int(n_types)], deg[:, K:K + int(n_types)], torch.stack([t[:, 0] / per_um2, t[:, 1] / per_um2], dim=1)], dim=1)
+    rows = torch.cat([torch.stack(head, dim=1), t, deg[:, :int(n_types)], deg[:, K:K + int(n_types)], _over(t[:, :2], scale * scale)],
+                     dim=1)
     f, a, bb = pairs["frame"], pairs["a"], pairs["b"]
     inside = (a <= cap) & (bb <= cap)  # (every site label is: near only ever holds site labels)
     f, a, bb = f[inside], a[inside], bb[inside]

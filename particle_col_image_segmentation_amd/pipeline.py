@@ -169,12 +169,7 @@ def _lanes_for(device, lanes):
     return _LANES[key]
 
 
-class TableSwitches(collections.namedtuple("TableSwitches", "neighbours pair_edges mixing mixing_seed refined surface surface_edges territory territory_reach skeleton convex shape")):
-    """The switches of the optional tables, as ``tables`` / ``tables_device`` / ``host_tables`` / ``table_columns`` /
-    ``empty_device_tables`` take them (see :meth:`FramePipeline.tables_device`)."""
-
-
-TableSwitches.__new__.__defaults__ = (False, None, None, 0, False, False, None, False, None, False, False, False)
+TableSwitches = ops.TableSwitches  # the switches of the optional tables and their defaults, described in tables_device
 
 # THE schema of the optional tables, in the order table_columns names them: name, on(switches), columns(type names,
 # switches), key columns of the gather's sort (distributed._SORT_COLS) and rows(pipeline, frame ids, ops.build_tables
@@ -580,21 +575,11 @@ class FramePipeline:
         _, _, res["ws_sums"], _ = ops.region_reduce(res["ws_labels"], res["n_markers"], planes=stack, cap=cap)
 
     # ------------------------------------------------------------------ table output
-    def table_columns(self, C, ratios=RATIOS_5, neighbours=False, pair_edges=None, mixing=None, mixing_seed=0, refined=False, surface=False,
-                      surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
+    def table_columns(self, C, ratios=RATIOS_5, **switches):
         """Column names of every table of :meth:`tables` (known without any data: ranks that own no frame of a
-        dataset still agree on the schema, see ``distributed.run_sharded``).  ``neighbours`` / ``pair_edges`` add the
-        ``neighbours`` / ``pair_hist`` tables of :meth:`tables_device`, ``refined`` its ``refined`` /
-        ``cell_resolution`` / ``frames_refined`` tables (and with the other two ``refined_neighbours`` /
-        ``refined_pair_hist``), ``mixing`` (with ``pair_edges``) its ``mixing`` table (and with ``refined``
-        ``refined_mixing``), ``surface`` its ``surface`` / ``frames_surface`` tables, ``surface_edges`` its
-        ``surface_hist`` / ``surface_shells`` tables (and with ``refined`` ``refined_surface`` /
-        ``refined_surface_hist``), ``shape`` its ``shapes`` table (and with ``refined`` ``refined_shapes``), ``convex`` its ``convexity`` table (and
-        with ``refined`` ``refined_convexity``), ``territory`` (with ``territory_reach``) its ``territories`` / ``adjacency``
-        tables (and with ``refined`` ``refined_territories`` / ``refined_adjacency``)."""
-        return self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined, surface=surface,
-                                                        surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                                                        territory_reach=territory_reach, skeleton=skeleton))
+        dataset still agree on the schema, see ``distributed.run_sharded``).  ``switches``: the optional tables, as
+        :meth:`tables_device` takes and describes them."""
+        return self._columns(C, ratios, TableSwitches(**switches))
 
     @staticmethod
     def _check_switches(o):
@@ -633,8 +618,7 @@ class FramePipeline:
             raise TypeError("unknown table keyword(s): %s" % ", ".join(sorted(unknown)))
         return {k: given[k] for k in cls._TABLE_KEYWORDS[method] if k in given}
 
-    def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0, neighbours=False,
-                      pair_edges=None, mixing=None, mixing_seed=0, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
+    def tables_device(self, res, frame_ids=None, ratios=RATIOS_5, check=True, distances=False, raster=19.0, **switches):
         """The batch as dense row tables, assembled ON THE DEVICE (``csrc/tables.hip``): float64 CUDA tensors ``rois``,
         ``cells``, ``groups`` and ``frames_rec`` (one row per frame: frame id + the int64 record of
         ``pcseg_table_write``, see include/pcseg.h).  One small device-to-host copy (three row totals) sizes the
@@ -642,6 +626,10 @@ class FramePipeline:
         nearest-other-type table of BASELINE config 5 (.m:260-268) as ``distances`` = ``[frame, label, distance]`` -- one
         batched launch over the cell rows of every frame (rows of type slot 0, then of slot 1, inside each frame); always
         present (empty unless requested) so that every rank gathers the same set of tables.
+
+        ``switches`` are the fields of :class:`TableSwitches`, all off by default and keyword only (an unknown name is a
+        ``TypeError``); :meth:`tables`, :meth:`host_tables`, :meth:`table_columns` and :meth:`empty_device_tables` take the same
+        ones, and ``OPTIONAL_TABLES`` is the schema of what they add:
 
         ``neighbours``: also ``neighbours`` = ``[frame, label, slot, nn_um_<type>.., nn_label_<type>..]``, one row per row
         of ``cells`` in its order: the distance (same scale as ``distances``) to the nearest OTHER row of every cell type
@@ -718,6 +706,8 @@ class FramePipeline:
         junction: a clump), the full iterations the thinning took, ``(n_orth + n_diag sqrt 2)`` and ``area / length`` at the
         scale of ``distances``.  With ``refined`` also ``refined_skeletons``: the same over the refined rows of kind >= 1.
         Runs in the table stage and waits for the device between its launches."""
+        o = TableSwitches(**switches)
+        self._check_switches(o)
         res.synchronize()
         B, C, H, W = res["shape"]
         dev = res["stats"].device
@@ -739,20 +729,9 @@ class FramePipeline:
             else:
                 fid = torch.tensor(ids, dtype=torch.int64).to(dev)
             groups = (res.get("groups") or {}) if self.merged else {}
-            o = TableSwitches(neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined, surface=surface,
-                              surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                              territory_reach=territory_reach, skeleton=skeleton)
-            self._check_switches(o)
-            want_nn, want_sf = neighbours or pair_edges is not None, surface or surface_edges is not None
             raw = ops.build_tables(res, groups, fid, C, ratios, check=check,  # raises what BatchResult.check() raises
-                                   distance_slots=self.tables_.slot if distances else None, raster=raster,
-                                   neighbour_slots=self.tables_.slot if want_nn else None,
-                                   n_types=len(self.tables_.slot_names), pair_edges=pair_edges,
-                                   mixing=int(mixing or 0), mixing_seed=mixing_seed,
-                                   refined=self.tables_ if refined else None, refined_points=refined and want_nn,
-                                   surface=self.tables_ if want_sf else None, surface_edges=surface_edges, shape=shape, convex=convex,
-                                   territory=self.tables_ if territory else None, territory_reach=territory_reach,
-                                   skeleton=skeleton)
+                                   distance_slots=self.tables_.slot if distances else None, raster=raster, tables=self.tables_,
+                                   switches=o)
             dt = {k: raw[k] for k in ("rois", "cells", "groups")}
             dt["frames_rec"] = torch.cat([fid[:, None].to(torch.float64), raw["frames"].to(torch.float64)], dim=1)
             dt["distances"] = self._distance_rows(dt["cells"], raw.get("cell_dist"))
@@ -828,12 +807,9 @@ class FramePipeline:
         return torch.cat([fid.to(torch.float64)[:, None, None].expand(B, R, 1), key[None].expand(B, R, key.shape[1]),
                           hist.reshape(B, R, -1).to(torch.float64)], dim=2).reshape(B * R, -1)
 
-    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, neighbours=False, pair_edges=None, mixing=None, mixing_seed=0, refined=False,
-                            surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
-        """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset)."""
-        cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined, surface=surface,
-                                                        surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                                                        territory_reach=territory_reach, skeleton=skeleton))
+    def empty_device_tables(self, C, ratios=RATIOS_5, device=None, **switches):
+        """What :meth:`tables_device` returns for zero frames (a rank that owns no frame of a dataset), with its ``switches``."""
+        cols = self._columns(C, ratios, TableSwitches(**switches))
         mk = lambda n: torch.zeros((0, n), dtype=torch.float64, device=device)
         out = {"rois": mk(len(cols["rois"])), "cells": mk(len(cols["cells"])), "groups": mk(len(cols["groups"])),
                "frames_rec": mk(18), "distances": mk(3)}
@@ -842,16 +818,14 @@ class FramePipeline:
                 out[k] = mk(len(cols[k]))
         return out
 
-    def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0, neighbours=False, pair_edges=None,
-                    mixing=None, mixing_seed=0, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
+    def host_tables(self, dt, C, ratios=RATIOS_5, distances=False, raster=19.0, **switches):
         """numpy tables from (downloaded or gathered) :meth:`tables_device` output: ``cells`` / ``rois`` / ``groups`` /
         ``distances`` as they are, ``frames`` after the two ``round(x, 5)`` of get_cell_counts_and_densities
         (tiff_analysis.py:1018-1038; Python's decimal rounding, a handful of numbers per frame).  Every table's width
-        must be the one :meth:`table_columns` names for ``C`` planes and these ``ratios``."""
+        must be the one :meth:`table_columns` names for ``C`` planes, these ``ratios`` and the ``switches`` the tables were
+        made with (those of :meth:`tables_device`)."""
+        cols = self._columns(C, ratios, TableSwitches(**switches))
         host = _download(dt)
-        cols = self._columns(C, ratios, TableSwitches(neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined, surface=surface,
-                                                        surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                                                        territory_reach=territory_reach, skeleton=skeleton))
         tb = self.tables_
         out = {k: host[k] for k in ("cells", "rois", "groups")}
         for k in out:
@@ -934,19 +908,11 @@ class FramePipeline:
                          host["links"] / (512.0 / float(raster))], axis=1).astype(np.float64).reshape(-1, 7)
         return {"borders": rows, "borders_columns": ["frame", "roi_a", "roi_b", "links", "mean", "saddle", "length_um"]}
 
-    def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, neighbours=False,
-               pair_edges=None, mixing=None, mixing_seed=0, refined=False, surface=False, surface_edges=None, shape=False, convex=False, territory=False, territory_reach=None, skeleton=False):
+    def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, **switches):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per
         refined ROI), ``frames`` (one row per frame) and ``groups`` (one row per merged group): :meth:`tables_device`
         followed by :meth:`host_tables`.  ``check=False`` skips ``BatchResult.check`` (a caller that has looked at the
         flags itself, e.g. to keep the ROI rows of a batch in which the reference would have raised on one frame's
-        cluster statistics).  ``neighbours`` / ``pair_edges`` / ``refined``: the ``neighbours`` / ``pair_hist`` and
-        refined tables of :meth:`tables_device`; ``mixing`` / ``mixing_seed``: its ``mixing`` / ``refined_mixing`` tables; ``surface`` / ``surface_edges``: its surface-distance tables; ``shape``: its
-        ``shapes`` / ``refined_shapes`` tables; ``convex``: its ``convexity`` / ``refined_convexity`` tables; ``territory`` /
-        ``territory_reach``: its ``territories`` / ``adjacency`` tables; ``skeleton``: its ``skeletons`` / ``refined_skeletons``
-        tables."""
-        C = res["shape"][1]
-        kw = dict(ratios=ratios, distances=distances, raster=raster, neighbours=neighbours, pair_edges=pair_edges, mixing=mixing, mixing_seed=mixing_seed, refined=refined,
-                  surface=surface, surface_edges=surface_edges, shape=shape, convex=convex, territory=territory,
-                  territory_reach=territory_reach, skeleton=skeleton)
-        return self.host_tables(self.tables_device(res, frame_ids, check=check, **kw), C, **kw)
+        cluster statistics).  ``switches``: the optional tables, as :meth:`tables_device` takes and describes them."""
+        dt = self.tables_device(res, frame_ids, ratios, check, distances, raster, **switches)
+        return self.host_tables(dt, res["shape"][1], ratios, distances, raster, **switches)

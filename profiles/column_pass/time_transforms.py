@@ -24,7 +24,7 @@ def main(path):
     res.synchronize()
     cap = res["stats"].shape[1]
     labels = res["labels"]
-    sel = ((res["kind"] >= 1) & ops._rows_below(res["counts"], cap)).view(torch.uint8)
+    sel = ops.class_rows(res).live.view(torch.uint8)
     lut = torch.cat([torch.ones((B, 1), dtype=torch.uint8, device=dev), 1 - sel], dim=1)
     not_site = torch.gather(lut, 1, labels.clamp(0, cap).to(torch.int64).reshape(B, -1)).reshape(B, H, W).contiguous()
     d2, near, _ = ops.nearest_label(labels, sel, cap)

@@ -8,7 +8,7 @@ import time
 import torch
 
 from particle_col_image_segmentation_amd import ops, synth
-from particle_col_image_segmentation_amd.pipeline import RATIOS_5, FramePipeline
+from particle_col_image_segmentation_amd.pipeline import RATIOS_5, FramePipeline, TableSwitches
 
 
 def timed(fn, wall=False, n=20, warm=2):
@@ -40,11 +40,10 @@ def main(path):
     res.synchronize()
     cap = res["stats"].shape[1]
     fid = torch.arange(B, dtype=torch.int64, device=dev)
-    raw = ops.build_tables(res, res.get("groups") or {}, fid, 5, RATIOS_5, refined=pipe.tables_)
-    live_c = (res["kind"] >= 1) & ops._rows_below(res["counts"], cap)
-    live_r = (raw["kind_r"] >= 1) & (res["ws_stats"][:, :, 0] > 0) & ops._rows_below(res["n_markers"], cap)
+    raw = ops.build_tables(res, res.get("groups") or {}, fid, 5, RATIOS_5, tables=pipe.tables_, switches=TableSwitches(refined=True))
     out = {"batch": [B, H, W], "cap": cap}
-    for name, labels, live, slot_of in (("cells", res["labels"], live_c, res["slot_of"]), ("refined", res["ws_labels"], live_r, raw["slot_r"])):
+    for name, rows in (("cells", ops.class_rows(res)), ("refined", ops.refined_rows(res, raw["kind_r"], raw["slot_r"]))):
+        labels, live, slot_of = rows.labels, rows.live, rows.slot_of
         sel = live.view(torch.uint8)
         # the same sites as a mask for the distance transform: 0 on a site, 1 elsewhere
         lut = torch.cat([torch.ones((B, 1), dtype=torch.uint8, device=dev), 1 - sel], dim=1)

@@ -280,6 +280,35 @@ def test_sort_keys_and_sharded_keywords_of_the_skeleton_tables():
         assert FramePipeline.table_kwargs(method, {"skeleton": True, "refined": True}) == {"skeleton": True, "refined": True}
 
 
+def test_every_table_method_takes_the_same_switches():
+    """the five table methods take the fields of TableSwitches and nothing else, and with every switch on the three that
+    work without a device name the same tables"""
+    import pytest
+    torch = pytest.importorskip("torch")
+    from particle_col_image_segmentation_amd.pipeline import OPTIONAL_TABLES, TableSwitches
+    pipe = _pipe()
+    res = {"shape": (1, 5, 8, 8)}  # (never read: the switches are looked at first)
+    for call in (lambda **kw: pipe.table_columns(5, **kw), lambda **kw: pipe.empty_device_tables(5, device="cpu", **kw),
+                 lambda **kw: pipe.host_tables({}, 5, **kw), lambda **kw: pipe.tables_device(res, **kw),
+                 lambda **kw: pipe.tables(res, **kw)):
+        with pytest.raises(TypeError, match="skeletons"):
+            call(skeletons=True)
+        with pytest.raises(TypeError, match="no_such_table"):
+            call(refined=True, no_such_table=1)
+    kw = dict(neighbours=True, pair_edges=[0.0, 1.0, 2.0], mixing=19, mixing_seed=3, refined=True, surface=True,
+              surface_edges=[0.0, 1.0], territory=True, territory_reach=3.0, skeleton=True, convex=True, shape=True)
+    assert set(kw) == set(TableSwitches._fields)
+    cols = pipe.table_columns(5, **kw)
+    always = {"rois", "cells", "groups", "frames", "distances"}
+    assert set(cols) == always | {t.name for t in OPTIONAL_TABLES}
+    dt = pipe.empty_device_tables(5, device="cpu", **kw)
+    assert set(dt) == (set(cols) - {"frames"}) | {"frames_rec"}
+    assert all(dt[k].shape == (0, len(cols[k])) for k in dt if k != "frames_rec")
+    host = pipe.host_tables(dt, 5, **kw)
+    assert {k for k in host if not k.endswith("_columns")} == set(cols)
+    assert all(host[k + "_columns"] == cols[k] and host[k].shape == (0, len(cols[k])) for k in cols)
+
+
 def test_skeleton_arguments_and_workspace():
     """argument checks and the workspace carve of the entry points, before any device call (the pointers are never
     dereferenced): one byte less than the size query's answer is refused"""
