@@ -9,7 +9,8 @@
 //                        neighbouring lanes with the same pair are summed by the segmented shuffle, and one table update per
 //                        run and wave goes into the frame's open-addressing table (key t << 32 | s, one counter).  Every pair
 //                        but (0, 0) is kept, so the marginals are row sums.  One read of each image, no per-pixel atomic.
-//   ag_write_kernel      the used slots of a frame as rows (key, frame, n), in table order
+//   pair_write_kernel    (pair_table.h, with AgEmit) the used slots of a frame as rows (key, frame, n), in table order.  Was
+//                        ag_write_kernel
 // pcseg_agreement_match: on the rows sorted by (frame, t, s)
 //   ag_area_kernel       A_t, B_s, S_pp and the column sum of s = 0 by integer atomics, one thread per row
 //   ag_best_kernel       per row with t, s >= 1: the partner counts, and the row competes for "best partner" of its t and of
@@ -83,30 +84,19 @@ __global__ void __launch_bounds__(256) ag_count_kernel(const int *__restrict__ l
     if (__any(above) && lane_id() == 0) atomicOr(overflow + b, AG_ABOVE_CAP);
 }
 
-// the used slots of frame b, in table order, as rows offsets[b] ..
-__global__ void __launch_bounds__(256) ag_write_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ cnt,
-                                                        int pair_cap, const long long *__restrict__ offsets, long long *__restrict__ key_out,
-                                                        int *__restrict__ frame_out, long long *__restrict__ n_out)
-{
-    __shared__ int wsum[4];
-    const int b = blockIdx.x;
-    const unsigned long long *k = keys + (int64_t)b * pair_cap;
-    const unsigned *v = cnt + (int64_t)b * pair_cap;
-    long long row0 = offsets[b];
-    for (int base = 0; base < pair_cap; base += 256) {
-        const int i = base + (int)threadIdx.x;
-        const unsigned long long key = i < pair_cap ? k[i] : 0ull;
-        int tot;
-        const int pos = block_exclusive_scan<256>((int)(key != 0), &tot, wsum);
-        if (key) {
-            const long long row = row0 + pos;
-            key_out[row] = (long long)key;
-            frame_out[row] = b;
-            n_out[row] = (long long)v[i];
-        }
-        row0 += tot;
+// a used slot as the row (key, frame, n) of pair_table.h's writer
+struct AgEmit {
+    static constexpr int NV = AG_NV;
+    long long *key_out;
+    int *frame_out;
+    long long *n_out;
+    __device__ __forceinline__ void operator()(int b, unsigned long long key, const unsigned *c, long long row) const
+    {
+        key_out[row] = (long long)key;
+        frame_out[row] = b;
+        n_out[row] = (long long)c[0];
     }
-}
+};
 
 // ---- the match step
 // frame_ints columns
@@ -292,9 +282,7 @@ extern "C" {
 size_t pcseg_contingency_workspace_bytes(int B, int pair_cap)
 {
     if (B < 1 || pair_cap < 1) return 0;
-    Carver cv(nullptr, 0);
-    pairs_carve<AG_NV>(cv, B, pair_cap);
-    return cv.off;
+    return carved_bytes(pairs_carve<AG_NV>, B, pair_cap, 0);
 }
 
 int pcseg_label_contingency(const int32_t *labels_t, const int32_t *labels_s, int cap_t, int cap_s, int pair_cap, int32_t *overflow,
@@ -305,11 +293,8 @@ int pcseg_label_contingency(const int32_t *labels_t, const int32_t *labels_s, in
                       cap_s >= 1 && pair_cap >= 1 && B <= 65535,
                   "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    const PairWs<AG_NV> ws = pairs_carve<AG_NV>(cv, B, pair_cap);
-    if (!cv.ok()) {
-        set_error("label_contingency: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    const PairWs<AG_NV> ws = pairs_carve<AG_NV>(cv, B, pair_cap, 0);
+    if (!cv.fits("label_contingency")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (const int rc = pairs_begin(ws, overflow, B, pair_cap, s)) return rc;
     const dim3 grid((W + 1023) / 1024, (H + RUN_ROWS - 1) / RUN_ROWS, B);
@@ -326,16 +311,8 @@ int pcseg_contingency_write(int pair_cap, const int64_t *offsets, int64_t *key, 
                             const void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
 {
     PCSEG_REQUIRE(offsets && key && frame && n && workspace && B >= 1 && B <= 65535 && pair_cap >= 1, "bad arguments");
-    Carver cv(const_cast<void *>(workspace), workspace_bytes);
-    const PairWs<AG_NV> ws = pairs_carve<AG_NV>(cv, B, pair_cap);
-    if (!cv.ok()) {
-        set_error("contingency_write: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    PCSEG_LAUNCH(ag_write_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const unsigned long long *)ws.keys,
-                 (const unsigned *)ws.cnt, pair_cap, (const long long *)offsets, (long long *)key, frame, (long long *)n);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    return pairs_write("contingency_write", workspace, workspace_bytes, B, pair_cap, 0, offsets,
+                       AgEmit{(long long *)key, frame, (long long *)n}, stream);
 }
 
 int pcseg_agreement_match(const int64_t *key, const int64_t *n, const int64_t *offsets, int64_t rows, int cap_t, int cap_s,

@@ -12,7 +12,8 @@
 //                        the one column the shuffle cannot give), and it becomes the current row of the next step in registers.
 //                        A link belongs to its upper (for "right": its left) pixel, so every seam link has one owner: the block
 //                        fetches the row below its last one, and the columns beside its first and last.
-//   border_write_kernel  the used slots of a frame as rows (key, frame, links, sum, saddle), in table order
+//   pair_write_kernel    (pair_table.h, with BorderEmit) the used slots of a frame as rows (key, frame, links, sum, saddle), in
+//                        table order.  Was border_write_kernel
 // pcseg_border_merge:
 //   border_merge_kernel  one block per frame: union-find over the labels 1 .. count with a joined pair as an edge (hooking to the
 //                        smaller label, fenced walks), parents in LDS where cap + 1 fits and in the workspace otherwise; the
@@ -32,6 +33,13 @@ constexpr int BD_ABOVE_CAP = 2;         // flag bit: a label above cap was seen 
 constexpr int BD_VALUE = 4;             // flag bit: a NaN or a value outside [0, 1] was seen (read as 0 / clamped)
 constexpr int BD_CORRUPT = 8;           // flag bit: the merge met a parent entry outside its fence
 constexpr unsigned BD_NO_SADDLE = 0xFFFFFFFFu;
+
+// the slot of a pair: its links, its saddle and the 64-bit sum of its link values in the four counters of a PairTable<4> slot --
+// [0] links, [1] ~(bits of the smallest link value) under an atomic max: a zero-filled slot reads as "no value yet" (bits
+// 0xFFFFFFFF, above every float in [0, 1]), [2..3] the sum as ONE aligned 64-bit word (the counters start on a 256-byte
+// boundary and a slot is 16 bytes)
+constexpr int BORDER_NV = 4;
+enum { BORDER_LINKS = 0, BORDER_SADDLE = 1, BORDER_SUM = 2 };
 
 // rint(v 2^32) of a float32 in [0, 1], ties to even, in integer arithmetic.  From 2^-9 on a float32 is a multiple of 2^-32 and
 // the result is a shift of its mantissa; below, the mantissa is rounded at the bit that 2^-32 leaves
@@ -114,7 +122,14 @@ __global__ void __launch_bounds__(256) border_fill_kernel(const int *__restrict_
         if (lane == 0) left = e;
         if (lane == WAVE - 1) right = e;
     };
-    auto commit = [&](const BdAcc &a) { pair_add_border(tab, a.key, a.n, a.sum, a.saddle); };
+    auto commit = [&](const BdAcc &a) {
+        const int s = pair_slot(tab, a.key);
+        if (s < 0) return;
+        unsigned *at = tab.cnt + BORDER_NV * (size_t)s;
+        atomicAdd(at + BORDER_LINKS, a.n);
+        atomicMax(at + BORDER_SADDLE, ~a.saddle);
+        atomicAdd(reinterpret_cast<unsigned long long *>(at + BORDER_SUM), a.sum);
+    };
     auto feed = [&](BdAcc &a, const BdPx &p, const BdPx &q) {
         if (p.l > 0 && q.l > 0 && p.l != q.l) {
             const unsigned long long key = ((unsigned long long)(unsigned)min(p.l, q.l) << 32) | (unsigned)max(p.l, q.l);
@@ -165,35 +180,22 @@ __global__ void __launch_bounds__(256) border_fill_kernel(const int *__restrict_
     }
 }
 
-// the used slots of frame b, in table order, as rows offsets[b] ..
-__global__ void __launch_bounds__(256) border_write_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ cnt,
-                                                            int pair_cap, const long long *__restrict__ offsets,
-                                                            long long *__restrict__ key_out, int *__restrict__ frame_out,
-                                                            int *__restrict__ links_out, long long *__restrict__ sum_out,
-                                                            float *__restrict__ saddle_out)
-{
-    __shared__ int wsum[4];
-    const int b = blockIdx.x;
-    const unsigned long long *k = keys + (int64_t)b * pair_cap;
-    const unsigned *v = cnt + (int64_t)b * pair_cap * BORDER_NV;
-    long long row0 = offsets[b];
-    for (int base = 0; base < pair_cap; base += 256) {
-        const int i = base + (int)threadIdx.x;
-        const unsigned long long key = i < pair_cap ? k[i] : 0ull;
-        int tot;
-        const int pos = block_exclusive_scan<256>((int)(key != 0), &tot, wsum);
-        if (key) {
-            const long long row = row0 + pos;
-            const unsigned *c = v + BORDER_NV * (size_t)i;
-            key_out[row] = (long long)key;
-            frame_out[row] = b;
-            links_out[row] = (int)c[BORDER_LINKS];
-            sum_out[row] = (long long)*reinterpret_cast<const unsigned long long *>(c + BORDER_SUM);
-            saddle_out[row] = __uint_as_float(~c[BORDER_SADDLE]);
-        }
-        row0 += tot;
+// a used slot as the row (key, frame, links, sum, saddle) of pair_table.h's writer
+struct BorderEmit {
+    static constexpr int NV = BORDER_NV;
+    long long *key_out;
+    int *frame_out, *links_out;
+    long long *sum_out;
+    float *saddle_out;
+    __device__ __forceinline__ void operator()(int b, unsigned long long key, const unsigned *c, long long row) const
+    {
+        key_out[row] = (long long)key;
+        frame_out[row] = b;
+        links_out[row] = (int)c[BORDER_LINKS];
+        sum_out[row] = (long long)*reinterpret_cast<const unsigned long long *>(c + BORDER_SUM);
+        saddle_out[row] = __uint_as_float(~c[BORDER_SADDLE]);
     }
-}
+};
 
 // (1024 threads: one block per frame scans the whole table, 64 blocks on 256 CUs -- the kernel is latency, not work)
 // LDS: cap + 1 <= BD_LDS_LABELS, the parents live in the block's LDS; otherwise in gpar (B, cap + 1)
@@ -273,17 +275,12 @@ __global__ void __launch_bounds__(256) relabel_map_kernel(const int *__restrict_
     }
 }
 
-struct BorderWs {
-    PairWs<BORDER_NV> pairs;
-    int *parent;  // (B, cap + 1): the merge's parents where they do not fit its LDS
-};
+// the workspace: the tables, and behind them (B, cap + 1) parents of the merge for where they do not fit its LDS
+static inline size_t border_parents(int B, int cap) { return (size_t)B * ((size_t)cap + 1); }
 
-static BorderWs border_carve(Carver &cv, int B, int pair_cap, int cap)
+static PairWs<BORDER_NV> border_carve(Carver &cv, int B, int pair_cap, int cap)
 {
-    BorderWs ws;
-    ws.pairs = pairs_carve<BORDER_NV>(cv, B, pair_cap);
-    ws.parent = cv.take<int>((size_t)B * ((size_t)cap + 1));
-    return ws;
+    return pairs_carve<BORDER_NV>(cv, B, pair_cap, border_parents(B, cap));
 }
 
 static inline bool border_sizes_ok(int B, int pair_cap, int cap) { return B >= 1 && B <= 65535 && pair_cap >= 1 && cap >= 1 && cap < (1 << 30); }
@@ -306,9 +303,7 @@ int pcseg_border_block(int32_t *rows_cols_lds)
 size_t pcseg_label_borders_workspace_bytes(int B, int pair_cap, int cap)
 {
     if (!border_sizes_ok(B, pair_cap, cap)) return 0;
-    Carver cv(nullptr, 0);
-    border_carve(cv, B, pair_cap, cap);
-    return cv.off;
+    return carved_bytes(border_carve, B, pair_cap, cap);
 }
 
 int pcseg_label_borders(const int32_t *labels, const float *values, int64_t value_stride, int cap, int conn, int pair_cap,
@@ -320,39 +315,27 @@ int pcseg_label_borders(const int32_t *labels, const float *values, int64_t valu
                   "bad arguments");
     PCSEG_REQUIRE(conn == 4 || conn == 8, "conn must be 4 or 8");
     Carver cv(workspace, workspace_bytes);
-    const BorderWs ws = border_carve(cv, B, pair_cap, cap);
-    if (!cv.ok()) {
-        set_error("label_borders: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    const PairWs<BORDER_NV> ws = border_carve(cv, B, pair_cap, cap);
+    if (!cv.fits("label_borders")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    if (const int rc = pairs_begin(ws.pairs, overflow, B, pair_cap, s)) return rc;
+    if (const int rc = pairs_begin(ws, overflow, B, pair_cap, s)) return rc;
     const dim3 grid((W + BD_COLS - 1) / BD_COLS, (H + BD_ROWS - 1) / BD_ROWS, B);
     if (conn == 8)
-        PCSEG_LAUNCH(border_fill_kernel<8>, grid, dim3(256), 0, s, labels, values, (long long)value_stride, cap, H, W, ws.pairs.keys,
-                     ws.pairs.cnt, overflow, pair_cap);
+        PCSEG_LAUNCH(border_fill_kernel<8>, grid, dim3(256), 0, s, labels, values, (long long)value_stride, cap, H, W, ws.keys,
+                     ws.cnt, overflow, pair_cap);
     else
-        PCSEG_LAUNCH(border_fill_kernel<4>, grid, dim3(256), 0, s, labels, values, (long long)value_stride, cap, H, W, ws.pairs.keys,
-                     ws.pairs.cnt, overflow, pair_cap);
+        PCSEG_LAUNCH(border_fill_kernel<4>, grid, dim3(256), 0, s, labels, values, (long long)value_stride, cap, H, W, ws.keys,
+                     ws.cnt, overflow, pair_cap);
     PCSEG_CHECK_LAUNCH();
-    return pairs_finish(ws.pairs, overflow, offsets, totals, B, pair_cap, s);
+    return pairs_finish(ws, overflow, offsets, totals, B, pair_cap, s);
 }
 
 int pcseg_label_borders_write(int pair_cap, int cap, const int64_t *offsets, int64_t *key, int32_t *frame, int32_t *links, int64_t *sum,
                               float *saddle, int B, const void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
 {
     PCSEG_REQUIRE(offsets && key && frame && links && sum && saddle && workspace && border_sizes_ok(B, pair_cap, cap), "bad arguments");
-    Carver cv(const_cast<void *>(workspace), workspace_bytes);
-    const BorderWs ws = border_carve(cv, B, pair_cap, cap);
-    if (!cv.ok()) {
-        set_error("label_borders_write: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    PCSEG_LAUNCH(border_write_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const unsigned long long *)ws.pairs.keys,
-                 (const unsigned *)ws.pairs.cnt, pair_cap, (const long long *)offsets, (long long *)key, frame, links, (long long *)sum,
-                 saddle);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    return pairs_write("label_borders_write", workspace, workspace_bytes, B, pair_cap, border_parents(B, cap), offsets,
+                       BorderEmit{(long long *)key, frame, links, (long long *)sum, saddle}, stream);
 }
 
 int pcseg_border_merge(int pair_cap, int cap, const int32_t *counts, double below, int by, int32_t *flags, int32_t *map,
@@ -362,21 +345,18 @@ int pcseg_border_merge(int pair_cap, int cap, const int32_t *counts, double belo
     PCSEG_REQUIRE(below >= 0.0 && below <= 1.0, "the threshold must lie in [0, 1]");
     PCSEG_REQUIRE(by == PCSEG_BORDER_BY_MEAN || by == PCSEG_BORDER_BY_SADDLE, "by must be PCSEG_BORDER_BY_MEAN or PCSEG_BORDER_BY_SADDLE");
     Carver cv(workspace, workspace_bytes);
-    const BorderWs ws = border_carve(cv, B, pair_cap, cap);
-    if (!cv.ok()) {
-        set_error("border_merge: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    const PairWs<BORDER_NV> ws = border_carve(cv, B, pair_cap, cap);
+    if (!cv.fits("border_merge")) return PCSEG_ERR_WORKSPACE;
     const unsigned long long t_fixed = (unsigned long long)__builtin_rint(below * 4294967296.0);
     const float t_float = (float)below;
     const int by_saddle = by == PCSEG_BORDER_BY_SADDLE;
     hipStream_t s = (hipStream_t)stream;
     if (cap + 1 <= BD_LDS_LABELS)
-        PCSEG_LAUNCH(border_merge_kernel<true>, dim3(B), dim3(BD_MERGE_THREADS), 0, s, (const unsigned long long *)ws.pairs.keys,
-                     (const unsigned *)ws.pairs.cnt, pair_cap, cap, counts, t_fixed, t_float, by_saddle, flags, ws.parent, map, n_merged);
+        PCSEG_LAUNCH(border_merge_kernel<true>, dim3(B), dim3(BD_MERGE_THREADS), 0, s, (const unsigned long long *)ws.keys,
+                     (const unsigned *)ws.cnt, pair_cap, cap, counts, t_fixed, t_float, by_saddle, flags, ws.tail, map, n_merged);
     else
-        PCSEG_LAUNCH(border_merge_kernel<false>, dim3(B), dim3(BD_MERGE_THREADS), 0, s, (const unsigned long long *)ws.pairs.keys,
-                     (const unsigned *)ws.pairs.cnt, pair_cap, cap, counts, t_fixed, t_float, by_saddle, flags, ws.parent, map, n_merged);
+        PCSEG_LAUNCH(border_merge_kernel<false>, dim3(B), dim3(BD_MERGE_THREADS), 0, s, (const unsigned long long *)ws.keys,
+                     (const unsigned *)ws.cnt, pair_cap, cap, counts, t_fixed, t_float, by_saddle, flags, ws.tail, map, n_merged);
     PCSEG_CHECK_LAUNCH();
     return PCSEG_OK;
 }

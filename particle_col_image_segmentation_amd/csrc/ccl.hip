@@ -558,10 +558,7 @@ static int ccl_full(KeyFn keyfn, int32_t *labels, int32_t *counts, int B, int H,
 {
     Carver cv(workspace, workspace_bytes);
     CclWs ws = ccl_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("ccl: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("ccl")) return PCSEG_ERR_WORKSPACE;
     int rc = ccl_roots<KeyFn, CONN8>(keyfn, ws.parent, B, H, W, s, false, ws.corrupt);
     if (rc) return rc;
     return ccl_compact(ws.parent, ws.blockcount, ws.nblk, labels, counts, PredAll(), true, B, H, W, s, ws.corrupt);
@@ -571,10 +568,7 @@ int ccl_plan(void *workspace, size_t workspace_bytes, int B, int H, int W, CclPl
 {
     Carver cv(workspace, workspace_bytes);
     CclWs ws = ccl_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits(who)) return PCSEG_ERR_WORKSPACE;
     plan->parent = ws.parent;
     plan->blockcount = ws.blockcount;
     plan->nblk = ws.nblk;
@@ -1199,9 +1193,7 @@ extern "C" {
 size_t pcseg_ccl_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    ccl_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(ccl_carve, B, H, W);
 }
 
 int pcseg_ccl8_equal_u8(const uint8_t *in, int32_t *labels, int32_t *counts, int B, int H, int W, void *workspace,
@@ -1228,9 +1220,7 @@ int pcseg_ccl4_bool(const uint8_t *in, int32_t *labels, int32_t *counts, int B, 
 size_t pcseg_dilate_ccl_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    dilate_ccl_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(dilate_ccl_carve, B, H, W);
 }
 
 // the dilated bit planes of masks.n masks of a class map: dil[m * B + b] = dilate(mask m of frame b, disk(radius));
@@ -1278,10 +1268,7 @@ int pcseg_dilate_ccl_roots_u8(const uint8_t *in, uint64_t value_bits, int radius
     hipStream_t s = (hipStream_t)stream;
     Carver cv(workspace, workspace_bytes);
     const DilateCclWs ws = dilate_ccl_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("dilate_ccl_roots: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("dilate_ccl_roots")) return PCSEG_ERR_WORKSPACE;
     const int rc = dilated_bit_planes(in, mask_set(&value_bits, 1), radius, ws.bits, ws.dil, B, H, W, s);
     if (rc) return rc;
     return ccl_roots<KeyBits, true>(KeyBits{ws.dil, W, (H + 31) / 32}, roots, B, H, W, s);
@@ -1290,9 +1277,7 @@ int pcseg_dilate_ccl_roots_u8(const uint8_t *in, uint64_t value_bits, int radius
 size_t pcseg_dilate_ccl_runs_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    dilate_ccl_runs_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(dilate_ccl_runs_carve, B, H, W);
 }
 
 int pcseg_dilate_ccl_runs_multi_u8(const uint8_t *in, const uint64_t *value_bits, int n_masks, int radius, uint32_t *dilated_bits,
@@ -1306,10 +1291,7 @@ int pcseg_dilate_ccl_runs_multi_u8(const uint8_t *in, const uint64_t *value_bits
     const int BM = B * n_masks;
     Carver cv(workspace, workspace_bytes);
     unsigned *bits = dilate_ccl_runs_carve(cv, BM, H, W);
-    if (!cv.ok()) {
-        set_error("dilate_ccl_runs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("dilate_ccl_runs")) return PCSEG_ERR_WORKSPACE;
     const int rc = dilated_bit_planes(in, mask_set(value_bits, n_masks), radius, bits, (unsigned *)dilated_bits, B, H, W, s);
     if (rc) return rc;
     return bitrun_components((const unsigned *)dilated_bits, (int *)run_parent, BM, H, W, s);
@@ -1329,10 +1311,7 @@ int pcseg_compact_labels(const int32_t *roots, int32_t *labels, int32_t *counts,
     hipStream_t s = (hipStream_t)stream;
     Carver cv(workspace, workspace_bytes);
     CclWs ws = ccl_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("compact_labels: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("compact_labels")) return PCSEG_ERR_WORKSPACE;
     int64_t total = (int64_t)B * H * W;
     // the caller's roots are walked like the library's own parents: fenced (common.h, walk_ok) -- an entry that is not "index
     // of an earlier-or-equal pixel of the same frame, + 1" makes counts[b] = -1 instead of a wild load
@@ -1345,9 +1324,7 @@ int pcseg_compact_labels(const int32_t *roots, int32_t *labels, int32_t *counts,
 size_t pcseg_fill_holes_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    fill_holes_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(fill_holes_carve, B, H, W);
 }
 
 int pcseg_fill_holes(const uint8_t *mask, uint8_t *out, int B, int H, int W, void *workspace, size_t workspace_bytes,
@@ -1359,10 +1336,7 @@ int pcseg_fill_holes(const uint8_t *mask, uint8_t *out, int B, int H, int W, voi
     Carver cv(workspace, workspace_bytes);
     const FillHolesWs ws = fill_holes_carve(cv, B, H, W);
     uint8_t *flag = ws.flag;
-    if (!cv.ok()) {
-        set_error("fill_holes: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("fill_holes")) return PCSEG_ERR_WORKSPACE;
     int rc = ccl_roots<KeyZeroU8, false>(KeyZeroU8{mask, W, (int64_t)H * W}, ws.parent, B, H, W, s);
     if (rc) return rc;
     dim3 g1((unsigned)((n + 255) / 256), B);
@@ -1379,9 +1353,7 @@ int pcseg_fill_holes(const uint8_t *mask, uint8_t *out, int B, int H, int W, voi
 size_t pcseg_local_maxima_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    locmax_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(locmax_carve, B, H, W);
 }
 
 int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers, int32_t *counts, int B, int H, int W,
@@ -1398,10 +1370,7 @@ int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers
     unsigned long long *cbits = ws.cbits;
     uint8_t *bad = ws.bad;
     int *nonconst = ws.nonconst;
-    if (!cv.ok()) {
-        set_error("local_maxima: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("local_maxima")) return PCSEG_ERR_WORKSPACE;
     PCSEG_CHECK_HIP(hipMemsetAsync(nonconst, 0, sizeof(int) * B, s));
     PCSEG_CHECK_HIP(hipMemsetAsync(cbits, 0, sizeof(unsigned long long) * (nwords + 1), s));  // one bit per pixel
     dim3 g2((W + LM_TW - 1) / LM_TW, (H + LM_TH - 1) / LM_TH, B);
@@ -1438,9 +1407,7 @@ int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers
 size_t pcseg_overlap_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    overlap_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(overlap_carve, B, H, W);
 }
 
 int pcseg_remove_overlapping(const uint8_t *dapi, const uint8_t *other, double threshold, uint8_t *out, int B, int H, int W,
@@ -1452,10 +1419,7 @@ int pcseg_remove_overlapping(const uint8_t *dapi, const uint8_t *other, double t
     Carver cv(workspace, workspace_bytes);
     const OverlapWs ws = overlap_carve(cv, B, H, W);
     int *area = ws.area, *ov = ws.ov;
-    if (!cv.ok()) {
-        set_error("remove_overlapping: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("remove_overlapping")) return PCSEG_ERR_WORKSPACE;
     int rc = ccl_roots<KeyIsOneU8, true>(KeyIsOneU8{dapi, W, (int64_t)H * W}, ws.parent, B, H, W, s);
     if (rc) return rc;
     dim3 g1((unsigned)((n + 255) / 256), B);

@@ -81,7 +81,23 @@ struct Carver {
         return p;
     }
     bool ok() const { return off <= cap && base != nullptr; }
+    // the workspace guard of every entry point, asked once its layout is carved: false, with the error set, where the
+    // caller's workspace does not hold the layout (the entry point then returns PCSEG_ERR_WORKSPACE)
+    bool fits(const char *who) const
+    {
+        if (!ok()) set_error("%s: workspace too small (%zu < %zu)", who, cap, off);
+        return ok();
+    }
 };
+
+// what a pcseg_*_workspace_bytes query answers: the bytes that `carve(cv, args...)` takes
+template <typename Carve, typename... Args>
+inline size_t carved_bytes(Carve carve, Args... args)
+{
+    Carver cv(nullptr, 0);
+    carve(cv, args...);
+    return cv.off;
+}
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 

@@ -568,10 +568,7 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
 {
     Carver cv(workspace, workspace_bytes);
     EdtWs ws = edt_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits(who)) return PCSEG_ERR_WORKSPACE;
     size_t lds = (size_t)EDT_RB * ((W + 3) & ~3) * (sizeof(uint16_t) + 1);  // distances + the block's in / out bytes
     if (Epi::kThreshold && lds > 160 * 1024) {
         set_error("%s: W = %d too wide for the LDS row stage", who, W);
@@ -673,9 +670,7 @@ extern "C" {
 size_t pcseg_edt_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    edt_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(edt_carve, B, H, W);
 }
 
 int pcseg_edt_sq_u8(const uint8_t *mask, int32_t *d2, int B, int H, int W, int cap, void *workspace, size_t workspace_bytes,

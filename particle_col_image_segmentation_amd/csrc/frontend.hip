@@ -153,9 +153,7 @@ extern "C" {
 size_t pcseg_classmap_label_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    classmap_label_carve(cv, pcseg_ccl_workspace_bytes(B, H, W), B, H, W);
-    return cv.off;
+    return carved_bytes(classmap_label_carve, pcseg_ccl_workspace_bytes(B, H, W), B, H, W);
 }
 
 int pcseg_classmap_label_f32(const float *stack, int C, uint8_t *denoised, int32_t *labels, int32_t *counts, int B, int H, int W,

@@ -40,18 +40,15 @@ struct HuWorkspace {
     int *ntall;   // [B] tall ROIs of the frame
     int *tall;    // [B, cap] their labels
     char *slices; // [B, hull_tall_blocks(B)] of hull_slice_bytes(H)
-    size_t off;
 };
 
-// the ONE layout of the workspace (null base: sizes only)
-static HuWorkspace hull_carve(void *workspace, size_t bytes, int B, int H, int cap)
+// the ONE layout of the workspace
+static HuWorkspace hull_carve(Carver &cv, int B, int H, int cap)
 {
-    Carver cv(workspace, bytes);
     HuWorkspace w;
     w.ntall = cv.take<int>((size_t)B);
     w.tall = cv.take<int>((size_t)B * cap);
     w.slices = cv.take<char>((size_t)B * hull_tall_blocks(B) * hull_slice_bytes(H));
-    w.off = cv.off;
     return w;
 }
 
@@ -340,7 +337,7 @@ extern "C" {
 size_t pcseg_region_hull_workspace_bytes(int B, int H, int W, int cap)
 {
     if (!check_shape(B, H, W) || cap < 1) return 0;
-    return hull_carve(nullptr, 0, B, H, cap).off;
+    return carved_bytes(hull_carve, B, H, cap);
 }
 
 int pcseg_region_hull(const int32_t *labels, const int32_t *counts, const int64_t *stats, int64_t *hull_out, int32_t *overflow, int B,
@@ -348,11 +345,9 @@ int pcseg_region_hull(const int32_t *labels, const int32_t *counts, const int64_
 {
     PCSEG_REQUIRE(labels && counts && stats && hull_out && workspace && check_shape(B, H, W) && cap >= 1 && B <= 65535,
                   "bad arguments");
-    HuWorkspace w = hull_carve(workspace, workspace_bytes, B, H, cap);
-    if (w.off > workspace_bytes) {
-        set_error("region_hull: workspace too small (%zu < %zu)", workspace_bytes, w.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    const HuWorkspace w = hull_carve(cv, B, H, cap);
+    if (!cv.fits("region_hull")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     PCSEG_LAUNCH(hull_init_kernel, dim3((B + 255) / 256), dim3(256), 0, s, counts, w.ntall, overflow, B, cap);
     PCSEG_CHECK_LAUNCH();

@@ -364,14 +364,12 @@ struct MixWorkspace {
     ulonglong2 *lab;
     double *thr;
     unsigned long long *counts;
-    size_t off;
 };
 
 static int mix_groups(int P) { return (P + 1 + 63) / 64; }
 
-static MixWorkspace mix_carve(void *workspace, size_t bytes, int64_t n, int B, int K, int n_edges, int P, bool own_counts)
+static MixWorkspace mix_carve(Carver &cv, int64_t n, int B, int K, int n_edges, int P, bool own_counts)
 {
-    Carver cv(workspace, bytes);
     MixWorkspace w;
     w.cxy = cv.take<double2>((size_t)n);
     w.cslot = cv.take<int32_t>((size_t)n);
@@ -381,7 +379,6 @@ static MixWorkspace mix_carve(void *workspace, size_t bytes, int64_t n, int B, i
     w.lab = cv.take<ulonglong2>((size_t)n * mix_groups(P));
     w.thr = cv.take<double>((size_t)n_edges);
     w.counts = own_counts ? cv.take<unsigned long long>((size_t)B * (P + 1) * (K * (K + 1) / 2) * (n_edges - 1)) : nullptr;
-    w.off = cv.off;
     return w;
 }
 
@@ -402,7 +399,7 @@ int pcseg_mixing_tile(void) { return MIX_TILE; }
 size_t pcseg_mixing_workspace_bytes(int64_t n_points, int B, int K, int n_edges, int n_perm, int with_counts)
 {
     if (!mix_shape_ok(n_points, B, K, n_edges, n_perm)) return 0;
-    return mix_carve(nullptr, 0, n_points, B, K, n_edges, n_perm, with_counts != 0).off;
+    return carved_bytes(mix_carve, n_points, B, K, n_edges, n_perm, with_counts != 0);
 }
 
 int pcseg_pair_label_mixing(const double *xy, const int32_t *slot, const int64_t *frame_offsets, const int64_t *frame_keys,
@@ -414,11 +411,9 @@ int pcseg_pair_label_mixing(const double *xy, const int32_t *slot, const int64_t
                       scale > 0.0 && std::isfinite(scale) && hist_edges_ok(edges, n_edges),
                   "bad arguments");
     const int P = n_perm, m = n_edges - 1, Q = K * (K + 1) / 2, G = mix_groups(P);
-    MixWorkspace w = mix_carve(workspace, workspace_bytes, n_points, B, K, n_edges, P, counts == nullptr);
-    if (w.off > workspace_bytes) {
-        set_error("pair_label_mixing: workspace too small (%zu < %zu)", workspace_bytes, w.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    const MixWorkspace w = mix_carve(cv, n_points, B, K, n_edges, P, counts == nullptr);
+    if (!cv.fits("pair_label_mixing")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     MixArgs a;
     a.cxy = w.cxy; a.cslot = w.cslot; a.meta = w.meta; a.prefix = w.prefix; a.foff = frame_offsets; a.keys = frame_keys;

@@ -291,12 +291,10 @@ struct NbWorkspace {
     double2 *sxy;
     int32_t *sid, *sorig, *sstart, *items, *prefix, *part_id;
     double *part_d2, *thr;
-    size_t off;
 };
 
-static NbWorkspace nb_carve(void *workspace, size_t bytes, int64_t n, int B, int K, int n_edges, int S)
+static NbWorkspace nb_carve(Carver &cv, int64_t n, int B, int K, int n_edges, int S)
 {
-    Carver cv(workspace, bytes);
     NbWorkspace w;
     w.sxy = cv.take<double2>((size_t)n);
     w.sid = cv.take<int32_t>((size_t)n);
@@ -307,7 +305,6 @@ static NbWorkspace nb_carve(void *workspace, size_t bytes, int64_t n, int B, int
     w.part_d2 = cv.take<double>((size_t)S * n * K);
     w.part_id = cv.take<int32_t>((size_t)S * n * K);
     w.thr = cv.take<double>((size_t)(n_edges > 0 ? n_edges : 1));
-    w.off = cv.off;
     return w;
 }
 
@@ -320,7 +317,7 @@ extern "C" {
 size_t pcseg_neighbours_workspace_bytes(int64_t n_points, int B, int K, int n_edges)
 {
     if (n_points < 0 || B < 1 || K < 1 || K > NB_MAX_K || n_edges < 0) return 0;
-    return nb_carve(nullptr, 0, n_points, B, K, n_edges, nb_splits(n_points, B)).off;
+    return carved_bytes(nb_carve, n_points, B, K, n_edges, nb_splits(n_points, B));
 }
 
 int pcseg_point_neighbours(const double *xy, const int32_t *slot, const int32_t *id, const int64_t *frame_offsets, int64_t n_points,
@@ -332,11 +329,9 @@ int pcseg_point_neighbours(const double *xy, const int32_t *slot, const int32_t 
                       n_points >= 0 && n_points < ((int64_t)1 << 24) && scale > 0.0 && std::isfinite(scale) && edges_ok,
                   "bad arguments");
     const int S = nb_splits(n_points, B), m = n_edges > 0 ? n_edges - 1 : 0, P = K * (K + 1) / 2;
-    NbWorkspace w = nb_carve(workspace, workspace_bytes, n_points, B, K, n_edges, S);
-    if (w.off > workspace_bytes) {
-        set_error("point_neighbours: workspace too small (%zu < %zu)", workspace_bytes, w.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    const NbWorkspace w = nb_carve(cv, n_points, B, K, n_edges, S);
+    if (!cv.fits("point_neighbours")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     NbArgs a;
     a.sxy = w.sxy; a.sid = w.sid; a.sstart = w.sstart; a.prefix = w.prefix; a.foff = frame_offsets;

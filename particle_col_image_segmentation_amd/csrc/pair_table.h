@@ -1,7 +1,13 @@
 // The per-frame pair table of voronoi.hip (territory adjacency), agreement.hip (label contingency) and borders.hip (border
-// strength; its slot: pair_add_border): open addressing over 64-bit keys with NV 32-bit counters per slot, the probing and
-// overflow rule, and the count / scan kernels behind the `offsets` and `totals` of the two-call protocol (first call: fill,
-// count, scan; one host read of totals; second call: compact the used slots into rows).  One definition of each.
+// strength): open addressing over 64-bit keys with NV 32-bit counters per slot, and the two-call protocol around it.  One
+// definition of each:
+//   pair_slot          the probing and overflow rule: the slot of a key, or -1 where the pair is dropped.  What is added at the
+//                      slot is the caller's (pair_add: NV counters; borders.hip: links, saddle and a 64-bit sum)
+//   pair_count_kernel, pair_scan_kernel   behind `offsets` and `totals` of the first call (pairs_begin, the caller's fill
+//                      kernel, pairs_finish); then one host read of totals
+//   pair_write_kernel  the second call (pairs_write): a frame's used slots compacted into rows, in table order; what a row
+//                      holds is the caller's emit functor.  (Until this kernel the three files had a copy each:
+//                      terr_pairs_write_kernel, ag_write_kernel, border_write_kernel -- the names in timings recorded before)
 #pragma once
 #include "common.h"
 
@@ -24,14 +30,14 @@ __device__ __forceinline__ PairTable<NV> pair_table_of(unsigned long long *keys,
     return PairTable<NV>{keys + (int64_t)b * pair_cap, cnt + (int64_t)b * pair_cap * NV, overflow + b, pair_cap};
 }
 
-// v[0 .. NV) added to key's counters (v[0] always, the others where they are not zero).
+// the slot of key, claimed if the key is new; -1 where the pair is dropped.
 // bounded probing: at most pair_cap slots are looked at; a full table raises the flag and drops the pair.  Once the flag is up
 // every later pair of the frame is dropped at once (its rows are incomplete anyway): without that each of them would walk the
 // whole full table, pairs x pair_cap loads
 template <int NV>
-__device__ __forceinline__ void pair_add(const PairTable<NV> &t, unsigned long long key, const unsigned (&v)[NV])
+__device__ __forceinline__ int pair_slot(const PairTable<NV> &t, unsigned long long key)
 {
-    if (ld_agent(t.overflow) & PAIR_TABLE_FULL) return;
+    if (ld_agent(t.overflow) & PAIR_TABLE_FULL) return -1;
     unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) % (unsigned)t.pair_cap;
     for (int i = 0; i < t.pair_cap; ++i) {
         unsigned long long cur = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -39,46 +45,23 @@ __device__ __forceinline__ void pair_add(const PairTable<NV> &t, unsigned long l
             cur = atomicCAS(&t.keys[s], 0ull, key);
             if (cur == 0) cur = key;
         }
-        if (cur == key) {
-            atomicAdd(&t.cnt[NV * (size_t)s], v[0]);
-#pragma unroll
-            for (int k = 1; k < NV; ++k)
-                if (v[k]) atomicAdd(&t.cnt[NV * (size_t)s + k], v[k]);
-            return;
-        }
+        if (cur == key) return (int)s;
         s = s + 1 == (unsigned)t.pair_cap ? 0u : s + 1;
     }
     atomicOr(t.overflow, PAIR_TABLE_FULL);
+    return -1;
 }
 
-// ---- the border slot (borders.hip): a pair's links, its saddle and the 64-bit sum of its link values in the four counters of a
-// PairTable<4> slot -- [0] links, [1] ~(bits of the smallest link value) under an atomic max: a zero-filled slot reads as
-// "no value yet" (bits 0xFFFFFFFF, above every float in [0, 1]), [2..3] the sum as ONE aligned 64-bit word (the counters start
-// on a 256-byte boundary and a slot is 16 bytes).  pair_add's probing and overflow rule, with these three updates at the slot.
-constexpr int BORDER_NV = 4;
-enum { BORDER_LINKS = 0, BORDER_SADDLE = 1, BORDER_SUM = 2 };
-
-__device__ __forceinline__ void pair_add_border(const PairTable<BORDER_NV> &t, unsigned long long key, unsigned links,
-                                                unsigned long long sum, unsigned saddle_bits)
+// v[0 .. NV) added to key's counters (v[0] always, the others where they are not zero)
+template <int NV>
+__device__ __forceinline__ void pair_add(const PairTable<NV> &t, unsigned long long key, const unsigned (&v)[NV])
 {
-    if (ld_agent(t.overflow) & PAIR_TABLE_FULL) return;
-    unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 32) % (unsigned)t.pair_cap;
-    for (int i = 0; i < t.pair_cap; ++i) {
-        unsigned long long cur = __hip_atomic_load(&t.keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0) {
-            cur = atomicCAS(&t.keys[s], 0ull, key);
-            if (cur == 0) cur = key;
-        }
-        if (cur == key) {
-            unsigned *c = t.cnt + BORDER_NV * (size_t)s;
-            atomicAdd(c + BORDER_LINKS, links);
-            atomicMax(c + BORDER_SADDLE, ~saddle_bits);
-            atomicAdd(reinterpret_cast<unsigned long long *>(c + BORDER_SUM), sum);
-            return;
-        }
-        s = s + 1 == (unsigned)t.pair_cap ? 0u : s + 1;
-    }
-    atomicOr(t.overflow, PAIR_TABLE_FULL);
+    const int s = pair_slot(t, key);
+    if (s < 0) return;
+    atomicAdd(&t.cnt[NV * (size_t)s], v[0]);
+#pragma unroll
+    for (int k = 1; k < NV; ++k)
+        if (v[k]) atomicAdd(&t.cnt[NV * (size_t)s + k], v[k]);
 }
 
 // used slots of a frame's table
@@ -117,15 +100,17 @@ struct PairWs {
     unsigned long long *keys;
     unsigned *cnt;
     long long *n_pairs;
+    int *tail;  // tail_ints values of the caller's behind the tables (borders.hip: the merge's parents)
 };
 
 template <int NV>
-static PairWs<NV> pairs_carve(Carver &cv, int B, int pair_cap)
+static PairWs<NV> pairs_carve(Carver &cv, int B, int pair_cap, size_t tail_ints)
 {
     PairWs<NV> ws;
     ws.keys = cv.take<unsigned long long>((size_t)B * pair_cap);
     ws.cnt = cv.take<unsigned>((size_t)B * pair_cap * NV);
     ws.n_pairs = cv.take<long long>((size_t)B);
+    ws.tail = cv.take<int>(tail_ints);
     return ws;
 }
 
@@ -148,6 +133,41 @@ static int pairs_finish(const PairWs<NV> &ws, const int32_t *overflow, int64_t *
     PCSEG_CHECK_LAUNCH();
     PCSEG_LAUNCH(pair_scan_kernel, dim3(1), dim3(64), 0, s, (const long long *)ws.n_pairs, (const int *)overflow, B,
                  (long long *)offsets, (long long *)totals);
+    PCSEG_CHECK_LAUNCH();
+    return PCSEG_OK;
+}
+
+// the used slots of frame blockIdx.x, in table order, as rows offsets[b] ..: emit(b, key, c, row) writes the row of a used
+// slot, c its Emit::NV counters (one block of 256 per frame walks the table in chunks of 256 slots)
+template <class Emit>
+__global__ void __launch_bounds__(256) pair_write_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ cnt,
+                                                          int pair_cap, const long long *__restrict__ offsets, Emit emit)
+{
+    __shared__ int wsum[4];
+    const int b = blockIdx.x;
+    const unsigned long long *k = keys + (int64_t)b * pair_cap;
+    const unsigned *v = cnt + (int64_t)b * pair_cap * Emit::NV;
+    long long row0 = offsets[b];
+    for (int base = 0; base < pair_cap; base += 256) {
+        const int i = base + (int)threadIdx.x;
+        const unsigned long long key = i < pair_cap ? k[i] : 0ull;
+        int tot;
+        const int pos = block_exclusive_scan<256>((int)(key != 0), &tot, wsum);
+        if (key) emit(b, key, v + Emit::NV * (size_t)i, row0 + pos);
+        row0 += tot;
+    }
+}
+
+// the second call: the caller's workspace carved again (tail_ints: as pairs_carve) and the rows written
+template <class Emit>
+static int pairs_write(const char *who, const void *workspace, size_t workspace_bytes, int B, int pair_cap, size_t tail_ints,
+                       const int64_t *offsets, Emit emit, pcseg_stream_t stream)
+{
+    Carver cv(const_cast<void *>(workspace), workspace_bytes);
+    const PairWs<Emit::NV> ws = pairs_carve<Emit::NV>(cv, B, pair_cap, tail_ints);
+    if (!cv.fits(who)) return PCSEG_ERR_WORKSPACE;
+    PCSEG_LAUNCH(pair_write_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const unsigned long long *)ws.keys,
+                 (const unsigned *)ws.cnt, pair_cap, (const long long *)offsets, emit);
     PCSEG_CHECK_LAUNCH();
     return PCSEG_OK;
 }

@@ -328,10 +328,7 @@ static int reconstruct(const char *who, const T *seed, const T *mask, T *out, in
     }
     Carver cv(workspace, workspace_bytes);
     const RecWorkspace ws = rec_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits(who)) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (max_rounds <= 0) max_rounds = (tilesX * tilesY + 64) * 64;  // (the watershed's cap)
     PCSEG_CHECK_HIP(hipMemsetAsync(ws.counters, 0, (size_t)((char *)ws.list[0] - (char *)ws.counters), s));
@@ -490,9 +487,7 @@ extern "C" {
 size_t pcseg_reconstruct_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    rec_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(rec_carve, B, H, W);
 }
 
 int pcseg_reconstruct_i32(const int32_t *seed, const int32_t *mask, int32_t *out, int32_t *flags, int B, int H, int W, int conn, int method,

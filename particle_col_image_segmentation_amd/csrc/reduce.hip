@@ -940,10 +940,7 @@ static int merge_groups_launch(const char *who, Source src, const int64_t *stats
 {
     Carver cv(workspace, workspace_bytes);
     const GroupTables ws = merge_groups_carve(cv, (size_t)B * n_masks, list_cap);
-    if (!cv.ok()) {
-        set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits(who)) return PCSEG_ERR_WORKSPACE;
     PCSEG_LAUNCH((merge_groups_kernel<Source, SUMS>), dim3(B, n_masks), dim3(MG_THREADS), 0, (hipStream_t)stream, src,
                  (const long long *)stats, (const int *)region_list, (const int *)n_list, slots, n_slots, (int *)group_of,
                  (int *)n_groups, (long long *)group_stats, ws, H, W, cap, list_cap);
@@ -1077,9 +1074,7 @@ int pcseg_region_sums2(const int32_t *labels_a, const uint8_t *cls, uint64_t sum
 size_t pcseg_merge_groups_workspace_bytes(int B, int list_cap)
 {
     if (B < 1 || list_cap < 1) return 0;
-    Carver cv(nullptr, 0);
-    merge_groups_carve(cv, (size_t)B, list_cap);
-    return cv.off;
+    return carved_bytes(merge_groups_carve, (size_t)B, list_cap);
 }
 
 int pcseg_merge_groups(const int32_t *dilated_labels, int keys_are_roots, const int64_t *stats, const int32_t *region_list,

@@ -430,9 +430,7 @@ extern "C" {
 size_t pcseg_label_parent_workspace_bytes(int B, int H, int W, int cap)
 {
     if (!check_shape(B, H, W) || cap < 1) return 0;
-    Carver cv(nullptr, 0);
-    label_parent_carve(cv, (size_t)B * cap);
-    return cv.off;
+    return carved_bytes(label_parent_carve, (size_t)B * cap);
 }
 
 int pcseg_label_parent(const int32_t *labels_a, const int32_t *labels_r, const int32_t *counts_r, const int64_t *stats_r,
@@ -447,10 +445,7 @@ int pcseg_label_parent(const int32_t *labels_a, const int32_t *labels_r, const i
     Carver cv(workspace, workspace_bytes);
     const LabelParentWs ws = label_parent_carve(cv, rows);
     int *cand = ws.cand, *spilled = ws.spilled, *spill_list = ws.spill_list, *n_spill = ws.n_spill;
-    if (!cv.ok()) {
-        set_error("label_parent: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("label_parent")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int grid = (int)((rows + 255) / 256 < 4096 ? (rows + 255) / 256 : 4096);
     PCSEG_LAUNCH(lp_clear_kernel, dim3(grid), dim3(256), 0, s, counts_r, B, cap, cand, spilled, n_spill, overflow);
@@ -476,9 +471,7 @@ int pcseg_label_parent(const int32_t *labels_a, const int32_t *labels_r, const i
 size_t pcseg_refined_workspace_bytes(int B, int cap)
 {
     if (B < 1 || cap < 1) return 0;
-    Carver cv(nullptr, 0);
-    refined_carve(cv, B, cap);
-    return cv.off;
+    return carved_bytes(refined_carve, B, cap);
 }
 
 static int refined_check(const pcseg_refined_inputs *in)
@@ -495,10 +488,7 @@ int pcseg_refined_layout(const pcseg_refined_inputs *in, int64_t *totals, void *
     Carver cv(workspace, workspace_bytes);
     const RefinedWs ws = refined_carve(cv, in->B, in->cap);
     long long *n_points = ws.n_points, *offsets = ws.offsets;
-    if (!cv.ok()) {
-        set_error("refined_layout: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("refined_layout")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     PCSEG_LAUNCH(rf_count_kernel, dim3(in->B), dim3(256), 0, s, *in, n_points);
     PCSEG_CHECK_LAUNCH();
@@ -522,10 +512,7 @@ int pcseg_refined_table_write(const pcseg_refined_inputs *in, const void *table_
     const RefinedWs ws = refined_carve(cv, in->B, in->cap);
     const long long *pt_offsets = ws.offsets;
     int *acc = ws.acc;
-    if (!tv.ok() || !cv.ok()) {
-        set_error("refined_table_write: workspace too small");
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!tv.fits("refined_table_write") || !cv.fits("refined_table_write")) return PCSEG_ERR_WORKSPACE;
     PCSEG_LAUNCH(rf_write_kernel, dim3(in->B), dim3(256), 0, (hipStream_t)stream, *in, tb, pt_offsets, acc, refined, resolution,
                  frames, xy, slot, id, (long long *)frame_offsets);
     PCSEG_CHECK_LAUNCH();

@@ -26,16 +26,13 @@ namespace pcseg {
 
 struct ShWorkspace {
     int *nrows;  // [B] min(counts[b], cap): the label bound of both passes (labels above it own no initialised row)
-    size_t off;
 };
 
-// the ONE layout of the workspace (null base: sizes only)
-static ShWorkspace shape_carve(void *workspace, size_t bytes, int B)
+// the ONE layout of the workspace
+static ShWorkspace shape_carve(Carver &cv, int B)
 {
-    Carver cv(workspace, bytes);
     ShWorkspace w;
     w.nrows = cv.take<int>((size_t)B);
-    w.off = cv.off;
     return w;
 }
 
@@ -292,18 +289,16 @@ extern "C" {
 size_t pcseg_region_shape_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    return shape_carve(nullptr, 0, B).off;
+    return carved_bytes(shape_carve, B);
 }
 
 int pcseg_region_shape(const int32_t *labels, const int32_t *counts, int64_t *shape_out, int32_t *overflow, int B, int H, int W,
                        int cap, void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
 {
     PCSEG_REQUIRE(labels && counts && shape_out && workspace && check_shape(B, H, W) && cap >= 1 && B <= 65535, "bad arguments");
-    ShWorkspace w = shape_carve(workspace, workspace_bytes, B);
-    if (w.off > workspace_bytes) {
-        set_error("region_shape: workspace too small (%zu < %zu)", workspace_bytes, w.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    const ShWorkspace w = shape_carve(cv, B);
+    if (!cv.fits("region_shape")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     long long *out = (long long *)shape_out;
     PCSEG_LAUNCH(shape_init_kernel, dim3((unsigned)(((int64_t)cap * 8 + 255) / 256), B), dim3(256), 0, s, out, counts, w.nrows,

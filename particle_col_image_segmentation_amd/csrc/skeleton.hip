@@ -68,17 +68,15 @@ struct SkWorkspace {
     uint32_t *rule;     // [2][8]
     int *last;          // [B] last sub-iteration that deleted a pixel of the frame
     int *ctr;           // pixels deleted, tiles listed
-    size_t off;
 };
 
 static int sk_wpr(int W) { return (W + 31) / 32; }
 static int sk_tx(int W) { return (W + SK_TW - 1) / SK_TW; }
 static int sk_ty(int H) { return (H + SK_TH - 1) / SK_TH; }
 
-// the ONE layout of the workspace (null base: sizes only)
-static SkWorkspace thin_carve(void *workspace, size_t bytes, int B, int H, int W)
+// the ONE layout of the workspace
+static SkWorkspace thin_carve(Carver &cv, int B, int H, int W)
 {
-    Carver cv(workspace, bytes);
     SkWorkspace w;
     const size_t tiles = (size_t)B * sk_tx(W) * sk_ty(H);
     w.bits[0] = cv.take<uint32_t>((size_t)B * H * sk_wpr(W));
@@ -89,9 +87,11 @@ static SkWorkspace thin_carve(void *workspace, size_t bytes, int B, int H, int W
     w.rule = cv.take<uint32_t>(16);
     w.last = cv.take<int>((size_t)B);
     w.ctr = cv.take<int>(2);
-    w.off = cv.off;
     return w;
 }
+
+// (pcseg_region_skeleton keeps nothing in its workspace: the size conventions of the other entries)
+static void skeleton_carve(Carver &cv) { cv.take<char>(1); }
 
 __global__ void __launch_bounds__(256) thin_rule_kernel(uint32_t *__restrict__ rule)
 {
@@ -385,18 +385,16 @@ extern "C" {
 size_t pcseg_thin_labels_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    return thin_carve(nullptr, 0, B, H, W).off;
+    return carved_bytes(thin_carve, B, H, W);
 }
 
 int pcseg_thin_labels(const int32_t *labels, uint16_t *peel, int32_t *iters, int B, int H, int W, int max_iter, void *workspace,
                       size_t workspace_bytes, pcseg_stream_t stream)
 {
     PCSEG_REQUIRE(labels && peel && iters && workspace && check_shape(B, H, W) && B <= 65535, "bad arguments");
-    SkWorkspace w = thin_carve(workspace, workspace_bytes, B, H, W);
-    if (w.off > workspace_bytes) {
-        set_error("thin_labels: workspace too small (%zu < %zu)", workspace_bytes, w.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    const SkWorkspace w = thin_carve(cv, B, H, W);
+    if (!cv.fits("thin_labels")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int wpr = sk_wpr(W), tx = sk_tx(W), ty = sk_ty(H);
     const int64_t total64 = (int64_t)B * tx * ty;
@@ -448,18 +446,16 @@ int pcseg_thin_labels(const int32_t *labels, uint16_t *peel, int32_t *iters, int
 size_t pcseg_region_skeleton_workspace_bytes(int B, int H, int W, int cap)
 {
     if (!check_shape(B, H, W) || cap < 1) return 0;
-    return align_up(1);  // (nothing is carved: the size conventions of the other entries)
+    return carved_bytes(skeleton_carve);
 }
 
 int pcseg_region_skeleton(const int32_t *labels, const uint16_t *peel, const int32_t *counts, int64_t *table, int B, int H, int W,
                           int cap, void *workspace, size_t workspace_bytes, pcseg_stream_t stream)
 {
     PCSEG_REQUIRE(labels && peel && counts && table && workspace && check_shape(B, H, W) && cap >= 1 && B <= 65535, "bad arguments");
-    const size_t need = pcseg_region_skeleton_workspace_bytes(B, H, W, cap);
-    if (need > workspace_bytes) {
-        set_error("region_skeleton: workspace too small (%zu < %zu)", workspace_bytes, need);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    skeleton_carve(cv);
+    if (!cv.fits("region_skeleton")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     long long *out = (long long *)table;
     PCSEG_LAUNCH(skeleton_init_kernel, dim3((unsigned)(((int64_t)cap * 6 + 255) / 256), B), dim3(256), 0, s, out, counts, cap);

@@ -346,12 +346,10 @@ struct SfWorkspace {
     uint32_t *mbits;
     int32_t *rowcnt, *rowarea, *rowoff;  // (rowcnt and rowarea are one allocation: zeroed together)
     double *thr;
-    size_t off;
 };
 
-static SfWorkspace sf_carve(void *workspace, size_t bytes, int B, int H, int W)
+static SfWorkspace sf_carve(Carver &cv, int B, int H, int W)
 {
-    Carver cv(workspace, bytes);
     SfWorkspace w;
     const size_t WW = (size_t)(W + 31) / 32;
     w.mbits = cv.take<uint32_t>((size_t)B * H * WW);
@@ -359,7 +357,6 @@ static SfWorkspace sf_carve(void *workspace, size_t bytes, int B, int H, int W)
     w.rowarea = w.rowcnt + (size_t)B * H;
     w.rowoff = cv.take<int32_t>((size_t)B * H);
     w.thr = cv.take<double>(MAX_HIST_BINS + 1);
-    w.off = cv.off;
     return w;
 }
 
@@ -368,19 +365,17 @@ struct SfShellWorkspace {
     int32_t *d2;
     long long *thr;
     void *edt;
-    size_t edt_bytes, off;
+    size_t edt_bytes;
 };
 
-static SfShellWorkspace sf_shell_carve(void *workspace, size_t bytes, int B, int H, int W)
+static SfShellWorkspace sf_shell_carve(Carver &cv, int B, int H, int W)
 {
-    Carver cv(workspace, bytes);
     SfShellWorkspace w;
     w.img = cv.take<uint8_t>((size_t)B * H * W);
     w.d2 = cv.take<int32_t>((size_t)B * H * W);
     w.thr = cv.take<long long>(MAX_HIST_BINS + 1);
     w.edt_bytes = pcseg_edt_workspace_bytes(B, H, W);
     w.edt = cv.take<uint8_t>(w.edt_bytes);
-    w.off = cv.off;
     return w;
 }
 
@@ -399,7 +394,7 @@ extern "C" {
 size_t pcseg_surface_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    return sf_carve(nullptr, 0, B, H, W).off;
+    return carved_bytes(sf_carve, B, H, W);
 }
 
 int pcseg_surface_points(const uint8_t *in, uint64_t value_bits, uint32_t *bits, int64_t *counts, int64_t *offsets, int64_t *area,
@@ -408,11 +403,9 @@ int pcseg_surface_points(const uint8_t *in, uint64_t value_bits, uint32_t *bits,
     PCSEG_REQUIRE(in && bits && counts && offsets && workspace && check_shape(B, H, W) && points_cap >= 0 &&
                       (points != nullptr || points_cap == 0),
                   "bad arguments");
-    SfWorkspace w = sf_carve(workspace, workspace_bytes, B, H, W);
-    if (w.off > workspace_bytes) {
-        set_error("surface_points: workspace too small (%zu < %zu)", workspace_bytes, w.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    const SfWorkspace w = sf_carve(cv, B, H, W);
+    if (!cv.fits("surface_points")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int WW = (W + 31) / 32;
     const int64_t rows = (int64_t)B * H;
@@ -446,11 +439,9 @@ int pcseg_surface_distances(const double *rc, const int32_t *slot, const int64_t
     PCSEG_REQUIRE(rc && frame_offsets && bits && dist && nearest && workspace && check_shape(B, H, W) && n_points >= 0 &&
                       n_points < ((int64_t)1 << 31) && scale > 0.0 && std::isfinite(scale) && edges_ok,
                   "bad arguments");
-    SfWorkspace w = sf_carve(workspace, workspace_bytes, B, H, W);
-    if (w.off > workspace_bytes) {
-        set_error("surface_distances: workspace too small (%zu < %zu)", workspace_bytes, w.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    const SfWorkspace w = sf_carve(cv, B, H, W);
+    if (!cv.fits("surface_distances")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int m = n_edges > 0 ? n_edges - 1 : 0;
     if (n_edges > 0) {
@@ -486,7 +477,7 @@ int pcseg_surface_thresholds(const double *edges, int n_edges, double scale, int
 size_t pcseg_surface_shells_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    return sf_shell_carve(nullptr, 0, B, H, W).off;
+    return carved_bytes(sf_shell_carve, B, H, W);
 }
 
 int pcseg_surface_shells(const uint32_t *bits, const int64_t *counts, const uint8_t *mask, int B, int H, int W, double scale,
@@ -496,11 +487,9 @@ int pcseg_surface_shells(const uint32_t *bits, const int64_t *counts, const uint
     PCSEG_REQUIRE(bits && counts && mask && shells && workspace && check_shape(B, H, W) && B <= 65535 && scale > 0.0 &&
                       std::isfinite(scale) && hist_edges_ok(edges, n_edges),
                   "bad arguments");
-    SfShellWorkspace w = sf_shell_carve(workspace, workspace_bytes, B, H, W);
-    if (w.off > workspace_bytes) {
-        set_error("surface_shells: workspace too small (%zu < %zu)", workspace_bytes, w.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    Carver cv(workspace, workspace_bytes);
+    const SfShellWorkspace w = sf_shell_carve(cv, B, H, W);
+    if (!cv.fits("surface_shells")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int m = n_edges - 1, WW = (W + 31) / 32, HW = H * W;
     const int64_t rows = (int64_t)B * H;

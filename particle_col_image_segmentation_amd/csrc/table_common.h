@@ -155,10 +155,7 @@ inline int pack_cells(const char *who, const double *cells, int ncol, const uint
 {
     Carver cv(const_cast<void *>(table_workspace), table_workspace_bytes);
     const TableOffsets to = table_offsets(cv, B);
-    if (!cv.ok()) {
-        set_error("%s: workspace too small (%zu < %zu)", who, table_workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits(who)) return PCSEG_ERR_WORKSPACE;
     PCSEG_LAUNCH(pack_cells_kernel<XY1>, dim3(B), dim3(256), 0, (hipStream_t)stream, cells, ncol, to, ClassSlots(class_slot), B, pt, slot,
                  id, frame_offsets);
     PCSEG_CHECK_LAUNCH();

@@ -261,9 +261,7 @@ extern "C" {
 size_t pcseg_table_workspace_bytes(int B, int cap)
 {
     if (B < 1 || cap < 1) return 0;
-    Carver cv(nullptr, 0);
-    table_carve(cv, B, cap);
-    return cv.off;
+    return carved_bytes(table_carve, B, cap);
 }
 
 static int table_check(const pcseg_table_inputs *in)
@@ -279,10 +277,7 @@ int pcseg_table_layout(const pcseg_table_inputs *in, int64_t *totals, void *work
     PCSEG_REQUIRE(table_check(in) && totals && workspace, "bad arguments");
     Carver cv(workspace, workspace_bytes);
     const TableOffsets to = table_offsets(cv, in->B);
-    if (!cv.ok()) {
-        set_error("table_layout: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("table_layout")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     // (the one writer of the workspace's head)
     PCSEG_LAUNCH(table_count_kernel, dim3(in->B), dim3(256), 0, s, *in, const_cast<long long *>(to.counts));
@@ -299,10 +294,7 @@ int pcseg_table_write(const pcseg_table_inputs *in, double *rois, double *cells,
     PCSEG_REQUIRE(table_check(in) && rois && cells && groups && frames && workspace, "bad arguments");
     Carver cv(workspace, workspace_bytes);
     const TableWs ws = table_carve(cv, in->B, in->cap);
-    if (!cv.ok()) {
-        set_error("table_write: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("table_write")) return PCSEG_ERR_WORKSPACE;
     PCSEG_LAUNCH(table_write_kernel, dim3(in->B), dim3(256), 0, (hipStream_t)stream, *in, ws.to.offsets, rois, cells, groups,
                  (long long *)frames, ws.own, ws.comb);
     PCSEG_CHECK_LAUNCH();
@@ -316,10 +308,7 @@ int pcseg_cell_distances(const double *cells, int64_t n_rows, int ncol, const ui
                   "bad arguments");
     Carver cv(const_cast<void *>(workspace), workspace_bytes);
     const TableOffsets to = table_offsets(cv, B);
-    if (!cv.ok()) {
-        set_error("cell_distances: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("cell_distances")) return PCSEG_ERR_WORKSPACE;
     PCSEG_LAUNCH(cell_distance_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, cells, ncol, to, ClassSlots(class_slot),
                  size / raster, dist);
     PCSEG_CHECK_LAUNCH();

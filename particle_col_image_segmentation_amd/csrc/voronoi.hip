@@ -19,7 +19,8 @@
 //                        neighbouring lanes added up first, then into a per-frame open-addressing table keyed by (a, b) (64-bit
 //                        compare-and-swap, bounded probing, integer atomics); a full table raises the frame's flag.  The table,
 //                        its probing rule and the count / scan kernels behind offsets and totals are pair_table.h's
-//   terr_pairs_write_kernel   the compacted rows (and the number of distinct partners per ROI and type slot)
+//   pair_write_kernel    (pair_table.h, with TerrEmit) the compacted rows (and the number of distinct partners per ROI and type
+//                        slot).  Was terr_pairs_write_kernel
 #include <type_traits>
 
 #include "column_pass.h"
@@ -367,48 +368,37 @@ __global__ void __launch_bounds__(256) terr_pairs_kernel(const int *__restrict__
     }
 }
 
-// the used slots of frame b, in table order, as rows offsets[b] ..: key, frame position, (border, contact); with slot_of also
+// a used slot as the row (key, frame position, (border, contact)) of pair_table.h's writer; with `degree` also
 // degree (B, cap, 2 K) += 1 at [a][slot of b] and [b][slot of a], and at K + slot where the pair has contact
-__global__ void __launch_bounds__(256) terr_pairs_write_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ cnt,
-                                                                int pair_cap, const long long *__restrict__ offsets,
-                                                                const uint8_t *__restrict__ slot_of, int cap, int K,
-                                                                long long *__restrict__ key_out, int *__restrict__ frame_out,
-                                                                int *__restrict__ cnt_out, int *__restrict__ degree)
-{
-    __shared__ int wsum[4];
-    const int b = blockIdx.x;
-    const unsigned long long *k = keys + (int64_t)b * pair_cap;
-    const unsigned *v = cnt + (int64_t)b * pair_cap * 2;
-    long long row0 = offsets[b];
-    for (int base = 0; base < pair_cap; base += 256) {
-        const int i = base + (int)threadIdx.x;
-        const unsigned long long key = i < pair_cap ? k[i] : 0ull;
-        int tot;
-        const int pos = block_exclusive_scan<256>((int)(key != 0), &tot, wsum);
-        if (key) {
-            const long long row = row0 + pos;
-            const unsigned border = v[2 * (size_t)i], contact = v[2 * (size_t)i + 1];
-            key_out[row] = (long long)key;
-            frame_out[row] = b;
-            cnt_out[2 * row] = (int)border;
-            cnt_out[2 * row + 1] = (int)contact;
-            const unsigned la = (unsigned)(key >> 32), lb = (unsigned)key;
-            if (degree && la >= 1 && lb >= 1 && la <= (unsigned)cap && lb <= (unsigned)cap) {
-                const int sa = slot_of[(int64_t)b * cap + la - 1], sb = slot_of[(int64_t)b * cap + lb - 1];
-                int *da = degree + ((int64_t)b * cap + la - 1) * 2 * K, *db = degree + ((int64_t)b * cap + lb - 1) * 2 * K;
-                if (sb < K) {
-                    atomicAdd(&da[sb], 1);
-                    if (contact) atomicAdd(&da[K + sb], 1);
-                }
-                if (sa < K) {
-                    atomicAdd(&db[sa], 1);
-                    if (contact) atomicAdd(&db[K + sa], 1);
-                }
+struct TerrEmit {
+    static constexpr int NV = TERR_NV;
+    const uint8_t *slot_of;
+    int cap, K;
+    long long *key_out;
+    int *frame_out, *cnt_out, *degree;
+    __device__ __forceinline__ void operator()(int b, unsigned long long key, const unsigned *c, long long row) const
+    {
+        const unsigned border = c[0], contact = c[1];
+        key_out[row] = (long long)key;
+        frame_out[row] = b;
+        cnt_out[2 * row] = (int)border;
+        cnt_out[2 * row + 1] = (int)contact;
+        const unsigned la = (unsigned)(key >> 32), lb = (unsigned)key;
+        // (& not &&: one test and one branch per slot; with && the writer's loop took a second one)
+        if ((degree != nullptr) & (la >= 1) & (lb >= 1) & (la <= (unsigned)cap) & (lb <= (unsigned)cap)) {
+            const int sa = slot_of[(int64_t)b * cap + la - 1], sb = slot_of[(int64_t)b * cap + lb - 1];
+            int *da = degree + ((int64_t)b * cap + la - 1) * 2 * K, *db = degree + ((int64_t)b * cap + lb - 1) * 2 * K;
+            if (sb < K) {
+                atomicAdd(&da[sb], 1);
+                if (contact) atomicAdd(&da[K + sb], 1);
+            }
+            if (sa < K) {
+                atomicAdd(&db[sa], 1);
+                if (contact) atomicAdd(&db[K + sa], 1);
             }
         }
-        row0 += tot;
     }
-}
+};
 
 static inline int reach_arg(int64_t R2) { return (R2 < 0 || R2 > 0x7FFFFFFF) ? 0x7FFFFFFF : (int)R2; }
 
@@ -421,9 +411,7 @@ extern "C" {
 size_t pcseg_nearest_label_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    col_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(col_carve, B, H, W);
 }
 
 int pcseg_nearest_label_i32(const int32_t *labels, const uint8_t *sel, int cap, int32_t *d2, int32_t *near, int32_t *site, int B,
@@ -432,10 +420,7 @@ int pcseg_nearest_label_i32(const int32_t *labels, const uint8_t *sel, int cap, 
     PCSEG_REQUIRE(labels && d2 && near && workspace && check_shape(B, H, W) && cap >= 1 && B <= 65535, "bad arguments");
     Carver cv(workspace, workspace_bytes);
     const ColWs ws = col_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("nearest_label_i32: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("nearest_label_i32")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     PCSEG_CHECK_HIP(hipMemsetAsync(ws.any, 0, sizeof(int) * B, s));
     PCSEG_LAUNCH(vor_bits_kernel, dim3((W + 255) / 256, ws.nch, B), dim3(256), 0, s, labels, sel, cap, ws.bits, H, W, ws.nch);
@@ -488,9 +473,7 @@ int pcseg_territory_reduce(const int32_t *near, const int32_t *d2, const uint8_t
 size_t pcseg_territory_pairs_workspace_bytes(int B, int pair_cap)
 {
     if (B < 1 || pair_cap < 1) return 0;
-    Carver cv(nullptr, 0);
-    pairs_carve<TERR_NV>(cv, B, pair_cap);
-    return cv.off;
+    return carved_bytes(pairs_carve<TERR_NV>, B, pair_cap, 0);
 }
 
 int pcseg_territory_pairs(const int32_t *near, const int32_t *d2, int64_t R2, int pair_cap, int32_t *overflow, int64_t *offsets,
@@ -499,11 +482,8 @@ int pcseg_territory_pairs(const int32_t *near, const int32_t *d2, int64_t R2, in
     PCSEG_REQUIRE(near && d2 && overflow && offsets && totals && workspace && check_shape(B, H, W) && pair_cap >= 1 && B <= 65535,
                   "bad arguments");
     Carver cv(workspace, workspace_bytes);
-    const PairWs<TERR_NV> ws = pairs_carve<TERR_NV>(cv, B, pair_cap);
-    if (!cv.ok()) {
-        set_error("territory_pairs: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    const PairWs<TERR_NV> ws = pairs_carve<TERR_NV>(cv, B, pair_cap, 0);
+    if (!cv.fits("territory_pairs")) return PCSEG_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (const int rc = pairs_begin(ws, overflow, B, pair_cap, s)) return rc;
     PCSEG_LAUNCH(terr_pairs_kernel, dim3((W + 255) / 256, (H + RUN_ROWS - 1) / RUN_ROWS, B), dim3(256), 0, s, near, d2, reach_arg(R2), H,
@@ -518,17 +498,8 @@ int pcseg_territory_pairs_write(int pair_cap, const int64_t *offsets, const uint
 {
     PCSEG_REQUIRE(offsets && key && frame && counts && workspace && B >= 1 && B <= 65535 && pair_cap >= 1, "bad arguments");
     PCSEG_REQUIRE(!degree || (slot_of && cap >= 1 && n_types >= 1 && n_types <= 4), "degree needs slot_of, cap and 1..4 type slots");
-    Carver cv(const_cast<void *>(workspace), workspace_bytes);
-    const PairWs<TERR_NV> ws = pairs_carve<TERR_NV>(cv, B, pair_cap);
-    if (!cv.ok()) {
-        set_error("territory_pairs_write: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
-    PCSEG_LAUNCH(terr_pairs_write_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const unsigned long long *)ws.keys,
-                 (const unsigned *)ws.cnt, pair_cap, (const long long *)offsets, slot_of, cap, n_types, (long long *)key, frame, counts,
-                 degree);
-    PCSEG_CHECK_LAUNCH();
-    return PCSEG_OK;
+    return pairs_write("territory_pairs_write", workspace, workspace_bytes, B, pair_cap, 0, offsets,
+                       TerrEmit{slot_of, cap, n_types, (long long *)key, frame, counts, degree}, stream);
 }
 
 }  // extern "C"

@@ -2023,9 +2023,7 @@ void pcseg_watershed_counters(int64_t *out, int reset)
 size_t pcseg_watershed_workspace_bytes(int B, int H, int W)
 {
     if (!check_shape(B, H, W)) return 0;
-    Carver cv(nullptr, 0);
-    ws_carve(cv, B, H, W);
-    return cv.off;
+    return carved_bytes(ws_carve, B, H, W);
 }
 
 // No host round trip anywhere: the fixed points run a fixed number of grid rounds and finish in a per-frame tail kernel,
@@ -2044,10 +2042,7 @@ int pcseg_watershed4_f32(const float *img, int64_t frame_stride, const int32_t *
     if (frame_stride == 0) frame_stride = (int64_t)H * W;
     Carver cv(workspace, workspace_bytes);
     const WsWorkspace ws = ws_carve(cv, B, H, W);
-    if (!cv.ok()) {
-        set_error("watershed: workspace too small (%zu < %zu)", workspace_bytes, cv.off);
-        return PCSEG_ERR_WORKSPACE;
-    }
+    if (!cv.fits("watershed")) return PCSEG_ERR_WORKSPACE;
     const bool vec = (W & 3) == 0 && W >= 4 && (frame_stride & 3) == 0 && (((uintptr_t)img | (uintptr_t)markers | (uintptr_t)out |
                                                                              (uintptr_t)ws.val | (uintptr_t)ws.L) & 15) == 0 &&
                      ((uintptr_t)mask & 3) == 0;

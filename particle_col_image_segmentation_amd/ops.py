@@ -1207,6 +1207,44 @@ def label_parent(labels_a, labels_r, counts_r, cls_a=None, cap=None, stats_r=Non
     return out + (n_spilled,) if return_spilled else out
 
 
+def _pair_fill(entry, head, shape, dev, nbytes):
+    """The first call of a per-frame pair table (csrc/pair_table.h), ``pcseg_<entry>(*head, overflow, offsets, totals, B, H, W,
+    workspace, nbytes, stream)``: the workspace of ``nbytes`` (the table's size query), ``overflow`` int32 (B,), ``offsets``
+    int64 (B + 1,) and ``totals`` int64 (2,) = (rows, frames whose table was full).  Nothing is read back.  Returns the state
+    the second calls need."""
+    B = shape[0]
+    st = {"B": B, "nbytes": nbytes, "ws": _ws(nbytes, dev), "overflow": torch.empty((B,), dtype=torch.int32, device=dev),
+          "offsets": torch.empty((B + 1,), dtype=torch.int64, device=dev), "totals": torch.empty((2,), dtype=torch.int64, device=dev)}
+    _lib.check(getattr(_lib.load(), "pcseg_" + entry)(*head, _ptr(st["overflow"]), _ptr(st["offsets"]), _ptr(st["totals"]), *shape,
+                                                      _ptr(st["ws"]), nbytes, _stream()), entry)
+    return st
+
+
+def _pair_rows(st, columns, write):
+    """The second call on :func:`_pair_fill`'s state: the one host read (``totals``), the row buffers ``key`` int64, ``frame``
+    int32 and one per (name, dtype, trailing shape) of ``columns`` -- each with a spare row: never a null pointer --,
+    ``write(offsets, buffers, workspace, nbytes)`` with the buffers' pointers by name, and the rows in (frame, key) order.
+    Returns ``(rows, n_overflow, sorted)``: ``sorted`` holds ``key``, ``frame`` (int64) and the columns."""
+    dev = st["totals"].device
+    rows, n_over = (int(v) for v in st["totals"].cpu())
+    buf = {name: torch.empty((rows + 1,) + tuple(shape), dtype=dtype, device=dev)
+           for name, dtype, shape in (("key", torch.int64, ()), ("frame", torch.int32, ())) + tuple(columns)}
+    write(_ptr(st["offsets"]), {name: _ptr(t) for name, t in buf.items()}, _ptr(st["ws"]), st["nbytes"])
+    # (frame, key) order: the rows of a frame are contiguous already, in table order -- two stable sorts, plumbing; the
+    # frames' offsets hold for the sorted rows too
+    key, frame = buf["key"][:rows], buf["frame"][:rows].to(torch.int64)
+    order = torch.sort(key, stable=True)[1]
+    order = order[torch.sort(frame[order], stable=True)[1]]
+    out = {name: t[:rows][order] for name, t in buf.items()}
+    out["frame"] = frame[order]
+    return rows, n_over, out
+
+
+def _pair_ab(key):
+    """The two labels of a pair key."""
+    return key >> 32, key & 0xFFFFFFFF
+
+
 def _contingency_rows(labels_t, labels_s, cap_t, cap_s, pair_cap):
     """The two calls of the contingency table and the (frame, t, s) sort of its rows."""
     lt, ls = _label_batch(labels_t, "labels_t"), _label_batch(labels_s, "labels_s")
@@ -1223,26 +1261,13 @@ def _contingency_rows(labels_t, labels_s, cap_t, cap_s, pair_cap):
         pair_cap = 1 << (4 * (cap_t + cap_s) + 64 - 1).bit_length()
     pair_cap = int(pair_cap)
     lib = _lib.load()
-    nbytes = lib.pcseg_contingency_workspace_bytes(B, pair_cap)
-    ws = _ws(nbytes, dev)
-    overflow = torch.empty((B,), dtype=torch.int32, device=dev)
-    offsets = torch.empty((B + 1,), dtype=torch.int64, device=dev)
-    totals = torch.empty((2,), dtype=torch.int64, device=dev)
-    _lib.check(lib.pcseg_label_contingency(_ptr(lt), _ptr(ls), cap_t, cap_s, pair_cap, _ptr(overflow), _ptr(offsets), _ptr(totals),
-                                           B, H, W, _ptr(ws), nbytes, _stream()), "label_contingency")
-    rows, n_over = (int(v) for v in totals.cpu())
-    key = torch.empty((rows + 1,), dtype=torch.int64, device=dev)  # (a spare row: never a null pointer)
-    frame = torch.empty((rows + 1,), dtype=torch.int32, device=dev)
-    n = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
-    _lib.check(lib.pcseg_contingency_write(pair_cap, _ptr(offsets), _ptr(key), _ptr(frame), _ptr(n), B, _ptr(ws), nbytes, _stream()),
-               "contingency_write")
-    # (frame, t, s) order: the rows of a frame are contiguous already, in table order -- two stable sorts, plumbing; the
-    # frames' offsets hold for the sorted rows too
-    key, frame, n = key[:rows], frame[:rows].to(torch.int64), n[:rows]
-    order = torch.sort(key, stable=True)[1]
-    order = order[torch.sort(frame[order], stable=True)[1]]
-    return {"key": key[order].contiguous(), "frame": frame[order], "n": n[order].contiguous(), "offsets": offsets, "rows": rows,
-            "overflow": overflow, "n_overflow": n_over, "cap_t": cap_t, "cap_s": cap_s, "pair_cap": pair_cap, "shape": (B, H, W)}
+    st = _pair_fill("label_contingency", (_ptr(lt), _ptr(ls), cap_t, cap_s, pair_cap), (B, H, W), dev,
+                    lib.pcseg_contingency_workspace_bytes(B, pair_cap))
+    rows, n_over, r = _pair_rows(st, (("n", torch.int64, ()),), lambda offsets, out, ws, nbytes: _lib.check(
+        lib.pcseg_contingency_write(pair_cap, offsets, out["key"], out["frame"], out["n"], B, ws, nbytes, _stream()),
+        "contingency_write"))
+    return {"key": r["key"], "frame": r["frame"], "n": r["n"], "offsets": st["offsets"], "rows": rows, "overflow": st["overflow"],
+            "n_overflow": n_over, "cap_t": cap_t, "cap_s": cap_s, "pair_cap": pair_cap, "shape": (B, H, W)}
 
 
 def _agreement_match(rows, thresholds):
@@ -1278,8 +1303,8 @@ def label_contingency(labels_t, labels_s, cap_t=None, cap_s=None, pair_cap=None)
     (read back with the row total, the one host read between the two calls)."""
     rows = _contingency_rows(labels_t, labels_s, cap_t, cap_s, pair_cap)
     m = _agreement_match(rows, ())
-    key = rows["key"]
-    return {"frame": rows["frame"], "t": key >> 32, "s": key & 0xFFFFFFFF, "n": rows["n"], "area_t": m["area_t"], "area_s": m["area_s"],
+    t, s = _pair_ab(rows["key"])
+    return {"frame": rows["frame"], "t": t, "s": s, "n": rows["n"], "area_t": m["area_t"], "area_s": m["area_s"],
             "overflow": rows["overflow"], "n_overflow": rows["n_overflow"], "pair_cap": rows["pair_cap"]}
 
 
@@ -1430,19 +1455,13 @@ def _border_fill(labels, strength, conn, cap, pair_cap):
     if conn not in (4, 8):
         raise ValueError("conn must be 4 or 8")
     B, H, W = labels.shape
-    dev = labels.device
     if cap is None:
         cap = int(labels.max().item())
     cap = max(int(cap), 1)
     pair_cap = 4 * cap if pair_cap is None else int(pair_cap)
-    lib = _lib.load()
-    nbytes = lib.pcseg_label_borders_workspace_bytes(B, pair_cap, cap)
-    st = {"labels": labels, "B": B, "H": H, "W": W, "cap": cap, "pair_cap": pair_cap, "nbytes": nbytes, "ws": _ws(nbytes, dev),
-          "overflow": torch.empty((B,), dtype=torch.int32, device=dev), "offsets": torch.empty((B + 1,), dtype=torch.int64, device=dev),
-          "totals": torch.empty((2,), dtype=torch.int64, device=dev)}
-    _lib.check(lib.pcseg_label_borders(_ptr(labels), _ptr(strength), fstride, cap, conn, pair_cap, _ptr(st["overflow"]),
-                                       _ptr(st["offsets"]), _ptr(st["totals"]), B, H, W, _ptr(st["ws"]), nbytes, _stream()),
-               "label_borders")
+    st = _pair_fill("label_borders", (_ptr(labels), _ptr(strength), fstride, cap, conn, pair_cap), (B, H, W), labels.device,
+                    _lib.load().pcseg_label_borders_workspace_bytes(B, pair_cap, cap))
+    st.update(labels=labels, cap=cap, pair_cap=pair_cap)
     return st
 
 
@@ -1461,24 +1480,15 @@ def label_borders(labels, strength, conn=8, cap=None, pair_cap=None):
     ``4 * cap`` -- a region adjacency graph is planar for ``conn`` = 4 and nearly so for 8: about 3 pairs per label -- and a
     slot takes 24 bytes: 96 ``cap`` bytes of table per frame."""
     st = _border_fill(labels, strength, conn, cap, pair_cap)
-    dev = st["labels"].device
-    n, n_over = (int(v) for v in st["totals"].cpu())
-    key = torch.empty((n + 1,), dtype=torch.int64, device=dev)  # (a spare row: never a null pointer)
-    frame = torch.empty((n + 1,), dtype=torch.int32, device=dev)
-    links = torch.empty((n + 1,), dtype=torch.int32, device=dev)
-    total = torch.empty((n + 1,), dtype=torch.int64, device=dev)
-    saddle = torch.empty((n + 1,), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().pcseg_label_borders_write(st["pair_cap"], st["cap"], _ptr(st["offsets"]), _ptr(key), _ptr(frame), _ptr(links),
-                                                     _ptr(total), _ptr(saddle), st["B"], _ptr(st["ws"]), st["nbytes"], _stream()),
-               "label_borders_write")
-    # (frame, a, b) order: the rows of a frame are contiguous already, in table order -- two stable sorts, plumbing
-    key, frame = key[:n], frame[:n].to(torch.int64)
-    order = torch.sort(key, stable=True)[1]
-    order = order[torch.sort(frame[order], stable=True)[1]]
-    key, links, total = key[order], links[:n][order].to(torch.int64), total[:n][order]
+    _, n_over, r = _pair_rows(st, (("links", torch.int32, ()), ("sum", torch.int64, ()), ("saddle", torch.float32, ())),
+                              lambda offsets, out, ws, nbytes: _lib.check(_lib.load().pcseg_label_borders_write(
+                                  st["pair_cap"], st["cap"], offsets, out["key"], out["frame"], out["links"], out["sum"], out["saddle"],
+                                  st["B"], ws, nbytes, _stream()), "label_borders_write"))
+    a, b = _pair_ab(r["key"])
+    links, total = r["links"].to(torch.int64), r["sum"]
     mean = total.to(torch.float64) / (links.to(torch.float64) * 4294967296.0)
-    return {"frame": frame[order], "a": key >> 32, "b": key & 0xFFFFFFFF, "links": links, "sum": total, "saddle": saddle[:n][order],
-            "mean": mean, "overflow": st["overflow"], "n_overflow": n_over, "pair_cap": st["pair_cap"]}
+    return {"frame": r["frame"], "a": a, "b": b, "links": links, "sum": total, "saddle": r["saddle"], "mean": mean,
+            "overflow": st["overflow"], "n_overflow": n_over, "pair_cap": st["pair_cap"]}
 
 
 def relabel_map(labels, label_map):
@@ -1956,17 +1966,8 @@ def territory_pairs(near, d2, r2=-1, pair_cap=None, slot_of=None, n_types=0):
         pair_cap = 8 * (slot_of.shape[1] if slot_of is not None else max(int(near.max().item()), 1))
     pair_cap = int(pair_cap)
     lib = _lib.load()
-    nbytes = lib.pcseg_territory_pairs_workspace_bytes(B, pair_cap)
-    ws = _ws(nbytes, dev)
-    overflow = torch.empty((B,), dtype=torch.int32, device=dev)
-    offsets = torch.empty((B + 1,), dtype=torch.int64, device=dev)
-    totals = torch.empty((2,), dtype=torch.int64, device=dev)
-    _lib.check(lib.pcseg_territory_pairs(_ptr(near), _ptr(d2), int(r2), pair_cap, _ptr(overflow), _ptr(offsets), _ptr(totals), B, H,
-                                         W, _ptr(ws), nbytes, _stream()), "territory_pairs")
-    n, n_over = (int(v) for v in totals.cpu())
-    key = torch.empty((n + 1,), dtype=torch.int64, device=dev)  # (a spare row: never a null pointer)
-    frame = torch.empty((n + 1,), dtype=torch.int32, device=dev)
-    counts = torch.empty((n + 1, 2), dtype=torch.int32, device=dev)
+    st = _pair_fill("territory_pairs", (_ptr(near), _ptr(d2), int(r2), pair_cap), (B, H, W), dev,
+                    lib.pcseg_territory_pairs_workspace_bytes(B, pair_cap))
     degree, cap, K = None, 0, int(n_types)
     if slot_of is not None:
         slot_of = _req(slot_of, torch.uint8, 2)
@@ -1974,15 +1975,13 @@ def territory_pairs(near, d2, r2=-1, pair_cap=None, slot_of=None, n_types=0):
         if slot_of.shape[0] != B or not 1 <= K <= 4:
             raise ValueError("slot_of must be (B, cap), with 1 to 4 type slots")
         degree = torch.zeros((B, cap, 2 * K), dtype=torch.int32, device=dev)
-    _lib.check(lib.pcseg_territory_pairs_write(pair_cap, _ptr(offsets), _ptr(slot_of), cap, K, _ptr(key), _ptr(frame), _ptr(counts),
-                                               _ptr(degree), B, _ptr(ws), nbytes, _stream()), "territory_pairs_write")
-    # (frame, a, b) order: the rows of a frame are contiguous already, in table order -- two stable sorts, plumbing
-    key, frame, counts = key[:n], frame[:n].to(torch.int64), counts[:n].to(torch.int64)
-    order = torch.sort(key, stable=True)[1]
-    order = order[torch.sort(frame[order], stable=True)[1]]
-    key = key[order]
-    return {"frame": frame[order], "a": key >> 32, "b": key & 0xFFFFFFFF, "border": counts[order, 0], "contact": counts[order, 1],
-            "overflow": overflow, "n_overflow": n_over, "degree": degree}
+    _, n_over, r = _pair_rows(st, (("counts", torch.int32, (2,)),), lambda offsets, out, ws, nbytes: _lib.check(
+        lib.pcseg_territory_pairs_write(pair_cap, offsets, _ptr(slot_of), cap, K, out["key"], out["frame"], out["counts"], _ptr(degree),
+                                        B, ws, nbytes, _stream()), "territory_pairs_write"))
+    a, b = _pair_ab(r["key"])
+    counts = r["counts"].to(torch.int64)
+    return {"frame": r["frame"], "a": a, "b": b, "border": counts[:, 0].contiguous(), "contact": counts[:, 1].contiguous(),
+            "overflow": st["overflow"], "n_overflow": n_over, "degree": degree}
 
 
 def territory_rows(labels, live, slot_of, frame_ids, scale, n_types, r2=-1, mask=None, check=False, pair_cap=None):

@@ -44,15 +44,32 @@ def test_workspace_queries_and_argument_errors(lib):
 
 
 def test_workspace_size_is_what_the_entry_point_carves(lib):
-    """A size query and its entry point run the same carve function: one byte less than the query's answer is refused.
-    Only entry points whose argument and workspace checks come before their first device call are listed (the pointers are
-    never dereferenced); they are never called with `need` bytes."""
+    """A size query and its entry point run the same carve function: one byte less than the query's answer is refused, with
+    PCSEG_ERR_WORKSPACE and the message "<who>: workspace too small (<given> < <needed>)".  Every entry point whose argument
+    and workspace checks come before its first device call is listed (the device pointers are never dereferenced; what an
+    entry reads on the host -- bin edges, list slots, the input structs -- is real); they are never called with `need` bytes.
+    Left out: pcseg_classmap_label_f32, which answers a short workspace as an argument error (-1) -- every other entry point
+    that takes a workspace is here."""
     import ctypes
     from particle_col_image_segmentation_amd import _lib
     ERR_WORKSPACE = -3
-    p, q = ctypes.c_void_p(4096), ctypes.c_void_p(8192)
+    p, q, r = ctypes.c_void_p(4096), ctypes.c_void_p(8192), ctypes.c_void_p(12288)
     B, H, W, cap = 2, 96, 80, 16
     shape = (B, H, W)
+    pc, npt, K = 64, 100, 2  # pair_cap; points and type slots of the point tables
+    edges = (ctypes.c_double * 3)(0.0, 1.0, 2.0)
+    slots = (ctypes.c_int32 * 4)(0, 0, 0, 0)
+
+    def inputs(cls):  # a table / refined input struct with every pointer set
+        t = cls()
+        for name, kind in cls._fields_:
+            if kind is ctypes.c_void_p:
+                setattr(t, name, 4096)
+        t.B, t.cap = B, cap
+        return t
+
+    tin, rin = inputs(_lib.TableInputs), inputs(_lib.RefinedInputs)
+    tref, rref = ctypes.byref(tin), ctypes.byref(rin)
     cases = [
         ("ccl", shape, "pcseg_ccl8_equal_u8", lambda ws, n: (p, p, p, B, H, W, ws, n, None)),
         ("ccl", shape, "pcseg_ccl8_bool", lambda ws, n: (p, p, p, B, H, W, ws, n, None)),
@@ -71,13 +88,65 @@ def test_workspace_size_is_what_the_entry_point_carves(lib):
         ("watershed", shape, "pcseg_watershed4_f32", lambda ws, n: (p, 0, p, p, p, p, B, H, W, 0, ws, n, None)),
         ("merge_groups", (B, cap), "pcseg_merge_groups", lambda ws, n: (p, 0, p, p, p, p, p, B, H, W, cap, cap, ws, n, None)),
         ("merge_groups", (B, cap), "pcseg_merge_groups_runs", lambda ws, n: (p, p, p, p, p, p, p, B, H, W, cap, cap, ws, n, None)),
+        ("merge_groups", (B, cap), "pcseg_merge_groups_fused", lambda ws, n: (p, p, p, p, p, 0, 1, p, p, p, B, H, W, cap, ws, n, None)),
+        ("merge_groups", (3 * B, cap), "pcseg_merge_groups_fused_multi",
+         lambda ws, n: (p, p, p, p, p, slots, 3, 1, p, p, p, B, H, W, cap, ws, n, None)),
+        # the pair tables: both calls of each, and the merge on the border table
+        ("territory_pairs", (B, pc), "pcseg_territory_pairs", lambda ws, n: (p, p, -1, pc, p, p, p, B, H, W, ws, n, None)),
+        ("territory_pairs", (B, pc), "pcseg_territory_pairs_write", lambda ws, n: (pc, p, None, 0, 0, p, p, p, None, B, ws, n, None)),
+        ("territory_pairs", (B, pc), "pcseg_territory_pairs_write", lambda ws, n: (pc, p, p, cap, 2, p, p, p, p, B, ws, n, None)),
+        ("contingency", (B, pc), "pcseg_label_contingency", lambda ws, n: (p, p, cap, cap, pc, p, p, p, B, H, W, ws, n, None)),
+        ("contingency", (B, pc), "pcseg_contingency_write", lambda ws, n: (pc, p, p, p, p, B, ws, n, None)),
+        ("label_borders", (B, pc, cap), "pcseg_label_borders", lambda ws, n: (p, p, H * W, cap, 8, pc, p, p, p, B, H, W, ws, n, None)),
+        ("label_borders", (B, pc, cap), "pcseg_label_borders_write", lambda ws, n: (pc, cap, p, p, p, p, p, p, B, ws, n, None)),
+        ("label_borders", (B, pc, cap), "pcseg_border_merge", lambda ws, n: (pc, cap, p, 0.5, 0, p, p, p, B, ws, n, None)),
+        ("nearest_label", shape, "pcseg_nearest_label_i32", lambda ws, n: (p, None, cap, p, p, None, B, H, W, ws, n, None)),
+        ("reconstruct", shape, "pcseg_reconstruct_i32", lambda ws, n: (p, q, r, p, B, H, W, 8, 0, 0, ws, n, None)),
+        ("reconstruct", shape, "pcseg_reconstruct_f64", lambda ws, n: (p, q, r, p, B, H, W, 4, 1, 0, ws, n, None)),
+        ("region_shape", shape, "pcseg_region_shape", lambda ws, n: (p, p, p, p, B, H, W, cap, ws, n, None)),
+        ("region_hull", shape + (cap,), "pcseg_region_hull", lambda ws, n: (p, p, p, p, p, B, H, W, cap, ws, n, None)),
+        ("thin_labels", shape, "pcseg_thin_labels", lambda ws, n: (p, p, p, B, H, W, -1, ws, n, None)),
+        ("region_skeleton", shape + (cap,), "pcseg_region_skeleton", lambda ws, n: (p, p, p, p, B, H, W, cap, ws, n, None)),
+        ("mixing", (npt, B, K, 3, 4, 0), "pcseg_pair_label_mixing",
+         lambda ws, n: (p, p, p, p, npt, B, K, 1.0, edges, 3, 4, 7, p, p, ws, n, None)),
+        ("mixing", (npt, B, K, 3, 4, 1), "pcseg_pair_label_mixing",
+         lambda ws, n: (p, p, p, p, npt, B, K, 1.0, edges, 3, 4, 7, None, p, ws, n, None)),
+        ("neighbours", (npt, B, K, 0), "pcseg_point_neighbours",
+         lambda ws, n: (p, p, p, p, npt, B, K, 1.0, None, 0, p, p, None, ws, n, None)),
+        ("neighbours", (npt, B, K, 3), "pcseg_point_neighbours",
+         lambda ws, n: (p, p, p, p, npt, B, K, 1.0, edges, 3, p, p, p, ws, n, None)),
+        ("surface", shape, "pcseg_surface_points", lambda ws, n: (p, 2, p, p, p, p, None, 0, B, H, W, ws, n, None)),
+        ("surface", shape, "pcseg_surface_distances",
+         lambda ws, n: (p, None, p, npt, p, p, None, B, H, W, 1.0, None, 0, 0, p, p, None, None, None, ws, n, None)),
+        ("surface_shells", shape, "pcseg_surface_shells", lambda ws, n: (p, p, p, B, H, W, 1.0, edges, 3, p, ws, n, None)),
+        ("label_parent", shape + (cap,), "pcseg_label_parent",
+         lambda ws, n: (p, p, p, None, None, p, p, p, None, p, None, B, H, W, cap, ws, n, None)),
+        ("table", (B, cap), "pcseg_table_write", lambda ws, n: (tref, p, p, p, p, ws, n, None)),
+        ("refined", (B, cap), "pcseg_refined_layout", lambda ws, n: (rref, p, ws, n, None)),
+        ("refined", (B, cap), "pcseg_refined_table_write", lambda ws, n: (rref, p, 1 << 20, p, p, p, None, None, None, None, ws, n, None)),
     ]
     for query, qargs, entry, args in cases:
         need = getattr(lib, "pcseg_%s_workspace_bytes" % query)(*qargs)
         assert need > 0 and need % 256 == 0, (query, need)
         assert entry in _lib.SIGNATURES
         rc = getattr(lib, entry)(*args(p, need - 1))
-        assert rc == ERR_WORKSPACE and b"workspace too small" in lib.pcseg_last_error(), (entry, rc, lib.pcseg_last_error())
+        assert rc == ERR_WORKSPACE, (entry, rc, lib.pcseg_last_error())
+        assert lib.pcseg_last_error().endswith(b": workspace too small (%d < %d)" % (need - 1, need)), (entry, lib.pcseg_last_error())
+    # the readers of a table workspace's head (the frames' row counts and offsets: two 256-byte aligned regions of 3 B int64,
+    # what pcseg_table_layout writes) carve the head alone; no size query answers it
+    head = 2 * ((3 * 8 * B + 255) // 256 * 256)
+    class_slot = (ctypes.c_uint8 * 256)()
+    for entry, who, args in [
+        ("pcseg_table_layout", "table_layout", lambda ws, n: (tref, p, ws, n, None)),
+        ("pcseg_cell_distances", "cell_distances", lambda ws, n: (p, 10, 14, class_slot, 19.0, 1.0, p, B, ws, n, None)),
+        ("pcseg_neighbours_pack_cells", "neighbours_pack_cells", lambda ws, n: (p, 14, class_slot, B, ws, n, p, p, p, p, None)),
+        ("pcseg_surface_pack_cells", "surface_pack_cells", lambda ws, n: (p, 14, class_slot, B, ws, n, p, p, p, p, None)),
+        ("pcseg_refined_table_write", "refined_table_write",
+         lambda ws, n: (rref, ws, n, p, p, p, None, None, None, None, p, 1 << 20, None)),
+    ]:
+        rc = getattr(lib, entry)(*args(p, head - 1))
+        assert rc == ERR_WORKSPACE, (entry, rc, lib.pcseg_last_error())
+        assert lib.pcseg_last_error() == ("%s: workspace too small (%d < %d)" % (who, head - 1, head)).encode(), (entry, lib.pcseg_last_error())
     # a null workspace is refused as an argument, whatever its stated size
     assert lib.pcseg_fill_holes(p, p, B, H, W, None, 1 << 30, None) == -1
     # shapes a size query rejects
