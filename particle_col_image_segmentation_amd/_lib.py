@@ -134,6 +134,41 @@ SIGNATURES = {
     "pcseg_morph3x3": (c_int, [_P, _P, _I, _I, _I, _I, _P]),
 }
 
+# entry point -> the size query (pcseg_<value>_workspace_bytes) that sizes the (workspace, workspace_bytes) it is given; a
+# _multi entry takes its single form's query with B * M frames
+WORKSPACE = {
+    "pcseg_classmap_label_f32": "classmap_label",
+    "pcseg_ccl8_equal_u8": "ccl", "pcseg_ccl8_bool": "ccl", "pcseg_ccl4_bool": "ccl", "pcseg_compact_labels": "ccl",
+    "pcseg_edt_sq_u8": "edt", "pcseg_edt_sq_lt_f32": "edt", "pcseg_dilate_disk_u8": "edt", "pcseg_fill_particle": "edt",
+    "pcseg_fill_holes": "fill_holes",
+    "pcseg_local_maxima_i32": "local_maxima",
+    "pcseg_watershed4_f32": "watershed",
+    "pcseg_dilate_ccl_roots_u8": "dilate_ccl",
+    "pcseg_dilate_ccl_runs_u8": "dilate_ccl_runs", "pcseg_dilate_ccl_runs_multi_u8": "dilate_ccl_runs",
+    "pcseg_merge_groups": "merge_groups", "pcseg_merge_groups_runs": "merge_groups", "pcseg_merge_groups_fused": "merge_groups",
+    "pcseg_merge_groups_fused_multi": "merge_groups",
+    "pcseg_remove_overlapping": "overlap",
+    "pcseg_table_layout": "table", "pcseg_table_write": "table",
+    "pcseg_refined_layout": "refined", "pcseg_refined_table_write": "refined",
+    "pcseg_point_neighbours": "neighbours",
+    "pcseg_pair_label_mixing": "mixing",
+    "pcseg_label_parent": "label_parent",
+    "pcseg_surface_points": "surface", "pcseg_surface_distances": "surface",
+    "pcseg_surface_shells": "surface_shells",
+    "pcseg_region_shape": "region_shape",
+    "pcseg_region_hull": "region_hull",
+    "pcseg_nearest_label_i32": "nearest_label",
+    "pcseg_territory_pairs": "territory_pairs", "pcseg_territory_pairs_write": "territory_pairs",
+    "pcseg_label_contingency": "contingency", "pcseg_contingency_write": "contingency",
+    "pcseg_label_borders": "label_borders", "pcseg_label_borders_write": "label_borders", "pcseg_border_merge": "label_borders",
+    "pcseg_thin_labels": "thin_labels",
+    "pcseg_region_skeleton": "region_skeleton",
+    "pcseg_reconstruct_i32": "reconstruct", "pcseg_reconstruct_f64": "reconstruct",
+}
+# ... and the (workspace, workspace_bytes) pairs that no query sizes: they read the head of the table workspace that
+# pcseg_table_layout wrote (of pcseg_refined_table_write: its first pair; its second is its own, above)
+WORKSPACE_HANDED_ON = ("pcseg_cell_distances", "pcseg_neighbours_pack_cells", "pcseg_surface_pack_cells", "pcseg_refined_table_write")
+
 
 class TableInputs(ctypes.Structure):
     """struct pcseg_table_inputs of include/pcseg.h, field for field."""

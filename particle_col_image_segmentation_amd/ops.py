@@ -9,12 +9,13 @@ import collections
 import ctypes
 import functools
 
+import numpy as np
 import torch
 
 from . import _lib
 
 
-def _stream():
+def _stream():  # (for scripts that call the library themselves: _call takes the stream on its own)
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
@@ -47,13 +48,67 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+_HOST_ONLY = ("surface_thresholds", "border_block")  # the entries called through _call that take no stream
+
+
+@functools.lru_cache(maxsize=None)
+def _entry(entry):
+    """``pcseg_<entry>`` and whether a stream ends its arguments (looked up once per name: _call is on the launch path)."""
+    return getattr(_lib.load(), "pcseg_" + entry), entry not in _HOST_ONLY
+
+
+def _workspace(entry, device, *query):
+    """``(workspace, nbytes)`` for ``pcseg_<entry>``: ``nbytes`` is the answer of the size query that ``_lib.WORKSPACE`` names
+    for it, given ``query``.  :func:`_call` makes it; a wrapper does only where it allocates outputs after its workspace."""
+    nbytes = getattr(_lib.load(), "pcseg_%s_workspace_bytes" % _lib.WORKSPACE["pcseg_" + entry])(*query)
+    return _ws(nbytes, device), nbytes
+
+
+def _call(entry, *args, ws=None):
+    """``pcseg_<entry>(*args[, workspace, nbytes][, stream])``, the one way this module enters the library.  A tensor goes as
+    its address -- it is what ``_req`` / ``_label_batch`` / ``_plane_view`` returned: nothing is checked here --, None as a
+    null pointer, a numpy array as its data address; ctypes objects and numbers are left to the entry's ``argtypes``.
+    ``ws``: the arguments of the entry's size query (a workspace of that size is allocated on the device of the first tensor
+    argument) or the pair an earlier call returned; None: the entry has no workspace, or it stands among ``args``.  The
+    current stream is appended, read now.  A non-zero status raises ``PcsegError``.  Returns the workspace pair, or None.
+    Nothing but :func:`_entry`'s lookup is kept from one call to the next (eight host threads launch through here), and a
+    call costs the host what the spelled-out form did (profiles/ops_call): hence the int test first -- most arguments are
+    sizes."""
+    fn, has_stream = _entry(entry)
+    argv, first = [], None
+    for a in args:
+        if type(a) is not int and a is not None:
+            if isinstance(a, torch.Tensor):
+                first = a if first is None else first
+                a = a.data_ptr()
+            elif isinstance(a, np.ndarray):
+                if not a.flags.c_contiguous:
+                    raise ValueError("%s: a numpy argument must be C-contiguous" % entry)
+                a = a.ctypes.data
+        argv.append(a)
+    if ws is not None:
+        if not isinstance(ws[0], torch.Tensor):
+            ws = _workspace(entry, first.device, *ws)
+        argv += (ws[0].data_ptr(), ws[1])
+    if has_stream:
+        argv.append(torch.cuda.current_stream().cuda_stream)
+    rc = fn(*argv)
+    if rc:
+        _lib.check(rc, entry)
+    return ws
+
+
+def _default_cap(x):
+    """The cap of a table over the labels (or counts) ``x`` when the caller names none: the largest, read back; at least 1."""
+    return max(int(x.max().item()), 1)
+
+
 def argmax_planes(stack):
     """class map = argmax over planes + 1 (tiff_analysis.py:639-642 reads this from ilastik)."""
     stack = _req(stack, torch.float32, 4)
     B, C, H, W = stack.shape
     out = torch.empty((B, H, W), dtype=torch.uint8, device=stack.device)
-    lib = _lib.load()
-    _lib.check(lib.pcseg_argmax_planes_f32(_ptr(stack), _ptr(out), B, C, H, W, _stream()), "argmax_planes")
+    _call("argmax_planes_f32", stack, out, B, C, H, W)
     return out
 
 
@@ -62,8 +117,7 @@ def median5(x):
     x = _req(x, torch.uint8, 3)
     B, H, W = x.shape
     out = torch.empty_like(x)
-    lib = _lib.load()
-    _lib.check(lib.pcseg_median5_u8(_ptr(x), _ptr(out), B, H, W, _stream()), "median5")
+    _call("median5_u8", x, out, B, H, W)
     return out
 
 
@@ -76,51 +130,40 @@ def classmap_label(stack):
     z = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     labels = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.pcseg_classmap_label_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_classmap_label_f32(_ptr(stack), C, _ptr(z), _ptr(labels), _ptr(counts), B, H, W, _ptr(ws), nbytes, _stream()),
-               "classmap_label")
+    _call("classmap_label_f32", stack, C, z, labels, counts, B, H, W, ws=(B, H, W))
     return z, labels, counts
 
 
-def _ccl(fn_name, x):
+def _ccl(entry, x):
     x = _req(x, torch.uint8, 3)
     B, H, W = x.shape
-    lib = _lib.load()
     labels = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
     counts = torch.empty((B,), dtype=torch.int32, device=x.device)
-    nbytes = lib.pcseg_ccl_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, x.device)
-    _lib.check(getattr(lib, fn_name)(_ptr(x), _ptr(labels), _ptr(counts), B, H, W, _ptr(ws), nbytes, _stream()), fn_name)
+    _call(entry, x, labels, counts, B, H, W, ws=(B, H, W))
     return labels, counts
 
 
 def label_equal8(x):
     """skimage.measure.label(int image): equal-valued 8-connected components (tiff_analysis.py:743)."""
-    return _ccl("pcseg_ccl8_equal_u8", x)
+    return _ccl("ccl8_equal_u8", x)
 
 
 def label_bool8(x):
     """skimage.measure.label(bool image) (tiff_analysis.py:260, 829; refine_boundaries.py:64)."""
-    return _ccl("pcseg_ccl8_bool", x)
+    return _ccl("ccl8_bool", x)
 
 
 def label_bool4(x):
     """scipy.ndimage.label(bool image), 4-connectivity."""
-    return _ccl("pcseg_ccl4_bool", x)
+    return _ccl("ccl4_bool", x)
 
 
 def compact_labels(roots):
     roots = _req(roots, torch.int32, 3)
     B, H, W = roots.shape
-    lib = _lib.load()
     labels = torch.empty_like(roots)
     counts = torch.empty((B,), dtype=torch.int32, device=roots.device)
-    nbytes = lib.pcseg_ccl_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, roots.device)
-    _lib.check(lib.pcseg_compact_labels(_ptr(roots), _ptr(labels), _ptr(counts), B, H, W, _ptr(ws), nbytes, _stream()),
-               "compact_labels")
+    _call("compact_labels", roots, labels, counts, B, H, W, ws=(B, H, W))
     return labels, counts
 
 
@@ -132,8 +175,7 @@ def region_init(counts, cap, C, shape, device):
     stats = torch.empty((B, cap, 8), dtype=torch.int64, device=device)
     sums = torch.empty((B, cap, C), dtype=torch.float64, device=device)
     overflow = torch.empty((B,), dtype=torch.int32, device=device)
-    lib = _lib.load()
-    _lib.check(lib.pcseg_region_init(_ptr(counts), cap, C, B, H, W, _ptr(stats), _ptr(sums), _ptr(overflow), _stream()), "region_init")
+    _call("region_init", counts, cap, C, B, H, W, stats, sums, overflow)
     return stats, sums, overflow
 
 
@@ -155,10 +197,8 @@ def region_sums2(labels_a, cls, sum_classes, sums_a, labels_b, sums_b, planes, s
         stats_b = _req(stats_b, torch.int64, 3)
         if tuple(stats_b.shape) != (B, sums_b.shape[1], 8):
             raise ValueError("stats_b must be (B, cap_b, 8)")
-    lib = _lib.load()
-    _lib.check(lib.pcseg_region_sums2(_ptr(labels_a), _ptr(cls), int(sum_classes), sums_a.shape[1], _ptr(sums_a), _ptr(labels_b),
-                                      sums_b.shape[1], _ptr(sums_b), _ptr(stats_b), _ptr(overflow_b), _ptr(planes), C, B, H, W,
-                                      _stream()), "region_sums2")
+    _call("region_sums2", labels_a, cls, int(sum_classes), sums_a.shape[1], sums_a, labels_b, sums_b.shape[1], sums_b, stats_b,
+          overflow_b, planes, C, B, H, W)
 
 
 def region_reduce(labels, counts=None, cls=None, planes=None, cap=None, sum_classes=0, zero_sums=0):
@@ -175,7 +215,7 @@ def region_reduce(labels, counts=None, cls=None, planes=None, cap=None, sum_clas
     if cap is None:
         if counts is None:
             raise ValueError("cap or counts is required")
-        cap = max(1, int(counts.max().item()))
+        cap = _default_cap(counts)
     # no zero fill: the library initialises the rows it fills (all of them, or the first counts[b] of frame b); rows
     # beyond counts[b] are never read by anything that takes `counts`
     stats = torch.empty((B, cap, 8), dtype=torch.int64, device=dev)
@@ -195,12 +235,9 @@ def region_reduce(labels, counts=None, cls=None, planes=None, cap=None, sum_clas
     if counts is not None:
         counts = _req(counts, torch.int32, 1)
     overflow = torch.empty((B,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
     if sum_classes and (cls is None or planes is None):
         raise ValueError("sum_classes needs cls and planes")
-    _lib.check(lib.pcseg_region_reduce_sel(_ptr(labels), _ptr(counts), _ptr(cls), int(sum_classes), _ptr(planes), C, B, H, W,
-                                           cap, _ptr(stats), _ptr(cls_out), _ptr(sums), _ptr(overflow), _stream()),
-               "region_reduce")
+    _call("region_reduce_sel", labels, counts, cls, int(sum_classes), planes, C, B, H, W, cap, stats, cls_out, sums, overflow)
     return stats, cls_out, sums, overflow
 
 
@@ -219,33 +256,34 @@ def region_shape(labels, counts, cap=None):
     if counts.shape[0] != B:
         raise ValueError("counts must have one entry per frame")
     if cap is None:
-        cap = max(1, int(counts.max().item()))
+        cap = _default_cap(counts)
     cap = int(cap)
     dev = labels.device
     shape = torch.empty((B, cap, 8), dtype=torch.int64, device=dev)
     overflow = torch.empty((B,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.pcseg_region_shape_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_region_shape(_ptr(labels), _ptr(counts), _ptr(shape), _ptr(overflow), B, H, W, cap, _ptr(ws), nbytes,
-                                      _stream()), "region_shape")
+    _call("region_shape", labels, counts, shape, overflow, B, H, W, cap, ws=(B, H, W))
     return shape, overflow
+
+
+def _properties(entry, stats, table, width, counts, columns, mismatch):
+    """pcseg_<entry>: float64 (B, cap, columns) derived from ``stats`` (B, cap, 8) and the integer ``table`` (B, cap, width)."""
+    stats = _req(stats, torch.int64, 3)
+    table = _req(table, torch.int64, 3)
+    counts = _req(counts, torch.int32, 1)
+    B, cap = stats.shape[0], stats.shape[1]
+    if tuple(stats.shape) != (B, cap, 8) or tuple(table.shape) != (B, cap, width) or counts.shape[0] != B:
+        raise ValueError(mismatch)
+    out = torch.empty((B, cap, columns), dtype=torch.float64, device=stats.device)
+    _call(entry, stats, table, counts, out, B, cap)
+    return out
 
 
 def shape_properties(stats, shape, counts):
     """The derived shape columns (scikit-image 0.18.3 conventions, pixels): ``stats`` int64 (B, cap, 8) of
     :func:`region_reduce` and ``shape`` of :func:`region_shape` over the same labels -> float64 (B, cap, 12) in the order of
     ``SHAPE_COLUMNS``, rows below min(counts[b], cap); NaN for a label without pixel."""
-    stats = _req(stats, torch.int64, 3)
-    shape = _req(shape, torch.int64, 3)
-    counts = _req(counts, torch.int32, 1)
-    B, cap = stats.shape[0], stats.shape[1]
-    if tuple(stats.shape) != (B, cap, 8) or tuple(shape.shape) != (B, cap, 8) or counts.shape[0] != B:
-        raise ValueError("stats and shape must both be (B, cap, 8), counts (B,)")
-    out = torch.empty((B, cap, len(SHAPE_COLUMNS)), dtype=torch.float64, device=stats.device)
-    _lib.check(_lib.load().pcseg_shape_properties(_ptr(stats), _ptr(shape), _ptr(counts), _ptr(out), B, cap, _stream()),
-               "shape_properties")
-    return out
+    return _properties("shape_properties", stats, shape, 8, counts, len(SHAPE_COLUMNS),
+                       "stats and shape must both be (B, cap, 8), counts (B,)")
 
 
 HULL_COLUMNS = ("convex_area", "solidity", "feret_diameter_max", "euler_number")
@@ -271,11 +309,7 @@ def region_hull(labels, counts, stats, cap=None):
     dev = labels.device
     hull = torch.empty((B, cap, 4), dtype=torch.int64, device=dev)
     overflow = torch.empty((B,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.pcseg_region_hull_workspace_bytes(B, H, W, cap)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_region_hull(_ptr(labels), _ptr(counts), _ptr(stats), _ptr(hull), _ptr(overflow), B, H, W, cap, _ptr(ws),
-                                     nbytes, _stream()), "region_hull")
+    _call("region_hull", labels, counts, stats, hull, overflow, B, H, W, cap, ws=(B, H, W, cap))
     return hull, overflow
 
 
@@ -283,16 +317,8 @@ def hull_properties(stats, hull, counts):
     """The derived convexity columns (scikit-image 0.18.3 conventions, pixels): ``stats`` int64 (B, cap, 8) of
     :func:`region_reduce` and ``hull`` of :func:`region_hull` over the same labels -> float64 (B, cap, 4) in the order of
     ``HULL_COLUMNS``, rows below min(counts[b], cap); NaN for a label without pixel."""
-    stats = _req(stats, torch.int64, 3)
-    hull = _req(hull, torch.int64, 3)
-    counts = _req(counts, torch.int32, 1)
-    B, cap = stats.shape[0], stats.shape[1]
-    if tuple(stats.shape) != (B, cap, 8) or tuple(hull.shape) != (B, cap, 4) or counts.shape[0] != B:
-        raise ValueError("stats must be (B, cap, 8), hull (B, cap, 4), counts (B,)")
-    out = torch.empty((B, cap, len(HULL_COLUMNS)), dtype=torch.float64, device=stats.device)
-    _lib.check(_lib.load().pcseg_hull_properties(_ptr(stats), _ptr(hull), _ptr(counts), _ptr(out), B, cap, _stream()),
-               "hull_properties")
-    return out
+    return _properties("hull_properties", stats, hull, 4, counts, len(HULL_COLUMNS),
+                       "stats must be (B, cap, 8), hull (B, cap, 4), counts (B,)")
 
 
 SKELETON_COLUMNS = ("skel_px", "n_orth", "n_diag", "n_end", "n_junction", "passes", "length_px", "width_px")
@@ -312,11 +338,7 @@ def thin_labels(labels, max_iter=None):
     dev = labels.device
     peel = torch.empty((B, H, W), dtype=torch.uint16, device=dev)
     iters = torch.empty((B,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.pcseg_thin_labels_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_thin_labels(_ptr(labels), _ptr(peel), _ptr(iters), B, H, W, -1 if max_iter is None else int(max_iter),
-                                     _ptr(ws), nbytes, _stream()), "thin_labels")
+    _call("thin_labels", labels, peel, iters, B, H, W, -1 if max_iter is None else int(max_iter), ws=(B, H, W))
     return peel, iters
 
 
@@ -346,14 +368,10 @@ def region_skeleton(labels, peel, counts, cap=None):
     if counts.shape[0] != B:
         raise ValueError("counts must have one entry per frame")
     if cap is None:
-        cap = max(1, int(counts.max().item()))
+        cap = _default_cap(counts)
     cap = int(cap)
     table = torch.empty((B, cap, 6), dtype=torch.int64, device=labels.device)
-    lib = _lib.load()
-    nbytes = lib.pcseg_region_skeleton_workspace_bytes(B, H, W, cap)
-    ws = _ws(nbytes, labels.device)
-    _lib.check(lib.pcseg_region_skeleton(_ptr(labels), _ptr(peel), _ptr(counts), _ptr(table), B, H, W, cap, _ptr(ws), nbytes,
-                                         _stream()), "region_skeleton")
+    _call("region_skeleton", labels, peel, counts, table, B, H, W, cap, ws=(B, H, W, cap))
     return table
 
 
@@ -361,16 +379,7 @@ def skeleton_properties(stats, table, counts):
     """The derived skeleton columns, in pixels: ``stats`` int64 (B, cap, 8) of :func:`region_reduce` and ``table`` of
     :func:`region_skeleton` over the same labels -> float64 (B, cap, 2) = length_px (n_orth + n_diag * sqrt 2), width_px
     (area / length_px; inf for a one-pixel skeleton), rows below min(counts[b], cap); NaN for a label without pixel."""
-    stats = _req(stats, torch.int64, 3)
-    table = _req(table, torch.int64, 3)
-    counts = _req(counts, torch.int32, 1)
-    B, cap = stats.shape[0], stats.shape[1]
-    if tuple(stats.shape) != (B, cap, 8) or tuple(table.shape) != (B, cap, 6) or counts.shape[0] != B:
-        raise ValueError("stats must be (B, cap, 8), table (B, cap, 6), counts (B,)")
-    out = torch.empty((B, cap, 2), dtype=torch.float64, device=stats.device)
-    _lib.check(_lib.load().pcseg_skeleton_properties(_ptr(stats), _ptr(table), _ptr(counts), _ptr(out), B, cap, _stream()),
-               "skeleton_properties")
-    return out
+    return _properties("skeleton_properties", stats, table, 6, counts, 2, "stats must be (B, cap, 8), table (B, cap, 6), counts (B,)")
 
 
 def threshold_lt(img, threshold):
@@ -378,8 +387,7 @@ def threshold_lt(img, threshold):
     img = _req(img, torch.float32, 3)
     B, H, W = img.shape
     out = torch.empty((B, H, W), dtype=torch.uint8, device=img.device)
-    lib = _lib.load()
-    _lib.check(lib.pcseg_threshold_lt_f32(_ptr(img), float(threshold), _ptr(out), B, H, W, _stream()), "threshold_lt")
+    _call("threshold_lt_f32", img, float(threshold), out, B, H, W)
     return out
 
 
@@ -387,11 +395,8 @@ def edt_sq(mask, cap=-1):
     """exact squared EDT of a 0/1 mask (refine_boundaries.py:60, tiff_analysis.py:996)."""
     mask = _req(mask, torch.uint8, 3)
     B, H, W = mask.shape
-    lib = _lib.load()
     d2 = torch.empty((B, H, W), dtype=torch.int32, device=mask.device)
-    nbytes = lib.pcseg_edt_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, mask.device)
-    _lib.check(lib.pcseg_edt_sq_u8(_ptr(mask), _ptr(d2), B, H, W, int(cap), _ptr(ws), nbytes, _stream()), "edt_sq")
+    _call("edt_sq_u8", mask, d2, B, H, W, int(cap), ws=(B, H, W))
     return d2
 
 
@@ -409,13 +414,9 @@ def edt_sq_lt(img, threshold, want_mask=True):
     """fused threshold + squared EDT (refine_boundaries.py:44-45, 60); img may be a plane view of a stack."""
     img, fstride = _plane_view(img)
     B, H, W = img.shape
-    lib = _lib.load()
     d2 = torch.empty((B, H, W), dtype=torch.int32, device=img.device)
     mask = torch.empty((B, H, W), dtype=torch.uint8, device=img.device) if want_mask else None
-    nbytes = lib.pcseg_edt_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, img.device)
-    _lib.check(lib.pcseg_edt_sq_lt_f32(_ptr(img), fstride, float(threshold), _ptr(d2), _ptr(mask), B, H, W, _ptr(ws),
-                                       nbytes, _stream()), "edt_sq_lt")
+    _call("edt_sq_lt_f32", img, fstride, float(threshold), d2, mask, B, H, W, ws=(B, H, W))
     return d2, mask
 
 
@@ -423,12 +424,8 @@ def dilate_disk(x, value_bits, radius):
     """binary_dilation(((value_bits >> x) & 1), disk(radius)) (tiff_analysis.py:827-828, 990)."""
     x = _req(x, torch.uint8, 3)
     B, H, W = x.shape
-    lib = _lib.load()
     out = torch.empty_like(x)
-    nbytes = lib.pcseg_edt_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, x.device)
-    _lib.check(lib.pcseg_dilate_disk_u8(_ptr(x), ctypes.c_uint64(int(value_bits)), int(radius), _ptr(out), B, H, W,
-                                        _ptr(ws), nbytes, _stream()), "dilate_disk")
+    _call("dilate_disk_u8", x, int(value_bits), int(radius), out, B, H, W, ws=(B, H, W))
     return out
 
 
@@ -436,15 +433,11 @@ def fill_particle(ds, particle_label, cell_label, overlap_label, dilation_radius
     """fill_particle_area (tiff_analysis.py:982-1015); overlap_area int64 (B,) is accumulated in place."""
     ds = _req(ds, torch.uint8, 3)
     B, H, W = ds.shape
-    lib = _lib.load()
     out = torch.empty_like(ds)
     if overlap_area is None:
         overlap_area = torch.zeros((B,), dtype=torch.int64, device=ds.device)
-    nbytes = lib.pcseg_edt_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, ds.device)
-    _lib.check(lib.pcseg_fill_particle(_ptr(ds), _ptr(out), int(particle_label), int(cell_label), int(overlap_label),
-                                       int(dilation_radius), int(dist_threshold), _ptr(overlap_area), B, H, W,
-                                       _ptr(ws), nbytes, _stream()), "fill_particle")
+    _call("fill_particle", ds, out, int(particle_label), int(cell_label), int(overlap_label), int(dilation_radius),
+          int(dist_threshold), overlap_area, B, H, W, ws=(B, H, W))
     return out, overlap_area
 
 
@@ -452,11 +445,8 @@ def fill_holes(mask):
     """scipy.ndimage.binary_fill_holes (tiff_analysis.py:880)."""
     mask = _req(mask, torch.uint8, 3)
     B, H, W = mask.shape
-    lib = _lib.load()
     out = torch.empty_like(mask)
-    nbytes = lib.pcseg_fill_holes_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, mask.device)
-    _lib.check(lib.pcseg_fill_holes(_ptr(mask), _ptr(out), B, H, W, _ptr(ws), nbytes, _stream()), "fill_holes")
+    _call("fill_holes", mask, out, B, H, W, ws=(B, H, W))
     return out
 
 
@@ -464,14 +454,10 @@ def local_maxima(img, want_mask=True, want_markers=True):
     """skimage.morphology.local_maxima + measure.label on an int32 image (refine_boundaries.py:63-64)."""
     img = _req(img, torch.int32, 3)
     B, H, W = img.shape
-    lib = _lib.load()
     is_max = torch.empty((B, H, W), dtype=torch.uint8, device=img.device) if want_mask else None
     markers = torch.empty((B, H, W), dtype=torch.int32, device=img.device) if want_markers else None
     counts = torch.empty((B,), dtype=torch.int32, device=img.device)
-    nbytes = lib.pcseg_local_maxima_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, img.device)
-    _lib.check(lib.pcseg_local_maxima_i32(_ptr(img), _ptr(is_max), _ptr(markers), _ptr(counts), B, H, W, _ptr(ws),
-                                          nbytes, _stream()), "local_maxima")
+    _call("local_maxima_i32", img, is_max, markers, counts, B, H, W, ws=(B, H, W))
     return is_max, markers, counts
 
 
@@ -511,12 +497,8 @@ def _reconstruct(seed, mask, method, conn, max_rounds=0):
     dev = seed.device
     out = torch.empty_like(seed)
     flags = torch.empty((B,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.pcseg_reconstruct_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dev)
-    fn = lib.pcseg_reconstruct_i32 if seed.dtype == torch.int32 else lib.pcseg_reconstruct_f64
-    _lib.check(fn(_ptr(seed), _ptr(mask), _ptr(out), _ptr(flags), B, H, W, int(conn), _RECONSTRUCT_METHODS[method], int(max_rounds),
-                  _ptr(ws), nbytes, _stream()), "reconstruct")
+    ws, _ = _call("reconstruct_i32" if seed.dtype == torch.int32 else "reconstruct_f64", seed, mask, out, flags, B, H, W, int(conn),
+                  _RECONSTRUCT_METHODS[method], int(max_rounds), ws=(B, H, W))
     return out, flags, ws
 
 
@@ -555,7 +537,6 @@ def _h_extrema(image, h, conn, sign):
     image = image.contiguous()
     B, H, W = image.shape
     dev = image.device
-    lib = _lib.load()
     rng = torch.empty((B, 2), dtype=torch.int64, device=dev)
     seed = torch.empty_like(image)
     mark = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
@@ -566,16 +547,16 @@ def _h_extrema(image, h, conn, sign):
         h = int(h)
         if h > 0xFFFFFFFF:
             raise ValueError("The %s constant is not compatible with the image data type." % ("subtracted" if sign < 0 else "added"))
-        _lib.check(lib.pcseg_hmax_range_i32(_ptr(image), _ptr(rng), B, H, W, _stream()), "hmax_range")
-        _lib.check(lib.pcseg_hmax_shift_i32(_ptr(image), h, sign, _ptr(seed), B, H, W, _stream()), "hmax_shift")
+        _call("hmax_range_i32", image, rng, B, H, W)
+        _call("hmax_shift_i32", image, h, sign, seed, B, H, W)
         rec, flags, _ = _reconstruct(seed, image, method, conn)
-        _lib.check(lib.pcseg_hmax_mark_i32(_ptr(image), _ptr(rec), h, sign, _ptr(rng), _ptr(mark), B, H, W, _stream()), "hmax_mark")
+        _call("hmax_mark_i32", image, rec, h, sign, rng, mark, B, H, W)
     else:
         h = float(h)
-        _lib.check(lib.pcseg_hmax_range_f64(_ptr(image), _ptr(rng), B, H, W, _stream()), "hmax_range")
-        _lib.check(lib.pcseg_hmax_shift_f64(_ptr(image), h, sign, _ptr(seed), B, H, W, _stream()), "hmax_shift")
+        _call("hmax_range_f64", image, rng, B, H, W)
+        _call("hmax_shift_f64", image, h, sign, seed, B, H, W)
         rec, flags, _ = _reconstruct(seed, image, method, conn)
-        _lib.check(lib.pcseg_hmax_mark_f64(_ptr(image), _ptr(rec), h, sign, _ptr(rng), 0, _ptr(mark), B, H, W, _stream()), "hmax_mark")
+        _call("hmax_mark_f64", image, rec, h, sign, rng, 0, mark, B, H, W)
     _check_reconstruct_flags(flags)
     return mark
 
@@ -605,15 +586,14 @@ def edt_maxima(d2, h, conn=8, want_mask=True, want_markers=True, counters=False)
     h = float(h)
     B, H, W = d2.shape
     dev = d2.device
-    lib = _lib.load()
     rng = torch.empty((B, 2), dtype=torch.int64, device=dev)
     dist = torch.empty((B, H, W), dtype=torch.float64, device=dev)
     seed = torch.empty_like(dist)
     is_max = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-    _lib.check(lib.pcseg_hmax_range_i32(_ptr(d2), _ptr(rng), B, H, W, _stream()), "hmax_range")
-    _lib.check(lib.pcseg_hmax_shift_edt(_ptr(d2), h, _ptr(dist), _ptr(seed), B, H, W, _stream()), "hmax_shift_edt")
+    _call("hmax_range_i32", d2, rng, B, H, W)
+    _call("hmax_shift_edt", d2, h, dist, seed, B, H, W)
     rec, flags, ws = _reconstruct(seed, dist, "dilation", conn)
-    _lib.check(lib.pcseg_hmax_mark_f64(_ptr(dist), _ptr(rec), h, -1, _ptr(rng), 1, _ptr(is_max), B, H, W, _stream()), "hmax_mark")
+    _call("hmax_mark_f64", dist, rec, h, -1, rng, 1, is_max, B, H, W)
     markers = counts = None
     if want_markers:
         markers, counts = label_bool8(is_max)
@@ -634,13 +614,9 @@ def watershed(img, markers, mask, mode=0):
     markers = _req(markers, torch.int32, 3)
     mask = _req(mask, torch.uint8, 3)
     B, H, W = img.shape
-    lib = _lib.load()
     out = torch.empty((B, H, W), dtype=torch.int32, device=img.device)
     flags = torch.zeros((B,), dtype=torch.int32, device=img.device)
-    nbytes = lib.pcseg_watershed_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, img.device)
-    _lib.check(lib.pcseg_watershed4_f32(_ptr(img), fstride, _ptr(markers), _ptr(mask), _ptr(out), _ptr(flags), B, H, W, int(mode),
-                                        _ptr(ws), nbytes, _stream()), "watershed")
+    _call("watershed4_f32", img, fstride, markers, mask, out, flags, B, H, W, int(mode), ws=(B, H, W))
     return out, flags
 
 
@@ -648,12 +624,8 @@ def dilated_roots(x, value_bits, radius):
     """components of binary_dilation(((value_bits >> x) & 1), disk(radius)) as a union-find parent image (A6)."""
     x = _req(x, torch.uint8, 3)
     B, H, W = x.shape
-    lib = _lib.load()
     roots = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
-    nbytes = lib.pcseg_dilate_ccl_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, x.device)
-    _lib.check(lib.pcseg_dilate_ccl_roots_u8(_ptr(x), ctypes.c_uint64(int(value_bits)), int(radius), _ptr(roots), B, H, W,
-                                             _ptr(ws), nbytes, _stream()), "dilated_roots")
+    _call("dilate_ccl_roots_u8", x, int(value_bits), int(radius), roots, B, H, W, ws=(B, H, W))
     return roots
 
 
@@ -663,14 +635,10 @@ def dilated_runs(x, value_bits, radius, run_parent=None):
     of which only the run-head entries are written; pass ``run_parent`` to reuse one).  For merge_groups_runs."""
     x = _req(x, torch.uint8, 3)
     B, H, W = x.shape
-    lib = _lib.load()
     bits = torch.empty((B, (H + 31) // 32, W), dtype=torch.int32, device=x.device)
     if run_parent is None:
         run_parent = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
-    nbytes = lib.pcseg_dilate_ccl_runs_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, x.device)
-    _lib.check(lib.pcseg_dilate_ccl_runs_u8(_ptr(x), ctypes.c_uint64(int(value_bits)), int(radius), _ptr(bits), _ptr(run_parent),
-                                            B, H, W, _ptr(ws), nbytes, _stream()), "dilated_runs")
+    _call("dilate_ccl_runs_u8", x, int(value_bits), int(radius), bits, run_parent, B, H, W, ws=(B, H, W))
     return bits, run_parent
 
 
@@ -684,38 +652,29 @@ def merge_groups_runs(bits, run_parent, stats, region_list, n_list):
     B, H, W = run_parent.shape
     cap = stats.shape[1]
     list_cap = region_list.shape[1]
-    lib = _lib.load()
     group_of = torch.zeros((B, list_cap), dtype=torch.int32, device=stats.device)
     n_groups = torch.zeros((B,), dtype=torch.int32, device=stats.device)
-    nbytes = lib.pcseg_merge_groups_workspace_bytes(B, list_cap)
-    ws = _ws(nbytes, stats.device)
-    _lib.check(lib.pcseg_merge_groups_runs(_ptr(bits), _ptr(run_parent), _ptr(stats), _ptr(region_list), _ptr(n_list), _ptr(group_of),
-                                           _ptr(n_groups), B, H, W, cap, list_cap, _ptr(ws), nbytes, _stream()), "merge_groups_runs")
+    _call("merge_groups_runs", bits, run_parent, stats, region_list, n_list, group_of, n_groups, B, H, W, cap, list_cap,
+          ws=(B, list_cap))
     return group_of, n_groups
 
 
 def dilated_runs_multi(x, value_bits_list, radius):
     """dilated_runs for several masks of one class map in one go (the class map is read once; every later pass is ONE launch
     over all masks): returns (bits int32 (M, B, ceil(H/32), W), run_parent int32 (M, B, H, W))."""
-    import numpy as np
     x = _req(x, torch.uint8, 3)
     B, H, W = x.shape
     M = len(value_bits_list)
-    lib = _lib.load()
     bits = torch.empty((M, B, (H + 31) // 32, W), dtype=torch.int32, device=x.device)
     run_parent = torch.empty((M, B, H, W), dtype=torch.int32, device=x.device)
-    nbytes = lib.pcseg_dilate_ccl_runs_workspace_bytes(B * M, H, W)
-    ws = _ws(nbytes, x.device)
     vb = np.array([int(v) for v in value_bits_list], np.uint64)
-    _lib.check(lib.pcseg_dilate_ccl_runs_multi_u8(_ptr(x), ctypes.c_void_p(vb.ctypes.data), M, int(radius), _ptr(bits), _ptr(run_parent),
-                                                  B, H, W, _ptr(ws), nbytes, _stream()), "dilated_runs_multi")
+    _call("dilate_ccl_runs_multi_u8", x, vb, M, int(radius), bits, run_parent, B, H, W, ws=(B * M, H, W))
     return bits, run_parent
 
 
 def merge_groups_fused_multi(bits, run_parent, stats, region_lists, n_lists, slots):
     """merge_groups_fused for the M masks of dilated_runs_multi in one launch; mask m is grouped over the list of type slot
     ``slots[m]``.  Returns (group_of (M,B,cap), n_groups (M,B), group_stats (M,B,cap,8))."""
-    import numpy as np
     bits = _req(bits, torch.int32, 4)
     run_parent = _req(run_parent, torch.int32, 4)
     stats = _req(stats, torch.int64, 3)
@@ -727,16 +686,12 @@ def merge_groups_fused_multi(bits, run_parent, stats, region_lists, n_lists, slo
     if len(slots) != M or bits.shape[0] != M or region_lists.shape[2] != cap or tuple(n_lists.shape) != (B, n_slots):
         raise ValueError("masks / lists / region table do not match")
     dev = stats.device
-    lib = _lib.load()
     group_of = torch.empty((M, B, cap), dtype=torch.int32, device=dev)
     n_groups = torch.empty((M, B), dtype=torch.int32, device=dev)
     gstats = torch.empty((M, B, cap, 8), dtype=torch.int64, device=dev)
-    nbytes = lib.pcseg_merge_groups_workspace_bytes(B * M, cap)
-    ws = _ws(nbytes, dev)
     sl = np.array([int(v) for v in slots], np.int32)
-    _lib.check(lib.pcseg_merge_groups_fused_multi(_ptr(bits), _ptr(run_parent), _ptr(stats), _ptr(region_lists), _ptr(n_lists),
-                                                  ctypes.c_void_p(sl.ctypes.data), M, n_slots, _ptr(group_of), _ptr(n_groups),
-                                                  _ptr(gstats), B, H, W, cap, _ptr(ws), nbytes, _stream()), "merge_groups_fused_multi")
+    _call("merge_groups_fused_multi", bits, run_parent, stats, region_lists, n_lists, sl, M, n_slots, group_of, n_groups, gstats,
+          B, H, W, cap, ws=(B * M, cap))
     return group_of, n_groups, gstats
 
 
@@ -756,15 +711,11 @@ def merge_groups_fused(bits, run_parent, stats, region_lists, n_lists, slot):
     if region_lists.shape[2] != cap or tuple(n_lists.shape) != (B, n_slots):
         raise ValueError("region lists of shape %s / %s do not match the region table" % (tuple(region_lists.shape), tuple(n_lists.shape)))
     dev = stats.device
-    lib = _lib.load()
     group_of = torch.empty((B, cap), dtype=torch.int32, device=dev)
     n_groups = torch.empty((B,), dtype=torch.int32, device=dev)
     gstats = torch.empty((B, cap, 8), dtype=torch.int64, device=dev)
-    nbytes = lib.pcseg_merge_groups_workspace_bytes(B, cap)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_merge_groups_fused(_ptr(bits), _ptr(run_parent), _ptr(stats), _ptr(region_lists), _ptr(n_lists), int(slot),
-                                            n_slots, _ptr(group_of), _ptr(n_groups), _ptr(gstats), B, H, W, cap, _ptr(ws), nbytes,
-                                            _stream()), "merge_groups_fused")
+    _call("merge_groups_fused", bits, run_parent, stats, region_lists, n_lists, int(slot), n_slots, group_of, n_groups, gstats,
+          B, H, W, cap, ws=(B, cap))
     return group_of, n_groups, gstats
 
 
@@ -778,13 +729,10 @@ def merge_groups(dilated_labels, stats, region_list, n_list, roots=False):
     B, H, W = dl.shape
     cap = stats.shape[1]
     list_cap = region_list.shape[1]
-    lib = _lib.load()
     group_of = torch.zeros((B, list_cap), dtype=torch.int32, device=dl.device)
     n_groups = torch.zeros((B,), dtype=torch.int32, device=dl.device)
-    nbytes = lib.pcseg_merge_groups_workspace_bytes(B, list_cap)
-    ws = _ws(nbytes, dl.device)
-    _lib.check(lib.pcseg_merge_groups(_ptr(dl), int(bool(roots)), _ptr(stats), _ptr(region_list), _ptr(n_list), _ptr(group_of),
-                                      _ptr(n_groups), B, H, W, cap, list_cap, _ptr(ws), nbytes, _stream()), "merge_groups")
+    _call("merge_groups", dl, int(bool(roots)), stats, region_list, n_list, group_of, n_groups, B, H, W, cap, list_cap,
+          ws=(B, list_cap))
     return group_of, n_groups
 
 
@@ -792,10 +740,8 @@ def group_reduce(stats, region_list, n_list, group_of, n_groups, H, W):
     """member sums of merged groups (tiff_analysis.py:855-872): int64 (B, list_cap, 8)."""
     B, cap = stats.shape[0], stats.shape[1]
     list_cap = region_list.shape[1]
-    lib = _lib.load()
     gstats = torch.zeros((B, list_cap, 8), dtype=torch.int64, device=stats.device)
-    _lib.check(lib.pcseg_group_reduce(_ptr(stats), _ptr(region_list), _ptr(n_list), _ptr(group_of), _ptr(n_groups),
-                                      _ptr(gstats), B, H, W, cap, list_cap, _stream()), "group_reduce")
+    _call("group_reduce", stats, region_list, n_list, group_of, n_groups, gstats, B, H, W, cap, list_cap)
     return gstats
 
 
@@ -804,7 +750,6 @@ class ClassTables:
     MIN_CELL_AREA / MIN_CLUSTER_AREA constants (tiff_analysis.py:54-60, 754-773)."""
 
     def __init__(self, cell_types, cell_type_names, min_cell_area, min_cluster_area):
-        import numpy as np
         self.slot_names = []
         slot = np.full(256, 255, np.uint8)
         particle = np.zeros(256, np.uint8)
@@ -853,13 +798,9 @@ def classify_regions(stats, cls_out, counts, tables):
         "n_list": torch.empty((B, 5), dtype=torch.int32, device=dev),
         "nan_flag": torch.empty((B,), dtype=torch.int32, device=dev),
     }
-    lib = _lib.load()
-    hp = lambda a: ctypes.c_void_p(a.ctypes.data)
-    _lib.check(lib.pcseg_classify_regions(_ptr(stats), _ptr(cls_out), _ptr(counts), hp(tables.slot), hp(tables.particle),
-                                          hp(tables.min_cell), hp(tables.min_cluster), len(tables.slot_names),
-                                          _ptr(out["kind"]), _ptr(out["slot_of"]), _ptr(out["cells"]),
-                                          _ptr(out["particle_area"]), _ptr(out["type_stats"]), _ptr(out["region_list"]),
-                                          _ptr(out["n_list"]), _ptr(out["nan_flag"]), B, cap, _stream()), "classify_regions")
+    _call("classify_regions", stats, cls_out, counts, tables.slot, tables.particle, tables.min_cell, tables.min_cluster,
+          len(tables.slot_names), out["kind"], out["slot_of"], out["cells"], out["particle_area"], out["type_stats"],
+          out["region_list"], out["n_list"], out["nan_flag"], B, cap)
     return out
 
 
@@ -894,7 +835,6 @@ _Dense = collections.namedtuple("_Dense", "cells n_roi n_cell ws B")
 
 def _dense_tables(res, groups, frame_ids, C, ratios, check):
     """pcseg_table_layout + pcseg_table_write: (dict of ``rois`` / ``cells`` / ``groups`` / ``frames``, :class:`_Dense`)."""
-    lib = _lib.load()
     B, cap = res["stats"].shape[0], res["stats"].shape[1]
     dev = res["stats"].device
     if len(ratios) > 8 or any(len(den) > 4 for _, _, den in ratios):
@@ -931,10 +871,9 @@ def _dense_tables(res, groups, frame_ids, C, ratios, check):
     ti.overflow = ptr(res["overflow"], torch.int32, (B,))
     ti.ws_overflow = ptr(res["ws_overflow"], torch.int32, (B,))
     ti.nan_flag = ptr(res["nan_flag"], torch.int32, (B,))
-    nbytes = lib.pcseg_table_workspace_bytes(B, cap)
-    ws = _ws(nbytes, dev)
+    ws = _workspace("table_layout", dev, B, cap)
     totals = torch.empty((6,), dtype=torch.int64, device=dev)
-    _lib.check(lib.pcseg_table_layout(ctypes.byref(ti), _ptr(totals), _ptr(ws), nbytes, _stream()), "table_layout")
+    _call("table_layout", ctypes.byref(ti), totals, ws=ws)
     # the one host read: sizes of the outputs, plus the flags BatchResult.check() would otherwise fetch one by one
     n_roi, n_cell, n_group, n_overflow, n_ws_overflow, n_nan = (int(v) for v in totals.cpu())
     if check and (n_overflow or n_ws_overflow):
@@ -947,26 +886,22 @@ def _dense_tables(res, groups, frame_ids, C, ratios, check):
     cells = torch.empty((n_cell + 1, 14 + C + nr), dtype=torch.float64, device=dev)
     grp = torch.empty((n_group + 1, 11), dtype=torch.float64, device=dev)
     frames = torch.empty((B, 17), dtype=torch.int64, device=dev)
-    _lib.check(lib.pcseg_table_write(ctypes.byref(ti), _ptr(rois), _ptr(cells), _ptr(grp), _ptr(frames), _ptr(ws), nbytes,
-                                     _stream()), "table_write")
+    _call("table_write", ctypes.byref(ti), rois, cells, grp, frames, ws=ws)
     out = {"rois": rois[:n_roi], "cells": cells[:n_cell], "groups": grp[:n_group], "frames": frames, "frame_ids": frame_ids}
-    return out, _Dense(cells, n_roi, n_cell, ws, B)
+    return out, _Dense(cells, n_roi, n_cell, ws[0], B)
 
 
 def _cell_distances(d, slots, raster):
     """pcseg_cell_distances: one value per row of ``cells``, NaN = no entry."""
     dist = torch.empty((d.n_cell + 1,), dtype=torch.float64, device=d.cells.device)
-    _lib.check(_lib.load().pcseg_cell_distances(_ptr(d.cells), d.n_cell, d.cells.shape[1], ctypes.c_void_p(slots.ctypes.data),
-                                                float(raster), 512.0, _ptr(dist), d.B, _ptr(d.ws), d.ws.numel(), _stream()),
-               "cell_distances")
+    _call("cell_distances", d.cells, d.n_cell, d.cells.shape[1], slots, float(raster), 512.0, dist, d.B, d.ws, d.ws.numel())
     return dist[:d.n_cell]
 
 
 def _pack_cells(name, d, slots):
     """pcseg_<name>: the rows of ``cells`` as :class:`Points` (``slots``: class value -> type slot, uint8[256] numpy)."""
     pts = _alloc_points(d.n_cell, d.B, d.cells.device)
-    _lib.check(getattr(_lib.load(), "pcseg_" + name)(_ptr(d.cells), d.cells.shape[1], ctypes.c_void_p(slots.ctypes.data), d.B,
-                                                     _ptr(d.ws), d.ws.numel(), *[_ptr(t) for t in pts], _stream()), name)
+    _call(name, d.cells, d.cells.shape[1], slots, d.B, d.ws, d.ws.numel(), *pts)
     return _head(pts, d.n_cell)
 
 
@@ -987,8 +922,7 @@ def _refined_surface(res, points, surface, mask, scale, K, edges):
     """:func:`_surface_rows` of the refined points, at their centroids (pcseg_surface_pack_refined)."""
     B, cap, n = res["stats"].shape[0], res["stats"].shape[1], points.ids.shape[0]
     rc = torch.empty((n + 1, 2), dtype=torch.float64, device=points.ids.device)
-    _lib.check(_lib.load().pcseg_surface_pack_refined(_ptr(_req(res["ws_stats"], torch.int64, 3)), cap, _ptr(points.ids),
-                                                      _ptr(points.frame_offsets), n, B, _ptr(rc), _stream()), "surface_pack_refined")
+    _call("surface_pack_refined", _req(res["ws_stats"], torch.int64, 3), cap, points.ids, points.frame_offsets, n, B, rc)
     return _surface_rows(points._replace(coords=rc[:n]), surface, mask, scale, K, edges)
 
 
@@ -1197,39 +1131,35 @@ def label_parent(labels_a, labels_r, counts_r, cls_a=None, cap=None, stats_r=Non
     cls_r = torch.empty((B, cap), dtype=torch.uint8, device=dev)
     overflow = torch.empty((B,), dtype=torch.int32, device=dev)
     n_spilled = torch.empty((1,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    nbytes = lib.pcseg_label_parent_workspace_bytes(B, H, W, cap)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_label_parent(_ptr(la), _ptr(lr), _ptr(counts_r), _ptr(stats_r), _ptr(cls_a), _ptr(parent),
-                                      _ptr(parent_px), _ptr(n_overlap), _ptr(cls_r), _ptr(overflow), _ptr(n_spilled), B, H, W,
-                                      cap, _ptr(ws), nbytes, _stream()), "label_parent")
+    _call("label_parent", la, lr, counts_r, stats_r, cls_a, parent, parent_px, n_overlap, cls_r, overflow, n_spilled, B, H, W, cap,
+          ws=(B, H, W, cap))
     out = (parent, parent_px, n_overlap, cls_r, overflow)
     return out + (n_spilled,) if return_spilled else out
 
 
-def _pair_fill(entry, head, shape, dev, nbytes):
+def _pair_fill(entry, head, shape, dev, query):
     """The first call of a per-frame pair table (csrc/pair_table.h), ``pcseg_<entry>(*head, overflow, offsets, totals, B, H, W,
-    workspace, nbytes, stream)``: the workspace of ``nbytes`` (the table's size query), ``overflow`` int32 (B,), ``offsets``
+    workspace, nbytes, stream)``: the workspace of the table's size query at ``query``, ``overflow`` int32 (B,), ``offsets``
     int64 (B + 1,) and ``totals`` int64 (2,) = (rows, frames whose table was full).  Nothing is read back.  Returns the state
     the second calls need."""
     B = shape[0]
-    st = {"B": B, "nbytes": nbytes, "ws": _ws(nbytes, dev), "overflow": torch.empty((B,), dtype=torch.int32, device=dev),
+    ws, nbytes = _workspace(entry, dev, *query)
+    st = {"B": B, "nbytes": nbytes, "ws": ws, "overflow": torch.empty((B,), dtype=torch.int32, device=dev),
           "offsets": torch.empty((B + 1,), dtype=torch.int64, device=dev), "totals": torch.empty((2,), dtype=torch.int64, device=dev)}
-    _lib.check(getattr(_lib.load(), "pcseg_" + entry)(*head, _ptr(st["overflow"]), _ptr(st["offsets"]), _ptr(st["totals"]), *shape,
-                                                      _ptr(st["ws"]), nbytes, _stream()), entry)
+    _call(entry, *head, st["overflow"], st["offsets"], st["totals"], *shape, ws=(ws, nbytes))
     return st
 
 
 def _pair_rows(st, columns, write):
     """The second call on :func:`_pair_fill`'s state: the one host read (``totals``), the row buffers ``key`` int64, ``frame``
     int32 and one per (name, dtype, trailing shape) of ``columns`` -- each with a spare row: never a null pointer --,
-    ``write(offsets, buffers, workspace, nbytes)`` with the buffers' pointers by name, and the rows in (frame, key) order.
+    ``write(offsets, buffers, workspace, nbytes)`` with the buffers by name, and the rows in (frame, key) order.
     Returns ``(rows, n_overflow, sorted)``: ``sorted`` holds ``key``, ``frame`` (int64) and the columns."""
     dev = st["totals"].device
     rows, n_over = (int(v) for v in st["totals"].cpu())
     buf = {name: torch.empty((rows + 1,) + tuple(shape), dtype=dtype, device=dev)
            for name, dtype, shape in (("key", torch.int64, ()), ("frame", torch.int32, ())) + tuple(columns)}
-    write(_ptr(st["offsets"]), {name: _ptr(t) for name, t in buf.items()}, _ptr(st["ws"]), st["nbytes"])
+    write(st["offsets"], buf, st["ws"], st["nbytes"])
     # (frame, key) order: the rows of a frame are contiguous already, in table order -- two stable sorts, plumbing; the
     # frames' offsets hold for the sorted rows too
     key, frame = buf["key"][:rows], buf["frame"][:rows].to(torch.int64)
@@ -1260,12 +1190,9 @@ def _contingency_rows(labels_t, labels_s, cap_t, cap_s, pair_cap):
     if pair_cap is None:
         pair_cap = 1 << (4 * (cap_t + cap_s) + 64 - 1).bit_length()
     pair_cap = int(pair_cap)
-    lib = _lib.load()
-    st = _pair_fill("label_contingency", (_ptr(lt), _ptr(ls), cap_t, cap_s, pair_cap), (B, H, W), dev,
-                    lib.pcseg_contingency_workspace_bytes(B, pair_cap))
-    rows, n_over, r = _pair_rows(st, (("n", torch.int64, ()),), lambda offsets, out, ws, nbytes: _lib.check(
-        lib.pcseg_contingency_write(pair_cap, offsets, out["key"], out["frame"], out["n"], B, ws, nbytes, _stream()),
-        "contingency_write"))
+    st = _pair_fill("label_contingency", (lt, ls, cap_t, cap_s, pair_cap), (B, H, W), dev, (B, pair_cap))
+    rows, n_over, r = _pair_rows(st, (("n", torch.int64, ()),), lambda offsets, out, ws, nbytes: _call(
+        "contingency_write", pair_cap, offsets, out["key"], out["frame"], out["n"], B, ws=(ws, nbytes)))
     return {"key": r["key"], "frame": r["frame"], "n": r["n"], "offsets": st["offsets"], "rows": rows, "overflow": st["overflow"],
             "n_overflow": n_over, "cap_t": cap_t, "cap_s": cap_s, "pair_cap": pair_cap, "shape": (B, H, W)}
 
@@ -1285,10 +1212,8 @@ def _agreement_match(rows, thresholds):
            "best_s": new((B, cap_s, 3), torch.int32), "iou_s": new((B, cap_s), torch.float64),
            "match_t": new((B, cap_t), torch.uint8), "match_s": new((B, cap_s), torch.uint8),
            "frame_ints": new((B, 6 + len(thr)), torch.int64)}
-    _lib.check(_lib.load().pcseg_agreement_match(
-        _ptr(rows["key"]), _ptr(rows["n"]), _ptr(rows["offsets"]), rows["rows"], cap_t, cap_s, ctypes.cast(thr_arg, ctypes.c_void_p),
-        len(thr), _ptr(out["area_t"]), _ptr(out["area_s"]), _ptr(out["best_t"]), _ptr(out["iou_t"]), _ptr(out["best_s"]),
-        _ptr(out["iou_s"]), _ptr(out["match_t"]), _ptr(out["match_s"]), _ptr(out["frame_ints"]), B, _stream()), "agreement_match")
+    _call("agreement_match", rows["key"], rows["n"], rows["offsets"], rows["rows"], cap_t, cap_s, thr_arg, len(thr), out["area_t"],
+          out["area_s"], out["best_t"], out["iou_t"], out["best_s"], out["iou_s"], out["match_t"], out["match_s"], out["frame_ints"], B)
     return out
 
 
@@ -1319,7 +1244,6 @@ def agreement_scores(frame_ints, iou_t, match_t, frame, t, s, n, area_t, area_s,
     (``skimage.metrics.variation_of_information(T, S)``: label 0 and n(0, 0) included), (B,).  Sums of floats are
     ``math.fsum``: exactly rounded, so no order enters."""
     import math
-    import numpy as np
     B = frame_ints.shape[0]
     out = {k: np.zeros((B, n_thr), np.float64) for k in AGREEMENT_SCORES}
     for k in ("are", "are_precision", "are_recall", "vi_split", "vi_merge"):
@@ -1395,7 +1319,6 @@ def agreement_tables(ag, frame_ids=None):
     ``agreement_pairs`` (one row per pair of a truth label and a test label that share pixels), ``agreement_rois`` /
     ``agreement_truth`` (one row per test / truth label with pixels, in label order) and ``frames_agreement`` (one row per
     frame).  ``frame_ids``: the frames' ids (default: their position in the batch)."""
-    import numpy as np
     thr = ag["thresholds"]
     host = {k: ag[k].cpu().numpy() for k in ("frame", "t", "s", "n", "area_t", "area_s", "best_t", "best_s", "iou_t", "iou_s", "match_t",
                                            "match_s", "frame_ints")}
@@ -1442,7 +1365,7 @@ def border_block():
     """``(R, C, lds_labels)`` of csrc/borders.hip: rows and columns of a block of the fill kernel, and the ``cap + 1`` up to
     which the merge keeps its parents in LDS."""
     out = (ctypes.c_int32 * 3)()
-    _lib.check(_lib.load().pcseg_border_block(ctypes.cast(out, ctypes.c_void_p)), "border_block")
+    _call("border_block", out)
     return tuple(int(v) for v in out)
 
 
@@ -1459,8 +1382,7 @@ def _border_fill(labels, strength, conn, cap, pair_cap):
         cap = int(labels.max().item())
     cap = max(int(cap), 1)
     pair_cap = 4 * cap if pair_cap is None else int(pair_cap)
-    st = _pair_fill("label_borders", (_ptr(labels), _ptr(strength), fstride, cap, conn, pair_cap), (B, H, W), labels.device,
-                    _lib.load().pcseg_label_borders_workspace_bytes(B, pair_cap, cap))
+    st = _pair_fill("label_borders", (labels, strength, fstride, cap, conn, pair_cap), (B, H, W), labels.device, (B, pair_cap, cap))
     st.update(labels=labels, cap=cap, pair_cap=pair_cap)
     return st
 
@@ -1481,9 +1403,9 @@ def label_borders(labels, strength, conn=8, cap=None, pair_cap=None):
     slot takes 24 bytes: 96 ``cap`` bytes of table per frame."""
     st = _border_fill(labels, strength, conn, cap, pair_cap)
     _, n_over, r = _pair_rows(st, (("links", torch.int32, ()), ("sum", torch.int64, ()), ("saddle", torch.float32, ())),
-                              lambda offsets, out, ws, nbytes: _lib.check(_lib.load().pcseg_label_borders_write(
-                                  st["pair_cap"], st["cap"], offsets, out["key"], out["frame"], out["links"], out["sum"], out["saddle"],
-                                  st["B"], ws, nbytes, _stream()), "label_borders_write"))
+                              lambda offsets, out, ws, nbytes: _call(
+                                  "label_borders_write", st["pair_cap"], st["cap"], offsets, out["key"], out["frame"], out["links"],
+                                  out["sum"], out["saddle"], st["B"], ws=(ws, nbytes)))
     a, b = _pair_ab(r["key"])
     links, total = r["links"].to(torch.int64), r["sum"]
     mean = total.to(torch.float64) / (links.to(torch.float64) * 4294967296.0)
@@ -1499,8 +1421,7 @@ def relabel_map(labels, label_map):
     if label_map.shape[0] != B or label_map.shape[1] < 2:
         raise ValueError("label_map must be (B, cap + 1)")
     out = torch.empty_like(labels)
-    _lib.check(_lib.load().pcseg_relabel_map(_ptr(labels), _ptr(label_map), label_map.shape[1] - 1, _ptr(out), B, H, W, _stream()),
-               "relabel_map")
+    _call("relabel_map", labels, label_map, label_map.shape[1] - 1, out, B, H, W)
     return out
 
 
@@ -1529,9 +1450,8 @@ def merge_by_border(labels, strength, below, by="mean", conn=8, counts=None, cap
             raise ValueError("counts must be (B,)")
     label_map = torch.empty((B, cap + 1), dtype=torch.int32, device=dev)
     n_merged = torch.empty((B,), dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().pcseg_border_merge(st["pair_cap"], cap, _ptr(counts), below, _BORDER_BY[by], _ptr(st["overflow"]),
-                                              _ptr(label_map), _ptr(n_merged), B, _ptr(st["ws"]), st["nbytes"], _stream()),
-               "border_merge")
+    _call("border_merge", st["pair_cap"], cap, counts, below, _BORDER_BY[by], st["overflow"], label_map, n_merged, B,
+          ws=(st["ws"], st["nbytes"]))
     return relabel_map(st["labels"], label_map), n_merged, label_map, st["overflow"]
 
 
@@ -1588,11 +1508,9 @@ def refined_tables(res, frame_ids, tables, table_ws, table_rows, check=False, po
     lp = label_parent(res["labels"], res["ws_labels"], res["n_markers"], cls_a=res["cls_out"], cap=cap, stats_r=res["ws_stats"])
     rc = classify_regions(res["ws_stats"], lp[3], res["n_markers"], tables)
     ri, keep = refined_inputs(res, lp, rc, frame_ids, len(tables.slot_names))
-    lib = _lib.load()
-    nbytes = lib.pcseg_refined_workspace_bytes(B, cap)
-    ws = _ws(nbytes, dev)
+    ws = _workspace("refined_layout", dev, B, cap)
     totals = torch.empty((2,), dtype=torch.int64, device=dev)
-    _lib.check(lib.pcseg_refined_layout(ctypes.byref(ri), _ptr(totals), _ptr(ws), nbytes, _stream()), "refined_layout")
+    _call("refined_layout", ctypes.byref(ri), totals, ws=ws)
     n_pts, n_over = (int(v) for v in totals.cpu())
     if check and n_over:
         raise RuntimeError("refined ROI parent label above the region table capacity: raise FramePipeline(cap=...)")
@@ -1602,9 +1520,7 @@ def refined_tables(res, frame_ids, tables, table_ws, table_rows, check=False, po
     resolution = torch.empty((n_cell + 1, 5), dtype=torch.float64, device=dev)
     frames = torch.empty((B, 2 + 5 * K), dtype=torch.float64, device=dev)
     pts = _alloc_points(n_pts, B, dev) if points else Points(None, None, None, None)
-    _lib.check(lib.pcseg_refined_table_write(ctypes.byref(ri), _ptr(table_ws), table_ws.numel(), _ptr(refined), _ptr(resolution),
-                                             _ptr(frames), *[_ptr(t) for t in pts], _ptr(ws), nbytes, _stream()),
-               "refined_table_write")
+    _call("refined_table_write", ctypes.byref(ri), table_ws, table_ws.numel(), refined, resolution, frames, *pts, ws=ws)
     out = {"refined": refined[:n_roi], "cell_resolution": resolution[:n_cell], "frames_refined": frames,
            "parent_overflow": lp[4], "refined_nan_flag": rc["nan_flag"], "kind_r": rc["kind"], "slot_r": rc["slot_of"]}
     if points:
@@ -1628,7 +1544,7 @@ def point_neighbours(xy, slot, ids, frame_offsets, K, scale, edges=None):
     n, B, K = xy.shape[0], frame_offsets.shape[0] - 1, int(K)
     if xy.shape[1] != 2 or slot.shape[0] != n or ids.shape[0] != n:
         raise ValueError("xy must be (n, 2) with n slots and ids")
-    e, e_ptr, n_edges = _edges_arg(edges)
+    e, n_edges = _edges_arg(edges)
     dev = xy.device
     dist = torch.empty((n + 1, K), dtype=torch.float64, device=dev)  # (a spare row: never a null pointer)
     nn_id = torch.empty((n + 1, K), dtype=torch.int32, device=dev)
@@ -1638,11 +1554,8 @@ def point_neighbours(xy, slot, ids, frame_offsets, K, scale, edges=None):
         hist = torch.empty((max(B, 1), P, max(e.shape[0] + 1, 1)), dtype=torch.int64, device=dev)
     if B < 1:
         return dist[:n], nn_id[:n], (hist[:0] if hist is not None else None)
-    lib = _lib.load()
-    nbytes = lib.pcseg_neighbours_workspace_bytes(n, B, K, n_edges)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_point_neighbours(_ptr(xy), _ptr(slot), _ptr(ids), _ptr(frame_offsets), n, B, K, float(scale),
-                                          e_ptr, n_edges, _ptr(dist), _ptr(nn_id), _ptr(hist), _ptr(ws), nbytes, _stream()), "point_neighbours")
+    _call("point_neighbours", xy, slot, ids, frame_offsets, n, B, K, float(scale), e, n_edges, dist, nn_id, hist,
+          ws=(n, B, K, n_edges))
     return dist[:n], nn_id[:n], hist
 
 
@@ -1651,7 +1564,7 @@ MIXING_FIELDS = ("obs", "lo", "hi", "sum", "n_le", "n_ge", "cum_obs", "cum_lo", 
 
 def mixing_tile():
     """The points of one LDS tile of :func:`pair_label_mixing`'s pair walk (larger frames: tile against tile)."""
-    return int(_lib.load().pcseg_mixing_tile())
+    return int(_lib.load().pcseg_mixing_tile())  # (not through _call: what it returns is the answer, not a status)
 
 
 def pair_label_mixing(xy, slot, frame_offsets, K, scale, edges, permutations, seed=0, frame_keys=None, counts=False):
@@ -1677,7 +1590,7 @@ def pair_label_mixing(xy, slot, frame_offsets, K, scale, edges, permutations, se
     n, B, K, P = xy.shape[0], frame_offsets.shape[0] - 1, int(K), int(permutations)
     if xy.shape[1] != 2 or slot.shape[0] != n:
         raise ValueError("xy must be (n, 2) with n slots")
-    e, e_ptr, n_edges = _edges_arg(edges)
+    e, n_edges = _edges_arg(edges)
     if e is None:
         raise ValueError("pair_label_mixing needs edges")
     dev = xy.device
@@ -1692,16 +1605,12 @@ def pair_label_mixing(xy, slot, frame_offsets, K, scale, edges, permutations, se
         if counts:
             out["counts"] = torch.zeros((0, max(P, 0) + 1, Q, m), dtype=torch.int64, device=dev)
         return out
-    lib = _lib.load()
-    nbytes = lib.pcseg_mixing_workspace_bytes(n, B, K, n_edges, P, 0 if counts else 1)
-    ws = _ws(nbytes, dev)
+    ws = _workspace("pair_label_mixing", dev, n, B, K, n_edges, P, 0 if counts else 1)
     env = torch.empty((len(MIXING_FIELDS), B, Q, m), dtype=torch.int64, device=dev)
-    cnt = torch.empty((B, P + 1, Q, m), dtype=torch.int64, device=dev) if counts and nbytes else None
+    cnt = torch.empty((B, P + 1, Q, m), dtype=torch.int64, device=dev) if counts and ws[1] else None  # (0: a shape it refuses)
     spare = torch.empty((2,), dtype=torch.float64, device=dev)  # (an empty point set: never a null pointer)
-    _lib.check(lib.pcseg_pair_label_mixing(_ptr(xy) if n else _ptr(spare), _ptr(slot) if n else _ptr(spare), _ptr(frame_offsets),
-                                           _ptr(frame_keys), n, B, K, float(scale), e_ptr, n_edges, P,
-                                           int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(cnt), _ptr(env), _ptr(ws), nbytes, _stream()),
-               "pair_label_mixing")
+    _call("pair_label_mixing", xy if n else spare, slot if n else spare, frame_offsets, frame_keys, n, B, K, float(scale), e, n_edges,
+          P, int(seed) & 0xFFFFFFFFFFFFFFFF, cnt, env, ws=ws)
     out = dict(zip(MIXING_FIELDS, env))
     if counts:
         out["counts"] = cnt
@@ -1709,9 +1618,8 @@ def pair_label_mixing(xy, slot, frame_offsets, K, scale, edges, permutations, se
 
 
 def _edges_arg(edges):
-    import numpy as np
     e = None if edges is None else np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))  # checked by the library
-    return e, (ctypes.c_void_p(e.ctypes.data) if e is not None else ctypes.c_void_p(0)), (0 if e is None else int(e.shape[0]))
+    return e, (0 if e is None else int(e.shape[0]))
 
 
 def surface_points(x, value_bits, want_points=True):
@@ -1723,24 +1631,20 @@ def surface_points(x, value_bits, want_points=True):
     x = _req(x, torch.uint8, 3)
     B, H, W = x.shape
     dev = x.device
-    lib = _lib.load()
     out = {"bits": torch.empty((B, H, (W + 31) // 32), dtype=torch.int32, device=dev),
            "counts": torch.empty((B,), dtype=torch.int64, device=dev),
            "offsets": torch.empty((B + 1,), dtype=torch.int64, device=dev),
            "area": torch.empty((B,), dtype=torch.int64, device=dev), "shape": (B, H, W)}
-    nbytes = lib.pcseg_surface_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dev)
 
-    def call(points, cap):
-        _lib.check(lib.pcseg_surface_points(_ptr(x), ctypes.c_uint64(int(value_bits)), _ptr(out["bits"]), _ptr(out["counts"]),
-                                            _ptr(out["offsets"]), _ptr(out["area"]), _ptr(points), cap, B, H, W, _ptr(ws), nbytes,
-                                            _stream()), "surface_points")
+    def call(points, cap, ws):
+        return _call("surface_points", x, int(value_bits), out["bits"], out["counts"], out["offsets"], out["area"], points, cap,
+                     B, H, W, ws=ws)
 
-    call(None, 0)
+    ws = call(None, 0, (B, H, W))
     if want_points:
         n = int(out["offsets"][B].item())
         pts = torch.empty((n + 1, 2), dtype=torch.int32, device=dev)
-        call(pts, n)
+        call(pts, n, ws)
         out["points"] = pts[:n]
     return out
 
@@ -1770,19 +1674,15 @@ def surface_distances(points_rc, frame_offsets, surface, scale, mask=None, slot=
         slot = _req(slot, torch.int32, 1)
         if slot.shape[0] != n:
             raise ValueError("slot must be (n,)")
-    e, e_ptr, n_edges = _edges_arg(edges)
+    e, n_edges = _edges_arg(edges)
     K = int(n_types)
     dist = torch.empty((n + 1,), dtype=torch.float64, device=dev)  # (a spare row: never a null pointer)
     nearest = torch.empty((n + 1, 2), dtype=torch.int32, device=dev)
     inside = torch.empty((n + 1,), dtype=torch.uint8, device=dev)
     hist = torch.empty((B, 2, max(K, 1), n_edges + 1), dtype=torch.int64, device=dev) if e is not None else None
     visited = torch.empty((n + 1,), dtype=torch.int32, device=dev) if rows_visited else None
-    lib = _lib.load()
-    nbytes = lib.pcseg_surface_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_surface_distances(_ptr(rc), _ptr(slot), _ptr(foff), n, _ptr(surface["bits"]), _ptr(surface["counts"]),
-                                           _ptr(mask), B, H, W, float(scale), e_ptr, n_edges, K, _ptr(dist), _ptr(nearest),
-                                           _ptr(inside), _ptr(hist), _ptr(visited), _ptr(ws), nbytes, _stream()), "surface_distances")
+    _call("surface_distances", rc, slot, foff, n, surface["bits"], surface["counts"], mask, B, H, W, float(scale), e, n_edges, K, dist,
+          nearest, inside, hist, visited, ws=(B, H, W))
     out = (dist[:n], nearest[:n], inside[:n], hist)
     return out + (visited[:n],) if rows_visited else out
 
@@ -1790,11 +1690,9 @@ def surface_distances(points_rc, frame_offsets, surface, scale, mask=None, slot=
 def surface_thresholds(edges, scale):
     """Host only: for every edge the smallest integer squared distance n with ``sqrt(n) / scale >= edge`` (numpy int64),
     so that ``searchsorted(edges, sqrt(D2) / scale, side="right") - 1 == searchsorted(thresholds, D2, side="right") - 1``."""
-    import numpy as np
-    e, e_ptr, n_edges = _edges_arg(edges)
+    e, n_edges = _edges_arg(edges)
     out = np.zeros(max(n_edges, 1), np.int64)
-    lib = _lib.load()
-    _lib.check(lib.pcseg_surface_thresholds(e_ptr, n_edges, float(scale), ctypes.c_void_p(out.ctypes.data)), "surface_thresholds")
+    _call("surface_thresholds", e, n_edges, float(scale), out)
     return out[:n_edges]
 
 
@@ -1807,14 +1705,10 @@ def surface_shells(surface, mask, edges, scale):
     mask = _req(mask, torch.uint8, 3)
     if tuple(mask.shape) != (B, H, W):
         raise ValueError("mask must have the surface's shape")
-    e, e_ptr, n_edges = _edges_arg(edges)
+    e, n_edges = _edges_arg(edges)
     dev = mask.device
     shells = torch.empty((B, 2, n_edges + 1), dtype=torch.int64, device=dev)
-    lib = _lib.load()
-    nbytes = lib.pcseg_surface_shells_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_surface_shells(_ptr(surface["bits"]), _ptr(surface["counts"]), _ptr(mask), B, H, W, float(scale), e_ptr,
-                                        n_edges, _ptr(shells), _ptr(ws), nbytes, _stream()), "surface_shells")
+    _call("surface_shells", surface["bits"], surface["counts"], mask, B, H, W, float(scale), e, n_edges, shells, ws=(B, H, W))
     return shells
 
 
@@ -1852,17 +1746,13 @@ def nearest_label(labels, sel=None, cap=None, want_site=False):
         if tuple(sel.shape) != (B, int(cap)):
             raise ValueError("sel must be (B, cap)")
     if cap is None:
-        cap = max(int(labels.max().item()), 1)
+        cap = _default_cap(labels)
     cap = int(cap)
     dev = labels.device
     d2 = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     near = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     site = torch.empty((B, H, W), dtype=torch.int32, device=dev) if want_site else None
-    lib = _lib.load()
-    nbytes = lib.pcseg_nearest_label_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dev)
-    _lib.check(lib.pcseg_nearest_label_i32(_ptr(labels), _ptr(sel), cap, _ptr(d2), _ptr(near), _ptr(site), B, H, W, _ptr(ws), nbytes,
-                                           _stream()), "nearest_label")
+    _call("nearest_label_i32", labels, sel, cap, d2, near, site, B, H, W, ws=(B, H, W))
     return d2, near, site
 
 
@@ -1876,7 +1766,6 @@ def _near_pair(near, d2):
 def reach_r2(distance):
     """Host only: the largest integer n with ``np.sqrt(np.float64(n)) <= distance`` (a bisection over that very formula,
     which is non-decreasing in n); -1 = every n up to 2^53 (unbounded), None = none (``distance`` < 0 or NaN)."""
-    import numpy as np
     ok = lambda n: bool(np.sqrt(np.float64(n)) <= distance)
     if not ok(0):
         return None
@@ -1907,7 +1796,7 @@ def territory_labels(near, d2, r2=-1):
     """``near`` where the pixel belongs to it (``0 <= d2 <= r2``; ``r2`` < 0: unbounded), else 0: int32, ``near``'s shape."""
     near, d2 = _near_pair(near, d2)
     out = torch.empty_like(near)
-    _lib.check(_lib.load().pcseg_territory_labels(_ptr(near), _ptr(d2), int(r2), _ptr(out), near.numel(), _stream()), "territory_labels")
+    _call("territory_labels", near, d2, int(r2), out, near.numel())
     return out
 
 
@@ -1942,11 +1831,10 @@ def territory_reduce(near, d2, mask=None, r2=-1, cap=None):
         if tuple(mask.shape) != (B, H, W):
             raise ValueError("mask must have near's shape")
     if cap is None:
-        cap = max(int(near.max().item()), 1)
+        cap = _default_cap(near)
     cap = int(cap)
     out = torch.empty((B, cap, 4), dtype=torch.int64, device=near.device)
-    _lib.check(_lib.load().pcseg_territory_reduce(_ptr(near), _ptr(d2), _ptr(mask), int(r2), cap, _ptr(out), B, H, W, _stream()),
-               "territory_reduce")
+    _call("territory_reduce", near, d2, mask, int(r2), cap, out, B, H, W)
     return out
 
 
@@ -1963,11 +1851,9 @@ def territory_pairs(near, d2, r2=-1, pair_cap=None, slot_of=None, n_types=0):
     B, H, W = near.shape
     dev = near.device
     if pair_cap is None:
-        pair_cap = 8 * (slot_of.shape[1] if slot_of is not None else max(int(near.max().item()), 1))
+        pair_cap = 8 * (slot_of.shape[1] if slot_of is not None else _default_cap(near))
     pair_cap = int(pair_cap)
-    lib = _lib.load()
-    st = _pair_fill("territory_pairs", (_ptr(near), _ptr(d2), int(r2), pair_cap), (B, H, W), dev,
-                    lib.pcseg_territory_pairs_workspace_bytes(B, pair_cap))
+    st = _pair_fill("territory_pairs", (near, d2, int(r2), pair_cap), (B, H, W), dev, (B, pair_cap))
     degree, cap, K = None, 0, int(n_types)
     if slot_of is not None:
         slot_of = _req(slot_of, torch.uint8, 2)
@@ -1975,9 +1861,9 @@ def territory_pairs(near, d2, r2=-1, pair_cap=None, slot_of=None, n_types=0):
         if slot_of.shape[0] != B or not 1 <= K <= 4:
             raise ValueError("slot_of must be (B, cap), with 1 to 4 type slots")
         degree = torch.zeros((B, cap, 2 * K), dtype=torch.int32, device=dev)
-    _, n_over, r = _pair_rows(st, (("counts", torch.int32, (2,)),), lambda offsets, out, ws, nbytes: _lib.check(
-        lib.pcseg_territory_pairs_write(pair_cap, offsets, _ptr(slot_of), cap, K, out["key"], out["frame"], out["counts"], _ptr(degree),
-                                        B, ws, nbytes, _stream()), "territory_pairs_write"))
+    _, n_over, r = _pair_rows(st, (("counts", torch.int32, (2,)),), lambda offsets, out, ws, nbytes: _call(
+        "territory_pairs_write", pair_cap, offsets, slot_of, cap, K, out["key"], out["frame"], out["counts"], degree, B,
+        ws=(ws, nbytes)))
     a, b = _pair_ab(r["key"])
     counts = r["counts"].to(torch.int64)
     return {"frame": r["frame"], "a": a, "b": b, "border": counts[:, 0].contiguous(), "contact": counts[:, 1].contiguous(),
@@ -2017,12 +1903,8 @@ def remove_overlapping(dapi, other, threshold):
     dapi = _req(dapi, torch.uint8, 3)
     other = _req(other, torch.uint8, 3)
     B, H, W = dapi.shape
-    lib = _lib.load()
     out = torch.empty_like(dapi)
-    nbytes = lib.pcseg_overlap_workspace_bytes(B, H, W)
-    ws = _ws(nbytes, dapi.device)
-    _lib.check(lib.pcseg_remove_overlapping(_ptr(dapi), _ptr(other), float(threshold), _ptr(out), B, H, W, _ptr(ws),
-                                            nbytes, _stream()), "remove_overlapping")
+    _call("remove_overlapping", dapi, other, float(threshold), out, B, H, W, ws=(B, H, W))
     return out
 
 
@@ -2030,10 +1912,9 @@ def otsu_hist(img):
     """256-bin histogram of each frame over its own [min, max] (north_star extension X1)."""
     img = _req(img, torch.float32, 3)
     B, H, W = img.shape
-    lib = _lib.load()
     hist = torch.zeros((B, 256), dtype=torch.int64, device=img.device)
     lohi = torch.zeros((B, 2), dtype=torch.float32, device=img.device)
-    _lib.check(lib.pcseg_otsu_hist_f32(_ptr(img), _ptr(hist), _ptr(lohi), B, H, W, _stream()), "otsu_hist")
+    _call("otsu_hist_f32", img, hist, lohi, B, H, W)
     return hist, lohi
 
 
@@ -2041,9 +1922,8 @@ def morph3x3(mask, erode):
     """3x3 binary erosion / dilation (north_star extension X2)."""
     mask = _req(mask, torch.uint8, 3)
     B, H, W = mask.shape
-    lib = _lib.load()
     out = torch.empty_like(mask)
-    _lib.check(lib.pcseg_morph3x3(_ptr(mask), _ptr(out), int(bool(erode)), B, H, W, _stream()), "morph3x3")
+    _call("morph3x3", mask, out, int(bool(erode)), B, H, W)
     return out
 
 
@@ -2056,8 +1936,7 @@ def nearest_dist(a, b):
         return out
     if b.shape[0] == 0:
         return out.fill_(float("inf"))
-    lib = _lib.load()
-    _lib.check(lib.pcseg_nearest_dist_f64(_ptr(a), a.shape[0], _ptr(b), b.shape[0], _ptr(out), _stream()), "nearest_dist")
+    _call("nearest_dist_f64", a, a.shape[0], b, b.shape[0], out)
     return out
 
 
@@ -2067,9 +1946,8 @@ def threshold_otsu(img, return_hist=False):
     library returns.  ``return_hist``: also the (B,256) histogram and the (B,2) [min, max] it was taken from."""
     img = _req(img, torch.float32, 3)
     B, H, W = img.shape
-    lib = _lib.load()
     thr = torch.empty((B,), dtype=torch.float64, device=img.device)
     hist = torch.empty((B, 256), dtype=torch.int64, device=img.device)
     lohi = torch.empty((B, 2), dtype=torch.float32, device=img.device)
-    _lib.check(lib.pcseg_otsu_f32(_ptr(img), _ptr(thr), _ptr(hist), _ptr(lohi), B, H, W, _stream()), "otsu")
+    _call("otsu_f32", img, thr, hist, lohi, B, H, W)
     return (thr, hist, lohi) if return_hist else thr

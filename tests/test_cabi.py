@@ -43,13 +43,36 @@ def test_workspace_queries_and_argument_errors(lib):
     assert rc == -1
 
 
+def test_workspace_table_names_a_query_for_every_entry_that_takes_a_workspace(lib):
+    """_lib.WORKSPACE (entry point -> size query) against the signatures: every key is an entry point and every value an
+    exported query; no query is left without an entry; and every entry point with a (void *, size_t) pair among its
+    arguments is a key, or one of the few that are only ever handed another call's workspace."""
+    import ctypes
+    from particle_col_image_segmentation_amd import _lib
+    queries = {n for n in _lib.SIGNATURES if n.endswith("_workspace_bytes")}
+    assert len(_lib.WORKSPACE) >= 40 and set(_lib.WORKSPACE) <= set(_lib.SIGNATURES) - queries
+    named = {"pcseg_%s_workspace_bytes" % q for q in _lib.WORKSPACE.values()}
+    assert named == queries
+    for q in named:
+        assert hasattr(lib, q), q
+    # (c_size_t and c_uint64 are one ctypes type here, so a (pointer, 64-bit class set) pair looks the same in the argtypes: the
+    # header's parameter names tell them apart, and the argtypes must hold the pair wherever the header names one)
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pcseg.h")).read(), flags=re.S)
+    takes = {m.group(1) for m in re.finditer(r"\b(pcseg_[a-z0-9_]+)\s*\(([^;]*)\)\s*;", text) if "workspace_bytes" in m.group(2)}
+    assert takes == set(_lib.WORKSPACE) | set(_lib.WORKSPACE_HANDED_ON)
+    pairs = {n for n, (_, args) in _lib.SIGNATURES.items()
+             if any(a is ctypes.c_void_p and b is ctypes.c_size_t for a, b in zip(args, args[1:]))}
+    assert takes <= pairs and pairs - takes == {"pcseg_region_sums2", "pcseg_region_reduce_sel"}
+
+
 def test_workspace_size_is_what_the_entry_point_carves(lib):
     """A size query and its entry point run the same carve function: one byte less than the query's answer is refused, with
     PCSEG_ERR_WORKSPACE and the message "<who>: workspace too small (<given> < <needed>)".  Every entry point whose argument
     and workspace checks come before its first device call is listed (the device pointers are never dereferenced; what an
     entry reads on the host -- bin edges, list slots, the input structs -- is real); they are never called with `need` bytes.
-    Left out: pcseg_classmap_label_f32, which answers a short workspace as an argument error (-1) -- every other entry point
-    that takes a workspace is here."""
+    Each is held against the query that _lib.WORKSPACE names for it.  Left out: pcseg_classmap_label_f32, which answers a short
+    workspace as an argument error (-1) -- every other entry point that takes a workspace is here (pcseg_table_layout among
+    the readers of the head, below)."""
     import ctypes
     from particle_col_image_segmentation_amd import _lib
     ERR_WORKSPACE = -3
@@ -71,61 +94,63 @@ def test_workspace_size_is_what_the_entry_point_carves(lib):
     tin, rin = inputs(_lib.TableInputs), inputs(_lib.RefinedInputs)
     tref, rref = ctypes.byref(tin), ctypes.byref(rin)
     cases = [
-        ("ccl", shape, "pcseg_ccl8_equal_u8", lambda ws, n: (p, p, p, B, H, W, ws, n, None)),
-        ("ccl", shape, "pcseg_ccl8_bool", lambda ws, n: (p, p, p, B, H, W, ws, n, None)),
-        ("ccl", shape, "pcseg_ccl4_bool", lambda ws, n: (p, p, p, B, H, W, ws, n, None)),
-        ("ccl", shape, "pcseg_compact_labels", lambda ws, n: (p, q, p, B, H, W, ws, n, None)),
-        ("dilate_ccl", shape, "pcseg_dilate_ccl_roots_u8", lambda ws, n: (p, 2, 2, p, B, H, W, ws, n, None)),
-        ("dilate_ccl_runs", shape, "pcseg_dilate_ccl_runs_u8", lambda ws, n: (p, 2, 2, p, p, B, H, W, ws, n, None)),
-        ("dilate_ccl_runs", (3 * B, H, W), "pcseg_dilate_ccl_runs_multi_u8", lambda ws, n: (p, p, 3, 2, p, p, B, H, W, ws, n, None)),
-        ("fill_holes", shape, "pcseg_fill_holes", lambda ws, n: (p, p, B, H, W, ws, n, None)),
-        ("local_maxima", shape, "pcseg_local_maxima_i32", lambda ws, n: (p, p, p, p, B, H, W, ws, n, None)),
-        ("overlap", shape, "pcseg_remove_overlapping", lambda ws, n: (p, p, 0.5, p, B, H, W, ws, n, None)),
-        ("edt", shape, "pcseg_edt_sq_u8", lambda ws, n: (p, p, B, H, W, -1, ws, n, None)),
-        ("edt", shape, "pcseg_edt_sq_lt_f32", lambda ws, n: (p, 0, 0.5, p, p, B, H, W, ws, n, None)),
-        ("edt", shape, "pcseg_dilate_disk_u8", lambda ws, n: (p, 2, 2, q, B, H, W, ws, n, None)),
-        ("edt", shape, "pcseg_fill_particle", lambda ws, n: (p, q, 1, 2, 3, 2, 2, p, B, H, W, ws, n, None)),
-        ("watershed", shape, "pcseg_watershed4_f32", lambda ws, n: (p, 0, p, p, p, p, B, H, W, 0, ws, n, None)),
-        ("merge_groups", (B, cap), "pcseg_merge_groups", lambda ws, n: (p, 0, p, p, p, p, p, B, H, W, cap, cap, ws, n, None)),
-        ("merge_groups", (B, cap), "pcseg_merge_groups_runs", lambda ws, n: (p, p, p, p, p, p, p, B, H, W, cap, cap, ws, n, None)),
-        ("merge_groups", (B, cap), "pcseg_merge_groups_fused", lambda ws, n: (p, p, p, p, p, 0, 1, p, p, p, B, H, W, cap, ws, n, None)),
-        ("merge_groups", (3 * B, cap), "pcseg_merge_groups_fused_multi",
+        (shape, "pcseg_ccl8_equal_u8", lambda ws, n: (p, p, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_ccl8_bool", lambda ws, n: (p, p, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_ccl4_bool", lambda ws, n: (p, p, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_compact_labels", lambda ws, n: (p, q, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_dilate_ccl_roots_u8", lambda ws, n: (p, 2, 2, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_dilate_ccl_runs_u8", lambda ws, n: (p, 2, 2, p, p, B, H, W, ws, n, None)),
+        ((3 * B, H, W), "pcseg_dilate_ccl_runs_multi_u8", lambda ws, n: (p, p, 3, 2, p, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_fill_holes", lambda ws, n: (p, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_local_maxima_i32", lambda ws, n: (p, p, p, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_remove_overlapping", lambda ws, n: (p, p, 0.5, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_edt_sq_u8", lambda ws, n: (p, p, B, H, W, -1, ws, n, None)),
+        (shape, "pcseg_edt_sq_lt_f32", lambda ws, n: (p, 0, 0.5, p, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_dilate_disk_u8", lambda ws, n: (p, 2, 2, q, B, H, W, ws, n, None)),
+        (shape, "pcseg_fill_particle", lambda ws, n: (p, q, 1, 2, 3, 2, 2, p, B, H, W, ws, n, None)),
+        (shape, "pcseg_watershed4_f32", lambda ws, n: (p, 0, p, p, p, p, B, H, W, 0, ws, n, None)),
+        ((B, cap), "pcseg_merge_groups", lambda ws, n: (p, 0, p, p, p, p, p, B, H, W, cap, cap, ws, n, None)),
+        ((B, cap), "pcseg_merge_groups_runs", lambda ws, n: (p, p, p, p, p, p, p, B, H, W, cap, cap, ws, n, None)),
+        ((B, cap), "pcseg_merge_groups_fused", lambda ws, n: (p, p, p, p, p, 0, 1, p, p, p, B, H, W, cap, ws, n, None)),
+        ((3 * B, cap), "pcseg_merge_groups_fused_multi",
          lambda ws, n: (p, p, p, p, p, slots, 3, 1, p, p, p, B, H, W, cap, ws, n, None)),
         # the pair tables: both calls of each, and the merge on the border table
-        ("territory_pairs", (B, pc), "pcseg_territory_pairs", lambda ws, n: (p, p, -1, pc, p, p, p, B, H, W, ws, n, None)),
-        ("territory_pairs", (B, pc), "pcseg_territory_pairs_write", lambda ws, n: (pc, p, None, 0, 0, p, p, p, None, B, ws, n, None)),
-        ("territory_pairs", (B, pc), "pcseg_territory_pairs_write", lambda ws, n: (pc, p, p, cap, 2, p, p, p, p, B, ws, n, None)),
-        ("contingency", (B, pc), "pcseg_label_contingency", lambda ws, n: (p, p, cap, cap, pc, p, p, p, B, H, W, ws, n, None)),
-        ("contingency", (B, pc), "pcseg_contingency_write", lambda ws, n: (pc, p, p, p, p, B, ws, n, None)),
-        ("label_borders", (B, pc, cap), "pcseg_label_borders", lambda ws, n: (p, p, H * W, cap, 8, pc, p, p, p, B, H, W, ws, n, None)),
-        ("label_borders", (B, pc, cap), "pcseg_label_borders_write", lambda ws, n: (pc, cap, p, p, p, p, p, p, B, ws, n, None)),
-        ("label_borders", (B, pc, cap), "pcseg_border_merge", lambda ws, n: (pc, cap, p, 0.5, 0, p, p, p, B, ws, n, None)),
-        ("nearest_label", shape, "pcseg_nearest_label_i32", lambda ws, n: (p, None, cap, p, p, None, B, H, W, ws, n, None)),
-        ("reconstruct", shape, "pcseg_reconstruct_i32", lambda ws, n: (p, q, r, p, B, H, W, 8, 0, 0, ws, n, None)),
-        ("reconstruct", shape, "pcseg_reconstruct_f64", lambda ws, n: (p, q, r, p, B, H, W, 4, 1, 0, ws, n, None)),
-        ("region_shape", shape, "pcseg_region_shape", lambda ws, n: (p, p, p, p, B, H, W, cap, ws, n, None)),
-        ("region_hull", shape + (cap,), "pcseg_region_hull", lambda ws, n: (p, p, p, p, p, B, H, W, cap, ws, n, None)),
-        ("thin_labels", shape, "pcseg_thin_labels", lambda ws, n: (p, p, p, B, H, W, -1, ws, n, None)),
-        ("region_skeleton", shape + (cap,), "pcseg_region_skeleton", lambda ws, n: (p, p, p, p, B, H, W, cap, ws, n, None)),
-        ("mixing", (npt, B, K, 3, 4, 0), "pcseg_pair_label_mixing",
+        ((B, pc), "pcseg_territory_pairs", lambda ws, n: (p, p, -1, pc, p, p, p, B, H, W, ws, n, None)),
+        ((B, pc), "pcseg_territory_pairs_write", lambda ws, n: (pc, p, None, 0, 0, p, p, p, None, B, ws, n, None)),
+        ((B, pc), "pcseg_territory_pairs_write", lambda ws, n: (pc, p, p, cap, 2, p, p, p, p, B, ws, n, None)),
+        ((B, pc), "pcseg_label_contingency", lambda ws, n: (p, p, cap, cap, pc, p, p, p, B, H, W, ws, n, None)),
+        ((B, pc), "pcseg_contingency_write", lambda ws, n: (pc, p, p, p, p, B, ws, n, None)),
+        ((B, pc, cap), "pcseg_label_borders", lambda ws, n: (p, p, H * W, cap, 8, pc, p, p, p, B, H, W, ws, n, None)),
+        ((B, pc, cap), "pcseg_label_borders_write", lambda ws, n: (pc, cap, p, p, p, p, p, p, B, ws, n, None)),
+        ((B, pc, cap), "pcseg_border_merge", lambda ws, n: (pc, cap, p, 0.5, 0, p, p, p, B, ws, n, None)),
+        (shape, "pcseg_nearest_label_i32", lambda ws, n: (p, None, cap, p, p, None, B, H, W, ws, n, None)),
+        (shape, "pcseg_reconstruct_i32", lambda ws, n: (p, q, r, p, B, H, W, 8, 0, 0, ws, n, None)),
+        (shape, "pcseg_reconstruct_f64", lambda ws, n: (p, q, r, p, B, H, W, 4, 1, 0, ws, n, None)),
+        (shape, "pcseg_region_shape", lambda ws, n: (p, p, p, p, B, H, W, cap, ws, n, None)),
+        (shape + (cap,), "pcseg_region_hull", lambda ws, n: (p, p, p, p, p, B, H, W, cap, ws, n, None)),
+        (shape, "pcseg_thin_labels", lambda ws, n: (p, p, p, B, H, W, -1, ws, n, None)),
+        (shape + (cap,), "pcseg_region_skeleton", lambda ws, n: (p, p, p, p, B, H, W, cap, ws, n, None)),
+        ((npt, B, K, 3, 4, 0), "pcseg_pair_label_mixing",
          lambda ws, n: (p, p, p, p, npt, B, K, 1.0, edges, 3, 4, 7, p, p, ws, n, None)),
-        ("mixing", (npt, B, K, 3, 4, 1), "pcseg_pair_label_mixing",
+        ((npt, B, K, 3, 4, 1), "pcseg_pair_label_mixing",
          lambda ws, n: (p, p, p, p, npt, B, K, 1.0, edges, 3, 4, 7, None, p, ws, n, None)),
-        ("neighbours", (npt, B, K, 0), "pcseg_point_neighbours",
+        ((npt, B, K, 0), "pcseg_point_neighbours",
          lambda ws, n: (p, p, p, p, npt, B, K, 1.0, None, 0, p, p, None, ws, n, None)),
-        ("neighbours", (npt, B, K, 3), "pcseg_point_neighbours",
+        ((npt, B, K, 3), "pcseg_point_neighbours",
          lambda ws, n: (p, p, p, p, npt, B, K, 1.0, edges, 3, p, p, p, ws, n, None)),
-        ("surface", shape, "pcseg_surface_points", lambda ws, n: (p, 2, p, p, p, p, None, 0, B, H, W, ws, n, None)),
-        ("surface", shape, "pcseg_surface_distances",
+        (shape, "pcseg_surface_points", lambda ws, n: (p, 2, p, p, p, p, None, 0, B, H, W, ws, n, None)),
+        (shape, "pcseg_surface_distances",
          lambda ws, n: (p, None, p, npt, p, p, None, B, H, W, 1.0, None, 0, 0, p, p, None, None, None, ws, n, None)),
-        ("surface_shells", shape, "pcseg_surface_shells", lambda ws, n: (p, p, p, B, H, W, 1.0, edges, 3, p, ws, n, None)),
-        ("label_parent", shape + (cap,), "pcseg_label_parent",
+        (shape, "pcseg_surface_shells", lambda ws, n: (p, p, p, B, H, W, 1.0, edges, 3, p, ws, n, None)),
+        (shape + (cap,), "pcseg_label_parent",
          lambda ws, n: (p, p, p, None, None, p, p, p, None, p, None, B, H, W, cap, ws, n, None)),
-        ("table", (B, cap), "pcseg_table_write", lambda ws, n: (tref, p, p, p, p, ws, n, None)),
-        ("refined", (B, cap), "pcseg_refined_layout", lambda ws, n: (rref, p, ws, n, None)),
-        ("refined", (B, cap), "pcseg_refined_table_write", lambda ws, n: (rref, p, 1 << 20, p, p, p, None, None, None, None, ws, n, None)),
+        ((B, cap), "pcseg_table_write", lambda ws, n: (tref, p, p, p, p, ws, n, None)),
+        ((B, cap), "pcseg_refined_layout", lambda ws, n: (rref, p, ws, n, None)),
+        ((B, cap), "pcseg_refined_table_write", lambda ws, n: (rref, p, 1 << 20, p, p, p, None, None, None, None, ws, n, None)),
     ]
-    for query, qargs, entry, args in cases:
+    assert {entry for _, entry, _ in cases} == set(_lib.WORKSPACE) - {"pcseg_classmap_label_f32", "pcseg_table_layout"}
+    for qargs, entry, args in cases:
+        query = _lib.WORKSPACE[entry]
         need = getattr(lib, "pcseg_%s_workspace_bytes" % query)(*qargs)
         assert need > 0 and need % 256 == 0, (query, need)
         assert entry in _lib.SIGNATURES

@@ -66,38 +66,34 @@ def _reference(table):
 
 def _run(table, pair_cap):
     """both calls of one table through the protocol's helpers: (state of the fill, rows, n_overflow, sorted rows, degree)"""
-    from particle_col_image_segmentation_amd import _lib, ops
+    from particle_col_image_segmentation_amd import ops
     lab, val, slot_of = _inputs()
     dev = torch.device("cuda")
-    lib = _lib.load()
     L = torch.from_numpy(lab).to(dev)
-    ptr, stream = ops._ptr, ops._stream
     degree = None
     if table == "territory":
         d2 = torch.where(L > 0, 0, -1).to(torch.int32)
         slots = torch.from_numpy(slot_of).to(dev)
         degree = torch.zeros((B, CAP, 2 * K), dtype=torch.int32, device=dev)
-        nbytes = lib.pcseg_territory_pairs_workspace_bytes(B, pair_cap)
-        fill = ("territory_pairs", (ptr(L), ptr(d2), -1, pair_cap))
+        query = (B, pair_cap)
+        fill = ("territory_pairs", (L, d2, -1, pair_cap))
         columns = (("counts", torch.int32, (2,)),)
-        write = lambda off, out, ws, n: _lib.check(lib.pcseg_territory_pairs_write(
-            pair_cap, off, ptr(slots), CAP, K, out["key"], out["frame"], out["counts"], ptr(degree), B, ws, n, stream()),
-            "territory_pairs_write")
+        write = lambda off, out, ws, n: ops._call(
+            "territory_pairs_write", pair_cap, off, slots, CAP, K, out["key"], out["frame"], out["counts"], degree, B, ws=(ws, n))
     elif table == "contingency":
-        nbytes = lib.pcseg_contingency_workspace_bytes(B, pair_cap)
-        fill = ("label_contingency", (ptr(L), ptr(L), CAP, CAP, pair_cap))
+        query = (B, pair_cap)
+        fill = ("label_contingency", (L, L, CAP, CAP, pair_cap))
         columns = (("n", torch.int64, ()),)
-        write = lambda off, out, ws, n: _lib.check(lib.pcseg_contingency_write(
-            pair_cap, off, out["key"], out["frame"], out["n"], B, ws, n, stream()), "contingency_write")
+        write = lambda off, out, ws, n: ops._call(
+            "contingency_write", pair_cap, off, out["key"], out["frame"], out["n"], B, ws=(ws, n))
     else:
         V = torch.from_numpy(val).to(dev)
-        nbytes = lib.pcseg_label_borders_workspace_bytes(B, pair_cap, CAP)
-        fill = ("label_borders", (ptr(L), ptr(V), H * W, CAP, 8, pair_cap))
+        query = (B, pair_cap, CAP)
+        fill = ("label_borders", (L, V, H * W, CAP, 8, pair_cap))
         columns = (("links", torch.int32, ()), ("sum", torch.int64, ()), ("saddle", torch.float32, ()))
-        write = lambda off, out, ws, n: _lib.check(lib.pcseg_label_borders_write(
-            pair_cap, CAP, off, out["key"], out["frame"], out["links"], out["sum"], out["saddle"], B, ws, n, stream()),
-            "label_borders_write")
-    st = ops._pair_fill(*fill, (B, H, W), dev, nbytes)
+        write = lambda off, out, ws, n: ops._call(
+            "label_borders_write", pair_cap, CAP, off, out["key"], out["frame"], out["links"], out["sum"], out["saddle"], B, ws=(ws, n))
+    st = ops._pair_fill(*fill, (B, H, W), dev, query)
     rows, n_over, r = ops._pair_rows(st, columns, write)
     torch.cuda.synchronize()
     return st, rows, n_over, {k: v.cpu().numpy() for k, v in r.items()}, degree
