@@ -13,7 +13,9 @@
  *     row-major array (B, H, W) or (B, C, H, W); buffers are caller-owned
  *     (torch tensors' data_ptr()); the library allocates nothing persistent;
  *   - scratch comes from a caller-provided workspace sized by the matching
- *     *_workspace_bytes(B, H, W) query (256-byte aligned device memory);
+ *     *_workspace_bytes(B, H, W) query (256-byte aligned device memory); a
+ *     workspace's prior contents never affect a result, and nothing beyond
+ *     the size the query named is written;
  *   - work is enqueued on `stream` (a hipStream_t) and every compute entry point
  *     returns without waiting for it: no hidden host synchronisation, fixed
  *     points included (they finish in device-side tail kernels);
