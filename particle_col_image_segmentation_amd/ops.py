@@ -4,6 +4,10 @@ Every function takes ``(B, H, W)`` (or ``(B, C, H, W)``) CUDA tensors, allocates
 its outputs and workspace through torch's caching allocator and enqueues the
 libpcseg kernels on torch's current stream.  PyTorch is plumbing here (device
 memory + streams); all arithmetic is in ``csrc/*.hip``.
+
+The library takes bare pointers, so the wrappers are where an argument's device, dtype, rank and size are checked, against
+each other too, before anything is enqueued: what is refused, what is copied and what is read in place is stated once, in
+DESIGN.md ("The argument contract of ops"), and held by tests/ops_contract_cases.py.
 """
 import collections
 import ctypes
@@ -23,9 +27,20 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _on_device(t):
+    """The one test of "a tensor the library can be handed": a torch tensor in device memory (the HIP path has no CPU
+    fallback).  Every wrapper's first check goes through here (tests/test_ops_contract_cpu.py replaces it to run the argument
+    checks on a machine without a GPU)."""
+    return isinstance(t, torch.Tensor) and t.is_cuda
+
+
+_NOT_ON_DEVICE = "expected a CUDA tensor (the HIP path has no CPU fallback)"
+
+
 def _req(t, dtype, ndim):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    """An input: on the device, of ``dtype`` (bool is read as uint8) and ``ndim`` dimensions; a non-contiguous one is copied."""
+    if not _on_device(t):
+        raise TypeError(_NOT_ON_DEVICE)
     if t.dtype == torch.bool and dtype == torch.uint8:
         t = t.view(torch.uint8)
     if t.dtype != dtype:
@@ -37,11 +52,26 @@ def _req(t, dtype, ndim):
 
 def _label_batch(labels, what="labels"):
     """An int32 (B, H, W) CUDA tensor of any width and alignment (a contiguous view keeps its base address)."""
-    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
-        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    if not _on_device(labels):
+        raise TypeError(_NOT_ON_DEVICE)
     if labels.dtype != torch.int32 or labels.dim() != 3:
         raise TypeError("%s must be an int32 (B, H, W) tensor" % what)
     return labels if labels.is_contiguous() else labels.contiguous()
+
+
+def _inout(t, dtype, shape, what):
+    """An argument the library writes in place: it is never copied (the result would be lost in the copy) and never written
+    through strides the library does not know, so it must be on the device, of ``dtype`` and ``shape`` (-1: any size) -- and
+    contiguous."""
+    if not _on_device(t):
+        raise TypeError(_NOT_ON_DEVICE)
+    if t.dtype != dtype:
+        raise TypeError("%s: expected dtype %s, got %s" % (what, dtype, t.dtype))
+    if t.dim() != len(shape) or any(v != w and w >= 0 for v, w in zip(t.shape, shape)):
+        raise ValueError("%s of shape %s, expected %s" % (what, tuple(t.shape), shape))
+    if not t.is_contiguous():
+        raise ValueError("%s is written in place: it must be contiguous (strides %s)" % (what, t.stride()))
+    return t
 
 
 def _ws(nbytes, device):
@@ -172,6 +202,8 @@ def region_init(counts, cap, C, shape, device):
     reduction's neutral rows, sums float64 (B, cap, C) zeroed (rows below counts[b]), overflow int32 (B,) cleared."""
     B, H, W = shape
     counts = _req(counts, torch.int32, 1)
+    if counts.shape[0] != B:
+        raise ValueError("counts must have one entry per frame")
     stats = torch.empty((B, cap, 8), dtype=torch.int64, device=device)
     sums = torch.empty((B, cap, C), dtype=torch.float64, device=device)
     overflow = torch.empty((B,), dtype=torch.int32, device=device)
@@ -183,20 +215,24 @@ def region_sums2(labels_a, cls, sum_classes, sums_a, labels_b, sums_b, planes, s
     """Per-label plane sums of two label images in ONE pass over the planes (csrc/reduce.hip region_sums2_col_kernel):
     ``sums_a`` / ``sums_b`` (float64 (B, cap, C), zeroed by ``region_reduce(..., zero_sums=C)`` or ``region_init``) are
     added to in place; image A only under the class values in ``sum_classes`` (bit v = value v, 0 = everywhere).
-    ``stats_b`` / ``overflow_b`` (from ``region_init``): image B's integer columns are accumulated too, by the plane-free pass."""
+    ``stats_b`` / ``overflow_b`` (from ``region_init``): image B's integer columns are accumulated too, by the plane-free pass.
+    The four tables are written in place: each must be contiguous (a copy would take the sums with it)."""
     labels_a = _req(labels_a, torch.int32, 3)
     labels_b = _req(labels_b, torch.int32, 3)
     planes = _req(planes, torch.float32, 4)
-    sums_a = _req(sums_a, torch.float64, 3)
-    sums_b = _req(sums_b, torch.float64, 3)
-    cls = _req(cls, torch.uint8, 3) if cls is not None else None
     B, C, H, W = planes.shape
-    if tuple(labels_a.shape) != (B, H, W) or tuple(labels_b.shape) != (B, H, W) or sums_a.shape[2] != C or sums_b.shape[2] != C:
-        raise ValueError("label images / sums tables do not match the planes")
+    if tuple(labels_a.shape) != (B, H, W) or labels_b.shape != labels_a.shape:
+        raise ValueError("the label images do not match the planes")
+    if cls is not None:
+        cls = _req(cls, torch.uint8, 3)
+        if cls.shape != labels_a.shape:
+            raise ValueError("cls must have the labels' shape")
+    _inout(sums_a, torch.float64, (B, -1, C), "sums_a")
+    _inout(sums_b, torch.float64, (B, -1, C), "sums_b")
     if stats_b is not None:
-        stats_b = _req(stats_b, torch.int64, 3)
-        if tuple(stats_b.shape) != (B, sums_b.shape[1], 8):
-            raise ValueError("stats_b must be (B, cap_b, 8)")
+        _inout(stats_b, torch.int64, (B, sums_b.shape[1], 8), "stats_b")
+    if overflow_b is not None:
+        _inout(overflow_b, torch.int32, (B,), "overflow_b")
     _call("region_sums2", labels_a, cls, int(sum_classes), sums_a.shape[1], sums_a, labels_b, sums_b.shape[1], sums_b, stats_b,
           overflow_b, planes, C, B, H, W)
 
@@ -210,7 +246,8 @@ def region_reduce(labels, counts=None, cls=None, planes=None, cap=None, sum_clas
     Returns (stats int64 (B,cap,8), cls_out uint8 (B,cap) | None, sums float64 (B,cap,C) | None,
     overflow int32 (B,))."""
     labels = _req(labels, torch.int32, 3)
-    B, H, W = labels.shape
+    shape = labels.shape  # (read once: every .shape makes a torch.Size, and this is the launch path)
+    B, H, W = shape
     dev = labels.device
     if cap is None:
         if counts is None:
@@ -224,16 +261,22 @@ def region_reduce(labels, counts=None, cls=None, planes=None, cap=None, sum_clas
     C = 0
     if cls is not None:
         cls = _req(cls, torch.uint8, 3)
+        if cls.shape != shape:
+            raise ValueError("cls must have the labels' shape")
         cls_out = torch.empty((B, cap), dtype=torch.uint8, device=dev)
     if planes is not None:
         planes = _req(planes, torch.float32, 4)
-        C = planes.shape[1]
+        pb, C, ph, pw = planes.shape
+        if pb != B or ph != H or pw != W:
+            raise ValueError("planes must be (B, C, H, W) over the labels' (B, H, W)")
         sums = torch.empty((B, cap, C), dtype=torch.float64, device=dev)
     elif zero_sums:
         C = int(zero_sums)
         sums = torch.empty((B, cap, C), dtype=torch.float64, device=dev)
     if counts is not None:
         counts = _req(counts, torch.int32, 1)
+        if counts.shape[0] != B:
+            raise ValueError("counts must have one entry per frame")
     overflow = torch.empty((B,), dtype=torch.int32, device=dev)
     if sum_classes and (cls is None or planes is None):
         raise ValueError("sum_classes needs cls and planes")
@@ -362,8 +405,10 @@ def region_skeleton(labels, peel, counts, cap=None):
     labels = _label_batch(labels)
     counts = _req(counts, torch.int32, 1)
     B, H, W = labels.shape
-    if not isinstance(peel, torch.Tensor) or not peel.is_cuda or peel.dtype != torch.uint16 or tuple(peel.shape) != (B, H, W):
-        raise TypeError("peel must be a uint16 CUDA tensor of the labels' shape")
+    if not _on_device(peel) or peel.dtype != torch.uint16 or peel.dim() != 3:
+        raise TypeError("peel must be a uint16 (B, H, W) CUDA tensor")
+    if peel.shape != labels.shape:
+        raise ValueError("peel must have the labels' shape")
     peel = peel.contiguous()
     if counts.shape[0] != B:
         raise ValueError("counts must have one entry per frame")
@@ -402,7 +447,7 @@ def edt_sq(mask, cap=-1):
 
 def _plane_view(img):
     """(B,H,W) float32 view whose frames may be strided (a plane of a (B,C,H,W) stack): (tensor, frame stride)."""
-    if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.float32 or img.dim() != 3:
+    if not _on_device(img) or img.dtype != torch.float32 or img.dim() != 3:
         raise TypeError("expected a (B,H,W) float32 CUDA tensor")
     B, H, W = img.shape
     if img.stride(2) == 1 and img.stride(1) == W and (B == 1 or img.stride(0) >= H * W):
@@ -436,6 +481,8 @@ def fill_particle(ds, particle_label, cell_label, overlap_label, dilation_radius
     out = torch.empty_like(ds)
     if overlap_area is None:
         overlap_area = torch.zeros((B,), dtype=torch.int64, device=ds.device)
+    else:
+        _inout(overlap_area, torch.int64, (B,), "overlap_area")
     _call("fill_particle", ds, out, int(particle_label), int(cell_label), int(overlap_label), int(dilation_radius),
           int(dist_threshold), overlap_area, B, H, W, ws=(B, H, W))
     return out, overlap_area
@@ -472,8 +519,8 @@ _SEED_MESSAGES = {"dilation": "Intensity of seed image must be less than that of
 def _gray_pair(seed, mask):
     """two (B, H, W) CUDA tensors of one dtype, int32 or float64 (float32 is widened, which is exact)"""
     for t in (seed, mask):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+        if not _on_device(t):
+            raise TypeError(_NOT_ON_DEVICE)
         if t.dtype not in (torch.int32, torch.float32, torch.float64):
             raise TypeError("expected an int32, float32 or float64 image, got %s" % t.dtype)
         if t.dim() != 3:
@@ -528,8 +575,8 @@ def reconstruct(seed, mask, method="dilation", conn=8, check=True, counters=Fals
 
 
 def _h_extrema(image, h, conn, sign):
-    if not isinstance(image, torch.Tensor) or not image.is_cuda:
-        raise TypeError("expected a CUDA tensor (the HIP path has no CPU fallback)")
+    if not _on_device(image):
+        raise TypeError(_NOT_ON_DEVICE)
     if image.dtype not in (torch.int32, torch.float64) or image.dim() != 3:
         raise TypeError("expected an int32 or float64 (B, H, W) image, got %s %s" % (image.dtype, tuple(image.shape)))
     if not h > 0:
@@ -613,7 +660,10 @@ def watershed(img, markers, mask, mode=0):
     img, fstride = _plane_view(img)
     markers = _req(markers, torch.int32, 3)
     mask = _req(mask, torch.uint8, 3)
-    B, H, W = img.shape
+    shape = img.shape  # (read once: every .shape makes a torch.Size, and this is the launch path)
+    if markers.shape != shape or mask.shape != shape:
+        raise ValueError("img, markers and mask must have one shape")
+    B, H, W = shape
     out = torch.empty((B, H, W), dtype=torch.int32, device=img.device)
     flags = torch.zeros((B,), dtype=torch.int32, device=img.device)
     _call("watershed4_f32", img, fstride, markers, mask, out, flags, B, H, W, int(mode), ws=(B, H, W))
@@ -638,8 +688,18 @@ def dilated_runs(x, value_bits, radius, run_parent=None):
     bits = torch.empty((B, (H + 31) // 32, W), dtype=torch.int32, device=x.device)
     if run_parent is None:
         run_parent = torch.empty((B, H, W), dtype=torch.int32, device=x.device)
+    else:
+        _inout(run_parent, torch.int32, (B, H, W), "run_parent")
     _call("dilate_ccl_runs_u8", x, int(value_bits), int(radius), bits, run_parent, B, H, W, ws=(B, H, W))
     return bits, run_parent
+
+
+def _list_args(B, stats, region_list, n_list):
+    """the region table and one region list per frame of a grouping over ``B`` frames"""
+    if tuple(stats.shape) != (B, stats.shape[1], 8):
+        raise ValueError("stats must be (B, cap, 8)")
+    if region_list.shape[0] != B or n_list.shape[0] != B:
+        raise ValueError("region_list must be (B, list_cap) and n_list (B,)")
 
 
 def merge_groups_runs(bits, run_parent, stats, region_list, n_list):
@@ -652,6 +712,9 @@ def merge_groups_runs(bits, run_parent, stats, region_list, n_list):
     B, H, W = run_parent.shape
     cap = stats.shape[1]
     list_cap = region_list.shape[1]
+    if tuple(bits.shape) != (B, (H + 31) // 32, W):
+        raise ValueError("bits must be (B, ceil(H / 32), W) for run_parent's (B, H, W)")
+    _list_args(B, stats, region_list, n_list)
     group_of = torch.zeros((B, list_cap), dtype=torch.int32, device=stats.device)
     n_groups = torch.zeros((B,), dtype=torch.int32, device=stats.device)
     _call("merge_groups_runs", bits, run_parent, stats, region_list, n_list, group_of, n_groups, B, H, W, cap, list_cap,
@@ -683,7 +746,8 @@ def merge_groups_fused_multi(bits, run_parent, stats, region_lists, n_lists, slo
     M, B, H, W = run_parent.shape
     cap = stats.shape[1]
     n_slots = region_lists.shape[1]
-    if len(slots) != M or bits.shape[0] != M or region_lists.shape[2] != cap or tuple(n_lists.shape) != (B, n_slots):
+    if (len(slots) != M or tuple(bits.shape) != (M, B, (H + 31) // 32, W) or tuple(stats.shape) != (B, cap, 8)
+            or tuple(region_lists.shape) != (B, n_slots, cap) or tuple(n_lists.shape) != (B, n_slots)):
         raise ValueError("masks / lists / region table do not match")
     dev = stats.device
     group_of = torch.empty((M, B, cap), dtype=torch.int32, device=dev)
@@ -708,7 +772,9 @@ def merge_groups_fused(bits, run_parent, stats, region_lists, n_lists, slot):
     B, H, W = run_parent.shape
     cap = stats.shape[1]
     n_slots = region_lists.shape[1]
-    if region_lists.shape[2] != cap or tuple(n_lists.shape) != (B, n_slots):
+    if tuple(bits.shape) != (B, (H + 31) // 32, W) or tuple(stats.shape) != (B, cap, 8):
+        raise ValueError("bits must be (B, ceil(H / 32), W) for run_parent's (B, H, W), stats (B, cap, 8)")
+    if tuple(region_lists.shape) != (B, n_slots, cap) or tuple(n_lists.shape) != (B, n_slots):
         raise ValueError("region lists of shape %s / %s do not match the region table" % (tuple(region_lists.shape), tuple(n_lists.shape)))
     dev = stats.device
     group_of = torch.empty((B, cap), dtype=torch.int32, device=dev)
@@ -729,6 +795,7 @@ def merge_groups(dilated_labels, stats, region_list, n_list, roots=False):
     B, H, W = dl.shape
     cap = stats.shape[1]
     list_cap = region_list.shape[1]
+    _list_args(B, stats, region_list, n_list)
     group_of = torch.zeros((B, list_cap), dtype=torch.int32, device=dl.device)
     n_groups = torch.zeros((B,), dtype=torch.int32, device=dl.device)
     _call("merge_groups", dl, int(bool(roots)), stats, region_list, n_list, group_of, n_groups, B, H, W, cap, list_cap,
@@ -738,8 +805,16 @@ def merge_groups(dilated_labels, stats, region_list, n_list, roots=False):
 
 def group_reduce(stats, region_list, n_list, group_of, n_groups, H, W):
     """member sums of merged groups (tiff_analysis.py:855-872): int64 (B, list_cap, 8)."""
+    stats = _req(stats, torch.int64, 3)
+    region_list = _req(region_list, torch.int32, 2)
+    n_list = _req(n_list, torch.int32, 1)
+    group_of = _req(group_of, torch.int32, 2)
+    n_groups = _req(n_groups, torch.int32, 1)
     B, cap = stats.shape[0], stats.shape[1]
     list_cap = region_list.shape[1]
+    _list_args(B, stats, region_list, n_list)
+    if group_of.shape != region_list.shape or n_groups.shape[0] != B:
+        raise ValueError("group_of must have region_list's shape, n_groups one entry per frame")
     gstats = torch.zeros((B, list_cap, 8), dtype=torch.int64, device=stats.device)
     _call("group_reduce", stats, region_list, n_list, group_of, n_groups, gstats, B, H, W, cap, list_cap)
     return gstats
@@ -785,6 +860,8 @@ def classify_regions(stats, cls_out, counts, tables):
     cls_out = _req(cls_out, torch.uint8, 2)
     counts = _req(counts, torch.int32, 1)
     B, cap = stats.shape[0], stats.shape[1]
+    if tuple(stats.shape) != (B, cap, 8) or tuple(cls_out.shape) != (B, cap) or counts.shape[0] != B:
+        raise ValueError("stats must be (B, cap, 8), cls_out (B, cap), counts (B,)")
     dev = stats.device
     # no fills: the kernel writes kind / slot_of / cells for every region below counts[b], the lists up to their lengths and
     # every per-frame scalar; nothing reads beyond those (eight fill launches per batch, 26 MB of them, for nothing)
@@ -1369,12 +1446,17 @@ def border_block():
     return tuple(int(v) for v in out)
 
 
-def _border_fill(labels, strength, conn, cap, pair_cap):
-    """pcseg_label_borders: the filled tables.  Returns the state the second calls need."""
+def _border_fill(labels, strength, conn, cap, pair_cap, counts=None):
+    """pcseg_label_borders: the filled tables.  Returns the state the second calls need (``counts``, checked before anything
+    is enqueued, among them)."""
     labels = _label_batch(labels)
     strength, fstride = _plane_view(strength)
     if tuple(strength.shape) != tuple(labels.shape):
         raise ValueError("labels and strength must have one shape")
+    if counts is not None:
+        counts = _req(counts, torch.int32, 1)
+        if counts.shape[0] != labels.shape[0]:
+            raise ValueError("counts must be (B,)")
     if conn not in (4, 8):
         raise ValueError("conn must be 4 or 8")
     B, H, W = labels.shape
@@ -1383,7 +1465,7 @@ def _border_fill(labels, strength, conn, cap, pair_cap):
     cap = max(int(cap), 1)
     pair_cap = 4 * cap if pair_cap is None else int(pair_cap)
     st = _pair_fill("label_borders", (labels, strength, fstride, cap, conn, pair_cap), (B, H, W), labels.device, (B, pair_cap, cap))
-    st.update(labels=labels, cap=cap, pair_cap=pair_cap)
+    st.update(labels=labels, cap=cap, pair_cap=pair_cap, counts=counts)
     return st
 
 
@@ -1442,12 +1524,8 @@ def merge_by_border(labels, strength, below, by="mean", conn=8, counts=None, cap
     below = float(below)
     if not 0.0 <= below <= 1.0:
         raise ValueError("below must lie in [0, 1]")
-    st = _border_fill(labels, strength, conn, cap, pair_cap)
-    B, cap, dev = st["B"], st["cap"], st["labels"].device
-    if counts is not None:
-        counts = _req(counts, torch.int32, 1)
-        if counts.shape[0] != B:
-            raise ValueError("counts must be (B,)")
+    st = _border_fill(labels, strength, conn, cap, pair_cap, counts)
+    B, cap, dev, counts = st["B"], st["cap"], st["labels"].device, st["counts"]
     label_map = torch.empty((B, cap + 1), dtype=torch.int32, device=dev)
     n_merged = torch.empty((B,), dtype=torch.int32, device=dev)
     _call("border_merge", st["pair_cap"], cap, counts, below, _BORDER_BY[by], st["overflow"], label_map, n_merged, B,
@@ -1850,16 +1928,17 @@ def territory_pairs(near, d2, r2=-1, pair_cap=None, slot_of=None, n_types=0):
     near, d2 = _near_pair(near, d2)
     B, H, W = near.shape
     dev = near.device
-    if pair_cap is None:
-        pair_cap = 8 * (slot_of.shape[1] if slot_of is not None else _default_cap(near))
-    pair_cap = int(pair_cap)
-    st = _pair_fill("territory_pairs", (near, d2, int(r2), pair_cap), (B, H, W), dev, (B, pair_cap))
     degree, cap, K = None, 0, int(n_types)
-    if slot_of is not None:
+    if slot_of is not None:  # (checked before anything is enqueued)
         slot_of = _req(slot_of, torch.uint8, 2)
         cap = slot_of.shape[1]
         if slot_of.shape[0] != B or not 1 <= K <= 4:
             raise ValueError("slot_of must be (B, cap), with 1 to 4 type slots")
+    if pair_cap is None:
+        pair_cap = 8 * (cap if slot_of is not None else _default_cap(near))
+    pair_cap = int(pair_cap)
+    st = _pair_fill("territory_pairs", (near, d2, int(r2), pair_cap), (B, H, W), dev, (B, pair_cap))
+    if slot_of is not None:
         degree = torch.zeros((B, cap, 2 * K), dtype=torch.int32, device=dev)
     _, n_over, r = _pair_rows(st, (("counts", torch.int32, (2,)),), lambda offsets, out, ws, nbytes: _call(
         "territory_pairs_write", pair_cap, offsets, slot_of, cap, K, out["key"], out["frame"], out["counts"], degree, B,
@@ -1902,6 +1981,8 @@ def remove_overlapping(dapi, other, threshold):
     """combine_cell_positions_and_clusters (tiff_analysis.py:252-287)."""
     dapi = _req(dapi, torch.uint8, 3)
     other = _req(other, torch.uint8, 3)
+    if other.shape != dapi.shape:
+        raise ValueError("dapi and other must have one shape")
     B, H, W = dapi.shape
     out = torch.empty_like(dapi)
     _call("remove_overlapping", dapi, other, float(threshold), out, B, H, W, ws=(B, H, W))
@@ -1931,6 +2012,8 @@ def nearest_dist(a, b):
     """min over b of the Euclidean distance, for every row of a: (na,2), (nb,2) float64 CUDA tensors (.m:260-263)."""
     a = _req(a, torch.float64, 2)
     b = _req(b, torch.float64, 2)
+    if a.shape[1] != 2 or b.shape[1] != 2:
+        raise ValueError("a and b must be (n, 2)")
     out = torch.empty((a.shape[0],), dtype=torch.float64, device=a.device)
     if a.shape[0] == 0:
         return out

@@ -3,7 +3,9 @@
 ``fill_holes``, ``edt_sq`` and ``region_shape`` on a 1 x 64 x 64 input -- N calls in a row with no synchronise between them (one
 after the last, outside the clock: the kernels are a few us each and the queue never fills, so the clock sees the host side
 of a call: checks, allocations, marshalling, the launches) -- and of ``label_contingency`` (a pair table: two calls, its
-readback and its sorts between them).  The best of five repeats of N = 2000 calls (200 for the pair table)."""
+readback and its sorts between them) -- and of ``watershed`` and ``region_reduce`` (with a class map and planes), the two
+wrappers with the most argument checks (profiles/ops_contract).  The best of five repeats of N = 2000 calls (200 for the
+pair table)."""
 import json
 import sys
 import time
@@ -37,11 +39,16 @@ def main():
     labels, counts = ops.label_bool8(mask)
     cap = int(counts.max().item())
     other = torch.roll(labels, 3, dims=2).contiguous()
+    img = torch.rand((1, 64, 64), generator=g).to(dev)
+    planes = torch.rand((1, 5, 64, 64), generator=g).to(dev)
+    markers = labels * (labels % 7 == 1)
     out = {"median5": us_per_call(lambda: ops.median5(mask), 2000),
            "fill_holes": us_per_call(lambda: ops.fill_holes(mask), 2000),
            "edt_sq": us_per_call(lambda: ops.edt_sq(mask), 2000),
            "region_shape": us_per_call(lambda: ops.region_shape(labels, counts, cap=cap), 2000),
-           "label_contingency": us_per_call(lambda: ops.label_contingency(labels, other, cap_t=cap, cap_s=cap), 200)}
+           "label_contingency": us_per_call(lambda: ops.label_contingency(labels, other, cap_t=cap, cap_s=cap), 200),
+           "watershed": us_per_call(lambda: ops.watershed(img, markers, mask, mode=2), 2000),
+           "region_reduce": us_per_call(lambda: ops.region_reduce(labels, counts, mask, planes, cap=cap), 2000)}
     print(json.dumps(out), flush=True)
 
 

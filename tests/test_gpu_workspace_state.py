@@ -6,66 +6,15 @@ library the true size.  The cases of tests/workspace_cases.py run under four sta
 process tends to get), the bytes the same entry left after a call on other data of the same shape, the bytes it left at
 another shape (stale regions land in other regions), every byte 0xFF -- and must give, bit for bit, what they gave under
 zeros, which in turn is held against the CPU reference.  The 4096 bytes behind every workspace must keep their fill."""
-import threading
-
-import numpy as np
 import pytest
 
 import workspace_cases as wc
+from device_helpers import Hooks, to_device as _device, settled as _settled, to_host as _host, same as _same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 SEED = 5
-
-
-class Hooks:
-    """ops._workspace and ops._call with a controlled prior state; ``begin`` a pass, run the case, ``finish`` it."""
-
-    def __init__(self, ops, monkeypatch):
-        self.real_workspace, self.real_call = ops._workspace, ops._call
-        self.lock = threading.Lock()  # the pipeline launches from its lane threads
-        self.begin("zeros", {})
-        monkeypatch.setattr(ops, "_workspace", self.workspace)
-        monkeypatch.setattr(ops, "_call", self.call)
-
-    def begin(self, state, donors):
-        self.state, self.donors = state, donors
-        self.handed, self.seen, self.ordinal, self.by_ptr, self.snaps = [], [], {}, {}, {}
-
-    def workspace(self, entry, device, *query):
-        _, nbytes = self.real_workspace(entry, device, *query)  # the real size query; its buffer is dropped
-        with self.lock:
-            key = (entry, self.ordinal.get(entry, 0))
-            self.ordinal[entry] = key[1] + 1
-        fill = wc.state_fill(self.state, nbytes, wc.donor(self.donors, key))
-        whole = torch.from_numpy(fill).to(device)  # (on the current stream, like the call that follows)
-        with self.lock:
-            self.handed.append((key, nbytes, whole, wc.red_zone(fill, nbytes)))
-            self.by_ptr[whole.data_ptr()] = (key, nbytes)
-        return whole[:max(nbytes, 256)], nbytes  # what ops._ws would have returned: its numel() is handed on by some callers
-
-    def call(self, entry, *args, ws=None):
-        with self.lock:
-            self.seen.append("pcseg_" + entry)
-        pair = self.real_call(entry, *args, ws=ws)
-        if pair is not None:
-            known = self.by_ptr.get(pair[0].data_ptr())
-            if known is not None:  # what the last call on this workspace leaves in it, cloned on the call's stream
-                self.snaps[known[0]] = pair[0][:known[1]].clone()
-        return pair
-
-    def finish(self):
-        """Waits for the device; returns (entries seen, leftovers by (entry, ordinal), touched red zones as messages)."""
-        torch.cuda.synchronize()
-        touched = []
-        for key, nbytes, whole, want in self.handed:
-            got = wc.red_zone(whole, nbytes).cpu().numpy()
-            at = wc.first_changed(got, want)
-            if at >= 0:
-                touched.append("%s (call %d, %d bytes): red zone byte %d is 0x%02x, was 0x%02x" % (key[0], key[1], nbytes, at, got[at], want[at]))
-        snaps = {k: v.cpu().numpy() for k, v in self.snaps.items()}
-        return set(self.seen), snaps, touched
 
 
 @pytest.fixture
@@ -74,39 +23,6 @@ def hooks(monkeypatch):
         pytest.fail("no GPU visible: the HIP path has no CPU fallback")
     from particle_col_image_segmentation_amd import ops
     return ops, Hooks(ops, monkeypatch)
-
-
-def _device(x):
-    return {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in x.items()}
-
-
-def _settled(out):
-    """the outputs as copies of their own (some are views of buffers a later pass reuses), private entries apart"""
-    torch.cuda.synchronize()
-    return {k: (v.clone() if isinstance(v, torch.Tensor) else np.array(v, copy=True)) for k, v in out.items() if not k.startswith("_")}
-
-
-def _host(out):
-    return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
-
-
-def _bytes(v):
-    return v.cpu().numpy().tobytes() if isinstance(v, torch.Tensor) else np.ascontiguousarray(v).tobytes()
-
-
-def _same(case, shape, name, got, want):
-    """bit for bit; an output the case lists as unordered: bit for bit in front of its first unordered column, within the
-    reordering bound of a float64 sum from there on"""
-    assert type(got) is type(want) and got.dtype == want.dtype and tuple(got.shape) == tuple(want.shape), name
-    if name not in case.unordered:
-        return _bytes(got) == _bytes(want)  # by their bits: NaN rows and signed zeros included, uint16 too
-    col = case.unordered[name]
-    g, w = (v.cpu().numpy() if isinstance(v, torch.Tensor) else v for v in (got, want))
-    g, w = g.reshape(-1, g.shape[-1]), w.reshape(-1, w.shape[-1])
-    if g[:, :col].tobytes() != w[:, :col].tobytes():
-        return False
-    # a ratio column is a quotient of two such sums: twice the bound, and the division's rounding
-    return bool(np.allclose(g[:, col:], w[:, col:], rtol=4 * wc.sum_rtol(shape), atol=0, equal_nan=True))
 
 
 _LEFTOVERS = {}  # (case, shape) -> the workspaces a recording pass left, shared by the cases that need them
