@@ -207,7 +207,8 @@ int pcseg_fill_holes(const uint8_t *mask, uint8_t *out, int B, int H, int W,
 /* ---- R3 + R4: skimage.morphology.local_maxima(distance) and
  * measure.label(local_max) (refine_boundaries.py:63-64) on an int32 image
  * (d2 is order-isomorphic to the float64 distance).  is_max: uint8 (NULL to
- * skip); markers: int32 1..K raster order (NULL to skip); counts: int32[B]. */
+ * skip); markers: int32 1..K raster order (NULL to skip); counts: int32[B],
+ * the K of every frame: written with the markers only (NULL without them). */
 size_t pcseg_local_maxima_workspace_bytes(int B, int H, int W);
 int pcseg_local_maxima_i32(const int32_t *img, uint8_t *is_max, int32_t *markers, int32_t *counts,
                            int B, int H, int W, void *workspace, size_t workspace_bytes, pcseg_stream_t stream);

@@ -498,12 +498,13 @@ def fill_holes(mask):
 
 
 def local_maxima(img, want_mask=True, want_markers=True):
-    """skimage.morphology.local_maxima + measure.label on an int32 image (refine_boundaries.py:63-64)."""
+    """skimage.morphology.local_maxima + measure.label on an int32 image (refine_boundaries.py:63-64): (is_max, markers,
+    counts); the counts come out of the numbering of the markers, so without markers there are none (None)."""
     img = _req(img, torch.int32, 3)
     B, H, W = img.shape
     is_max = torch.empty((B, H, W), dtype=torch.uint8, device=img.device) if want_mask else None
     markers = torch.empty((B, H, W), dtype=torch.int32, device=img.device) if want_markers else None
-    counts = torch.empty((B,), dtype=torch.int32, device=img.device)
+    counts = torch.empty((B,), dtype=torch.int32, device=img.device) if want_markers else None
     _call("local_maxima_i32", img, is_max, markers, counts, B, H, W, ws=(B, H, W))
     return is_max, markers, counts
 
