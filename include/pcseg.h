@@ -148,8 +148,11 @@ int pcseg_threshold_lt_f32(const float *img, float threshold, uint8_t *mask, int
  * tiff_analysis.py:996); the float64 distance is sqrt((double)d2).  cap < 0:
  * exact everywhere; cap >= 0: values above cap are reported as cap + 1.  A
  * frame without any zero pixel follows scipy: virtual zero pixel at (-1, 0).
- * The threshold members of the EDT family (dilation, particle fill) stage 8 rows of uint16 distances plus the rows' bytes in
- * LDS: W <= 6800. */
+ * Every shape check_shape admits is exact: squared distances reach (H - 1)^2 + (W - 1)^2 < 2^31 (H * W < 2^30).
+ * The threshold members of the EDT family (dilation, particle fill) with a reach of at most 31 pixels -- the radius, or for
+ * the particle fill floor(sqrt(max(radius^2, threshold^2 - 1))) -- work on bit words and take any width.  With a larger reach
+ * they stage 8 rows of uint16 distances plus the rows' bytes in LDS beside 1056 bytes of the kernel's own:
+ * 24 * ((W + 3) & ~3) + 1056 <= 163 840, i.e. W <= 6780; a wider frame is refused ("too wide"), nothing is launched. */
 size_t pcseg_edt_workspace_bytes(int B, int H, int W);
 int pcseg_edt_sq_u8(const uint8_t *mask, int32_t *d2, int B, int H, int W, int cap,
                     void *workspace, size_t workspace_bytes, pcseg_stream_t stream);

@@ -237,7 +237,12 @@ struct EpiFillParticle {
 // no bounds tests, only clamped indices); a candidate then costs an add and a min.  The search expands four offsets per
 // trip (the 8 LDS reads are issued together) and stops as soon as k^2 >= best, which is exact: offsets past the exit
 // point are still true candidates (g^2 + k^2 of a real pixel), and no closer one is left.
-constexpr unsigned EDT_D2_INF = 0x40000000u;  // > any g^2 (g <= 32767); g^2 + k^2 stays below 2^32
+// The sentinel lies above every REAL distance, not only above every g^2: check_shape admits H, W <= 32768 with H * W < 2^30,
+// so a true g^2 + k^2 reaches (H - 1)^2 + (W - 1)^2 < 2^31 (0x40000000 here reported the pixels at 2^30 and beyond as "no
+// zero pixel": 0 in exact mode).  A staged g^2 is at most 32767^2 < 2^30; the search prices offsets up to klim + 3 <= 32770,
+// so the sentinel plus k^2 stays below 2^31 + 2^30 + 2^18 < 2^32: no sum wraps.  A candidate priced ABOVE its true
+// offset (clamped reads, see the kernel) may itself pass 2^31; it only ever loses to the one examined at the true offset.
+constexpr unsigned EDT_D2_INF = 0x80000000u;
 
 // guard cells either side of a staged row: the search reads five neighbouring cells from a CLAMPED base address without any
 // test (see the kernel).  (Round 3 had one guard cell and a branch per trip that clamped ten indices one by one near a row end,
@@ -324,6 +329,14 @@ __device__ __forceinline__ int reach_halfwidth(unsigned g, int R2)
     else if ((w + 1) * (w + 1) <= t) ++w;
     return w;
 }
+
+// LDS of a workgroup: the staged rows (dynamic: 2 bytes of distance and 1 in / out byte per column, EDT_RB rows, the width
+// rounded up to 4) next to what the kernel declares itself (static: reach_w, wsum and the block-wide OR; 1056 bytes in the
+// gfx950 build, checked against the kernel's attributes before a launch).  24 * W4 + 1056 <= 163 840 gives W <= 6780.
+constexpr int LDS_BYTES = 160 * 1024;
+constexpr int EDT_REACH_STATIC_LDS = 1056;
+constexpr int EDT_REACH_MAX_W = (LDS_BYTES - EDT_REACH_STATIC_LDS) / (EDT_RB * 3) & ~3;
+static_assert(EDT_REACH_MAX_W == 6780, "include/pcseg.h states this bound");
 
 template <typename Epi>
 __global__ void __launch_bounds__(256, 1) edt_reach_kernel(const unsigned *__restrict__ bits, const uint16_t *__restrict__ up,
@@ -569,12 +582,6 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
     Carver cv(workspace, workspace_bytes);
     EdtWs ws = edt_carve(cv, B, H, W);
     if (!cv.fits(who)) return PCSEG_ERR_WORKSPACE;
-    size_t lds = (size_t)EDT_RB * ((W + 3) & ~3) * (sizeof(uint16_t) + 1);  // distances + the block's in / out bytes
-    if (Epi::kThreshold && lds > 160 * 1024) {
-        set_error("%s: W = %d too wide for the LDS row stage", who, W);
-        return PCSEG_ERR_ARG;
-    }
-    PCSEG_CHECK_HIP(hipMemsetAsync(ws.any, 0, sizeof(int) * B, s));
     dim3 g1((W + 255) / 256, ws.nch, B);
     bool wide = false;
     if constexpr (Fg::kBytes) wide = (W & 3) == 0 && ((uintptr_t)fg.p & 3) == 0 && ((uintptr_t)ws.bits & 15) == 0;
@@ -605,6 +612,28 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
             }
         }
     }
+    // the row-block threshold pass stages its rows in LDS next to the kernel's own tables: refused before anything is launched
+    // (the bit-word pass has no width bound)
+    [[maybe_unused]] const size_t lds = (size_t)EDT_RB * ((W + 3) & ~3) * (sizeof(uint16_t) + 1);  // distances + the block's in / out bytes
+    if constexpr (Epi::kThreshold) {
+        if (!bit_path) {
+            if (W > EDT_REACH_MAX_W) {
+                set_error("%s: W = %d too wide for the LDS row stage (reach above %d pixels: W <= %d)", who, W, RBIT_MAXD, EDT_REACH_MAX_W);
+                return PCSEG_ERR_ARG;
+            }
+            // EDT_REACH_STATIC_LDS against the kernel as it was built: more than LDS_BYTES in all is never asked for
+            static const int static_lds = [] {
+                hipFuncAttributes attr;
+                return hipFuncGetAttributes(&attr, (const void *)edt_reach_kernel<Epi>) == hipSuccess ? (int)attr.sharedSizeBytes : -1;
+            }();
+            if (static_lds < 0 || lds + (size_t)static_lds > (size_t)LDS_BYTES) {
+                set_error("%s: the row-block pass has %d bytes of static LDS, built for %d: W = %d does not fit", who, static_lds,
+                          EDT_REACH_STATIC_LDS, W);
+                return PCSEG_ERR_ARG;
+            }
+        }
+    }
+    PCSEG_CHECK_HIP(hipMemsetAsync(ws.any, 0, sizeof(int) * B, s));
     int *bits_any = bit_path ? ws.any : nullptr;  // (the carry pass sets the flag on the other paths)
     if (wide) {
         if constexpr (Fg::kBytes)
@@ -653,7 +682,7 @@ static int edt_run(Fg fg, Epi epi, unsigned long long *count, int B, int H, int 
         int rc;
         // rows per block: the search is a chain of dependent LDS reads, so occupancy beats amortising the staging --
         // 4 rows (17 KB at W = 1024, 8+ blocks per CU) measured 20 % faster than 8, 2 rows were tried too
-        if (4 * per_row <= 160 * 1024) rc = launch_rows(std::integral_constant<int, 4>());
+        if (4 * per_row <= (size_t)LDS_BYTES) rc = launch_rows(std::integral_constant<int, 4>());
         else rc = launch_rows(std::integral_constant<int, 1>());
         if (rc) return rc;
     }
