@@ -13,7 +13,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + ["common.h", "tile_ops.h", "table_common.h", "label_reduce.h", "column_pass.h", "tile_rounds.h", "pair_table.h"]]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + ["common.h", "union_find.h", "tile_ops.h", "table_common.h", "label_reduce.h", "column_pass.h", "tile_rounds.h", "pair_table.h"]]
     deps.append(os.path.join(HERE, "..", "include", "pcseg.h"))
     return any(os.path.getmtime(d) > t for d in deps)
 

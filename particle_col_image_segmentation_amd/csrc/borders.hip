@@ -22,6 +22,7 @@
 //   relabel_map_kernel   out = map[b, L]
 #include "label_reduce.h"
 #include "pair_table.h"
+#include "union_find.h"
 
 namespace pcseg {
 

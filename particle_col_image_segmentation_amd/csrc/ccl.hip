@@ -145,7 +145,7 @@ __global__ void __launch_bounds__(256) ccl_border_kernel(KeyFn keyfn, int *__res
     const bool nw_same = r > 0 && c > 0 && k_nw == k;
     // (at a tile corner both the W and the N link cross tiles and would justify each other: keep both there)
     const bool corner = top && left;
-    int *bad = corrupt ? corrupt + b : nullptr;  // raised by a fenced walk (common.h, walk_ok)
+    int *bad = corrupt ? corrupt + b : nullptr;  // raised by a fenced walk (union_find.h, walk_ok)
     if (left && w_same && (corner || !(n_same && nw_same))) unite_glb(par, p, p - 1, bad);
     if (r > 0) {
         if (top && n_same && (corner || !(w_same && nw_same))) unite_glb(par, p, p - W, bad);
@@ -174,7 +174,7 @@ struct PredNotFlagged {  // root accepted unless flag[root] != 0 or its whole fr
 template <typename Pred>
 __global__ void __launch_bounds__(256) ccl_flatten_count_kernel(int *__restrict__ parent, int *__restrict__ labels,
                                                                  int *__restrict__ blockcount, Pred pred, int64_t n, int nblk,
-                                                                 bool flatten, int *__restrict__ corrupt)
+                                                                 int *__restrict__ corrupt)
 {
     __shared__ int wsum[4];
     const int b = blockIdx.y;
@@ -198,11 +198,6 @@ __global__ void __launch_bounds__(256) ccl_flatten_count_kernel(int *__restrict_
         if (!walk_ok((int)i, p)) {  // an entry above its own index (or past the frame): not a union-find image
             walk_corrupt(corrupt ? corrupt + b : nullptr);
             continue;
-        }
-        if (flatten) {
-            const int x = walk_root(par, p, corrupt ? corrupt + b : nullptr);
-            if (x != p) par[i] = x;
-            p = x;
         }
         isroot[j] = p == (int)i && pred((int64_t)b * n + i);
         cnt += isroot[j];
@@ -229,8 +224,17 @@ __global__ void __launch_bounds__(256) ccl_scan_blocks_kernel(int *__restrict__ 
         if (i < nblk) bc[i] = carry + ex;
         carry += total;
     }
-    // a frame whose union-find image broke a walk's fence (common.h, walk_ok) reports -1 components
+    // a frame whose union-find image broke a walk's fence (union_find.h, walk_ok) reports -1 components
     if (threadIdx.x == 0 && counts) counts[blockIdx.x] = (corrupt && corrupt[blockIdx.x]) ? -1 : carry;
+}
+
+// the label at root p: its rank code (negative: rank inside its SCAN_PIX block) or the final label that the root's own
+// thread has written meanwhile
+__device__ __forceinline__ int rank_label(const int *lab, const int *blockoff, int b, int nblk, int p)
+{
+    int v = __hip_atomic_load(lab + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (v < 0) v = blockoff[b * nblk + p / SCAN_PIX] - v;
+    return v;
 }
 
 // chase: the parents are not flattened (the counting pass only looked for roots, parent[i] == i): every pixel walks to
@@ -255,7 +259,7 @@ __global__ void __launch_bounds__(256) ccl_relabel_kernel(const int *__restrict_
     }
     int out[4];
     int root_of_prev = -1, prev_p = -2;
-    int bad = 0;  // a walk left its fence (common.h, walk_ok): the frame's count becomes -1, nothing is followed
+    int bad = 0;  // a walk left its fence (union_find.h, walk_ok): the frame's count becomes -1, nothing is followed
     for (int j = 0; j < 4; ++j) {
         int p = pv[j];
         int v = 0;
@@ -272,10 +276,7 @@ __global__ void __launch_bounds__(256) ccl_relabel_kernel(const int *__restrict_
                 root_of_prev = p;
             }
         }
-        if (p >= 0 && pred((int64_t)b * n + p)) {
-            v = __hip_atomic_load(lab + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // rank code or final label
-            if (v < 0) v = blockoff[b * nblk + p / SCAN_PIX] - v;
-        }
+        if (p >= 0 && pred((int64_t)b * n + p)) v = rank_label(lab, blockoff, b, nblk, p);
         out[j] = v;
     }
     if (vec) {
@@ -301,10 +302,7 @@ __device__ __forceinline__ int relabel_decode(const int *par, int *lab, const in
                                               int p, bool chase, int *bad)
 {
     if (chase) p = walk_root(par, p, bad);
-    if (!pred((int64_t)b * n + p)) return 0;
-    int v = __hip_atomic_load(lab + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // rank code or final label
-    if (v < 0) v = blockoff[b * nblk + p / SCAN_PIX] - v;
-    return v;
+    return pred((int64_t)b * n + p) ? rank_label(lab, blockoff, b, nblk, p) : 0;
 }
 
 // NCH chains in lockstep: root[q] (-1 = none) walks to its root, val[q] becomes the root's decoded label
@@ -318,7 +316,7 @@ __device__ __forceinline__ void relabel_chains(const int *par, int *lab, const i
             int nx[NCH];
 #pragma unroll
             for (int q = 0; q < NCH; ++q) nx[q] = root[q] >= 0 ? par[root[q]] : -1;
-            // fenced (common.h, walk_ok), without branches: an entry above its index ends the chain where it stands and flags
+            // fenced (union_find.h, walk_ok), without branches: an entry above its index ends the chain where it stands and flags
             // the frame
             unsigned differ = 0, broke = 0;
 #pragma unroll
@@ -364,7 +362,7 @@ __global__ void __launch_bounds__(256, 8) ccl_relabel_quads_kernel(const int *__
         const int64_t i = i0 + (int64_t)q * SCAN_PIX;
         pq[q] = i < n ? *reinterpret_cast<const int4 *>(par + i) : make_int4(-1, -1, -1, -1);
     }
-    // the entries themselves are fenced first (common.h, walk_ok): an entry above the index it is stored at -- or past the
+    // the entries themselves are fenced first (union_find.h, walk_ok): an entry above the index it is stored at -- or past the
     // frame -- is not a union-find entry; it becomes background and the frame's count -1
     int bad = 0;
 #pragma unroll
@@ -387,23 +385,10 @@ __global__ void __launch_bounds__(256, 8) ccl_relabel_quads_kernel(const int *__
     // the second batch altogether; the watershed's label pass, where borders are everywhere, is the other way round)
     int lead[RELABEL_Q], lead2[RELABEL_Q], root[RELABEL_Q], val[RELABEL_Q], val2[RELABEL_Q], head_lane[RELABEL_Q];
     bool third = false;  // a quad with three different entries: its odd pixels walk on their own below
-    const int lane = lane_id();
 #pragma unroll
     for (int q = 0; q < RELABEL_Q; ++q) {
-        const int pv[4] = {pq[q].x, pq[q].y, pq[q].z, pq[q].w};
-        lead[q] = pv[0] >= 0 ? pv[0] : (pv[1] >= 0 ? pv[1] : (pv[2] >= 0 ? pv[2] : pv[3]));
-        const int left = __shfl_up(lead[q], 1);
-        const bool head = lane == 0 || lead[q] != left;
-        const unsigned long long heads = __ballot(head);
-        head_lane[q] = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
+        const bool head = elect_quad(pq[q], lead[q], lead2[q], head_lane[q], third);  // (union_find.h)
         root[q] = head ? lead[q] : -1;
-        lead2[q] = -1;
-#pragma unroll
-        for (int j = 1; j < 4; ++j) {
-            if (pv[j] < 0 || pv[j] == lead[q]) continue;
-            if (lead2[q] < 0) lead2[q] = pv[j];
-            else if (pv[j] != lead2[q]) third = true;
-        }
     }
     relabel_chains(par, lab, blockoff, pred, b, n, nblk, chase, root, val, &bad);
     bool any2 = false;
@@ -536,7 +521,7 @@ static int ccl_compact(int *parent, int *blockcount, int nblk, int *labels, int 
     dim3 grid(nblk, B);
     // roots are exact after the border pass (parent[i] == i), so they can be counted and ranked without flattening;
     // `flatten` (the parents are not flat yet) only tells the relabel pass to walk to the roots itself
-    PCSEG_LAUNCH((ccl_flatten_count_kernel<Pred>), grid, dim3(256), 0, s, parent, labels, blockcount, pred, n, nblk, false, corrupt);
+    PCSEG_LAUNCH((ccl_flatten_count_kernel<Pred>), grid, dim3(256), 0, s, parent, labels, blockcount, pred, n, nblk, corrupt);
     PCSEG_CHECK_LAUNCH();
     PCSEG_LAUNCH(ccl_scan_blocks_kernel, dim3(B), dim3(256), 0, s, blockcount, counts, nblk, (const int *)corrupt);
     PCSEG_CHECK_LAUNCH();
@@ -579,19 +564,8 @@ int ccl_plan(void *workspace, size_t workspace_bytes, int B, int H, int W, CclPl
 int ccl_equal_u8_finish(const uint8_t *in, const CclPlan &plan, bool tile_pass_done, int *labels, int *counts, int B, int H, int W,
                         hipStream_t s)
 {
-    const KeyEqU8 keyfn{in, W, (int64_t)H * W};
-    PCSEG_CHECK_HIP(hipMemsetAsync(plan.corrupt, 0, sizeof(int) * (size_t)B, s));
-    dim3 tgrid((W + CCL_TW - 1) / CCL_TW, (H + CCL_TH - 1) / CCL_TH, B);
-    if (!tile_pass_done) {
-        PCSEG_LAUNCH((ccl_tile_kernel<KeyEqU8, true>), tgrid, dim3(256), 0, s, keyfn, plan.parent, H, W);
-        PCSEG_CHECK_LAUNCH();
-    }
-    if (tgrid.x > 1 || tgrid.y > 1) {
-        const int64_t border_px = (int64_t)((H - 1) / CCL_TH) * W + (int64_t)2 * ((W - 1) / CCL_TW) * H;
-        dim3 bgrid((unsigned)((border_px + 255) / 256), B);
-        PCSEG_LAUNCH((ccl_border_kernel<KeyEqU8, true>), bgrid, dim3(256), 0, s, keyfn, plan.parent, H, W, plan.corrupt);
-        PCSEG_CHECK_LAUNCH();
-    }
+    const int rc = ccl_roots<KeyEqU8, true>(KeyEqU8{in, W, (int64_t)H * W}, plan.parent, B, H, W, s, tile_pass_done, plan.corrupt);
+    if (rc) return rc;
     return ccl_compact(plan.parent, plan.blockcount, plan.nblk, labels, counts, PredAll(), true, B, H, W, s, plan.corrupt);
 }
 
@@ -884,7 +858,7 @@ __global__ void __launch_bounds__(256) ccl_flatten_kernel(int *__restrict__ pare
     int *par = parent + (int64_t)blockIdx.y * n;
     int p = par[i];
     if (p < 0 || !walk_ok((int)i, p)) return;
-    const int x = walk_root(par, p);  // fenced (common.h, walk_ok)
+    const int x = walk_root(par, p);  // fenced (union_find.h, walk_ok)
     if (x != p) par[i] = x;
 }
 
@@ -1073,7 +1047,7 @@ __global__ void __launch_bounds__(256) locmax_propagate_kernel(int *__restrict__
         const int i = (int)(g - fbase);
         int *par = parent + fbase;
         const int p = par[i];
-        if (!walk_ok(i, p)) continue;   // fenced (common.h, walk_ok)
+        if (!walk_ok(i, p)) continue;   // fenced (union_find.h, walk_ok)
         const int x = walk_root(par, p);
         if (x != p) par[i] = x;
         if (x != i && bad[g]) bad[fbase + x] = 1;
@@ -1146,12 +1120,7 @@ __global__ void __launch_bounds__(256) locmax_relabel_kernel(const int *__restri
     for (unsigned long long m = cand_word(cbits, b, i0, n); m; m &= m - 1) {
         const int64_t i = i0 + (__ffsll((long long)m) - 1);
         const int p = par[i];  // the component's root
-        int v = 0;
-        if (pred((int64_t)b * n + p)) {
-            v = __hip_atomic_load(lab + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // rank code or final label
-            if (v < 0) v = blockoff[b * nblk + p / SCAN_PIX] - v;
-        }
-        lab[i] = v;
+        lab[i] = pred((int64_t)b * n + p) ? rank_label(lab, blockoff, b, nblk, p) : 0;
     }
 }
 
@@ -1313,7 +1282,7 @@ int pcseg_compact_labels(const int32_t *roots, int32_t *labels, int32_t *counts,
     CclWs ws = ccl_carve(cv, B, H, W);
     if (!cv.fits("compact_labels")) return PCSEG_ERR_WORKSPACE;
     int64_t total = (int64_t)B * H * W;
-    // the caller's roots are walked like the library's own parents: fenced (common.h, walk_ok) -- an entry that is not "index
+    // the caller's roots are walked like the library's own parents: fenced (union_find.h, walk_ok) -- an entry that is not "index
     // of an earlier-or-equal pixel of the same frame, + 1" makes counts[b] = -1 instead of a wild load
     PCSEG_CHECK_HIP(hipMemsetAsync(ws.corrupt, 0, sizeof(int) * (size_t)B, s));
     PCSEG_LAUNCH(roots_to_parent_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, roots, ws.parent, total);

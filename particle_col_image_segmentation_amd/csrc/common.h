@@ -199,153 +199,6 @@ __device__ __forceinline__ unsigned ld_agent(const unsigned *p)
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ---- LDS union-find
-// (relaxed workgroup-scope atomic accesses, not `volatile`: the compiler keeps a volatile access through a pointer
-// argument in the generic address space -- flat_load / flat_store instead of ds_read / ds_write, 68 of them in the
-// watershed tile pass -- while it does infer LDS for these)
-__device__ __forceinline__ int ld_lds(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void st_lds(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ int find_lds(int *par, int x)
-{
-    int p;
-    while ((p = ld_lds(par + x)) != x) x = p;
-    return x;
-}
-__device__ __forceinline__ void unite_lds(int *par, int a, int b)
-{
-    for (;;) {
-        a = find_lds(par, a);
-        b = find_lds(par, b);
-        if (a == b) return;
-        if (a < b) { int t = a; a = b; b = t; }
-        int old = atomicMin(&par[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-// the same with both walks in lockstep (two independent LDS reads per step).  Pays in the class-map tile pass (451 -> 434
-// us); the run-based tile pass got slower with it (155 -> 168 us) and so did the watershed's, which is bound by its
-// vector instructions, not by LDS latency (360 -> 424 us): they keep the plain form.
-__device__ __forceinline__ void unite_lds_pair(int *par, int a, int b)
-{
-    for (;;) {
-        for (;;) {
-            if (a == b) return;
-            const int pa = ld_lds(par + a), pb = ld_lds(par + b);
-            if (pa == a && pb == b) break;
-            a = pa;
-            b = pb;
-        }
-        if (a < b) { int t = a; a = b; b = t; }
-        int old = atomicMin(&par[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// with path halving (long chains: the lake components of the watershed's second level wind through a tile)
-__device__ __forceinline__ int find_lds_halving(int *par, int x)
-{
-    int p;
-    while ((p = ld_lds(par + x)) != x) {
-        const int g = ld_lds(par + p);
-        if (g != p) st_lds(par + x, g);  // re-pointing x at its grandparent keeps it in its set (parents only ever decrease)
-        x = g;
-    }
-    return x;
-}
-__device__ __forceinline__ void unite_lds_halving(int *par, int a, int b)
-{
-    for (;;) {
-        a = find_lds_halving(par, a);
-        b = find_lds_halving(par, b);
-        if (a == b) return;
-        if (a < b) { int t = a; a = b; b = t; }
-        const int old = atomicMin(&par[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// ---- global union-find (parents only ever decrease; stale reads cost iterations, never correctness)
-//
-// WALKS ARE FENCED.  In a well-formed union-find image the entry stored at index x is a smaller-or-equal index of the same
-// set and never negative (roots are minima; unions only ever lower an entry), so a walk is strictly decreasing: finite and
-// inside [0, x].  `walk_ok` is ONE unsigned compare that holds a walk to exactly that, whatever the array contains -- an
-// image that is being rewritten by another instance of the same chain (one captured graph replayed on several streams at
-// once: profiles/r03/exp_graph_r3a.log) or roots handed in by a caller (pcseg_compact_labels) then
-// ends in an error flag (`corrupt`, may be null: the walk just stops) instead of a load from a wild address or a loop
-// that never ends.
-__device__ __forceinline__ bool walk_ok(int x, int p) { return (unsigned)p <= (unsigned)x; }
-__device__ __forceinline__ void walk_corrupt(int *corrupt)
-{
-    if (corrupt) __hip_atomic_store(corrupt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// plain (read-only) walk to the root of x; x must be a valid index
-__device__ __forceinline__ int walk_root(const int *par, int x, int *corrupt = nullptr)
-{
-    int q;
-    while ((q = par[x]) != x) {
-        if (!walk_ok(x, q)) {
-            walk_corrupt(corrupt);
-            break;
-        }
-        x = q;
-    }
-    return x;
-}
-
-__device__ __forceinline__ int find_glb(int *par, int x, int *corrupt = nullptr)
-{
-    // path halving: re-pointing x at its grandparent is always valid (any ancestor is) and races are benign
-    int p;
-    while ((p = ld_agent(par + x)) != x) {
-        if (!walk_ok(x, p)) { walk_corrupt(corrupt); return x; }
-        int g = ld_agent(par + p);
-        if (!walk_ok(p, g)) { walk_corrupt(corrupt); return p; }
-        if (g != p) __hip_atomic_store(par + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = g;
-    }
-    return x;
-}
-// the two walks to the roots advance in LOCKSTEP (path halving on both, as in find_glb): a step of the pair is two
-// independent loads in flight instead of one, and the border passes are nothing but these dependent walks.
-// Returns false (and raises `corrupt`) when an entry breaks the fence: the caller must not link anything then.
-__device__ __forceinline__ bool find2_glb(int *par, int &a, int &b, int *corrupt = nullptr)
-{
-    for (;;) {
-        if (a == b) return true;
-        const int pa = ld_agent(par + a), pb = ld_agent(par + b);
-        if (pa == a && pb == b) return true;
-        if (!walk_ok(a, pa) || !walk_ok(b, pb)) break;
-        const int ga = ld_agent(par + pa), gb = ld_agent(par + pb);
-        if (!walk_ok(pa, ga) || !walk_ok(pb, gb)) break;
-        if (pa != a) {
-            if (ga != pa) __hip_atomic_store(par + a, ga, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a = ga;
-        }
-        if (pb != b) {
-            if (gb != pb) __hip_atomic_store(par + b, gb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            b = gb;
-        }
-    }
-    walk_corrupt(corrupt);
-    return false;
-}
-__device__ __forceinline__ void unite_glb(int *par, int a, int b, int *corrupt = nullptr)
-{
-    for (;;) {
-        if (!find2_glb(par, a, b, corrupt)) return;
-        if (a == b) return;
-        if (a < b) { int t = a; a = b; b = t; }
-        int old = atomicMin(par + a, b);
-        if (old == a) return;
-        if (!walk_ok(a, old)) { walk_corrupt(corrupt); return; }
-        a = old;
-    }
-}
-
 // ccl.hip, for the fused class-map front end (frontend.hip): where the union-find image and the per-block root counts
 // live in a pcseg_ccl_workspace_bytes workspace, and the passes after the tile pass for equal-valued 8-connected
 // components of a uint8 image (border links, flatten + count, scan, relabel -> raster-order labels)
@@ -353,7 +206,7 @@ struct CclPlan {
     int *parent;
     int *blockcount;
     int nblk;
-    int *corrupt;  // [B] raised by a fenced walk (see walk_ok): the frame's count comes out as -1
+    int *corrupt;  // [B] raised by a fenced walk (union_find.h, walk_ok): the frame's count comes out as -1
 };
 int ccl_plan(void *workspace, size_t workspace_bytes, int B, int H, int W, CclPlan *plan, const char *who);
 int ccl_equal_u8_finish(const uint8_t *in, const CclPlan &plan, bool tile_pass_done, int *labels, int *counts, int B, int H, int W,

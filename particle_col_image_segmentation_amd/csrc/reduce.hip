@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "label_reduce.h"
+#include "union_find.h"
 
 namespace pcseg {
 
@@ -600,7 +601,7 @@ struct RootKeys {  // the parent image of a union-find (-1 = background): walk t
     {
         const int *par = parent + (int64_t)fb * H * W;
         int k = par[y * W + x];
-        if (k >= 0) k = (unsigned)k < (unsigned)(H * W) ? walk_root(par, k) : -1;  // fenced (common.h, walk_ok)
+        if (k >= 0) k = (unsigned)k < (unsigned)(H * W) ? walk_root(par, k) : -1;  // fenced (union_find.h, walk_ok)
         return k + 1;
     }
 };
@@ -616,7 +617,7 @@ struct RunRoots {  // components by vertical runs (pcseg_dilate_ccl_runs_u8): th
         if (!((word >> j) & 1u)) return 0;
         const unsigned below = ~word & ((1u << j) - 1u);
         const int start = below ? 32 - __clz(below) : 0;
-        return walk_root(parent + (int64_t)fb * H * W, (int)((y - j + start) * W + x)) + 1;  // fenced (common.h, walk_ok)
+        return walk_root(parent + (int64_t)fb * H * W, (int)((y - j + start) * W + x)) + 1;  // fenced (union_find.h, walk_ok)
     }
 };
 

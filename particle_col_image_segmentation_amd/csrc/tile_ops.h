@@ -1,6 +1,7 @@
 // LDS tile building blocks shared by the stand-alone kernels (median5, ccl_tile) and the fused class-map front end.
 #pragma once
 #include "common.h"
+#include "union_find.h"
 
 namespace pcseg {
 

@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "tile_rounds.h"
+#include "union_find.h"
 
 namespace pcseg {
 
@@ -518,84 +519,8 @@ __global__ void __launch_bounds__(256) ws_list_tiles_kernel(const int *__restric
 constexpr int UF_TW = 64, UF_TH = 32, UF_SW = UF_TW + 2, UF_SH = UF_TH + 2;
 constexpr int UF_LNS = UF_TW * UF_TH;  // non-seed offset of tile-local virtual indices
 constexpr int UF_NS = 1 << 30;         // non-seed offset of frame-wide virtual indices (H * W < 2^30)
-
-__device__ __forceinline__ int vfind_lds(int *par, int v)
-{
-    // path halving: re-pointing v at its grandparent keeps it inside its set (concurrent unions only ever lower parents)
-    int p;
-    while ((p = ld_lds(par + (v & (UF_LNS - 1)))) != v) {
-        const int g = ld_lds(par + (p & (UF_LNS - 1)));
-        if (g != p) st_lds(par + (v & (UF_LNS - 1)), g);
-        v = g;
-    }
-    return v;
-}
-__device__ __forceinline__ void vunite_lds(int *par, int a, int b)
-{
-    for (;;) {
-        a = vfind_lds(par, a);
-        b = vfind_lds(par, b);
-        if (a == b) return;
-        if (a < b) { int t = a; a = b; b = t; }
-        int old = atomicMin(&par[a & (UF_LNS - 1)], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-// The walks over the frame-wide parent image are FENCED like the plain ones (common.h, walk_ok): an entry stored for the node
-// with virtual index x is a virtual index <= x (roots are minima of the virtual order, unions only lower entries) whose
-// pixel lies inside the frame.  Anything else -- the image being rewritten by a second instance of the same captured chain
-// (profiles/r03/exp_graph_r3a.log), a stale workspace -- stops the walk and raises the frame's tie flag (the exact flood
-// then recomputes the frame in mode 0, mode 2 reports it) instead of loading from a wild address or walking for ever.
-__device__ __forceinline__ bool vwalk_ok(int x, int p, int n) { return (unsigned)p <= (unsigned)x && (p & (UF_NS - 1)) < n; }
-
-// p, q: pixel indices; the walk starts from their parents, which are virtual indices of nodes in the same sets
-__device__ __forceinline__ void vunite_glb(int *par, int p, int q, int n, int *corrupt)
-{
-    int a = ld_agent(par + p), b = ld_agent(par + q);
-    // (the pixels' own entries: any virtual index of the frame -- a seed elsewhere may precede both)
-    bool ok = a >= 0 && b >= 0 && (a & (UF_NS - 1)) < n && (b & (UF_NS - 1)) < n;
-    while (ok) {
-        // both walks in lockstep (see find2_glb)
-        for (;;) {
-            if (a == b) return;
-            const int pa = ld_agent(par + (a & (UF_NS - 1))), pb = ld_agent(par + (b & (UF_NS - 1)));
-            if (pa == a && pb == b) break;
-            if (!vwalk_ok(a, pa, n) || !vwalk_ok(b, pb, n)) { ok = false; break; }
-            const int ga = ld_agent(par + (pa & (UF_NS - 1))), gb = ld_agent(par + (pb & (UF_NS - 1)));
-            if (!vwalk_ok(pa, ga, n) || !vwalk_ok(pb, gb, n)) { ok = false; break; }
-            if (pa != a) {
-                if (ga != pa) __hip_atomic_store(par + (a & (UF_NS - 1)), ga, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                a = ga;
-            }
-            if (pb != b) {
-                if (gb != pb) __hip_atomic_store(par + (b & (UF_NS - 1)), gb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                b = gb;
-            }
-        }
-        if (!ok) break;
-        if (a == b) return;
-        if (a < b) { int t = a; a = b; b = t; }
-        int old = atomicMin(par + (a & (UF_NS - 1)), b);
-        if (old == a) return;
-        if (!vwalk_ok(a, old, n)) break;
-        a = old;
-    }
-    walk_corrupt(corrupt);
-}
-// read-only walk to the root of virtual index x (x's pixel must lie inside the frame)
-__device__ __forceinline__ int vwalk_root(const int *par, int x, int n, bool &bad)
-{
-    int q;
-    while ((q = par[x & (UF_NS - 1)]) != x) {
-        if (!vwalk_ok(x, q, n)) {
-            bad = true;
-            break;
-        }
-        x = q;
-    }
-    return x;
-}
+using UfTileNodes = VirtualNodes<UF_LNS>;   // (union_find.h: the finds and unions over either kind of virtual index)
+using UfFrameNodes = VirtualNodes<UF_NS>;
 
 template <typename KeyT>
 __device__ __forceinline__ void ws_uf_tile_frame(KeyT *sK, int *par, uint8_t *sM, const int b, const int tile_x, const int tile_y,
@@ -728,7 +653,7 @@ __device__ __forceinline__ void ws_uf_tile_frame(KeyT *sK, int *par, uint8_t *sM
             const bool same_run = (m & 2) || (ml & 4), same_run_up = (mu & 2) || (mul & 4), left_vertical = (ml & 1) || (mul & 8);
             if (same_run && same_run_up && left_vertical) continue;
         }
-        vunite_lds(par, par[t], par[t - UF_TW]);
+        unite_lds<UF_HALVING>(par, par[t], par[t - UF_TW], UfTileNodes());
     }
     __syncthreads();
     for (int t = threadIdx.x; t < UF_TH * UF_TW; t += 256) {
@@ -736,7 +661,7 @@ __device__ __forceinline__ void ws_uf_tile_frame(KeyT *sK, int *par, uint8_t *sM
         if (r >= H || c >= W) continue;
         int v = -1;
         if (par[t] >= 0) {
-            const int root = vfind_lds(par, par[t]);
+            const int root = find_lds<UF_HALVING>(par, par[t], UfTileNodes());
             const int lt = root & (UF_LNS - 1);
             v = ((r0 + lt / UF_TW) * W + c0 + lt % UF_TW) | (root >= UF_LNS ? UF_NS : 0);
         }
@@ -801,6 +726,14 @@ __global__ void __launch_bounds__(256, 8) ws_uf_border_kernel(const int *__restr
     int *par = parent + fbase;
     const int p = r * W + c;
     const uint8_t *mm = minmask + fbase;
+    // the union of pixels p and q: the walks start from their parents, which are virtual indices of nodes in the same sets
+    // (the pixels' own entries are fenced here: any virtual index of the frame -- a seed elsewhere may precede both)
+    const auto unite_pixels = [&](const int p, const int q) {
+        const UfFrameNodes nodes{H * W};
+        const int ep = ld_agent(par + p), eq = ld_agent(par + q);
+        if (ep >= 0 && eq >= 0 && nodes.slot(ep) < nodes.n && nodes.slot(eq) < nodes.n) unite_glb(par, ep, eq, exact_flags + b, nodes);
+        else walk_corrupt(exact_flags + b);
+    };
     // the four masks as one batch of loads (offsets clamped at the frame's edge, where the value is not used): tested one
     // after the other they were up to four dependent memory round trips per pixel
     const int up = r > 0 ? W : 0, lf = c > 0 ? 1 : 0;
@@ -812,14 +745,14 @@ __global__ void __launch_bounds__(256, 8) ws_uf_border_kernel(const int *__restr
         if ((mp & 1) || (mu & 8)) {
             bool implied = false;
             if (!left && c > 0) implied = ((mp & 2) || (ml & 4)) && ((mu & 2) || (mul & 4)) && ((ml & 1) || (mul & 8));
-            if (!implied) vunite_glb(par, p, p - W, H * W, exact_flags + b);
+            if (!implied) unite_pixels(p, p - W);
         }
     }
     if (left && ws_active(active, b, r, c - 1, tilesX, tilesY)) {
         if ((mp & 2) || (ml & 4)) {
             bool implied = false;
             if (!top && r > 0) implied = ((mp & 1) || (mu & 8)) && ((ml & 1) || (mul & 8)) && ((mu & 2) || (mul & 4));
-            if (!implied) vunite_glb(par, p, p - 1, H * W, exact_flags + b);
+            if (!implied) unite_pixels(p, p - 1);
         }
     }
     });
@@ -851,9 +784,10 @@ __device__ __forceinline__ void ws_uf_label_pixel(const int b, const int64_t i, 
     int x = parent[g];
     if (x < 0) return;
     const int *par = parent + fbase;
-    bool broken = (x & (UF_NS - 1)) >= (int)n;
-    if (!broken) x = vwalk_root(par, x, (int)n, broken);
-    if (broken) {  // a walk left its fence (vwalk_ok): the frame is recomputed by the exact flood / reported
+    const UfFrameNodes nodes{(int)n};
+    int broken = nodes.slot(x) >= nodes.n;
+    if (!broken) x = walk_root(par, x, &broken, nodes);
+    if (broken) {  // a walk left its fence (union_find.h, VirtualNodes): the frame is recomputed by the exact flood / reported
         exact_flags[b] = 1;
         return;
     }
@@ -933,9 +867,9 @@ constexpr int LABEL4_Q = 3;  // quads a lane carries (3 x 2 lockstep chains): 78
 // (never outside the frame, whatever the entry says), a node whose pixel lies outside the frame reads as -1 (the compare that
 // tells a live chain from none does it), and an entry above its node's virtual index -- or a negative one -- is cut down to
 // the node itself by an unsigned min: the chain then simply ends there (strictly decreasing: never a cycle).  `cut` (entry ^
-// its cut value, nonzero once an entry was cut) holds everything vwalk_ok tests, one compare at the end raises the frame's
+// its cut value, nonzero once an entry was cut) holds everything VirtualNodes::ok tests, one compare at the end raises the frame's
 // flag -- a chain that ENDS outside the frame, e.g. on a seed index in [n, UF_NS), included: its last node is loaded too.
-// (vwalk_ok written out per chain -- as `if`s or as selects fed
+// (that fence written out per chain -- as `if`s or as selects fed
 // by compares -- parks sixteen lane masks in scalar register pairs: the kernel went from 96 to 106 scalar registers, i.e.
 // from seven to six workgroups per CU, and this pass is nothing but memory latency: 204 -> 265 us.  What the compiler's
 // occupancy figure does not show: residency of 256-thread workgroups is min(8, 800 / (ceil(sgpr / 16) * 16 + 16)) --
@@ -1010,20 +944,11 @@ __global__ void __launch_bounds__(256, LABEL4_OCC) ws_uf_label4_kernel(const int
     // read its answer across lanes); chains 4..7: the second entry of quads that straddle two components (walked pixel by
     // pixel these were most of the pass: see ccl_relabel_quads_kernel).  All eight advance in lockstep.
     int lead[LABEL4_Q], lead2[LABEL4_Q], rt[2 * LABEL4_Q], lb[2 * LABEL4_Q], head_lane[LABEL4_Q];
-    const int lane = lane_id();
 #pragma unroll
     for (int q = 0; q < LABEL4_Q; ++q) {
-        const int pv[4] = {p4[q].x, p4[q].y, p4[q].z, p4[q].w};
-        lead[q] = pv[0] >= 0 ? pv[0] : (pv[1] >= 0 ? pv[1] : (pv[2] >= 0 ? pv[2] : pv[3]));
-        const int left = __shfl_up(lead[q], 1);
-        const bool head = lane == 0 || lead[q] != left;
-        const unsigned long long heads = __ballot(head);
-        head_lane[q] = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
+        bool third = false;  // (not asked: a pixel with a third entry is found by comparing below)
+        const bool head = elect_quad(p4[q], lead[q], lead2[q], head_lane[q], third);  // (union_find.h)
         rt[q] = head ? lead[q] : -1;
-        lead2[q] = -1;
-#pragma unroll
-        for (int j = 1; j < 4; ++j)
-            if (pv[j] >= 0 && pv[j] != lead[q] && lead2[q] < 0) lead2[q] = pv[j];
         rt[LABEL4_Q + q] = lead2[q];
     }
     bool broken = false;
@@ -1080,7 +1005,7 @@ __global__ void __launch_bounds__(256, LABEL4_OCC) ws_uf_label4_kernel(const int
         }
         if (wrote) *reinterpret_cast<int4 *>(F + fbase + i) = make_int4(fv[0], fv[1], fv[2], fv[3]);
     }
-    if (broken) exact_flags[b] = 1;  // a walk left its fence (vwalk_ok): recomputed by the exact flood / reported
+    if (broken) exact_flags[b] = 1;  // a walk left its fence (union_find.h, VirtualNodes): recomputed by the exact flood / reported
 }
 
 // ---- test-only hook (PCSEG_WS_POISON_*, pcseg.h): overwrite root entries of the parent image between two passes of the label
@@ -1316,8 +1241,8 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
         const int t = threadIdx.x + K2T * q, lr = t / WS_T + 1, lc = t % WS_T + 1, i = lr * P + lc;
         if (!sLake[i]) continue;
         const unsigned l = sL[i];
-        if (lc < WS_T && sLake[i + 1] && sL[i + 1] == l) unite_lds_halving(par, i, i + 1);
-        if (lr < WS_T && sLake[i + P] && sL[i + P] == l) unite_lds_halving(par, i, i + P);
+        if (lc < WS_T && sLake[i + 1] && sL[i + 1] == l) unite_lds<UF_HALVING>(par, i, i + 1);
+        if (lr < WS_T && sLake[i + P] && sL[i + P] == l) unite_lds<UF_HALVING>(par, i, i + P);
     }
     __syncthreads();
     // every lake cell brings its own key and the keys of the same-level cells around it that are not members (entries,
@@ -1333,7 +1258,7 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
 #pragma unroll
         for (int d = 0; d < 4; ++d)
             if (sL[nb[d]] == l && !(interior[d] && sLake[nb[d]])) m = min(m, sK[nb[d]]);  // (members meet at the root anyway)
-        const int root = find_lds_halving(par, i);
+        const int root = find_lds<UF_HALVING>(par, i);
         if (root != i || m != k_old[q]) atomicMin(&sK[root], m);
     }
     __syncthreads();
@@ -1342,7 +1267,7 @@ __device__ __forceinline__ void ws_k2_relax_tile(WsK2Lds &lds, const unsigned *_
 #pragma unroll
     for (int q = 0; q < CELLS; ++q) {
         const int t = threadIdx.x + K2T * q, i = (t / WS_T + 1) * P + t % WS_T + 1;
-        k_new[q] = sLake[i] ? sK[find_lds_halving(par, i)] : k_old[q];
+        k_new[q] = sLake[i] ? sK[find_lds<UF_HALVING>(par, i)] : k_old[q];
         changed = changed || k_new[q] != k_old[q];
     }
     __syncthreads();  // every root has been read before a member overwrites its own cell (a root's own write is the value it holds)

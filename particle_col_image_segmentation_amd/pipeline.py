@@ -135,7 +135,7 @@ class BatchResult(dict):
         if int(self["overflow"].sum().item()) or int(self["ws_overflow"].sum().item()):
             raise RuntimeError("region table capacity exceeded: raise FramePipeline(cap=...)")
         if int((self["counts"] < 0).sum().item()):
-            # a label pass found a union-find entry outside its fence (csrc/common.h, walk_ok) and reported -1 components:
+            # a label pass found a union-find entry outside its fence (csrc/union_find.h, walk_ok) and reported -1 components:
             # the workspace was overwritten while the chain ran (e.g. one captured graph replayed on two streams at once)
             raise RuntimeError("corrupt union-find image in the class-map labelling (counts < 0)")
         if int(self["nan_flag"].sum().item()):

@@ -163,7 +163,7 @@ def test_exact_flood_with_more_frames_than_cus():
 
 def test_corrupted_root_image_raises_the_flag_not_a_fault():
     """The label passes walk parent entries to their roots.  A well-formed union-find image only ever points at an earlier
-    pixel of the same frame, and every walk is FENCED to exactly that (csrc/common.h, walk_ok): a deliberately corrupted
+    pixel of the same frame, and every walk is FENCED to exactly that (csrc/union_find.h, walk_ok): a deliberately corrupted
     root image -- an entry far past the frame, a forward pointer, a two-cycle -- must come back as counts[b] = -1 for that
     frame, with the other frames of the call labelled as usual, and never as a wild load (round-3 review: the fault in
     profiles/r03/exp_graph_r3a.log came from a parent array rewritten under a running chain)."""

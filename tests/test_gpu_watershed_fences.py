@@ -116,14 +116,14 @@ def _first_level(ops, stage, shape, seed):
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_poisoned_roots_before_border_pass_raise_the_flag(ops, shape):
-    """Roots named from a union-find tile seam, poisoned before ws_uf_border_kernel: vunite_glb's fences."""
+    """Roots named from a union-find tile seam, poisoned before ws_uf_border_kernel: the fences of unite_glb over virtual nodes."""
     _first_level(ops, ops.WS_POISON_BORDER, shape, 1)
 
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_poisoned_roots_before_label_pass_raise_the_flag(ops, shape):
     """Roots poisoned before the first level's label pass: label4_chains and the third-entry walk of ws_uf_label4_kernel
-    (W % 4 == 0), vwalk_root in ws_uf_label_kernel<UF_OPTIMISTIC> (otherwise); flagged frames also go through UF_REPAIR."""
+    (W % 4 == 0), walk_root over virtual nodes in ws_uf_label_kernel<UF_OPTIMISTIC> (otherwise); flagged frames also go through UF_REPAIR."""
     _first_level(ops, ops.WS_POISON_LABEL, shape, 2)
 
 
