@@ -16,6 +16,9 @@
  *     *_workspace_bytes(B, H, W) query (256-byte aligned device memory); a
  *     workspace's prior contents never affect a result, and nothing beyond
  *     the size the query named is written;
+ *   - an output buffer's prior contents never affect a result either (only an
+ *     argument documented as accumulated in place is read before it is
+ *     written), and nothing outside an output is written;
  *   - work is enqueued on `stream` (a hipStream_t) and every compute entry point
  *     returns without waiting for it: no hidden host synchronisation, fixed
  *     points included (they finish in device-side tail kernels);
