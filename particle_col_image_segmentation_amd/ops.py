@@ -998,10 +998,15 @@ def _surface_rows(points, surface, mask, scale, K, edges):
 
 def _refined_surface(res, points, surface, mask, scale, K, edges):
     """:func:`_surface_rows` of the refined points, at their centroids (pcseg_surface_pack_refined)."""
+    return _surface_rows(points._replace(coords=_refined_centroids(res, points)), surface, mask, scale, K, edges)
+
+
+def _refined_centroids(res, points):
+    """(row, col) of the refined points, 0-based, as the ``refined`` table prints them (pcseg_surface_pack_refined)."""
     B, cap, n = res["stats"].shape[0], res["stats"].shape[1], points.ids.shape[0]
     rc = torch.empty((n + 1, 2), dtype=torch.float64, device=points.ids.device)
     _call("surface_pack_refined", _req(res["ws_stats"], torch.int64, 3), cap, points.ids, points.frame_offsets, n, B, rc)
-    return _surface_rows(points._replace(coords=rc[:n]), surface, mask, scale, K, edges)
+    return rc[:n]
 
 
 # The ROIs of one label batch that a per-ROI table has a row for: the label image, its per-frame label counts, its region

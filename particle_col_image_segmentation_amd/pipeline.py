@@ -19,7 +19,7 @@ import collections
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, spatial
 from . import tiff_analysis as ta
 from .synth import BOUNDARY_PLANE, CELL_TYPES_5
 
@@ -907,6 +907,57 @@ class FramePipeline:
         rows = np.stack([fid[host["frame"]], host["a"], host["b"], host["links"], host["mean"], host["saddle"].astype(np.float64),
                          host["links"] / (512.0 / float(raster))], axis=1).astype(np.float64).reshape(-1, 7)
         return {"borders": rows, "borders_columns": ["frame", "roi_a", "roi_b", "links", "mean", "saddle", "length_um"]}
+
+    def clustering(self, res, edges, window="particle", of="cells", frame_ids=None, raster=19.0):
+        """Are the cells of one batch clumped or spread evenly over the window they can sit in?  Observed pair counts against
+        complete spatial randomness on that window, exactly (``spatial.window_pair_counts``, csrc/window_pairs.hip): no edge
+        correction, no simulation.  ``edges``: m + 1 increasing values from 0, in um at ``512 / raster`` pixels per um (the
+        scale of ``distances``).  ``window``: "particle" (``ops.particle_mask(res["recreated"], <Particle value>)``, the mask of
+        the surface tables), "frame" (every pixel) or a uint8 (B, H, W) CUDA tensor (non-zero: in the window).  ``of``:
+        "cells" (the rows of ``cells``) or "refined" (the refined rows of kind >= 1): the points, slots and order of
+        ``pair_hist`` / ``refined_pair_hist``.  A point is in the window when the mask is set at pixel ``(floor(row + 0.5),
+        floor(col + 0.5))`` of its centroid (the rule of ``surface``'s ``inside``); the others are left out of the observed
+        counts, which are ``ops.point_neighbours``' histogram of the rest.  Returns numpy tables with ``<name>_columns`` lists:
+        ``window_pairs`` = ``[frame, n_px, bin_0 .. bin_m-1, over]``, one row per frame: the window's pixels A and the ordered
+        pairs of window pixels (self pairs included) per distance bin, ``over`` the rest of the A^2 pairs -- exact integers,
+        stored as float64 like every table: exact up to 2^53; ``clustering`` = ``[frame, slot_a, slot_b, bin, r_lo_um, r_hi_um,
+        n_a, n_b, n_out_a, n_out_b, obs, window_pairs, expected, ratio, cum_obs, cum_window_pairs, cum_expected, cum_ratio]``,
+        one row per (frame, slot pair a <= b, bin): the points of the two slots in the window and left out, the observed
+        pairs, the window's count G of the bin, ``expected = (npairs * G) / (A * A)`` with ``npairs = n_a (n_a - 1) / 2`` (a ==
+        b) or ``n_a n_b`` -- the expectation for points placed independently and uniformly on the window's pixels --, ``ratio =
+        obs / expected`` (above 1: clustering at that range, below 1: spacing) and the same of the counts summed over the
+        bins 0 .. k (the K-function form); NaN where A == 0 or expected == 0.  ``frame_ids`` as in :meth:`borders`.
+        ``res`` is only read."""
+        if of not in ("cells", "refined"):
+            raise ValueError('of must be "cells" or "refined"')
+        if isinstance(window, str) and window not in ("particle", "frame"):
+            raise ValueError('window must be "particle", "frame" or a uint8 (B, H, W) CUDA tensor')
+        B, C, H, W = res["shape"]
+        fid = np.arange(B, dtype=np.float64) if frame_ids is None else np.asarray(frame_ids, np.float64)
+        if fid.shape != (B,):
+            raise ValueError("frame_ids must name every frame of the batch")
+        if not isinstance(window, str):
+            window = ops._req(window, torch.uint8, 3)
+            if tuple(window.shape) != (B, H, W):
+                raise ValueError("window must have the batch's (B, H, W)")
+        spatial._reach_within_limit(edges, 512.0 / float(raster))  # edges the library refuses: ValueError before any launch
+        tb = self.tables_
+        dev = res["stats"].device
+        if isinstance(window, str):
+            window = (ops.particle_mask(res["recreated"], tb.particle_value) if window == "particle"
+                      else torch.ones((B, H, W), dtype=torch.uint8, device=dev))
+        pos = torch.arange(B, dtype=torch.int64, device=dev)
+        groups = (res.get("groups") or {}) if self.merged else {}
+        _, d = ops._dense_tables(res, groups, pos, C, (), True)
+        if of == "cells":
+            points = ops._pack_cells("neighbours_pack_cells", d, tb.slot)
+            rc = ops._pack_cells("surface_pack_cells", d, tb.slot).coords
+        else:
+            points = ops.refined_tables(res, pos, tb, d.ws, (d.n_roi, d.n_cell), check=True, points=True)["points"]
+            rc = ops._refined_centroids(res, points)
+        out = _download(spatial._clustering_tables(points, rc, window, edges, 512.0 / float(raster), len(tb.slot_names), fid))
+        out.update((k + "_columns", v) for k, v in spatial.clustering_columns(edges).items())
+        return out
 
     def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, **switches):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per

@@ -598,6 +598,52 @@ def get_cell_surface_distances(z_slice, cell_types, cell_pos=None, cell_clusters
                  "shells": {side: {"n_px": int(sh[side, 0]), "bins": sh[side, 1:-1], "over": int(sh[side, -1])} for side in (0, 1)}}
 
 
+def get_cell_clustering(z_slice, cell_types, cell_pos=None, cell_clusters=None, edges=None, window="particle", px_to_um=PX_TO_UM_CONV):
+    """Are the cells of one denoised class map clumped or spread evenly over the window they can sit in?  The two tables of
+    ``FramePipeline.clustering`` (which describes them) for one frame: ``window_pairs`` and ``clustering`` with their
+    ``<name>_columns``, frame 0.  The points are the regions of ``cell_pos`` and ``cell_clusters`` (strain -> regions; those
+    of ``get_cell_positions_and_areas`` when none are passed) at their centroids, the slots the strains in ``cell_pos`` order;
+    ``window``: "particle" (the particle reconstructed as ``recreate_particle_area`` does, holes filled: the mask of
+    ``get_cell_surface_distances``), "frame" or an (H, W) mask of the caller's; ``edges`` (increasing, from 0) in um."""
+    from . import spatial
+    if edges is None:
+        raise ValueError("get_cell_clustering needs edges")
+    if isinstance(window, str) and window not in ("particle", "frame"):
+        raise ValueError('window must be "particle", "frame" or an (H, W) mask')
+    if cell_pos is None:
+        cell_pos, found_clusters, _, _ = get_cell_positions_and_areas(z_slice, cell_types)
+        cell_clusters = found_clusters if cell_clusters is None else cell_clusters
+    cell_clusters = cell_clusters or {}
+    names = list(cell_pos) + [n for n in cell_clusters if n not in cell_pos]
+    if len(names) > 4:
+        raise ValueError("at most 4 strains")
+    regs = [(t, r) for t, name in enumerate(names) for r in list(cell_pos.get(name, [])) + list(cell_clusters.get(name, []))]
+    z_dev, _ = _to_dev_u8(z_slice)
+    dev = z_dev.device
+    if not isinstance(window, str):
+        mask = (torch.as_tensor(np.asarray(window.cpu() if isinstance(window, torch.Tensor) else window)) != 0).to(torch.uint8)
+        mask = mask.reshape((1,) + tuple(z_dev.shape[-2:])).to(dev)
+    elif window == "frame":
+        mask = torch.ones_like(z_dev)
+    else:
+        particle_labels = [label for label, name in cell_types.items() if name == "Particle"]
+        particle_label = particle_labels[-1] if particle_labels else None
+        gained = None
+        for cell_label in ([label for label, name in cell_types.items() if name in CELL_TYPES] if particle_label is not None else []):
+            z_dev, gained = ops.fill_particle(z_dev, particle_label, cell_label, particle_label, DILATION_RADIUS, DISTANCE_THRESHOLD,
+                                              gained)
+        mask = ops.particle_mask(z_dev, particle_label)
+    rc = torch.tensor([[float(r.centroid[0]), float(r.centroid[1])] for _, r in regs], dtype=torch.float64).reshape(-1, 2).to(dev)
+    xy = torch.stack([rc[:, 1] + 1.0, rc[:, 0] + 1.0], dim=1)  # positions as the pair tables take them (pcseg_point_neighbours)
+    points = ops.Points(xy, torch.tensor([t for t, _ in regs], dtype=torch.int32).to(dev),
+                        torch.tensor([int(r.label) for _, r in regs], dtype=torch.int32).to(dev),
+                        torch.tensor([0, len(regs)], dtype=torch.int64).to(dev))
+    out = {k: v.cpu().numpy() for k, v in
+           spatial._clustering_tables(points, rc, mask, edges, px_to_um, max(len(names), 1), np.zeros(1)).items()}
+    out.update((k + "_columns", v) for k, v in spatial.clustering_columns(edges).items())
+    return out
+
+
 def _group_regions(dl_dev, stats_dev, og_cell_regions):
     """device grouping (pcseg_merge_groups) + host assembly of the reference's merged-region dicts (:850-872)."""
     n = len(og_cell_regions)
