@@ -19,7 +19,7 @@ import collections
 import numpy as np
 import torch
 
-from . import ops, spatial
+from . import gaps, ops, spatial
 from . import tiff_analysis as ta
 from .synth import BOUNDARY_PLANE, CELL_TYPES_5
 
@@ -958,6 +958,43 @@ class FramePipeline:
         out = _download(spatial._clustering_tables(points, rc, window, edges, 512.0 / float(raster), len(tb.slot_names), fid))
         out.update((k + "_columns", v) for k, v in spatial.clustering_columns(edges).items())
         return out
+
+    def gaps(self, res, of="cells", reach=None, frame_ids=None, raster=19.0):
+        """How far is every ROI of one batch from the nearest OTHER ROI of each strain, rim to rim?  The gap of two ROIs is the
+        smallest distance between a pixel of one and a pixel of the other (``gaps.label_gaps``, csrc/gaps.hip): exact, where
+        ``neighbours`` measures between centroids -- which for rods and for unresolved clusters can lie many pixels from the
+        rim.  ``of``: "cells" (the class-map components of kind >= 1: one row per row of ``cells``) or "refined" (the refined
+        rows of kind >= 1): the rows, slots and order of ``neighbours`` / ``refined_neighbours``.  ``reach``: in um at ``512 /
+        raster`` pixels per um (the scale of ``distances``), gaps of ``reach`` and more count as none; None: unbounded.
+        Returns ``{"gaps": float64 numpy rows, "gaps_columns": [...]}`` (``gaps.gap_columns``): ``frame`` (``frame_ids`` as in
+        :meth:`borders`), ``label``, ``slot``, then per type slot ``gap_um_<type>`` (``sqrt(gap_px2) / scale``; NaN where there
+        is no other ROI of that type), ``gap_label_<type>`` (the nearest one, the smallest label among equally near ones; -1
+        for none) and ``gap_px2_<type>`` (the squared gap in pixels; -1 for none).  Refined ROIs flooded against each other
+        have ``gap_px2 == 1`` (or 2 where they meet only diagonally); components of one class are never closer than
+        ``gap_px2 == 4`` (they are 8-connected components: two of them cannot have neighbouring pixels), components of
+        different classes can touch.  ``gap_px2_<t> == 1`` exactly where ``territories`` reports ``n_contact_<t> > 0``.
+        ``res`` is only read."""
+        if of not in ("cells", "refined"):
+            raise ValueError('of must be "cells" or "refined"')
+        B, C, H, W = res["shape"]
+        fid = np.arange(B, dtype=np.float64) if frame_ids is None else np.asarray(frame_ids, np.float64)
+        if fid.shape != (B,):
+            raise ValueError("frame_ids must name every frame of the batch")
+        scale = 512.0 / float(raster)
+        r2 = ops.reach_um_r2(reach, scale)
+        tb = self.tables_
+        names = list(tb.slot_names)
+        dev = res["stats"].device
+        if of == "cells":
+            rows = ops.class_rows(res)
+        else:
+            pos = torch.arange(B, dtype=torch.int64, device=dev)
+            groups = (res.get("groups") or {}) if self.merged else {}
+            _, d = ops._dense_tables(res, groups, pos, C, (), True)
+            rt = ops.refined_tables(res, pos, tb, d.ws, (d.n_roi, d.n_cell), check=True)
+            rows = ops.refined_rows(res, rt["kind_r"], rt["slot_r"])
+        table = gaps.gap_rows(rows.labels, rows.live, rows.slot_of, torch.from_numpy(fid).to(dev), scale, names, r2)
+        return {"gaps": table.cpu().numpy().reshape(-1, 3 + 3 * len(names)), "gaps_columns": gaps.gap_columns(names)}
 
     def tables(self, res, frame_ids=None, ratios=RATIOS_5, distances=False, raster=19.0, check=True, **switches):
         """Download one batch as numpy tables: ``cells`` (one row per cell / cluster region), ``rois`` (one row per

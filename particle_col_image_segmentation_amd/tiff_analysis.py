@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import gaps, ops
 
 # --- constants: tiff_analysis.py:47-82 (they are the reference's whole flag system)
 BASE_TYPE_MAP = {1: "3D05", 2: "6B07", 3: "C3M10", 4: "Particle", 5: "Background"}
@@ -548,6 +548,40 @@ def get_cell_territories(z_slice, cell_pos, cell_clusters, cell_types, reach=Non
                                       r2=ops.reach_um_r2(reach, float(px_to_um)), mask=ops.particle_mask(z_dev, particle_label),
                                       check=True)
     out.update(territories=rows.cpu().numpy()[:, 1:], adjacency=adj.cpu().numpy()[:, 1:])
+    return out
+
+
+def get_cell_gaps(cell_pos, cell_clusters=None, reach=None, px_to_um=PX_TO_UM_CONV):
+    """How far every cell is from the nearest OTHER cell of each strain, rim to rim (csrc/gaps.hip; refine_boundaries.py:8-12,
+    goal 3, between the regions' pixels instead of their centroids): the regions of ``cell_pos`` and ``cell_clusters``
+    (strain -> regions of ONE frame, as get_cell_positions_and_areas returns them, all carrying one label image).  Returns
+    a dict: ``names`` (the strains: type slot k = ``names[k]``, at most 4) and ``gaps`` float64 (n, 2 + 3 K) in label order
+    with ``gaps_columns`` = label, slot, gap_um_<strain>.. (the smallest distance between a pixel of the region and a pixel
+    of another region of that strain, / px_to_um; NaN where there is none closer than ``reach`` um, None: unbounded),
+    gap_label_<strain>.. (that region's label, the smallest among equally near ones; -1 for none), gap_px2_<strain>.. (the
+    squared gap in pixels; 1: the two touch along an edge; -1 for none).  One device call chain for the frame."""
+    cell_clusters = cell_clusters or {}
+    names = list(cell_pos) + [n for n in cell_clusters if n not in cell_pos]
+    if len(names) > 4:
+        raise ValueError("at most 4 strains")
+    regs = [(t, r) for t, name in enumerate(names) for r in list(cell_pos.get(name, [])) + list(cell_clusters.get(name, []))]
+    holders = {id(r._im): r._im for _, r in regs}
+    if None in [r._im for _, r in regs] or len(holders) > 1:
+        raise AttributeError("the regions must carry the label image of one frame")
+    out = {"names": names, "gaps_columns": gaps.gap_columns(names)[1:]}
+    if not regs:
+        out["gaps"] = np.zeros((0, 2 + 3 * len(names)))
+        return out
+    labels = next(iter(holders.values())).dev[None]
+    dev = labels.device
+    cap = max(r.label for _, r in regs)
+    live, slot_of = np.zeros((1, cap), bool), np.full((1, cap), 255, np.uint8)
+    for t, r in regs:
+        live[0, r.label - 1], slot_of[0, r.label - 1] = True, t
+    rows = gaps.gap_rows(labels, torch.from_numpy(live).to(dev), torch.from_numpy(slot_of).to(dev),
+                         torch.zeros((1,), dtype=torch.int64, device=dev), float(px_to_um), names,
+                         r2=ops.reach_um_r2(reach, float(px_to_um)))
+    out["gaps"] = rows.cpu().numpy()[:, 1:]
     return out
 
 
