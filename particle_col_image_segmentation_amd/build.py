@@ -5,7 +5,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["stencil.hip", "ccl.hip", "reduce.hip", "edt.hip", "watershed.hip", "tables.hip", "frontend.hip", "neighbours.hip", "refined.hip", "surface.hip", "shape.hip", "hull.hip", "voronoi.hip", "skeleton.hip", "reconstruct.hip", "agreement.hip", "mixing.hip", "borders.hip", "window_pairs.hip", "gaps.hip"]
+SOURCES = ["stencil.hip", "ccl.hip", "reduce.hip", "edt.hip", "watershed.hip", "tables.hip", "frontend.hip", "neighbours.hip", "refined.hip", "surface.hip", "shape.hip", "hull.hip", "voronoi.hip", "skeleton.hip", "reconstruct.hip", "agreement.hip", "mixing.hip", "borders.hip", "window_pairs.hip", "gaps.hip", "local_counts.hip"]
 LIB = os.path.join(HERE, "libpcseg.so")
 
 
@@ -14,7 +14,7 @@ def _stale():
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in SOURCES + ["common.h", "union_find.h", "tile_ops.h", "table_common.h", "label_reduce.h", "column_pass.h", "tile_rounds.h", "pair_table.h"]]
-    deps += [os.path.join(HERE, "..", "include", h) for h in ("pcseg.h", "pcseg_spatial.h", "pcseg_gaps.h")]
+    deps += [os.path.join(HERE, "..", "include", h) for h in ("pcseg.h", "pcseg_spatial.h", "pcseg_gaps.h", "pcseg_local.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

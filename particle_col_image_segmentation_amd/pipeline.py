@@ -19,7 +19,7 @@ import collections
 import numpy as np
 import torch
 
-from . import gaps, ops, spatial
+from . import gaps, local, ops, spatial
 from . import tiff_analysis as ta
 from .synth import BOUNDARY_PLANE, CELL_TYPES_5
 
@@ -908,26 +908,10 @@ class FramePipeline:
                          host["links"] / (512.0 / float(raster))], axis=1).astype(np.float64).reshape(-1, 7)
         return {"borders": rows, "borders_columns": ["frame", "roi_a", "roi_b", "links", "mean", "saddle", "length_um"]}
 
-    def clustering(self, res, edges, window="particle", of="cells", frame_ids=None, raster=19.0):
-        """Are the cells of one batch clumped or spread evenly over the window they can sit in?  Observed pair counts against
-        complete spatial randomness on that window, exactly (``spatial.window_pair_counts``, csrc/window_pairs.hip): no edge
-        correction, no simulation.  ``edges``: m + 1 increasing values from 0, in um at ``512 / raster`` pixels per um (the
-        scale of ``distances``).  ``window``: "particle" (``ops.particle_mask(res["recreated"], <Particle value>)``, the mask of
-        the surface tables), "frame" (every pixel) or a uint8 (B, H, W) CUDA tensor (non-zero: in the window).  ``of``:
-        "cells" (the rows of ``cells``) or "refined" (the refined rows of kind >= 1): the points, slots and order of
-        ``pair_hist`` / ``refined_pair_hist``.  A point is in the window when the mask is set at pixel ``(floor(row + 0.5),
-        floor(col + 0.5))`` of its centroid (the rule of ``surface``'s ``inside``); the others are left out of the observed
-        counts, which are ``ops.point_neighbours``' histogram of the rest.  Returns numpy tables with ``<name>_columns`` lists:
-        ``window_pairs`` = ``[frame, n_px, bin_0 .. bin_m-1, over]``, one row per frame: the window's pixels A and the ordered
-        pairs of window pixels (self pairs included) per distance bin, ``over`` the rest of the A^2 pairs -- exact integers,
-        stored as float64 like every table: exact up to 2^53; ``clustering`` = ``[frame, slot_a, slot_b, bin, r_lo_um, r_hi_um,
-        n_a, n_b, n_out_a, n_out_b, obs, window_pairs, expected, ratio, cum_obs, cum_window_pairs, cum_expected, cum_ratio]``,
-        one row per (frame, slot pair a <= b, bin): the points of the two slots in the window and left out, the observed
-        pairs, the window's count G of the bin, ``expected = (npairs * G) / (A * A)`` with ``npairs = n_a (n_a - 1) / 2`` (a ==
-        b) or ``n_a n_b`` -- the expectation for points placed independently and uniformly on the window's pixels --, ``ratio =
-        obs / expected`` (above 1: clustering at that range, below 1: spacing) and the same of the counts summed over the
-        bins 0 .. k (the K-function form); NaN where A == 0 or expected == 0.  ``frame_ids`` as in :meth:`borders`.
-        ``res`` is only read."""
+    def _window_points(self, res, edges, window, of, frame_ids, raster):
+        """What :meth:`clustering` and :meth:`neighbourhoods` are made from, after their refusals: ``(fid, window, points, rc)``
+        -- the frames' ids (numpy float64), the window as a uint8 (B, H, W) tensor, the points of ``pair_hist`` /
+        ``refined_pair_hist`` (:class:`ops.Points`) and their (row, col) centroids."""
         if of not in ("cells", "refined"):
             raise ValueError('of must be "cells" or "refined"')
         if isinstance(window, str) and window not in ("particle", "frame"):
@@ -955,8 +939,64 @@ class FramePipeline:
         else:
             points = ops.refined_tables(res, pos, tb, d.ws, (d.n_roi, d.n_cell), check=True, points=True)["points"]
             rc = ops._refined_centroids(res, points)
+        return fid, window, points, rc
+
+    def clustering(self, res, edges, window="particle", of="cells", frame_ids=None, raster=19.0):
+        """Are the cells of one batch clumped or spread evenly over the window they can sit in?  Observed pair counts against
+        complete spatial randomness on that window, exactly (``spatial.window_pair_counts``, csrc/window_pairs.hip): no edge
+        correction, no simulation.  ``edges``: m + 1 increasing values from 0, in um at ``512 / raster`` pixels per um (the
+        scale of ``distances``).  ``window``: "particle" (``ops.particle_mask(res["recreated"], <Particle value>)``, the mask of
+        the surface tables), "frame" (every pixel) or a uint8 (B, H, W) CUDA tensor (non-zero: in the window).  ``of``:
+        "cells" (the rows of ``cells``) or "refined" (the refined rows of kind >= 1): the points, slots and order of
+        ``pair_hist`` / ``refined_pair_hist``.  A point is in the window when the mask is set at pixel ``(floor(row + 0.5),
+        floor(col + 0.5))`` of its centroid (the rule of ``surface``'s ``inside``); the others are left out of the observed
+        counts, which are ``ops.point_neighbours``' histogram of the rest.  Returns numpy tables with ``<name>_columns`` lists:
+        ``window_pairs`` = ``[frame, n_px, bin_0 .. bin_m-1, over]``, one row per frame: the window's pixels A and the ordered
+        pairs of window pixels (self pairs included) per distance bin, ``over`` the rest of the A^2 pairs -- exact integers,
+        stored as float64 like every table: exact up to 2^53; ``clustering`` = ``[frame, slot_a, slot_b, bin, r_lo_um, r_hi_um,
+        n_a, n_b, n_out_a, n_out_b, obs, window_pairs, expected, ratio, cum_obs, cum_window_pairs, cum_expected, cum_ratio]``,
+        one row per (frame, slot pair a <= b, bin): the points of the two slots in the window and left out, the observed
+        pairs, the window's count G of the bin, ``expected = (npairs * G) / (A * A)`` with ``npairs = n_a (n_a - 1) / 2`` (a ==
+        b) or ``n_a n_b`` -- the expectation for points placed independently and uniformly on the window's pixels --, ``ratio =
+        obs / expected`` (above 1: clustering at that range, below 1: spacing) and the same of the counts summed over the
+        bins 0 .. k (the K-function form); NaN where A == 0 or expected == 0.  ``frame_ids`` as in :meth:`borders`.
+        ``res`` is only read."""
+        fid, window, points, rc = self._window_points(res, edges, window, of, frame_ids, raster)
+        tb = self.tables_
         out = _download(spatial._clustering_tables(points, rc, window, edges, 512.0 / float(raster), len(tb.slot_names), fid))
         out.update((k + "_columns", v) for k, v in spatial.clustering_columns(edges).items())
+        return out
+
+    def neighbourhoods(self, res, edges, window="particle", of="cells", frame_ids=None, raster=19.0):
+        """What lies around ONE cell of a batch: for every typed point and every distance bin the cells of each strain, the
+        pixels of each strain and the pixels of the window in that ring around it (``local.point_counts``, ``local.disk_counts``,
+        csrc/local_counts.hip) -- the per-cell marks of :meth:`clustering`: the local K-function with its edge-correction term
+        and a segregation index per cell.  ``edges``, ``window``, ``of``, ``frame_ids`` and ``raster`` mean what they mean in
+        :meth:`clustering`; the points, slots and row order are those of ``pair_hist`` / ``refined_pair_hist``, and a point is in
+        the window by the same ``(floor(row + 0.5), floor(col + 0.5))`` rule.  A point outside the window counts for nobody
+        (``clustering`` leaves it out of ``obs`` in the same way).  The pixel sets are the window and, per type slot, the pixels
+        of ``res["denoised"]`` whose class value maps to the slot -- no resolved cells are needed, so the pixel columns also
+        describe unresolved clusters; the query pixel of a point is its rounded centroid.
+        Returns ``{"neighbourhoods": float64 numpy rows, "neighbourhoods_columns": [...]}`` (``local.neighbourhood_columns``), one
+        row per (typed point, bin) in point order then bin order: ``frame``, ``label``, ``slot``, ``in_window``, ``bin``,
+        ``r_lo_um``, ``r_hi_um``; ``win_px`` / ``cum_win_px``, the window's pixels in the ring and in the disk up to the bin (how
+        much of the particle lies within that distance: a cell at the rim has less of it, and looks lonely for that reason
+        alone); per type slot ``n_<t>`` / ``cum_n_<t>`` (the OTHER in-window points of the slot), ``px_<t>`` / ``cum_px_<t>`` (the
+        strain's pixels, the cell's own included) and ``expected_<t>`` / ``cum_expected_<t>`` = ``(N_t * win_px) / A`` with ``N_t``
+        the slot's in-window points, less one for the row's own slot, and ``A`` the window's area -- the count expected around
+        this cell for points placed uniformly on the window; NaN where A == 0; then ``own_frac = cum_n_own / sum_t cum_n_t`` and
+        ``own_px_frac = cum_px_own / sum_t cum_px_t``, NaN where the denominator is 0.  The row of a point outside the window has
+        ``in_window = 0`` and NaN in every count column.  For every frame, slot pair a <= b and bin the sum of ``n_<b>`` over the
+        in-window rows of slot a is ``clustering``'s ``obs`` (twice it when a == b).
+        The lattice caveat of DESIGN section 22 holds here too: the window and the pixel sets are counted from the ROUNDED
+        centroid on the pixel lattice, while the point counts use the unrounded centroids -- below a few pixels ``expected``
+        carries the lattice's steps, and bins narrower than a pixel are better merged.  ``res`` is only read."""
+        fid, window, points, rc = self._window_points(res, edges, window, of, frame_ids, raster)
+        tb = self.tables_
+        K = len(tb.slot_names)
+        planes = local.set_planes(window, res["denoised"], tb.slot)
+        out = _download(local.neighbourhood_tables(points, rc, planes, edges, 512.0 / float(raster), K, fid))
+        out["neighbourhoods_columns"] = local.neighbourhood_columns(list(tb.slot_names), edges)
         return out
 
     def gaps(self, res, of="cells", reach=None, frame_ids=None, raster=19.0):

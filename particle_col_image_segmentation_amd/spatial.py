@@ -5,6 +5,7 @@ prototypes on ``_lib.load()``'s handle and enters the library through ``ops._cal
 (DESIGN.md, "The argument contract of ops": a tensor that is not on the device, or of another dtype, is a ``TypeError``;
 another rank or shape a ``ValueError``; a non-contiguous input is copied).
 """
+import collections
 import ctypes
 from ctypes import c_double, c_int, c_int64, c_size_t, c_void_p
 
@@ -155,6 +156,27 @@ def _points_in_window(points_rc, frame_offsets, mask):
     return ok & (mask.reshape(-1)[idx] != 0)
 
 
+_WindowSlots = collections.namedtuple("_WindowSlots", "inside typed slot_in frame n_in n_out")
+
+
+def _window_slots(points, points_rc, mask, K):
+    """The points of a packed set against a window, for the tables that count only the points IN it: ``inside`` (n,) bool
+    (:func:`_points_in_window`), ``typed`` (n,) bool (slot in 0 .. K - 1), ``slot_in`` (n,) int32 = the slot, -1 outside the
+    window, ``frame`` (n,) int64 and ``n_in`` / ``n_out`` int64 (B, K): the typed points per frame and slot in the window and
+    left out."""
+    dev = mask.device
+    B = mask.shape[0]
+    foff = points.frame_offsets
+    inside = _points_in_window(points_rc, foff, mask)
+    typed = (points.slot >= 0) & (points.slot < K)
+    slot_in = torch.where(inside, points.slot, torch.full_like(points.slot, -1))
+    n = points.slot.shape[0]
+    frame = torch.repeat_interleave(torch.arange(B, dtype=torch.int64, device=dev), foff[1:] - foff[:-1], output_size=n)
+    key = frame * K + points.slot.clamp(0, K - 1).to(torch.int64)
+    count = lambda sel: torch.zeros((B * K,), dtype=torch.int64, device=dev).index_add_(0, key, sel.to(torch.int64)).reshape(B, K)
+    return _WindowSlots(inside, typed, slot_in, frame, count(typed & inside), count(typed & ~inside))
+
+
 def _clustering_tables(points, points_rc, mask, edges, scale, K, frame_ids):
     """The two tables of ``FramePipeline.clustering`` (which describes them) for one packed point set: ``points``
     (:class:`ops.Points`, coordinates as :func:`ops.point_neighbours` takes them), ``points_rc`` (n, 2) float64 (row, col) of
@@ -163,15 +185,9 @@ def _clustering_tables(points, points_rc, mask, edges, scale, K, frame_ids):
     dev = mask.device
     B = mask.shape[0]
     K = int(K)
-    inside = _points_in_window(points_rc, points.frame_offsets, mask)
-    typed = (points.slot >= 0) & (points.slot < K)
-    slot_in = torch.where(inside, points.slot, torch.full_like(points.slot, -1))
-    n = points.slot.shape[0]
     foff = points.frame_offsets
-    frame = torch.repeat_interleave(torch.arange(B, dtype=torch.int64, device=dev), foff[1:] - foff[:-1], output_size=n)
-    key = frame * K + points.slot.clamp(0, K - 1).to(torch.int64)
-    count = lambda sel: torch.zeros((B * K,), dtype=torch.int64, device=dev).index_add_(0, key, sel.to(torch.int64)).reshape(B, K)
-    n_in, n_out = count(typed & inside), count(typed & ~inside)
+    ws = _window_slots(points, points_rc, mask, K)
+    slot_in, n_in, n_out = ws.slot_in, ws.n_in, ws.n_out
     _, _, pair_hist = ops.point_neighbours(points.coords, slot_in, points.ids, foff, K, scale, edges)
     window = window_pair_counts(mask, edges, scale)
     ex = pair_expectation(pair_hist, n_in, window)

@@ -632,16 +632,13 @@ def get_cell_surface_distances(z_slice, cell_types, cell_pos=None, cell_clusters
                  "shells": {side: {"n_px": int(sh[side, 0]), "bins": sh[side, 1:-1], "over": int(sh[side, -1])} for side in (0, 1)}}
 
 
-def get_cell_clustering(z_slice, cell_types, cell_pos=None, cell_clusters=None, edges=None, window="particle", px_to_um=PX_TO_UM_CONV):
-    """Are the cells of one denoised class map clumped or spread evenly over the window they can sit in?  The two tables of
-    ``FramePipeline.clustering`` (which describes them) for one frame: ``window_pairs`` and ``clustering`` with their
-    ``<name>_columns``, frame 0.  The points are the regions of ``cell_pos`` and ``cell_clusters`` (strain -> regions; those
-    of ``get_cell_positions_and_areas`` when none are passed) at their centroids, the slots the strains in ``cell_pos`` order;
-    ``window``: "particle" (the particle reconstructed as ``recreate_particle_area`` does, holes filled: the mask of
-    ``get_cell_surface_distances``), "frame" or an (H, W) mask of the caller's; ``edges`` (increasing, from 0) in um."""
-    from . import spatial
+def _window_points(who, z_slice, cell_types, cell_pos, cell_clusters, edges, window):
+    """What :func:`get_cell_clustering` and :func:`get_cell_neighbourhoods` are made from, after their refusals: ``(names, z_dev,
+    mask, points, rc)`` -- the strains in slot order, the class map as a (1, H, W) uint8 CUDA tensor, the window as one, the
+    regions of ``cell_pos`` and ``cell_clusters`` as :class:`ops.Points` (positions as the pair tables take them) and their
+    (row, col) centroids."""
     if edges is None:
-        raise ValueError("get_cell_clustering needs edges")
+        raise ValueError("%s needs edges" % who)
     if isinstance(window, str) and window not in ("particle", "frame"):
         raise ValueError('window must be "particle", "frame" or an (H, W) mask')
     if cell_pos is None:
@@ -663,18 +660,50 @@ def get_cell_clustering(z_slice, cell_types, cell_pos=None, cell_clusters=None, 
         particle_labels = [label for label, name in cell_types.items() if name == "Particle"]
         particle_label = particle_labels[-1] if particle_labels else None
         gained = None
+        filled = z_dev
         for cell_label in ([label for label, name in cell_types.items() if name in CELL_TYPES] if particle_label is not None else []):
-            z_dev, gained = ops.fill_particle(z_dev, particle_label, cell_label, particle_label, DILATION_RADIUS, DISTANCE_THRESHOLD,
-                                              gained)
-        mask = ops.particle_mask(z_dev, particle_label)
+            filled, gained = ops.fill_particle(filled, particle_label, cell_label, particle_label, DILATION_RADIUS, DISTANCE_THRESHOLD,
+                                               gained)
+        mask = ops.particle_mask(filled, particle_label)
     rc = torch.tensor([[float(r.centroid[0]), float(r.centroid[1])] for _, r in regs], dtype=torch.float64).reshape(-1, 2).to(dev)
     xy = torch.stack([rc[:, 1] + 1.0, rc[:, 0] + 1.0], dim=1)  # positions as the pair tables take them (pcseg_point_neighbours)
     points = ops.Points(xy, torch.tensor([t for t, _ in regs], dtype=torch.int32).to(dev),
                         torch.tensor([int(r.label) for _, r in regs], dtype=torch.int32).to(dev),
                         torch.tensor([0, len(regs)], dtype=torch.int64).to(dev))
+    return names, z_dev, mask, points, rc
+
+
+def get_cell_clustering(z_slice, cell_types, cell_pos=None, cell_clusters=None, edges=None, window="particle", px_to_um=PX_TO_UM_CONV):
+    """Are the cells of one denoised class map clumped or spread evenly over the window they can sit in?  The two tables of
+    ``FramePipeline.clustering`` (which describes them) for one frame: ``window_pairs`` and ``clustering`` with their
+    ``<name>_columns``, frame 0.  The points are the regions of ``cell_pos`` and ``cell_clusters`` (strain -> regions; those
+    of ``get_cell_positions_and_areas`` when none are passed) at their centroids, the slots the strains in ``cell_pos`` order;
+    ``window``: "particle" (the particle reconstructed as ``recreate_particle_area`` does, holes filled: the mask of
+    ``get_cell_surface_distances``), "frame" or an (H, W) mask of the caller's; ``edges`` (increasing, from 0) in um."""
+    from . import spatial
+    names, _, mask, points, rc = _window_points("get_cell_clustering", z_slice, cell_types, cell_pos, cell_clusters, edges, window)
     out = {k: v.cpu().numpy() for k, v in
            spatial._clustering_tables(points, rc, mask, edges, px_to_um, max(len(names), 1), np.zeros(1)).items()}
     out.update((k + "_columns", v) for k, v in spatial.clustering_columns(edges).items())
+    return out
+
+
+def get_cell_neighbourhoods(z_slice, cell_types, cell_pos=None, cell_clusters=None, edges=None, window="particle", px_to_um=PX_TO_UM_CONV):
+    """What lies around every cell of one denoised class map: the table of ``FramePipeline.neighbourhoods`` (which describes
+    it) for one frame, ``neighbourhoods`` with ``neighbourhoods_columns``, frame 0.  Points, slots, ``window`` and ``edges`` as in
+    :func:`get_cell_clustering`; the pixels of strain t are the pixels of ``z_slice`` whose class value ``cell_types`` maps to
+    the strain of slot t."""
+    from . import local
+    names, z_dev, mask, points, rc = _window_points("get_cell_neighbourhoods", z_slice, cell_types, cell_pos, cell_clusters, edges,
+                                                    window)
+    K = max(len(names), 1)
+    slot = np.full(256, 255, np.uint8)
+    for value, name in cell_types.items():
+        if name in names and 0 <= int(value) < 256:
+            slot[int(value)] = names.index(name)
+    planes = local.set_planes(mask, z_dev, slot)
+    out = {k: v.cpu().numpy() for k, v in local.neighbourhood_tables(points, rc, planes, edges, px_to_um, K, np.zeros(1)).items()}
+    out["neighbourhoods_columns"] = local.neighbourhood_columns(names if names else K, edges)
     return out
 
 
